@@ -2,6 +2,7 @@
 """Benchmark of the DH3D hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload local|global|cfg5|train] [--scaling weak|strong]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic clouds already resident in HBM:
   local  (default, BASELINE config[1]): local-descriptor forward, basic_config, N=8192 K=8, batch 8
@@ -131,7 +132,7 @@ def real_oxford_clouds(B, N, dev):
     return torch.from_numpy(out).to(dev)
 
 
-def time_steps(run, pts, steps, warmup, dev):
+def time_steps(run, pts, steps, warmup, dev, align=None):
     from dh3d_amd import dist as D
     # clock ramp: a fresh process finds the GPU in a low power state and a millisecond-scale step does not pull it
     # up within a handful of warmup steps (measured: the same graph at 0.97 vs 0.91 ms).  ~0.2 s of untimed
@@ -141,6 +142,10 @@ def time_steps(run, pts, steps, warmup, dev):
         run(pts)
         torch.cuda.synchronize(dev)
     for _ in range(warmup):
+        run(pts)
+    # align() -> further untimed steps that bring a pipeline back to its first slot: the ramp's step count varies from run
+    # to run, this way the K timed steps (and the batch the last of them runs on) do not
+    for _ in range(align() if align else 0):
         run(pts)
     torch.cuda.synchronize(dev)
     D.barrier()
@@ -746,6 +751,7 @@ def cpu_baseline(workload):
 
 
 # --------------------------------------------------------------------------------------------- the stdout line
+DUMP_LIMIT = 64 << 20   # bytes: --dump-outputs writes at most this much
 LINE_LIMIT = 8192   # bytes: the driver could not parse round 4's 32.8 kB line; everything but the contract goes to a side file
 
 _ROOF_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes", "launch_ms")
@@ -858,6 +864,39 @@ def compact_line(full, extras_path=None, limit=LINE_LIMIT):
     return text
 
 
+def host_output(t):
+    """A device output as a numpy array in float32 (f32 / f16 / bf16) or float64 (everything else)."""
+    t = t.detach()
+    if t.dtype in (torch.float16, torch.bfloat16):
+        t = t.float()
+    elif t.dtype != torch.float32:
+        t = t.double()
+    return t.cpu().numpy()
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT, seed=0):
+    """Write {name: numpy array} as out_dir/<name>.npy, at most `limit` bytes in all.  An array over its share of the
+    limit is cut to a fixed, seeded sample of its rows (all axes but the last flattened): <name>.npy holds those rows,
+    <name>_rows.npy their row numbers (float64).  Returns {name: {"shape", "dtype", "sampled_rows"}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    manifest = {}
+    for name in sorted(arrays):
+        a = np.asarray(arrays[name])
+        a = a.astype(np.float32 if a.dtype in (np.float32, np.float16) else np.float64, copy=False)
+        rec = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled_rows": None}
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1] if a.ndim > 1 else 1)
+            n = max(1, min(rows.shape[0], share // (rows.shape[1] * a.itemsize + 8)))
+            idx = np.sort(np.random.default_rng(seed).choice(rows.shape[0], n, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), idx.astype(np.float64))
+            a = np.ascontiguousarray(rows[idx])
+            rec["sampled_rows"] = int(n)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        manifest[name] = rec
+    return manifest
+
+
 def write_side_file(full, path=None, workload="local"):
     """The full record (everything measured, full precision) as indented JSON; returns the path relative to the repo
     root, or None when nothing could be written (the stdout line never depends on it)."""
@@ -911,7 +950,16 @@ def main():
                          "cloud) followed by chip-wide kernels, so the engine overlaps consecutive batches; 1 = one step "
                          "at a time (also measured and reported as `one_step_at_a_time` in every line).  The training "
                          "step always runs one at a time")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed, seeded sample of the rows beyond that); the "
+                         "inputs are the same in every run with the same arguments (forward workloads only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload in ("train", "train_local"):
+        ap.error("--dump-outputs: a training step's results depend on every step before it, including the time-based "
+                 "clock ramp; only the forward workloads have reproducible outputs")
     explicit_inflight = args.inflight > 0
     if not explicit_inflight:
         args.inflight = WORKLOADS[args.workload]["inflight"]
@@ -1096,6 +1144,8 @@ def main():
             # the batch is resident in the graph's input buffer (where a loader's H2D copy would put it)
             run.static_input.copy_(pts)
             dt = time_steps(run, run.static_input, args.steps, args.warmup, dev)
+            if args.dump_outputs and workload == args.workload and batch is None and strong_ is None:
+                _LAST_OUTPUTS["serial"] = {k: host_output(v) for k, v in run.outputs.items()}
             info = {"clouds_per_gpu": per}
             if workload == args.workload and args.repeats > 0:
                 blocks = repeat_blocks(run, run.static_input, args.steps, dev, args.repeats)
@@ -1129,11 +1179,15 @@ def main():
                 pipe.input_buffer(k).copy_(synthetic_clouds(per, wl["N"], wl["seed"] + 7919 * k, dev, rank))
             torch.cuda.synchronize()
 
+            last = [None]
+
             def step(p):
-                pipe.submit()  # zero-copy: the slot's batch is already in its input buffer
+                last[0] = pipe.submit()  # zero-copy: the slot's batch is already in its input buffer
 
             nsteps = steps or args.steps
-            dt = time_steps(step, pts, nsteps, args.warmup, dev)
+            dt = time_steps(step, pts, nsteps, args.warmup, dev, align=lambda: (depth - pipe.next_slot) % depth)
+            if args.dump_outputs and workload == args.workload and not steps and strong_ is None:
+                _LAST_OUTPUTS["in_flight"] = {k: host_output(v) for k, v in pipe.result(last[0], wait="host").items()}
             if workload == args.workload and not steps:
                 # the same pipeline over the OTHER K: 20 = the K of rounds 1-5 and of the driver's command line, 100 = this
                 # file's default (the timed region includes the fill and the drain of the slots: ~5 % at K = 20)
@@ -1156,6 +1210,7 @@ def main():
 
     _STREAMING = {}
     _AT20 = {}
+    _LAST_OUTPUTS = {}   # --dump-outputs: the last timed step's outputs, "serial" / "in_flight"
 
     def measure_streaming(pipe, wl, per, total, nsteps):
         """The same pipeline as a SERVING loop (what engine.Pipeline.map runs; localdesc_extract.py:106-138,
@@ -1515,6 +1570,10 @@ def main():
                         "more than one GPU in rounds 1-5 (no 8-GPU node was available to the driver)"}
     if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("local", "global"):
         line["cpu_baseline"] = cpu_baseline(args.workload)
+    if rank == 0 and args.dump_outputs:
+        outs = _LAST_OUTPUTS["in_flight" if pipelined else "serial"]
+        line["outputs_dumped"] = {"dir": args.dump_outputs, "path": "steps in flight" if pipelined else "one step at a time",
+                                  "arrays": dump_outputs(outs, args.dump_outputs)}
     D.barrier()
     if rank == 0:
         path = write_side_file(line, args.extras_file, args.workload)

@@ -136,3 +136,22 @@ def test_side_file_holds_the_full_record(tmp_path):
     back = json.load(open(tmp_path / "sub" / "extras.json"))
     assert back["roofline_step"]["kernels"][3]["kernel"] == "k3" and back["value"] == full["value"]
     assert bench.write_side_file(full, "/proc/nope/x.json") is None   # never fatal
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(5)
+    big = rng.random((4, 300, 16), dtype=np.float32)           # 76.8 kB: over its half of a 64 kB limit
+    small = np.arange(32, dtype=np.int64).reshape(4, 8)         # integers are written as float64
+    man = bench.dump_outputs({"big": big, "small": small}, str(tmp_path), limit=64 << 10)
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["big.npy", "big_rows.npy", "small.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 10
+    s = np.load(tmp_path / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small) and man["small"]["sampled_rows"] is None
+    b, rows = np.load(tmp_path / "big.npy"), np.load(tmp_path / "big_rows.npy")
+    assert b.dtype == np.float32 and rows.dtype == np.float64 and man["big"]["sampled_rows"] == len(rows) == len(b)
+    assert np.array_equal(b, big.reshape(-1, 16)[rows.astype(np.int64)])
+    again = tmp_path / "again"
+    bench.dump_outputs({"big": big, "small": small}, str(again), limit=64 << 10)
+    assert np.array_equal(np.load(again / "big_rows.npy"), rows)   # the same sample every run
