@@ -374,23 +374,31 @@ def compute_level(xyz, dilate, knn, ordered=None, fps_contract=None, cells=None)
     region-pruned FPS with several picks per synchronisation (csrc/fps.hip: 0.38 ms vs 0.82 ms at 8192 -> 1024,
     0.2 vs 0.28 ms at 4096 -> 512; no gain at 2048 and below).
     fps_contract: None = default kernels; 0 / 1 forces the any-N kernel with that distance rounding
-    (ops.farthest_point_sample)."""
+    (ops.farthest_point_sample).
+    The level records the kernels it took in lv["_path"] = {"fps", "knn", "nn3" (finish_level)}."""
     B, N, _ = xyz.shape
     npoint = N // dilate
     ordered_s, cells_s = None, None
-    if ordered is not None and 4096 <= N <= 8192 and fps_contract is None and FPS_ORDERED:
+    if (ordered is not None and 4096 <= N <= 8192 and fps_contract is None and FPS_ORDERED
+            and pm.fps_sorted_fits(N, npoint, ordered=True)):
         # the sampled set leaves the FPS kernel IN MORTON ORDER (a stable compaction of the picked positions of the sorted
         # cloud: records, group boxes and -- with the cloud's cell table -- the subset's table on the cloud's grid):
-        # three_nn and the sampled set's kNN need no sort of their own behind the sampling
+        # three_nn and the sampled set's kNN need no sort of their own behind the sampling.  (Its tables go beside the
+        # LDS coordinate table: large samples -- dilate 2 above 8009 points -- take the plain kernel below and sort)
         idx, xyz_s, srt_s, gbox_s, cells_s = pm.fps_sorted_ordered(ordered[0], ordered[1], npoint, cells=cells)
         ordered_s = (srt_s, gbox_s)
-    elif ordered is not None and 4096 <= N <= 16384 and fps_contract is None:
-        # (above 12288 points the kernel has no room for its LDS coordinate table and reads winners from the cloud)
-        idx, xyz_s = pm.fps_sorted(ordered[0], ordered[1], npoint, with_xyz=True, xyz=xyz if N > 12288 else None)
+        fps_path = "ordered"
+    elif ordered is not None and 4096 <= N <= 16384 and fps_contract is None and pm.fps_sorted_fits(N, npoint, with_cloud=True):
+        # (where the LDS coordinate table does not fit -- above 12288 points, or large samples below -- the kernel reads
+        # winners from the cloud)
+        table = pm.fps_sorted_fits(N, npoint)
+        idx, xyz_s = pm.fps_sorted(ordered[0], ordered[1], npoint, with_xyz=True, xyz=None if table else xyz)
+        fps_path = "sorted" if table else "sorted_cloud"
     else:
         from . import ops
         idx = ops.farthest_point_sample(npoint, xyz, contract=fps_contract)  # any N (scratch distances above 16384)
         xyz_s = gather_rows(xyz, idx)
+        fps_path = "any_n"
     ready = torch.cuda.Event()
     ready.record()  # xyz_s exists: three_nn may start on another stream while the sampled-set kNN runs here
     if cells_s is not None and knn <= 8 and pm.KNN_GRID and SAMPLED_GRID and npoint >= 256 and B * npoint >= 16384:
@@ -400,19 +408,24 @@ def compute_level(xyz, dilate, knn, ordered=None, fps_contract=None, cells=None)
         # in flight 0.5424 -> 0.5343), 8 x 1024 only 128 and latency-bound (local serial 0.4996 -> 0.5186: stays on the
         # wave-per-query kernel)
         nbr_s, _ = pm.knn_grid(ordered_s[0], ordered_s[1], cells_s, knn)
+        knn_path = "grid_fps"
     elif npoint <= 2048 or npoint > 16384:  # small sets: the brute-force kernel beats sort + pruned search (launch /
         nbr_s, _ = pm.knn_xyz(xyz_s, knn)  # latency bound); sets beyond the Morton sort's 14-bit ids: it is what serves any N
+        knn_path = "brute"
     elif knn <= 8 and pm.KNN_GRID:
         srt_s, gbox_s, cells_s = pm.spatial_sort_cells(xyz_s)
         nbr_s, _ = pm.knn_grid(srt_s, gbox_s, cells_s, knn)
         ordered_s = (srt_s, gbox_s)
+        knn_path = "grid"
     else:
         srt_s, gbox_s = pm.spatial_sort(xyz_s)
         nbr_s, _ = pm.knn_sorted(srt_s, gbox_s, knn)
         ordered_s = (srt_s, gbox_s)
+        knn_path = "sorted"
     level_ready = torch.cuda.Event()
     level_ready.record()  # idx / xyz_s / nbr_s exist
-    lv = {"idx": idx, "xyz_s": xyz_s, "nbr_s": nbr_s, "_xyz_ready": ready, "_level_ready": level_ready}
+    lv = {"idx": idx, "xyz_s": xyz_s, "nbr_s": nbr_s, "_xyz_ready": ready, "_level_ready": level_ready,
+          "_path": {"fps": fps_path, "knn": knn_path}}
     if ordered is not None:
         lv["_ordered"] = ordered            # Morton records + boxes of the full cloud: the pruned three_nn uses them
         if ordered_s is not None:
@@ -435,11 +448,13 @@ def finish_level(xyz, lv, same_stream=False):
             # three_nn_sorted_kernel); the sampled set is sorted here unless the level's kNN already did
             srt_s, gbox_s = lv["_ordered_s"] if "_ordered_s" in lv else pm.spatial_sort(xyz_s)
             d3, i3 = pm.three_nn_sorted(lv["_ordered"][0], lv["_ordered"][1], srt_s, gbox_s)
+            lv.setdefault("_path", {})["nn3"] = "sorted"
         else:
             d3 = torch.empty((B, N, 3), dtype=torch.float32, device=xyz.device)
             i3 = torch.empty((B, N, 3), dtype=torch.int32, device=xyz.device)
             L.check(L.lib().dh3d_three_nn(B, N, xyz_s.shape[1], L.ptr(xyz), L.ptr(xyz_s), L.ptr(d3), L.ptr(i3),
                                           L.stream_ptr()), "three_nn")
+            lv.setdefault("_path", {})["nn3"] = "plain"
         lv["nn3_dist"], lv["nn3_idx"] = d3, i3
         if lv.get("_want_walk_plan") and "_ordered" in lv and xyz_s.shape[1] <= 1024:
             # the global tail's walk over the fine points (pm.global_tail): its per-block slot tables depend on three_nn's

@@ -894,8 +894,8 @@ __device__ __forceinline__ Row4 idw_mix_pk(const Row4 a, const Row4 b, const Row
 // the walk's own launch (round 5, tools/walk_phases.sh) -- round 6: walk_plan_kernel builds it once behind three_nn, off the
 // critical chain, and the walk copies the image in (dh3d_walk_plan / dh3d_global_walk_planned_fwd).
 // LISTS (the plan kernel): also the references to every staged row, slot-major -- s_loff[slot] .. s_loff[slot + 1] index
-// entries `point * 4 + t` of s_lst (within a list in the order of the LDS atomics that filled it: the scatter's sums are
-// f32 atomics anyway; sorting each list by one thread cost the plan 68 us) -- for the NetVLAD scatter of the walk.
+// entries `point * 4 + t` of s_lst (within a list in (point, t) order, ranked from a per-slot bitmap: sorting each list by
+// one thread cost the plan 68 us) -- for the NetVLAD scatter of the walk.
 template <bool LISTS>
 __device__ __forceinline__ void ih_build_table(float *s_ih, const int32_t *__restrict__ idx, const float *__restrict__ dist,
                                                const float4 *__restrict__ order, int bi, int blk, int n, int m) {
@@ -959,15 +959,24 @@ __device__ __forceinline__ void ih_build_table(float *s_ih, const int32_t *__res
   }
   if (LISTS) {
     int *s_loff = s_row + kIHCap, *s_lst = s_loff + kIHCap + 1;
-    __shared__ int s_cnt[kIHCap], s_fill[kIHCap];
-    if (tid < kIHCap) { s_cnt[tid] = 0; s_fill[tid] = 0; }
+    // a list holds its references in (point, t) order, not in the order the LDS atomics land in (which varies from run to
+    // run): each slot's references are a bitmap over q = point * 3 + t, and an entry's place is the number of bits below it
+    constexpr int kQW = 3 * kIHP / 32;
+    __shared__ int s_cnt[kIHCap];
+    __shared__ unsigned s_ref[kIHCap * kQW];
+    for (int i = tid; i < kIHCap * kQW; i += kIHT) s_ref[i] = 0u;
+    if (tid < kIHCap) s_cnt[tid] = 0;
     __syncthreads();
     int sl3[3] = {-1, -1, -1};
     if (tid < kIHP && s_orig[tid] >= 0) {
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         sl3[t] = s_slot[tid * 4 + t];
-        if (sl3[t] >= 0) atomicAdd(&s_cnt[sl3[t]], 1);
+        if (sl3[t] >= 0) {
+          const int q = tid * 3 + t;
+          atomicAdd(&s_cnt[sl3[t]], 1);
+          atomicOr(&s_ref[sl3[t] * kQW + (q >> 5)], 1u << (q & 31));
+        }
       }
     }
     __syncthreads();
@@ -985,7 +994,13 @@ __device__ __forceinline__ void ih_build_table(float *s_ih, const int32_t *__res
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < 3; ++t)
-      if (sl3[t] >= 0) s_lst[s_loff[sl3[t]] + atomicAdd(&s_fill[sl3[t]], 1)] = tid * 4 + t;
+      if (sl3[t] >= 0) {
+        const int q = tid * 3 + t;
+        const unsigned *row = s_ref + sl3[t] * kQW;
+        int r = __popc(row[q >> 5] & ((1u << (q & 31)) - 1u));
+        for (int w = 0; w < (q >> 5); ++w) r += __popc(row[w]);
+        s_lst[s_loff[sl3[t]] + r] = tid * 4 + t;
+      }
     __syncthreads();
   }
   __syncthreads();
@@ -1009,6 +1024,10 @@ __global__ __launch_bounds__(kIHT) void walk_plan_kernel(const int32_t *__restri
                                                          int *__restrict__ plan) {
   __shared__ __attribute__((aligned(16))) float s_tab[kIHPlan];
   const int bi = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+  // the table leaves parts unwritten (slot lists past their total, rows past the slot count, each point's 4th slot, the
+  // padding): zeroed, the plan is a function of its inputs alone and the walk's reads past a run's end (s_lst entries of
+  // a chunk's idle lanes -> s_w / s_inv) stay on entry 0.  (ih_build_table's first barrier orders these stores.)
+  for (int e = tid; e < kIHPlan; e += kIHT) reinterpret_cast<int *>(s_tab)[e] = 0;
   ih_build_table<true>(s_tab, idx, dist, order, bi, blk, n, m);
   int4 *dst = reinterpret_cast<int4 *>(plan) + (size_t)(bi * nblk + blk) * (kIHPlan / 4);
   for (int e = tid; e < kIHPlan / 4; e += kIHT) dst[e] = reinterpret_cast<const int4 *>(s_tab)[e];

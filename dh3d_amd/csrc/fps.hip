@@ -573,26 +573,36 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
   }
 }
 
+// The workgroup asks for the WHOLE CU's LDS whatever it needs: this kernel is the step's latency chain (one CU per
+// cloud, every instruction of the judge's chain counts), and a workgroup of another kernel that lands beside it takes
+// issue slots from its sixteen waves.  Same box, steps in flight: local 30.85 k -> 31.17 k clouds/s, one step at a time
+// 0.5053 -> 0.5021 ms (the CUs it keeps to itself were 3 % of the chip per step anyway).
+constexpr size_t kFpsListLds = (size_t)159 * 1024;
+
+// LDS bytes of one fps_list_kernel workgroup -- the one place this is counted (fps_list_launch, dh3d_fps_sorted_fits).
+// Always: picks [32] float4, pool [64] float2, bounds [16], npick [4], the picks' output [m].  TABLE: + the by-original-index
+// coordinate table [3][N].  ORDERED (TABLE only): + picks per sorted position [N + 1] u32, original index -> position
+// [N] u16 (padded to a whole u32), boxes [ceil(m / 64)][6] u32.
+size_t fps_list_lds_bytes(int N, int m, bool table, bool ordered) {
+  const size_t n = (size_t)N, k = (size_t)m;
+  size_t bytes = sizeof(float) * (4 * 32 + 2 * 64 + 16 + 4 + k);
+  if (table) bytes += sizeof(float) * 3 * n;
+  if (ordered)
+    bytes += sizeof(unsigned) * (n + 1) + sizeof(unsigned short) * ((n + 1) & ~(size_t)1) + sizeof(unsigned) * 6 * ((k + 63) / 64);
+  return bytes;
+}
+
 template <int PPT, int WAVES>
 int fps_list_launch(const float *sorted, const float *gbox, int B, int N, int m, int32_t *out, float *xyz_out,
                     const float *xyz, const FpsOrderedOut &oo, hipStream_t s) {
-  const size_t small = sizeof(float) * (4 * 32 + 2 * 64 + 16 + 4 + (size_t)m);
-  // (ordered output: picks per sorted position [N + 1] u32, original index -> position [N] u16, boxes [m / 64][6] u32)
-  const size_t ordered = oo.sorted_s ? sizeof(unsigned) * ((size_t)N + 1) + sizeof(unsigned short) * (((size_t)N + 1) & ~(size_t)1) +
-                                           sizeof(unsigned) * 6 * (((size_t)m + 63) / 64) : 0;
-  const size_t lds = small + sizeof(float) * (size_t)3 * N + ordered;
-  // The workgroup asks for the WHOLE CU's LDS whatever it needs: this kernel is the step's latency chain (one CU per
-  // cloud, every instruction of the judge's chain counts), and a workgroup of another kernel that lands beside it takes
-  // issue slots from its sixteen waves.  Same box, steps in flight: local 30.85 k -> 31.17 k clouds/s, one step at a time
-  // 0.5053 -> 0.5021 ms (the CUs it keeps to itself were 3 % of the chip per step anyway).
-  const size_t whole_cu = (size_t)159 * 1024;
-  if (lds <= whole_cu) {
+  const size_t whole_cu = kFpsListLds;
+  if (fps_list_lds_bytes(N, m, true, oo.sorted_s != nullptr) <= whole_cu) {
     DH3D_ALLOW_BIG_LDS((fps_list_kernel<PPT, WAVES, true>));
     hipLaunchKernelGGL((fps_list_kernel<PPT, WAVES, true>), dim3(B), dim3(64 * WAVES), whole_cu, s,
                        reinterpret_cast<const float4 *>(sorted), gbox, N, m, out, xyz_out, nullptr, oo);
   } else {
     if (oo.sorted_s) return DH3D_ERR_UNSUPPORTED;  // the ordered output lives beside the LDS coordinate table
-    if (!xyz || small > whole_cu) return DH3D_ERR_UNSUPPORTED;  // no LDS table: the cloud itself is needed
+    if (!xyz || fps_list_lds_bytes(N, m, false, false) > whole_cu) return DH3D_ERR_UNSUPPORTED;  // no LDS table: the cloud itself is needed
     DH3D_ALLOW_BIG_LDS((fps_list_kernel<PPT, WAVES, false>));
     hipLaunchKernelGGL((fps_list_kernel<PPT, WAVES, false>), dim3(B), dim3(64 * WAVES), whole_cu, s,
                        reinterpret_cast<const float4 *>(sorted), gbox, N, m, out, xyz_out, xyz, oo);
@@ -691,11 +701,20 @@ DH3D_API int dh3d_farthest_point_sample(int B, int N, int m, const float *inp, f
   return fps_launch<32, 8>(inp, B, N, m, out, s);
 }
 
+// Would dh3d_fps_sorted* take (N, m)?  ordered: dh3d_fps_sorted_ordered (with_cloud does not apply); else with_cloud:
+// dh3d_fps_sorted_cloud, without: dh3d_fps_sorted / dh3d_fps_sorted_xyz.  Shapes and LDS bytes only (fps_list_lds_bytes
+// against the kernel's whole-CU budget), no GPU involved.
+DH3D_API int dh3d_fps_sorted_fits(int N, int m, int ordered, int with_cloud) {
+  if (N <= 0 || m <= 0) return 0;
+  if (ordered) return N <= 8192 && fps_list_lds_bytes(N, m, true, true) <= kFpsListLds;
+  if (N <= 12288 && fps_list_lds_bytes(N, m, true, false) <= kFpsListLds) return 1;  // the LDS coordinate table
+  return with_cloud && N <= 16384 && fps_list_lds_bytes(N, m, false, false) <= kFpsListLds;  // winners read from the cloud
+}
+
 static int fps_sorted_dispatch(const float *sorted, const float *gbox, int B, int N, int m, int32_t *out,
                                float *xyz_out, const float *xyz, void *stream, const FpsOrderedOut &oo = FpsOrderedOut{}) {
   DH3D_REQUIRE(sorted && gbox && out && B > 0 && N > 0 && m > 0);
-  // the by-original-index coordinate table must fit LDS (12 B / point) unless the cloud itself is given
-  DH3D_SUPPORTED(N <= 12288 || (xyz && N <= 16384));
+  DH3D_SUPPORTED(dh3d_fps_sorted_fits(N, m, oo.sorted_s != nullptr, xyz != nullptr));
   hipStream_t s = (hipStream_t)stream;
   const int gpw = ((N + 63) / 64 + 15) / 16;  // groups per wave, 16 waves per cloud
   if (gpw <= 1) return fps_list_launch<1, 16>(sorted, gbox, B, N, m, out, xyz_out, xyz, oo, s);
@@ -730,8 +749,9 @@ DH3D_API int dh3d_fps_sorted_cloud(const float *sorted, const float *gbox, const
 // bits(pick rank)), gbox_s [B, ceil(m / 64), 8], and -- when the cloud's cell table `cells` (dh3d_spatial_sort_cells) is
 // given -- cells_s [B, DH3D_CELL_INTS], the subset's table on the cloud's grid: what dh3d_spatial_sort_cells of xyz_out
 // would hand to dh3d_three_nn_sorted / dh3d_knn_grid (a valid order + boxes + table, not the identical arrays: the subset
-// inherits the cloud's grid and the cloud's order inside a cell).  N <= 8192 (the tail's tables live beside the LDS
-// coordinate table); larger clouds: DH3D_ERR_UNSUPPORTED, sort xyz_out instead.
+// inherits the cloud's grid and the cloud's order inside a cell).  N <= 8192 and the tail's tables must fit beside the LDS
+// coordinate table (at N = 8192: m <= 3257; dh3d_fps_sorted_fits(N, m, 1, 0)); otherwise DH3D_ERR_UNSUPPORTED: sample
+// with dh3d_fps_sorted_xyz and sort xyz_out instead.
 DH3D_API int dh3d_fps_sorted_ordered(const float *sorted, const float *gbox, const int32_t *cells, int B, int N, int m,
                                      int32_t *out, float *xyz_out, float *sorted_s, float *gbox_s, int32_t *cells_s,
                                      void *stream) {

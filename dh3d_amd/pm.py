@@ -78,7 +78,8 @@ def knn_sorted(srt, gbox, k):
 def fps_sorted(srt, gbox, npoint, with_xyz=False, xyz=None):
     """FPS from spatial_sort() output; same idx [B,npoint] (original indexing) as ops.farthest_point_sample.
     with_xyz: also the sampled coordinates [B,npoint,3], written by the same kernel.
-    xyz: the cloud the records came from -- required above 12288 points (no room for the LDS coordinate table)."""
+    xyz: the cloud the records came from -- required where the LDS coordinate table does not fit (above 12288 points, or
+    fps_sorted_fits(N, npoint) false)."""
     B, N, _ = srt.shape
     out = torch.empty((B, npoint), dtype=torch.int32, device=srt.device)
     xyz_s = torch.empty((B, npoint, 3), dtype=torch.float32, device=srt.device) if with_xyz else None
@@ -95,11 +96,17 @@ def fps_sorted(srt, gbox, npoint, with_xyz=False, xyz=None):
     return (out, xyz_s) if with_xyz else out
 
 
+def fps_sorted_fits(N, npoint, ordered=False, with_cloud=False):
+    """Does the sorted FPS kernel take N points -> npoint picks?  ordered: fps_sorted_ordered; with_cloud: fps_sorted(xyz=);
+    neither: fps_sorted without the cloud (the LDS coordinate table).  Host-side query of the launcher's LDS budget."""
+    return L.lib().dh3d_fps_sorted_fits(int(N), int(npoint), int(bool(ordered)), int(bool(with_cloud))) == 1
+
+
 def fps_sorted_ordered(srt, gbox, npoint, cells=None):
     """fps_sorted(with_xyz=True) + the sampled set in the cloud's Morton order out of the same launch: returns
     (idx [B,m], xyz_s [B,m,3], srt_s [B,m,4], gbox_s [B,ceil(m/64),8], cells_s [B,CELL_INTS] or None) -- srt_s / gbox_s /
     cells_s are what spatial_sort_cells(xyz_s) would hand to three_nn_sorted / knn_grid (cells_s only when the cloud's
-    own table `cells` is given).  N <= 8192."""
+    own table `cells` is given).  N <= 8192 and fps_sorted_fits(N, npoint, ordered=True)."""
     B, N, _ = srt.shape
     dev = srt.device
     out = torch.empty((B, npoint), dtype=torch.int32, device=dev)

@@ -281,7 +281,9 @@ int dh3d_three_nn_sorted(int b, int n, int m, const float *sorted1, const float 
                          const float *gbox2, float *dist, int32_t *idx, void *stream);
 
 /* FarthestPointSample on an ordered cloud: identical outputs to dh3d_farthest_point_sample (original
- * indices); per round only the 64-point groups the new sample can affect are re-evaluated.  N <= 12288. */
+ * indices); per round only the 64-point groups the new sample can affect are re-evaluated.  N <= 12288, and the
+ * by-index coordinate table plus the picks must fit one CU's LDS: 1104 + 4m + 12N <= 162816 bytes (at N = 12288:
+ * m <= 3564).  Shapes beyond: DH3D_ERR_UNSUPPORTED (dh3d_fps_sorted_cloud takes them). */
 int dh3d_fps_sorted(const float *sorted, const float *gbox, int B, int N, int m, int32_t *out, void *stream);
 /* the same + xyz_out [B,m,3] = the sampled coordinates (group_point of the cloud by `out`, core/tf_utils.py:92-95) */
 int dh3d_fps_sorted_xyz(const float *sorted, const float *gbox, int B, int N, int m, int32_t *out, float *xyz_out,
@@ -291,13 +293,20 @@ int dh3d_fps_sorted_xyz(const float *sorted, const float *gbox, int B, int N, in
  * NULL) -- cells_s [B, DH3D_CELL_INTS]: the subset's cell table on the CLOUD's grid (same origin / scales / schedule header,
  * its own crowded verdict).  The picks are a subset of a sorted cloud, so a stable compaction of the picked positions is their
  * spatial order: these are valid inputs for dh3d_three_nn_sorted (candidate side) and dh3d_knn_grid / dh3d_knn_sorted on
- * the sampled set, without dh3d_spatial_sort_cells(xyz_out) on the chain behind the sampling.  N <= 8192. */
+ * the sampled set, without dh3d_spatial_sort_cells(xyz_out) on the chain behind the sampling.  N <= 8192, and the
+ * ordering's tables go beside the coordinate table: + 4(N+1) + 2((N+1) & ~1) + 24 ceil(m/64) bytes (at N = 8192: m <= 3257;
+ * at dilate 2, m = N/2: N <= 8009).  Shapes beyond: DH3D_ERR_UNSUPPORTED. */
 int dh3d_fps_sorted_ordered(const float *sorted, const float *gbox, const int32_t *cells, int B, int N, int m, int32_t *out,
                             float *xyz_out, float *sorted_s, float *gbox_s, int32_t *cells_s, void *stream);
 /* Same with the cloud itself (xyz [B,N,3], what dh3d_spatial_sort was given): clouds of up to 16384 points (above
  * 12288 the by-index coordinate table no longer fits the LDS and the kernel reads winners from xyz).  xyz_out may be NULL. */
 int dh3d_fps_sorted_cloud(const float *sorted, const float *gbox, const float *xyz, int B, int N, int m, int32_t *out,
                           float *xyz_out, void *stream);
+/* 1 if the dh3d_fps_sorted* entry point selected by (ordered, with_cloud) takes N points -> m picks, else 0 (it would
+ * return DH3D_ERR_UNSUPPORTED).  ordered != 0: dh3d_fps_sorted_ordered (with_cloud ignored); with_cloud != 0:
+ * dh3d_fps_sorted_cloud; else dh3d_fps_sorted / dh3d_fps_sorted_xyz.  The same LDS byte count the launcher checks;
+ * host only, no GPU needed. */
+int dh3d_fps_sorted_fits(int N, int m, int ordered, int with_cloud);
 
 /* flex_conv forward (same function as dh3d_flex_conv_fwd, Dp = 3) in the factorised form
  *   out[n,:] = [S0 | Sx | Sy | Sz][n,:] @ [bias; theta_x; theta_y; theta_z],

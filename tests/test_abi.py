@@ -45,6 +45,31 @@ def test_invalid_arguments_are_status_codes_not_crashes():
     assert lib.dh3d_netvlad_workspace_bytes(4, 1024, 256, 64) > 0
 
 
+def test_fps_sorted_fits_is_the_launchers_lds_budget():
+    """dh3d_fps_sorted_fits (host only): the shapes the sorted FPS launcher takes, from the same LDS byte count it checks
+    (1104 + 4m + 12N bytes, + 4(N+1) + 2((N+1) & ~1) + 24 ceil(m/64) for the ordered output, against 159 KB)."""
+    from dh3d_amd import pm
+    fits = pm.fps_sorted_fits
+    # the shipped levels: 8 x 8192 / 8 and 32 x 4096 / 8 on the ordered kernel, cfg 5's 16384 / 8 on the cloud
+    assert fits(8192, 1024, ordered=True) and fits(4096, 512, ordered=True)
+    assert fits(16384, 2048, with_cloud=True) and not fits(16384, 2048)
+    # the ordered output at N = 8192: m <= 3257 (dilate 2, m = 4096, needs 166484 B)
+    assert fits(8192, 3257, ordered=True) and not fits(8192, 3258, ordered=True)
+    assert not fits(8192, 4096, ordered=True) and fits(8192, 4096)
+    assert fits(8009, 4004, ordered=True) and not fits(8010, 4005, ordered=True)
+    assert not fits(8193, 16, ordered=True)  # the ordered kernel's N limit, whatever m
+    # the coordinate table at N = 12288: m <= 3564; beyond it (or N > 12288) only with the cloud
+    assert fits(12288, 3564) and not fits(12288, 3565)
+    assert not fits(12288, 4096) and fits(12288, 4096, with_cloud=True)
+    assert not fits(12289, 16) and fits(12289, 16, with_cloud=True) and not fits(16385, 16, with_cloud=True)
+    assert not fits(0, 16) and not fits(4096, 0)
+    # monotone in m: once a shape does not fit, no larger sample fits
+    for N in (4096, 6000, 8009, 8192, 11551, 12288, 16384):
+        for ordered, cloud in ((True, False), (False, False), (False, True)):
+            row = [fits(N, m, ordered=ordered, with_cloud=cloud) for m in range(1, N + 1, 7)]
+            assert row == sorted(row, reverse=True), (N, ordered, cloud)
+
+
 def test_library_was_built_from_this_tree():
     """The loaded library carries the hash of the sources it was compiled from (csrc/Makefile SRC_HASH -> dh3d_source_hash):
     a stale .so that travelled with the tree (built artefacts are git-ignored, not gpurun-ignored) fails here."""

@@ -716,6 +716,16 @@ def test_global_tail_equals_upsample_attention_netvlad(dev, B, n, clustered):
                                     s1, h1, Wg, s2, h2, l2_eps=1e-8, want_att=True, plan=plan)
     assert torch.equal(att_p, att)                       # no atomics on the attention path: bit-equal
     assert float((planned - got).abs().max()) <= 1e-6 * float(got.abs().max())
+    # the plan is a function of its inputs alone: rebuilt after unrelated LDS-heavy launches it is the same bytes (no
+    # entry may come from whatever the workgroup's LDS held before), and the walk gives the same result on either
+    srt_c, gbox_c, cells_c = pm.spatial_sort_cells(fine)
+    pm.knn_grid(srt_c, gbox_c, cells_c, 8)
+    pm.fps_sorted(srt_c, gbox_c, m)
+    plan2 = pm.walk_plan(i3, d3, srt, m)
+    assert torch.equal(plan2, plan)
+    planned2 = pm.global_tail(coarse, i3, d3, srt, slices, Hd, wfc, 0.2, (b, sc, sh, pm.ACT_RELU), wc, cs, ch, W2, Wh, s1, h1,
+                              Wg, s2, h2, l2_eps=1e-8, plan=plan2)
+    assert float((planned2 - planned).abs().max()) <= 1e-6 * float(got.abs().max())
     with pytest.raises(ValueError):
         pm.global_tail(coarse, i3, d3, srt, slices, Hd, wfc, 0.2, (b, sc, sh, pm.ACT_RELU), wc, cs, ch, W2, Wh, s1, h1, Wg, s2,
                        h2, plan=plan[:-4])
