@@ -1476,35 +1476,59 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   }
 }
 
+#ifndef DH3D_GRID_LANES
+#define DH3D_GRID_LANES 4
+#endif
+constexpr int kGridLanes = DH3D_GRID_LANES;  // per query
+
+// The launch plan of dh3d_knn_grid -- the one place its thresholds live (dh3d_knn_grid, dh3d_knn_grid_plan).
+//   sf: how a crowded cloud is served.  4 / 2 = the pruned scan inside knn_grid_kernel<4, sf> (one launch); 0 =
+//       knn_grid_kernel<kGridLanes, 0> for the uniform clouds, then knn_sorted_launch gated on the crowded flag.
+//   drop: D, the grid bits dropped for small sets (2^D consecutive cells of the table searched as one).
+struct KnnGridPlan {
+  int sf, drop;
+};
+static KnnGridPlan knn_grid_plan(int B, int N) {
+  KnnGridPlan p{0, 0};
+  // one to two points per cell: all 4096 cells down to 4096 points (measured: 32 x 4096 77 us against 83 with half the
+  // cells), one bit of the cell code less for every halving below that
+  while (p.drop < 6 && ((long long)N << p.drop) <= 3072) ++p.drop;
+#ifdef DH3D_GRID_DROP_BIAS
+  p.drop = p.drop + (DH3D_GRID_DROP_BIAS) < 0 ? 0 : p.drop + (DH3D_GRID_DROP_BIAS);
+#endif
+  // The clouds whose points crowd into few cells (the sort's verdict, cells[kCellFlag]) go to the pruned scan -- in the SAME
+  // launch (four waves per query group = the cell lists' 256-thread workgroup) up to 4096 query groups, as a second launch
+  // (whose workgroups leave at once for the other clouds) for the one-wave scan beyond that.
+  // (four waves per query group up to 1280 groups, as the scan on its own; beyond that two groups per workgroup with two
+  // waves each -- ONE two-wave group per 256-thread workgroup left half its waves unused while it held its LDS: 139.8 us;
+  // 32 x 4096 demo clouds: 97.7 us against 117.9)
+  const long long groups = (long long)((N + 63) / 64) * B;
+  if (kGridLanes == 4 && groups <= 4096) p.sf = groups > 1280 ? 2 : 4;
+  return p;
+}
+
+DH3D_API int dh3d_knn_grid_plan(int B, int N, int K) {
+  if (B <= 0 || N <= 0 || K <= 0 || K > 8 || N > 16384 || B > 65535) return -1;
+  const KnnGridPlan p = knn_grid_plan(B, N);
+  return p.sf + 16 * p.drop;
+}
+
 DH3D_API int dh3d_knn_grid(const float *sorted, const float *gbox, const int32_t *cells, int B, int N, int K, int32_t *nn,
                            float *dist, void *stream) {
   DH3D_REQUIRE(sorted && gbox && cells && nn && dist && B > 0 && N > 0 && K > 0);
   DH3D_SUPPORTED(K <= 8 && N <= 16384 && B <= 65535);
   const KnnLadder lad = knn_ladder(N);
-#ifndef DH3D_GRID_LANES
-#define DH3D_GRID_LANES 4
-#endif
-  constexpr int kLanes = DH3D_GRID_LANES;  // per query
-  // one to two points per cell: all 4096 cells down to 4096 points (measured: 32 x 4096 77 us against 83 with half the
-  // cells), one bit of the cell code less for every halving below that
-  int D = 0;
-  while (D < 6 && ((long long)N << D) <= 3072) ++D;
-#ifdef DH3D_GRID_DROP_BIAS
-  D = D + (DH3D_GRID_DROP_BIAS) < 0 ? 0 : D + (DH3D_GRID_DROP_BIAS);
-#endif
-  // The clouds whose points crowd into few cells (the sort's verdict, cells[kCellFlag]) go to the pruned scan -- in the SAME
-  // launch (four waves per query group = the cell lists' 256-thread workgroup) up to 4096 query groups, as a second launch
-  // (whose workgroups leave at once for the other clouds) for the one-wave scan beyond that
-  const long long groups = (long long)((N + 63) / 64) * B;
+  constexpr int kLanes = kGridLanes;
+  const KnnGridPlan plan = knn_grid_plan(B, N);
+  const int D = plan.drop;
   const dim3 grid(dh3d_cdiv(N, 256 / kLanes), B);
   const float4 *so = reinterpret_cast<const float4 *>(sorted);
-  if (kLanes == 4 && groups <= 4096) {
-    // (four waves per query group up to 1280 groups, as the scan on its own; beyond that two groups per workgroup with two
-    // waves each -- ONE two-wave group per 256-thread workgroup left half its waves unused while it held its LDS: 139.8 us)
-    if (groups > 1280)   // many query groups: two groups per workgroup, two waves each (32 x 4096 demo clouds: 97.7 us against 117.9)
-      hipLaunchKernelGGL((knn_grid_kernel<4, 2>), grid, dim3(256), 0, (hipStream_t)stream, so, gbox, cells, N, K, D, lad, nn, dist);
-    else
-      hipLaunchKernelGGL((knn_grid_kernel<4, 4>), grid, dim3(256), 0, (hipStream_t)stream, so, gbox, cells, N, K, D, lad, nn, dist);
+  if (plan.sf == 2) {
+    hipLaunchKernelGGL((knn_grid_kernel<4, 2>), grid, dim3(256), 0, (hipStream_t)stream, so, gbox, cells, N, K, D, lad, nn, dist);
+    return dh3d_launch_status();
+  }
+  if (plan.sf == 4) {
+    hipLaunchKernelGGL((knn_grid_kernel<4, 4>), grid, dim3(256), 0, (hipStream_t)stream, so, gbox, cells, N, K, D, lad, nn, dist);
     return dh3d_launch_status();
   }
   hipLaunchKernelGGL((knn_grid_kernel<kLanes, 0>), grid, dim3(256), 0, (hipStream_t)stream, so, gbox, cells, N, K, D, lad, nn, dist);

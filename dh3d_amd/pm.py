@@ -55,14 +55,30 @@ def spatial_sort_cells(xyz):
     return srt, gbox, cells
 
 
-def knn_grid(srt, gbox, cells, k):
+def knn_grid(srt, gbox, cells, k, out=None):
     """kNN by cell lists on the three outputs of spatial_sort_cells(); same (nbr [B,N,K], dist) as knn_xyz bit for bit.
-    K <= 8."""
+    K <= 8.  out: optional (nn int32 [B,N,K], dist float32 [B,N,K]), contiguous on the device, to write into."""
     B, N, _ = srt.shape
-    nn = torch.empty((B, N, k), dtype=torch.int32, device=srt.device)
-    dist = torch.empty((B, N, k), dtype=torch.float32, device=srt.device)
+    if out is None:
+        nn = torch.empty((B, N, k), dtype=torch.int32, device=srt.device)
+        dist = torch.empty((B, N, k), dtype=torch.float32, device=srt.device)
+    else:
+        nn, dist = out
+        for t, dt, name in ((nn, torch.int32, "nn"), (dist, torch.float32, "dist")):
+            if tuple(t.shape) != (B, N, k) or t.dtype != dt or t.device != srt.device or not t.is_contiguous():
+                raise ValueError("knn_grid: out %s must be contiguous %s [%d, %d, %d] on %s, got %s %s on %s"
+                                 % (name, dt, B, N, k, srt.device, t.dtype, tuple(t.shape), t.device))
     L.check(L.lib().dh3d_knn_grid(L.ptr(srt), L.ptr(gbox), L.ptr(cells), B, N, k, L.ptr(nn), L.ptr(dist), L.stream_ptr()), "knn_grid")
     return nn, dist
+
+
+def knn_grid_plan(B, N, k):
+    """The launch plan knn_grid makes for B clouds of N points and K neighbours (host only): (code, D).  code 4 / 2: the
+    crowded clouds' pruned scan runs inside knn_grid_kernel<4, code> (G = B * ceil(N / 64) <= 1280 / <= 4096); 0: the cell
+    lists, then the knn_sorted kernel gated on the crowded flag in a second launch.  D: grid bits dropped for small sets.
+    None where knn_grid refuses the shape."""
+    r = L.lib().dh3d_knn_grid_plan(int(B), int(N), int(k))
+    return None if r < 0 else (r % 16, r // 16)
 
 
 def knn_sorted(srt, gbox, k):

@@ -270,6 +270,14 @@ int dh3d_spatial_sort_cells(const float *xyz, int B, int N, float *sorted, float
  * kernels instead, from the same launch sequence (same results either way). */
 int dh3d_knn_grid(const float *sorted, const float *gbox, const int32_t *cells, int B, int N, int K, int32_t *nn, float *dist,
                   void *stream);
+/* The launch plan dh3d_knn_grid makes for (B, N, K), from the same function the launcher uses; host only, no GPU needed.
+ * Returns sf + 16 * D, or -1 where dh3d_knn_grid would refuse the shape (K > 8, N > 16384, ...).  G = B * ceil(N / 64)
+ * query groups decide sf, i.e. how a cloud flagged as crowded is served:
+ *   4: G <= 1280, one launch: the pruned scan inside the cell-list kernel, four waves per query group;
+ *   2: G <= 4096, one launch: the same with two query groups per 256-thread workgroup, two waves each;
+ *   0: beyond, two launches: the cell lists for the uniform clouds, then dh3d_knn_sorted's kernel gated on cells[4106].
+ * D (0..6): the grid bits dropped for small sets -- 2^D consecutive cells of the table are searched as one. */
+int dh3d_knn_grid_plan(int B, int N, int K);
 
 
 /* ThreeNN on ordered clouds: identical dist / idx to dh3d_three_nn (original indexing on both sides) from the

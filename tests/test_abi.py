@@ -70,6 +70,25 @@ def test_fps_sorted_fits_is_the_launchers_lds_budget():
             assert row == sorted(row, reverse=True), (N, ordered, cloud)
 
 
+def test_knn_grid_plan_is_the_launchers_choice():
+    """dh3d_knn_grid_plan (host only): the launch dh3d_knn_grid makes, by G = B * ceil(N / 64) query groups -- the pruned
+    scan for crowded clouds inside knn_grid_kernel<4, 4> up to G = 1280, <4, 2> up to 4096, a second gated launch
+    beyond -- and the grid drop D (one bit less per halving of N below 4096 points, down to 2^-6)."""
+    from dh3d_amd import pm
+    plan = pm.knn_grid_plan
+    assert plan(6, 8192, 8) == (4, 0) and plan(20, 4096, 8) == (4, 0)         # G 768, 1280
+    assert plan(21, 3904, 8) == (2, 0) and plan(32, 4096, 8) == (2, 0)        # G 1281, 2048 (the shipped global batch)
+    assert plan(64, 4096, 1) == (2, 0) and plan(241, 1088, 8) == (0, 2)       # G 4096, 4097
+    assert plan(300, 1000, 3) == (0, 2) and plan(1, 16384, 8) == (4, 0)
+    assert [plan(1, n, 8)[1] for n in (3073, 3072, 1536, 1537, 768, 384, 96, 48, 1)] == [0, 1, 2, 1, 3, 4, 6, 6, 6]
+    assert plan(1, 16385, 8) is None and plan(1, 4096, 9) is None and plan(1, 4096, 0) is None
+    assert plan(0, 4096, 8) is None and plan(65536, 64, 8) is None and plan(65535, 64, 8) == (0, 6)
+    # monotone in G: more query groups never go back to a plan with more waves per group
+    for N in (64, 1000, 3904, 4031, 4096, 8000, 16384):
+        codes = [plan(B, N, 8)[0] for B in range(1, 300)]
+        assert codes == sorted(codes, reverse=True), N
+
+
 def test_library_was_built_from_this_tree():
     """The loaded library carries the hash of the sources it was compiled from (csrc/Makefile SRC_HASH -> dh3d_source_hash):
     a stale .so that travelled with the tree (built artefacts are git-ignored, not gpurun-ignored) fails here."""
