@@ -217,6 +217,10 @@ _SIGNATURES = {
                                c_int, c_int, c_float, c_fp, c_size_t, c_fp, c_fp],
     "dh3d_netvlad_head_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_float, c_fp,
                               c_size_t, c_fp, c_fp],
+    "dh3d_keypoint_nms_workspace_bytes": [c_int, c_int, c_int],
+    "dh3d_keypoint_nms": [c_fp, c_ll, c_int, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_fp,
+                          c_fp, c_fp, c_size_t, c_fp],
+    "dh3d_gather_rows": [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_int, c_fp, c_fp],
 }
 _RESTYPES = {
     "dh3d_arch": ctypes.c_char_p,
@@ -231,6 +235,7 @@ _RESTYPES = {
     "dh3d_flex_conv_bwd_workspace_bytes": c_size_t,
     "dh3d_flex_pool_fwd_workspace_bytes": c_size_t,
     "dh3d_flex_conv_pm_bwd_workspace_bytes": c_size_t,
+    "dh3d_keypoint_nms_workspace_bytes": c_size_t,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1,0 +1,279 @@
+// Batched keypoint non-maximum suppression for gfx950 (localdesc_extract.py --perform_nms; core/utils.py:15-43) and the
+// row gather that fetches only the keypoints' rows.  Same ids, cloud by cloud, as dh3d_amd/utils.py:single_nms, which
+// runs the same rule one cloud at a time with host syncs.  Three launches per call, no atomics on global memory, no
+// memset, no host sync (graph-capturable):
+//   K1 nms_mute_kernel    one thread per point: a' = score (or 1 - score), muted to 0 when the 8th neighbour lies beyond
+//                         2.0; one maximum of a' per 256-point block (wave DPP reduction + LDS);
+//   K2 nms_keys_kernel    every block reduces its cloud's block maxima -> thr = max * ratio; one thread per point walks its
+//                         K neighbours: a point is kept iff no neighbour inside the radius beats rank 0 and a' > thr.  The
+//                         point's key is (ordered_bits(a') << 32) | i, or 0 when it is not kept;
+//   K3 nms_select_kernel  one 1024-lane workgroup per cloud: compact the non-zero keys (in place), radix-select the M-th
+//                         largest (8 passes of 8 bits over the survivors), bitonic-sort the <= M winners in LDS (keys are
+//                         unique -- the index sits in the low bits -- so the order is total), write count and ids.
+// Only comparisons, one f32 multiply and 1 - x: exact by construction (compiled without contraction, csrc/Makefile EXACT).
+#include "common.h"
+#include "wave_ops.h"
+
+namespace {
+
+constexpr int kPtThreads = 256;     // K1 / K2: points per block
+constexpr int kSelThreads = 1024;   // K3: one workgroup per cloud
+constexpr int kSelWaves = kSelThreads / 64;
+constexpr int kMaxKeep = 4096;      // M limit: the winners' sort buffer in LDS (32 KB)
+constexpr int kMaxK = 64;           // the kNN kernels' limit
+
+__device__ __forceinline__ int clamp_valid(const int32_t *num_valid, int b, int N) {
+  if (!num_valid) return N;
+  const int n = num_valid[b];
+  return n < 0 ? 0 : (n > N ? N : n);
+}
+
+// monotone map f32 -> u32 (total order of the finite floats; -0 is canonicalised before)
+__device__ __forceinline__ unsigned ordered_bits(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// max over a 256-lane block; every lane must call it (DPP reads all 64 lanes)
+__device__ __forceinline__ float block256_max(float v, float *s_red) {
+  const float w = wave_max_f32(v);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+}
+
+__global__ __launch_bounds__(kPtThreads) void nms_mute_kernel(const float *__restrict__ score, long long sstride, int invert,
+                                                              const float *__restrict__ dist, int K,
+                                                              const int32_t *__restrict__ num_valid, int N, int remove_noise,
+                                                              float *__restrict__ ap, float *__restrict__ bmax) {
+  __shared__ float s_red[kPtThreads / 64];
+  const int b = blockIdx.y, i = blockIdx.x * kPtThreads + threadIdx.x;
+  const int nb = clamp_valid(num_valid, b, N);
+  float m = -INFINITY;
+  if (i < N) {
+    const long long p = (long long)b * N + i;
+    float a = score[p * sstride];
+    if (invert) a = 1.f - a;
+    if (remove_noise && K > 7 && dist[p * K + 7] > 2.0f) a = 0.f;
+    if (a == 0.f) a = 0.f;  // -0.0 -> +0.0: the key order below must not tell them apart
+    ap[p] = a;
+    if (i < nb) m = a;
+  }
+  m = block256_max(m, s_red);
+  if (threadIdx.x == 0) bmax[(long long)b * gridDim.x + blockIdx.x] = m;
+}
+
+__global__ __launch_bounds__(kPtThreads) void nms_keys_kernel(const float *__restrict__ ap, const float *__restrict__ bmax,
+                                                              const int32_t *__restrict__ nn, const float *__restrict__ dist,
+                                                              int K, const int32_t *__restrict__ num_valid, int N, float radius,
+                                                              float ratio, unsigned long long *__restrict__ keys) {
+  __shared__ float s_red[kPtThreads / 64];
+  const int b = blockIdx.y, i = blockIdx.x * kPtThreads + threadIdx.x, nblk = gridDim.x;
+  const int nb = clamp_valid(num_valid, b, N);
+  float m = -INFINITY;
+  for (int j = threadIdx.x; j < nblk; j += kPtThreads) m = fmaxf(m, bmax[(long long)b * nblk + j]);
+  const float thr = block256_max(m, s_red) * ratio;  // f32(max a') * f32(ratio)
+  if (i >= N) return;
+  const long long p = (long long)b * N + i;
+  const float *cloud = ap + (long long)b * N;
+  unsigned long long key = 0;
+  const float a = ap[p];
+  if (i < nb && a > thr) {
+    const int32_t *row = nn + p * K;
+    const float *drow = dist + p * K;
+    // s[r] = a'[nn[r]] inside the ball (a real point), else 0; kept iff s[r] <= s[0] for every r >= 1 (first max wins)
+    const int j0 = row[0];
+    const float s0 = (drow[0] > radius || j0 < 0 || j0 >= nb) ? 0.f : cloud[j0];
+    bool is_max = true;
+    for (int r = 1; r < K && is_max; ++r) {
+      const int j = row[r];
+      const float s = (drow[r] > radius || j < 0 || j >= nb) ? 0.f : cloud[j];
+      is_max = !(s > s0);
+    }
+    if (is_max) key = ((unsigned long long)ordered_bits(a) << 32) | (unsigned)i;
+  }
+  keys[p] = key;
+}
+
+__device__ __forceinline__ unsigned long long lanes_below() {
+  const unsigned lane = threadIdx.x & 63;
+  return lane ? (~0ull >> (64 - lane)) : 0ull;
+}
+
+__global__ __launch_bounds__(kSelThreads) void nms_select_kernel(unsigned long long *__restrict__ keys, int N, int M,
+                                                                 int32_t *__restrict__ count, int32_t *__restrict__ inds) {
+  __shared__ unsigned long long s_win[kMaxKeep];
+  __shared__ int s_hist[256];
+  __shared__ int s_suf[256];
+  __shared__ int s_wave[kSelWaves];
+  __shared__ int s_bin, s_above, s_n;
+  const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+  unsigned long long *ck = keys + (long long)b * N;
+
+  // (1) compact the non-zero keys to the front, in place, in index order: every store of a chunk lands below the chunk's
+  //     end and the chunk was read before the barrier
+  int c = 0;
+  for (int base = 0; base < N; base += kSelThreads) {
+    const int i = base + tid;
+    const unsigned long long key = i < N ? ck[i] : 0ull;
+    const unsigned long long bal = __ballot(key != 0ull);
+    if ((tid & 63) == 0) s_wave[w] = __popcll(bal);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int q = 0; q < kSelWaves; ++q) {
+      const int v = s_wave[q];
+      off += q < w ? v : 0;
+      tot += v;
+    }
+    if (key) ck[c + off + __popcll(bal & lanes_below())] = key;
+    c += tot;
+    __syncthreads();
+  }
+
+  // (2) the M-th largest key (MSB-first radix select); with c <= M every survivor is a winner
+  unsigned long long thr = 1ull;
+  if (c > M) {
+    unsigned long long prefix = 0ull, mask = 0ull;
+    int rem = M;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      if (tid < 256) s_hist[tid] = 0;
+      __syncthreads();
+      for (int base = 0; base < c; base += kSelThreads) {
+        const int j = base + tid;
+        const unsigned long long key = j < c ? ck[j] : 0ull;
+        const bool in = j < c && (key & mask) == prefix;
+        const int bin = (int)((key >> shift) & 255ull);
+        // a whole wave in one bin (the scores' top bits mostly agree): one LDS atomic instead of 64 on one address
+        const unsigned long long act = __ballot(in);
+        const int first = __shfl(bin, __builtin_ffsll((long long)act) - 1);  // the bin of the lowest lane in the subset
+        const unsigned long long same = __ballot(in && bin == first);
+        if (act && same == act) {
+          if (in && (same & lanes_below()) == 0ull) atomicAdd(&s_hist[first], __popcll(act));
+        } else if (in) {
+          atomicAdd(&s_hist[bin], 1);
+        }
+      }
+      __syncthreads();
+      if (tid < 256) s_suf[tid] = s_hist[tid];
+      __syncthreads();
+      for (int off = 1; off < 256; off <<= 1) {  // s_suf[t] = sum of s_hist[t..255]
+        const int v = (tid < 256 && tid + off < 256) ? s_suf[tid + off] : 0;
+        __syncthreads();
+        if (tid < 256) s_suf[tid] += v;
+        __syncthreads();
+      }
+      if (tid < 256) {
+        const int above = s_suf[tid] - s_hist[tid];
+        if (above < rem && rem <= s_suf[tid]) {  // exactly one bin: the one where the count from the top reaches rem
+          s_bin = tid;
+          s_above = above;
+        }
+      }
+      __syncthreads();
+      rem -= s_above;
+      prefix |= (unsigned long long)s_bin << shift;
+      mask |= 255ull << shift;
+      __syncthreads();
+    }
+    thr = prefix;  // the M-th largest key itself: exactly M keys are >= it
+  }
+  const int nw = c < M ? c : M;
+
+  // (3) the winners into LDS (any order), padded with zeros to a power of two, bitonic-sorted descending
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+  for (int base = 0; base < c; base += kSelThreads) {
+    const int j = base + tid;
+    const unsigned long long key = j < c ? ck[j] : 0ull;
+    const bool win = j < c && key >= thr;
+    const unsigned long long bal = __ballot(win);
+    int slot0 = 0;
+    if (bal && (tid & 63) == __builtin_ffsll((long long)bal) - 1) slot0 = atomicAdd(&s_n, __popcll(bal));
+    slot0 = __shfl(slot0, __builtin_ffsll((long long)bal) - 1);
+    const int slot = slot0 + __popcll(bal & lanes_below());
+    if (win && slot < nw) s_win[slot] = key;  // (exactly nw winners; the bound only guards the LDS buffer)
+  }
+  int P = 1;
+  while (P < nw) P <<= 1;
+  for (int j = nw + tid; j < P; j += kSelThreads) s_win[j] = 0ull;
+  __syncthreads();
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int jj = k >> 1; jj > 0; jj >>= 1) {
+      for (int x = tid; x < P; x += kSelThreads) {
+        const int y = x ^ jj;
+        if (y > x) {
+          const unsigned long long u = s_win[x], v = s_win[y];
+          const bool desc = (x & k) == 0;
+          if (desc ? (u < v) : (u > v)) {
+            s_win[x] = v;
+            s_win[y] = u;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int j = tid; j < M; j += kSelThreads)
+    inds[(long long)b * M + j] = j < nw ? (int32_t)(unsigned)(s_win[j] & 0xffffffffull) : -1;
+  if (tid == 0) count[b] = nw;
+}
+
+// dst[b, j, :] = src[b, inds[b, j], :] for j < count[b], zero rows after that (and for an id outside [0, N)); one wave
+// per row, 4-byte elements: any C (131 is not 16-byte aligned per row)
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restrict__ src, int N, int C,
+                                                          const int32_t *__restrict__ inds, const int32_t *__restrict__ count,
+                                                          int M, long long rows, float *__restrict__ dst) {
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const int b = (int)(r / M), j = (int)(r % M);
+  int id = j < count[b] ? inds[r] : -1;
+  if (id >= N) id = -1;
+  const float *s = src + ((long long)b * N + (id < 0 ? 0 : id)) * C;
+  float *d = dst + r * C;
+  for (int c = threadIdx.x & 63; c < C; c += 64) d[c] = id >= 0 ? s[c] : 0.f;
+}
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}  // namespace
+
+DH3D_API size_t dh3d_keypoint_nms_workspace_bytes(int B, int N, int M) {
+  if (B <= 0 || N <= 0 || M <= 0 || M > kMaxKeep) return 0;
+  const size_t nblk = (size_t)dh3d_cdiv(N, kPtThreads);
+  return align256((size_t)B * N * sizeof(float)) + align256((size_t)B * nblk * sizeof(float)) +
+         align256((size_t)B * N * sizeof(unsigned long long));
+}
+
+DH3D_API int dh3d_keypoint_nms(const float *score, long long score_stride, int invert, const int32_t *nn, const float *dist,
+                               const int32_t *num_valid, int B, int N, int K, float radius, float ratio, int M,
+                               int remove_noise, int32_t *count, int32_t *inds, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+  DH3D_REQUIRE(score && nn && dist && count && inds && workspace);
+  DH3D_REQUIRE(B > 0 && N > 0 && K > 0 && M > 0 && score_stride >= 1);
+  DH3D_SUPPORTED(M <= kMaxKeep && K <= kMaxK && B <= 65535);
+  const size_t need = dh3d_keypoint_nms_workspace_bytes(B, N, M);
+  DH3D_REQUIRE(workspace_bytes >= need);
+  const int nblk = dh3d_cdiv(N, kPtThreads);
+  char *ws = static_cast<char *>(workspace);
+  float *ap = reinterpret_cast<float *>(ws);
+  float *bmax = reinterpret_cast<float *>(ws + align256((size_t)B * N * sizeof(float)));
+  auto *keys = reinterpret_cast<unsigned long long *>(ws + align256((size_t)B * N * sizeof(float)) +
+                                                      align256((size_t)B * nblk * sizeof(float)));
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(nms_mute_kernel, dim3(nblk, B), dim3(kPtThreads), 0, s, score, score_stride, invert, dist, K,
+                     num_valid, N, remove_noise, ap, bmax);
+  hipLaunchKernelGGL(nms_keys_kernel, dim3(nblk, B), dim3(kPtThreads), 0, s, ap, bmax, nn, dist, K, num_valid, N, radius,
+                     ratio, keys);
+  hipLaunchKernelGGL(nms_select_kernel, dim3(B), dim3(kSelThreads), 0, s, keys, N, M, count, inds);
+  return dh3d_launch_status();
+}
+
+DH3D_API int dh3d_gather_rows(const float *src, int B, int N, int C, const int32_t *inds, const int32_t *count, int M,
+                              float *dst, void *stream) {
+  DH3D_REQUIRE(src && inds && count && dst);
+  DH3D_REQUIRE(B > 0 && N > 0 && C > 0 && M > 0);
+  const long long rows = (long long)B * M;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(dh3d_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, src, N, C, inds,
+                     count, M, rows, dst);
+  return dh3d_launch_status();
+}

@@ -36,7 +36,8 @@ class Pipeline:
     (`steps_in_flight` -> `Geometry.busy_cus_per_xcd` -> `reserve_cus_per_xcd`, a placement hint: speed only, the
     results do not depend on it -- tests/test_engine_gpu.py::test_flex_conv_x6_reserve_hint_vs_oracle)."""
 
-    def __init__(self, model, example_points, depth=2, outputs=None, example_knn=None, streams=None, warmup=2):
+    def __init__(self, model, example_points, depth=2, outputs=None, example_knn=None, streams=None, warmup=2,
+                 example_num_valid=None):
         if depth < 1:
             raise ValueError("depth must be >= 1")
         if streams is not None and len(streams) < depth:
@@ -48,7 +49,8 @@ class Pipeline:
         model.steps_in_flight = self.depth  # read by DH3D._geometry while the slots are captured
         try:
             with torch.no_grad():
-                self._runs = [model.graphed(example_points, example_knn, outputs=outputs, warmup=warmup if k == 0 else 1)
+                self._runs = [model.graphed(example_points, example_knn, outputs=outputs, warmup=warmup if k == 0 else 1,
+                                            example_num_valid=example_num_valid)
                               for k in range(self.depth)]
         finally:
             model.steps_in_flight = hint
@@ -78,12 +80,15 @@ class Pipeline:
     def knn_buffer(self, slot):
         return self._runs[slot].static_knn
 
+    def num_valid_buffer(self, slot):
+        return self._runs[slot].static_num_valid
+
     @property
     def next_slot(self):
         return self._seq % self.depth
 
     # ------------------------------------------------------------------ steps
-    def submit(self, points=None, knn_inds=None, after_current=None, fetch_to=None):
+    def submit(self, points=None, knn_inds=None, after_current=None, fetch_to=None, num_valid=None):
         """Enqueue one full forward on the next slot.  `points` (optional) is copied into the slot's input buffer on the
         slot's stream, after the caller's stream has reached this point (so a batch produced on the current stream is
         complete) and after the previous consumer of this slot's outputs (result()) is done with them.
@@ -101,25 +106,26 @@ class Pipeline:
         Zero-copy (no `points`): the batch must already be in `input_buffer(slot)`, written ON `stream(slot)` -- or on
         the current stream with `after_current=True`, which orders the slot's stream behind the current one first (an
         event record + wait per submit: measured 31.1 k -> 26.4 k clouds/s on the local workload four deep, which is why
-        it is not the default for the zero-copy path).  With DEVICE `points` given the order is always established."""
+        it is not the default for the zero-copy path).  With DEVICE `points` given the order is always established.
+        `num_valid` ([Bt] int32, pipelines built with example_num_valid): handed over like `knn_inds`."""
         if self.model.weights_version != self._version:
             raise RuntimeError("the model's weights changed (optimiser step / invalidate / load_state_dict) after this "
                                "pipeline was captured: build a new one")
         k = self._seq % self.depth
         run, st = self._runs[k], self._streams[k]
-        from_device = any(t is not None and t.is_cuda for t in (points, knn_inds))
+        from_device = any(t is not None and t.is_cuda for t in (points, knn_inds, num_valid))
         if after_current or (after_current is None and from_device):
             st.wait_stream(torch.cuda.current_stream(run.static_input.device))
         # the copies below run on the slot's stream: tell the caching allocator, or a caller that drops `points`
         # right after submit() may see its block handed out again (on ITS stream) before the copy has read it
-        for t in (points, knn_inds):
+        for t in (points, knn_inds, num_valid):
             if t is not None and t.is_cuda:
                 t.record_stream(st)
         if self._consumed[k] is not None:
             st.wait_event(self._consumed[k])
             self._consumed[k] = None
         with torch.cuda.stream(st):
-            outs = run(points, knn_inds)
+            outs = run(points, knn_inds, num_valid)
             if fetch_to:
                 from . import pm
                 for name, dst in fetch_to.items():

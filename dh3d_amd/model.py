@@ -446,17 +446,52 @@ class DH3D(nn.Module):
             att = self.globalatt(forglobal)
         return self._netvlad(forglobal, att, l2_eps=l2_eps)
 
+    # keypoint outputs (localdesc_extract.py --perform_nms): computed only when fetched by name, only with config.detection
+    KEYPOINT_OUTPUTS = ("kp_count", "kp_inds", "xyz_feat_att_nms")
     OUTPUT_NAMES = frozenset(("pointclouds", "xyz", "knn_inds", "feat", "xyz_feat", "feat_l2normed", "attention",
-                              "xyz_feat_att", "globaldesc", "fps_inds", "sampled_knn_inds", "nn3_inds"))
+                              "xyz_feat_att", "globaldesc", "fps_inds", "sampled_knn_inds", "nn3_inds") + KEYPOINT_OUTPUTS)
 
-    def forward(self, points, knn_inds=None, fetch=None):
+    def _keypoint_knn(self, geo, k):
+        """Enqueue the keypoint NMS's k-NN on the geometry side stream (beside the FPS chain, which leaves the chip mostly
+        idle), reusing the cloud's Morton records when the forward made them; returns (nn, dist, event) for the join."""
+        points, main = geo.xyz, torch.cuda.current_stream()
+        with torch.cuda.stream(geo._side):
+            if points.shape[1] <= 16384:
+                srt, gbox = geo.sorted if geo.sorted is not None else pm.spatial_sort(points)  # (no cache: main reads geo.sorted)
+                nn_k, d_k = pm.knn_sorted(srt, gbox, k)
+            else:
+                nn_k, d_k = pm.knn_xyz(points, k)
+            done = torch.cuda.Event()
+            done.record()
+            nn_k.record_stream(main)
+            d_k.record_stream(main)
+        return nn_k, d_k, done
+
+    def _keypoints(self, outs, xyz_feat_att, kp_knn, num_valid, fetch):
+        """--perform_nms on the device (localdesc_extract.py:85-102: single_nms(xyz, 1 - res[:, -1], nms_rad, nms_min_ratio,
+        nms_max_kp) per cloud): kp_count [Bt], kp_inds [Bt, M] (-1 padded) and -- fetched -- the keypoints' rows of
+        xyz_feat_att [Bt, M, 132] (zero rows past kp_count)."""
+        cfg = self.config
+        nn_k, d_k, done = kp_knn
+        torch.cuda.current_stream().wait_event(done)
+        count, inds = pm.keypoint_nms(xyz_feat_att[:, :, xyz_feat_att.shape[2] - 1], nn_k, d_k, cfg.get("nms_rad", 0.5),
+                                      cfg.get("nms_min_ratio", 0.01), cfg.get("nms_max_kp", 512), remove_noise=True,
+                                      num_valid=num_valid, invert=True)
+        outs["kp_count"], outs["kp_inds"] = count, inds
+        if "xyz_feat_att_nms" in fetch:
+            outs["xyz_feat_att_nms"] = pm.gather_rows(xyz_feat_att, inds, count)
+
+    def forward(self, points, knn_inds=None, fetch=None, num_valid=None):
         """points [Bt, N, 3] float32 on the GPU (anchor/pos/neg already concatenated, core/model.py:139-146).
         knn_inds [Bt, N, K] int32: optional precomputed neighbours (the reference requires them for
         num_points > 8192, core/model.py:148-155; here the device kNN serves every N: the Morton-pruned kernels up to
         16384 points, the brute-force kernel beyond).
         fetch: names of the outputs wanted (None = all).  Like a TF session fetch, tensors nobody asked for are not
         computed: the global-descriptor extraction (globaldesc_extract.py fetches 'globaldesc' only) skips the
-        normalised per-point descriptors and the detector."""
+        normalised per-point descriptors and the detector.
+        The keypoint outputs (kp_count, kp_inds, xyz_feat_att_nms; config.detection) are computed only when named in
+        `fetch`.  num_valid [Bt] int32 (optional, keypoints only): cloud b's real points are the first num_valid[b], the
+        rest is padding (utils.batched_nms)."""
         want = (lambda *names: True) if fetch is None else (lambda *names: any(n in fetch for n in names))
         if fetch is not None:
             unknown = sorted(set(fetch) - self.OUTPUT_NAMES)
@@ -466,6 +501,13 @@ class DH3D(nn.Module):
         cfg = self.config
         if points.dim() != 3 or points.shape[2] != 3:
             raise ValueError("points must be [Bt, N, 3]")
+        kp = fetch is not None and any(n in fetch for n in self.KEYPOINT_OUTPUTS)
+        if kp and not cfg.detection:
+            raise ValueError("the keypoint outputs %s need config.detection" % (self.KEYPOINT_OUTPUTS,))
+        if num_valid is not None and (num_valid.dim() != 1 or num_valid.shape[0] != points.shape[0]
+                                      or num_valid.dtype != torch.int32 or num_valid.device != points.device):
+            raise ValueError("num_valid must be int32 [Bt] on the device of points, got %s %s"
+                             % (tuple(num_valid.shape), num_valid.dtype))
         if knn_inds is not None:
             # the kernels never bounds-check neighbour ids (nor does the reference): do it here
             if (knn_inds.dim() != 3 or knn_inds.shape[0] != points.shape[0] or knn_inds.shape[1] != points.shape[1]
@@ -484,7 +526,8 @@ class DH3D(nn.Module):
                        and self.global_before_assemble.dilate == 8)
         geo = self._geometry(points, knn_inds, prezero_tail=prezero)
         outs["knn_inds"] = geo.nbr
-        needs_raw = want("feat", "attention", "xyz_feat_att", "globaldesc")
+        kp_knn = self._keypoint_knn(geo, min(50, points.shape[1])) if kp else None
+        needs_raw = want("feat", "attention", "xyz_feat_att", "globaldesc") or kp
         if fetch is not None and not needs_raw and want("xyz_feat", "feat_l2normed") and self._local.featdim == 128:
             # only the normalised descriptors are asked for: the last conv writes [xyz | l2_normalize(feat)] itself
             _, xyz_feat = self.compute_local(points, _geo=geo, _l2cat_eps=1e-8)
@@ -496,15 +539,17 @@ class DH3D(nn.Module):
         outs["feat"] = localdesc
         self._level_ids(geo, outs, fetch)
         xyz_feat = None
-        if want("xyz_feat", "feat_l2normed", "xyz_feat_att"):
+        if want("xyz_feat", "feat_l2normed", "xyz_feat_att") or kp:
             xyz_feat = pm.l2norm_concat(localdesc, 1e-8, prefix=newpoints)  # l2_normalize(dim=2, eps=1e-8) + concat
             outs["xyz_feat"] = xyz_feat
             outs["feat_l2normed"] = xyz_feat[:, :, 3:]
-        if cfg.detection and want("attention", "xyz_feat_att"):
+        if cfg.detection and (want("attention", "xyz_feat_att") or kp):
             att = self.detection_block_reliable(localdesc)
             outs["attention"] = att
             if xyz_feat is not None:
                 outs["xyz_feat_att"] = torch.cat([xyz_feat, att], dim=-1)
+            if kp:
+                self._keypoints(outs, outs["xyz_feat_att"], kp_knn, num_valid, fetch)
         if cfg.extract_global and want("globaldesc"):
             outs["_geo"] = geo
             outs["globaldesc"] = self.compute_global(outs, l2_eps=1e-8)  # model.py:205
@@ -523,38 +568,41 @@ class DH3D(nn.Module):
                 outs[name] = lv[key]
 
     # ------------------------------------------------------------------ hipGraph replay
-    def pipeline(self, example_points, depth=2, outputs=None, example_knn=None, streams=None):
+    def pipeline(self, example_points, depth=2, outputs=None, example_knn=None, streams=None, example_num_valid=None):
         """`depth` forwards in flight: one hipGraph instance + batch buffers + stream per slot (dh3d_amd/engine.py).
         Returns an engine.Pipeline: submit(batch) -> ticket, result(ticket) -> outputs, map(batches)."""
         from .engine import Pipeline
-        return Pipeline(self, example_points, depth=depth, outputs=outputs, example_knn=example_knn, streams=streams)
+        return Pipeline(self, example_points, depth=depth, outputs=outputs, example_knn=example_knn, streams=streams,
+                        example_num_valid=example_num_valid)
 
-    def graphed(self, example_points, example_knn=None, outputs=None, warmup=2):
+    def graphed(self, example_points, example_knn=None, outputs=None, warmup=2, example_num_valid=None):
         """Capture forward() for inputs shaped like `example_points` into a hipGraph.
 
         Returns a callable f(points[, knn_inds]) -> dict of output tensors (static buffers, overwritten by
         the next call).  Zero-copy hand-over: write the batch into `f.static_input` (`f.static_knn`) -- e.g. as the
         destination of the host-to-device copy -- and call f() / f(f.static_input); any other tensor is copied in
-        (a ~5 us kernel plus two dependency gaps per step)."""
+        (a ~5 us kernel plus two dependency gaps per step).  example_num_valid: the keypoint outputs' num_valid [Bt] is an
+        input of the graph too (f(points, num_valid=...), `f.static_num_valid`)."""
         self._check_mode()
         static_in = example_points.clone()
         static_knn = example_knn.clone() if example_knn is not None else None
+        static_nv = example_num_valid.clone() if example_num_valid is not None else None
         keep = outputs
         s = torch.cuda.Stream(device=example_points.device)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                self.forward(static_in, static_knn, fetch=keep)
+                self.forward(static_in, static_knn, fetch=keep, num_valid=static_nv)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            outs = self.forward(static_in, static_knn, fetch=keep)
+            outs = self.forward(static_in, static_knn, fetch=keep, num_valid=static_nv)
         if keep is not None:
             outs = {k: v for k, v in outs.items() if k in keep}
         version = self.weights_version
 
-        def run(points=None, knn_inds=None):
+        def run(points=None, knn_inds=None, num_valid=None):
             if self.weights_version != version:
                 raise RuntimeError("the model's weights changed (optimiser step / invalidate / load_state_dict) after this "
                                    "forward was captured: the graph holds packed copies of the old ones -- capture again")
@@ -564,6 +612,8 @@ class DH3D(nn.Module):
                 _copy_in(points, static_in)
             if static_knn is not None and knn_inds is not None and knn_inds is not static_knn:
                 _copy_in(knn_inds, static_knn)
+            if static_nv is not None and num_valid is not None and num_valid is not static_nv:
+                _copy_in(num_valid, static_nv)
             graph.replay()
             return outs
 
@@ -571,4 +621,5 @@ class DH3D(nn.Module):
         run.outputs = outs
         run.static_input = static_in
         run.static_knn = static_knn
+        run.static_num_valid = static_nv
         return run

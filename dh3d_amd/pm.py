@@ -91,6 +91,58 @@ def knn_sorted(srt, gbox, k):
     return nn, dist
 
 
+KEYPOINT_MAX = 4096  # include/dh3d_hip.h dh3d_keypoint_nms: M limit
+
+
+def keypoint_nms(scores, nn, dist, nms_radius, min_response_ratio, max_keypoints, remove_noise=True, num_valid=None,
+                 invert=False):
+    """Keypoint NMS of a batch (dh3d_keypoint_nms): scores [B,N] float32 (a strided view such as xyz_feat_att[:, :, 131] is
+    read in place), nn / dist [B,N,K] from knn_xyz / knn_sorted, num_valid [B] int32 or None, invert: the score is
+    1 - scores.  -> (count [B] int32, inds [B, max_keypoints] int32, -1 padded), on the device, no host sync."""
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or not scores.is_cuda or scores.dim() != 2:
+        raise ValueError("scores must be a float32 [B, N] tensor on the GPU")
+    B, N = scores.shape
+    if scores.stride(1) < 1 or scores.stride(0) != N * scores.stride(1):
+        scores = scores.contiguous()
+    nn = L.require_cuda_i32(nn, "nn", 3)
+    dist = L.require_cuda_f32(dist, "dist", 3)
+    K = nn.shape[2]
+    if tuple(nn.shape) != (B, N, K) or tuple(dist.shape) != (B, N, K):
+        raise ValueError("nn / dist must be [%d, %d, K], got %s / %s" % (B, N, tuple(nn.shape), tuple(dist.shape)))
+    if num_valid is not None:
+        num_valid = L.require_cuda_i32(num_valid, "num_valid", 1)
+        if num_valid.shape[0] != B:
+            raise ValueError("num_valid must be [%d], got %s" % (B, tuple(num_valid.shape)))
+    M = int(max_keypoints)
+    if not 1 <= M <= KEYPOINT_MAX:
+        raise ValueError("max_keypoints must be in [1, %d], got %d" % (KEYPOINT_MAX, M))
+    ws_bytes = L.lib().dh3d_keypoint_nms_workspace_bytes(B, N, M)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=scores.device)
+    count = torch.empty((B,), dtype=torch.int32, device=scores.device)
+    inds = torch.empty((B, M), dtype=torch.int32, device=scores.device)
+    L.check(L.lib().dh3d_keypoint_nms(L.ptr(scores), scores.stride(1), int(bool(invert)), L.ptr(nn), L.ptr(dist),
+                                      L.ptr(num_valid), B, N, K, float(nms_radius), float(min_response_ratio), M,
+                                      int(bool(remove_noise)), L.ptr(count), L.ptr(inds), L.ptr(ws), ws_bytes,
+                                      L.stream_ptr()), "keypoint_nms")
+    return count, inds
+
+
+def gather_rows(src, inds, count):
+    """src [B,N,C] float32, inds [B,M] / count [B] int32 (keypoint_nms) -> [B,M,C]: the rows src[b, inds[b, j]] for
+    j < count[b], zero rows after that (dh3d_gather_rows)."""
+    x = L.require_cuda_f32(src, "src", 3)
+    ix = L.require_cuda_i32(inds, "inds", 2)
+    cnt = L.require_cuda_i32(count, "count", 1)
+    B, N, C = x.shape
+    if ix.shape[0] != B or cnt.shape[0] != B:
+        raise ValueError("inds [%d, M] / count [%d] expected, got %s / %s" % (B, B, tuple(ix.shape), tuple(cnt.shape)))
+    M = ix.shape[1]
+    out = torch.empty((B, M, C), dtype=torch.float32, device=x.device)
+    L.check(L.lib().dh3d_gather_rows(L.ptr(x), B, N, C, L.ptr(ix), L.ptr(cnt), M, L.ptr(out), L.stream_ptr()),
+            "gather_rows")
+    return out
+
+
 def fps_sorted(srt, gbox, npoint, with_xyz=False, xyz=None):
     """FPS from spatial_sort() output; same idx [B,npoint] (original indexing) as ops.farthest_point_sample.
     with_xyz: also the sampled coordinates [B,npoint,3], written by the same kernel.

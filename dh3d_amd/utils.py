@@ -40,6 +40,40 @@ def single_nms(xyz, attention, nms_radius, min_response_ratio, max_keypoints, re
     return int(keep.numel()), keep
 
 
+def batched_knn(xyz, knn=50):
+    """The k-NN batched_nms runs on: (nn [B,N,k] int32, dist [B,N,k]), k = min(knn, N).  The Morton-ordered search up to
+    16384 points, the brute-force kernel beyond; both give the ids and distance bits of pm.knn_xyz (single_nms's)."""
+    N = xyz.shape[1]
+    k = min(int(knn), N)
+    if N <= 16384:
+        srt, gbox = pm.spatial_sort(xyz)
+        return pm.knn_sorted(srt, gbox, k)
+    return pm.knn_xyz(xyz, k)
+
+
+def batched_nms(xyz, scores, nms_radius, min_response_ratio, max_keypoints, remove_noise=True, knn=50, num_valid=None,
+                invert=False):
+    """single_nms for a batch, on the device end to end (HIP: dh3d_keypoint_nms), no host sync -- graph-capturable.
+
+    xyz [B,N,3], scores [B,N] float32 on the GPU (invert=True: the score is 1 - scores, e.g. scores =
+    xyz_feat_att[:, :, 131], read in place).  Returns (count [B] int32, inds [B, max_keypoints] int32 padded with -1):
+    cloud b's keypoints are inds[b, :count[b]], the ids single_nms(xyz[b], scores[b]) returns, in its order, bit for bit.
+
+    num_valid [B] int32 (optional): cloud b holds num_valid[b] real points followed by padding; padded points are never
+    kept, take no part in the maximum response and count as outside every ball.  That equals single_nms on the cropped
+    cloud xyz[b, :num_valid[b]] whenever no real point has a padded one among its k nearest neighbours -- the case of
+    get_fixednum_pcd(randsample=False) (dummies at 1e5, >= 50 real points).  Padding by re-drawn duplicates
+    (randsample=True) is not covered: the duplicates change the real points' neighbourhoods."""
+    x = xyz if xyz.is_contiguous() else xyz.contiguous()
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError("xyz must be [B,N,3]")
+    if scores.dim() != 2 or tuple(scores.shape) != tuple(x.shape[:2]):
+        raise ValueError("scores must be [B,N] = %s, got %s" % (tuple(x.shape[:2]), tuple(scores.shape)))
+    nn, dist = batched_knn(x, knn)
+    return pm.keypoint_nms(scores, nn, dist, nms_radius, min_response_ratio, max_keypoints, remove_noise=remove_noise,
+                           num_valid=num_valid, invert=invert)
+
+
 def load_descriptor_bin(filename, dim=131, dtype=np.float32):
     """Raw little-endian float32 rows of `dim` values: [x, y, z, 128-d descriptor(, score)]."""
     return np.fromfile(filename, dtype=dtype).reshape(-1, dim)

@@ -799,6 +799,29 @@ int dh3d_netvlad_fused_fwd(const float *x, const float *att, const float *wc_pac
                            int N, int D, int Cl, int O, float l2_eps, void *workspace, size_t workspace_bytes, float *out,
                            void *stream);
 
+/* Keypoint non-maximum suppression for a batch of clouds (localdesc_extract.py --perform_nms: core/utils.py:15-43
+ * single_nms, run by the reference once per cloud on the host; csrc/keypoints.hip).  Same ids as dh3d_amd/utils.py
+ * single_nms, cloud by cloud, bit for bit.  Per cloud b:
+ *   a[i]  = score[(b*N + i) * score_stride] (invert != 0: 1 - that), muted to 0 when remove_noise and K > 7 and
+ *           dist[i][7] > 2.0 (-0 reads as +0);
+ *   thr   = f32(max a over the real points) * ratio;
+ *   s[i][r] = a[nn[i][r]] when dist[i][r] <= radius and nn[i][r] is a real point, else 0;
+ *   i is kept iff it is a real point, s[i][r] <= s[i][0] for every r >= 1 (first maximum wins) and a[i] > thr.
+ * The kept points ordered by (a, i) descending and cut to M: count [B] = how many, inds [B, M] their ids, padded with -1.
+ * nn / dist [B, N, K] from the project's kNN (dh3d_knn_bruteforce_xyz / dh3d_knn_sorted, K = min(knn, N)).
+ * num_valid [B] (may be NULL: all N): points i >= num_valid[b] are never kept, take no part in the maximum and, as
+ * neighbours, count as outside the ball.  score_stride in elements (132 reads column 131 of xyz_feat_att given a pointer to
+ * its first row's column 131).  workspace: dh3d_keypoint_nms_workspace_bytes(B, N, M) bytes, caller-owned, no clearing
+ * needed.  1 <= M <= 4096 and K <= 64 (else DH3D_ERR_UNSUPPORTED), any N. */
+size_t dh3d_keypoint_nms_workspace_bytes(int B, int N, int M);
+int dh3d_keypoint_nms(const float *score, long long score_stride, int invert, const int32_t *nn, const float *dist,
+                      const int32_t *num_valid, int B, int N, int K, float radius, float ratio, int M, int remove_noise,
+                      int32_t *count, int32_t *inds, void *workspace, size_t workspace_bytes, void *stream);
+/* dst [B, M, C] <- src [B, N, C] rows: dst[b, j] = src[b, inds[b, j]] for j < count[b] (and 0 <= inds < N), zero rows
+ * after that.  Any C (4-byte elements).  With the outputs of dh3d_keypoint_nms: only the keypoints' rows of a map. */
+int dh3d_gather_rows(const float *src, int B, int N, int C, const int32_t *inds, const int32_t *count, int M, float *dst,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
