@@ -121,8 +121,6 @@ _SIGNATURES = {
                                      ctypes.POINTER(Epilogue), c_fp, c_fp],
     "dh3d_flex_conv_pm_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int,
                               ctypes.POINTER(Epilogue), c_fp, c_fp],
-    "dh3d_flex_conv_pm_post_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(Epilogue), c_fp,
-                                   c_fp, c_int, c_fp, c_fp],
     "dh3d_flex_conv_pm_tile_x6_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(Epilogue), c_fp,
                                    c_fp, c_int, c_fp, c_fp],
     "dh3d_pack_flex_weight_x3": [c_fp, c_fp, c_int, c_int, c_fp, c_fp],
@@ -176,9 +174,6 @@ _SIGNATURES = {
     "dh3d_se_res_pool_pm_packed_fwd": [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp],
     "dh3d_se_res_pool_conv_pm_fwd": [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp,
                                      ctypes.POINTER(Epilogue), c_int, c_fp, c_fp],
-    "dh3d_se_res_pool_conv_tails_pm_fwd": [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                           ctypes.POINTER(Epilogue), c_fp, c_fp, ctypes.POINTER(Epilogue), c_fp, c_fp,
-                                           ctypes.POINTER(Epilogue), c_fp, c_fp],
     "dh3d_flex_pool_pm_fwd": [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp],
     "dh3d_flex_avg_pm_fwd": [c_fp, c_fp, c_int, c_int, c_int, c_int, c_float, c_fp, c_fp],
     "dh3d_conv_pointset_pm_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, ctypes.POINTER(Epilogue),
@@ -199,19 +194,13 @@ _SIGNATURES = {
     "dh3d_netvlad_aggregate_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp,
                                    c_size_t, c_fp, c_fp],
     "dh3d_netvlad_head_workspace_bytes": [c_int, c_int, c_int],
-    "dh3d_global_tail_fwd": [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, ctypes.POINTER(Epilogue), c_fp,
-                             c_float, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_netvlad_tail_workspace_bytes": [c_int, c_int, c_int, c_int],
-    "dh3d_netvlad_tail_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_float,
-                              c_fp, c_size_t, c_fp, c_fp],
     "dh3d_walk_plan_bytes": [c_int, c_int],
     "dh3d_walk_plan": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp],
     "dh3d_global_walk_planned_fwd": [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, ctypes.POINTER(Epilogue),
                                      c_fp, c_float, c_fp, c_fp, c_fp, c_fp, c_int, c_fp],
     "dh3d_netvlad_tail_assign_fwd": [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int,
                                      c_float, c_fp, c_size_t, c_fp, c_fp],
-    "dh3d_global_walk_fwd": [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, ctypes.POINTER(Epilogue), c_fp,
-                             c_float, c_fp, c_fp, c_fp, c_fp, c_int, c_fp],
     "dh3d_netvlad_fused_workspace_bytes": [c_int, c_int, c_int, c_int, c_int],
     "dh3d_netvlad_fused_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int,
                                c_int, c_int, c_float, c_fp, c_size_t, c_fp, c_fp],

@@ -18,7 +18,6 @@ Parameter names follow the checkpoint variable names ('/' -> '.', 'mean/EMA' -> 
 dh3d_amd.model.tf_variable_name.
 """
 import math
-import os
 
 import torch
 from torch import nn
@@ -167,10 +166,9 @@ class Conv2D1x1(nn.Module):
         (DH3D._three_nn_before_sampled_level): one step at a time the two GEMMs are free beside the sampling chain and
         the one-launch tail only lengthens the chain behind it (0.4747 -> 0.4801 ms); with steps in flight that slack
         belongs to the other steps' kernels and 25 us of chip time + 130 MB of traffic less per step win (four in flight
-        0.2388 -> 0.2292 ms, round 6; placement only, same values).  DH3D_TAIL_FUSED=0 / 1 forces it off / on."""
+        0.2388 -> 0.2292 ms, round 6; placement only, same values)."""
         p, q = self._prep or self.prepare(), shortcut_conv._prep or shortcut_conv.prepare()
-        big = in_flight if TAIL_FUSED is None else TAIL_FUSED
-        return ((big if n > 4096 else TAIL_FUSED_SMALL) and self.cout == 128 and p.get("c_top") == 128
+        return ((in_flight or n <= 4096) and self.cout == 128 and p.get("c_top") == 128
                 and self.cin - 128 == 64 and "wp3_bot" in p and shortcut_conv.cin == 64 and shortcut_conv.cout == 128
                 and "wp3" in q and n % 32 == 0 and n >= 1024)
 
@@ -259,20 +257,14 @@ class SEBlock(nn.Module):
             return pm.se_res_pool_packed(x, nbr, *packed)
         return self.forward(x, pm.flex_pool(x, nbr))
 
-    def forward_on_max_pool_then_conv(self, x, nbr, conv, act=pm.ACT_RELU, tails=None):
+    def forward_on_max_pool_then_conv(self, x, nbr, conv, act=pm.ACT_RELU):
         """(y, conv(y)) with y = forward_on_max_pool(x, nbr): one launch when the block is 64 wide and `conv` a 64 -> 64
-        Conv2D1x1 (stage 1 -> before_stage2_conv1d, core/backbones.py:115-117); same values either way.
-        tails = (tail on y, tail on conv(y)), each (x3-packed [64,128] weight, pre_bias, scale, shift, act): two more 1x1
-        convs in the same launch -- returns (None, conv(y), tail outputs...) then (y is not stored), or the 2-tuple when
-        the fused kernel does not apply (the caller then runs the tails itself)."""
+        Conv2D1x1 (stage 1 -> before_stage2_conv1d, core/backbones.py:115-117); same values either way."""
         W1, b1, W2, b2, packed = self._prep or self.prepare()
         inner = getattr(conv, "tfconv0", conv)  # FeatureConv1d wraps its Conv2D1x1
         cp = inner._prep or inner.prepare()
         if (packed is not None and x.dim() == 3 and x.shape[2] == 64 and inner.cin == 64 and inner.cout == 64
                 and "wp" in cp and not cp.get("pad")):
-            if tails is not None and SE_TAILS:
-                return pm.se_res_pool_conv_tails(x, nbr, *packed, cp["wp"], cp["b"], cp["scale"], cp["shift"], tails[0],
-                                                 tails[1], act=act, store_y=False)
             return pm.se_res_pool_conv(x, nbr, *packed, cp["wp"], cp["b"], cp["scale"], cp["shift"], act=act)
         y = self.forward_on_max_pool(x, nbr)
         return y, conv(y, act=act)
@@ -346,27 +338,6 @@ def gather_rows(points, idx):
     return out
 
 
-# dev A/B switch (DH3D_SE_TAILS=1: the local step's shortcut conv and the lower concat block ride in stage 1's SE kernel.
-# Measured slower than the three launches -- DEADENDS.md -- so off by default; the kernel stays tested)
-SE_TAILS = os.environ.get("DH3D_SE_TAILS", "0") == "1"
-# dev A/B switch (DH3D_FLEX_TX6=0: the exact-f32 MFMA tile kernel for the sampled levels)
-FLEX_TX6 = os.environ.get("DH3D_FLEX_TX6", "1") != "0"
-# dev A/B switch (DH3D_TAIL_FUSED=0 / 1: the local step's tail -- shortcut conv, the concat conv's lower block, up-sampling,
-# epilogue, l2-normalised rows -- as ONE launch, csrc/dense_tail.hip, never / always for clouds of more than 4096 points.
-# 27.5 us instead of 52 us of kernels and 130 MB less HBM traffic per step, but the two GEMMs move from beside the sampling
-# chain to behind it.  Unset: with steps in flight only -- Conv2D1x1.tail_fusable)
-TAIL_FUSED = {"0": False, "1": True}.get(os.environ.get("DH3D_TAIL_FUSED", ""))   # None: by the engine's mode
-# (DH3D_TAIL_FUSED_SMALL=0: clouds of <= 4096 points back on the K = 256 GEMM with the fused up-sampling + shortcut)
-TAIL_FUSED_SMALL = os.environ.get("DH3D_TAIL_FUSED_SMALL", "1") != "0"
-
-
-# dev A/B switches (round 6).  DH3D_FPS_ORDERED=0: the sampled set is sorted by its own launch again (spatial_sort_kernel<1>
-# behind the sampling) instead of leaving the FPS kernel in Morton order; DH3D_SAMPLED_GRID=0: the sampled set's kNN back on
-# the brute-force wave-per-query kernel instead of the cell lists on the table the FPS kernel writes.
-FPS_ORDERED = os.environ.get("DH3D_FPS_ORDERED", "1") != "0"
-SAMPLED_GRID = os.environ.get("DH3D_SAMPLED_GRID", "1") != "0"
-
-
 def compute_level(xyz, dilate, knn, ordered=None, fps_contract=None, cells=None):
     """FPS -> gather xyz -> kNN on the sampled set (three_nn back to the full set: finish_level).
 
@@ -379,7 +350,7 @@ def compute_level(xyz, dilate, knn, ordered=None, fps_contract=None, cells=None)
     B, N, _ = xyz.shape
     npoint = N // dilate
     ordered_s, cells_s = None, None
-    if (ordered is not None and 4096 <= N <= 8192 and fps_contract is None and FPS_ORDERED
+    if (ordered is not None and 4096 <= N <= 8192 and fps_contract is None
             and pm.fps_sorted_fits(N, npoint, ordered=True)):
         # the sampled set leaves the FPS kernel IN MORTON ORDER (a stable compaction of the picked positions of the sorted
         # cloud: records, group boxes and -- with the cloud's cell table -- the subset's table on the cloud's grid):
@@ -401,7 +372,7 @@ def compute_level(xyz, dilate, knn, ordered=None, fps_contract=None, cells=None)
         fps_path = "any_n"
     ready = torch.cuda.Event()
     ready.record()  # xyz_s exists: three_nn may start on another stream while the sampled-set kNN runs here
-    if cells_s is not None and knn <= 8 and pm.KNN_GRID and SAMPLED_GRID and npoint >= 256 and B * npoint >= 16384:
+    if cells_s is not None and knn <= 8 and npoint >= 256 and B * npoint >= 16384:
         # cell lists on the table the FPS kernel wrote (a third of the brute-force kernel's instructions per query; with a
         # sort of its own on the chain this lost: DEADENDS.md "the sampled levels on cell lists").  Only where the launch
         # fills the chip: 64 queries per workgroup -- 32 x 512 is 256 workgroups (global serial 0.6732 -> 0.6671 ms, three
@@ -412,7 +383,7 @@ def compute_level(xyz, dilate, knn, ordered=None, fps_contract=None, cells=None)
     elif npoint <= 2048 or npoint > 16384:  # small sets: the brute-force kernel beats sort + pruned search (launch /
         nbr_s, _ = pm.knn_xyz(xyz_s, knn)  # latency bound); sets beyond the Morton sort's 14-bit ids: it is what serves any N
         knn_path = "brute"
-    elif knn <= 8 and pm.KNN_GRID:
+    elif knn <= 8:
         srt_s, gbox_s, cells_s = pm.spatial_sort_cells(xyz_s)
         nbr_s, _ = pm.knn_grid(srt_s, gbox_s, cells_s, knn)
         ordered_s = (srt_s, gbox_s)
@@ -544,7 +515,7 @@ class FlexConvDilate(nn.Module):
         return conv.lower_partial(feat)
 
     def forward(self, geo, feat, nbr=None, residual=None, l2cat=None, shortcut_src=None, lower_partial=None,
-                coarse_only=False, post_conv=None, post_linear=None, post_tails=None, fused_tail=None):
+                coarse_only=False, post_conv=None, post_linear=None, fused_tail=None):
         """geo: Geometry; feat [B,N,cin]; nbr [B,N,K] for dilate == 1 (else computed on the sampled set);
         residual [B,N,cout]: added to the concat conv's output in its store (the caller's shortcut branch);
         l2cat = (prefix [B,N,3], eps): return [prefix | l2_normalize(output)] instead of the output;
@@ -577,18 +548,13 @@ class FlexConvDilate(nn.Module):
                                     shift=p["shift"], act=pm.ACT_RELU,
                                     reserve_cus_per_xcd=getattr(geo, "busy_cus_per_xcd", 0))
             elif (post_linear is not None and coarse_only and p is prep[-1] and remap is None and not self.add_se
-                  and pm.flex_post_supported(x.shape[2], p["dout"], nbr_s.shape[2], post_linear[1])):
+                  and (x.shape[2], p["dout"], nbr_s.shape[2], post_linear[1]) == (128, 256, 8, 64)):
                 # post_linear = (packed [dout, 64] weight, 64): the caller's next linear layer on this block's coarse
-                # output rides in the last flex_conv's launch (NetVLAD's cluster logits, model.compute_global)
-                if FLEX_TX6 and p.get("wp3t") is not None:
-                    x, self._last_post = pm.flex_conv_tile_x6(x, xyz_s, nbr_s, p["wp3t"], p["dout"], pre_bias=p["fb"],
-                                                              scale=p["scale"], shift=p["shift"], act=pm.ACT_RELU,
-                                                              wpost_packed=post_linear[0], Dpost=post_linear[1])
-                else:
-                    x, self._last_post = pm.flex_conv_post(x, xyz_s, nbr_s, p["wp"], p["dout"], post_linear[0],
-                                                           post_linear[1], pre_bias=p["fb"], scale=p["scale"],
-                                                           shift=p["shift"], act=pm.ACT_RELU)
-            elif (FLEX_TX6 and p.get("wp3t") is not None and remap is None
+                # output rides in the last flex_conv's tile launch (NetVLAD's cluster logits, model.compute_global)
+                x, self._last_post = pm.flex_conv_tile_x6(x, xyz_s, nbr_s, p["wp3t"], p["dout"], pre_bias=p["fb"],
+                                                          scale=p["scale"], shift=p["shift"], act=pm.ACT_RELU,
+                                                          wpost_packed=post_linear[0], Dpost=post_linear[1])
+            elif (p.get("wp3t") is not None and remap is None
                   and pm.flex_tile_x6_supported(x.shape[2], p["dout"], nbr_s.shape[2])):
                 # the sampled levels (and cfg 5's K = 12 layer): 32-point tiles, tile GEMM on the bf16 pipe (csrc/flex_tx6.hip)
                 x = pm.flex_conv_tile_x6(x, xyz_s, nbr_s, p["wp3t"], p["dout"], pre_bias=p["fb"], scale=p["scale"],
@@ -602,10 +568,7 @@ class FlexConvDilate(nn.Module):
             cconv = self.concat_conv1d.tfconv0 if self.concat else None
             if (post_conv is not None and not (self.upsample and self.dilate > 1) and not self.concat
                     and residual is None and l2cat is None and shortcut_src is None):
-                r = self.se.forward_on_max_pool_then_conv(x, nbr_s, post_conv, tails=post_tails)
-                if len(r) == 4:  # (None, post_conv(output), tail on the output, tail on post_conv(output)): one launch
-                    return r
-                x, post = r  # x is this block's output
+                x, post = self.se.forward_on_max_pool_then_conv(x, nbr_s, post_conv)  # x is this block's output
             elif (self.upsample and self.dilate > 1 and not coarse_only and cconv is not None
                   and (lower_partial is not None or fused_tail is not None) and shortcut_src is None and x.shape[2] == 128 and cconv.cout == 128
                   and (self.se._prep or self.se.prepare())[4] is not None and cconv._prep.get("c_top") == 128):

@@ -665,30 +665,16 @@ DH3D_API int dh3d_pack_weight_x3(const float *W, int Kd, int Dout, void *packed,
   return dh3d_launch_status();
 }
 
-#ifdef DH3D_DEV  // dev builds only (tools/dense_bench.py): column waves of the head GEMM (4 = eight waves, 2 = four)
-static int g_head_wc = 4;
-DH3D_API void dh3d_dev_set_head_wc(int wc) { g_head_wc = wc == 2 ? 2 : 4; }
-#else
-static constexpr int g_head_wc = 4;
-#endif
-
 DH3D_API int dh3d_mlp_head_pm_x6_fwd(const float *h, int R, int C, const void *wpacked_x3, int H,
                                      const dh3d_epilogue *ep, const float *w_fc, float b_fc, float *att,
                                      void *stream) {
   DH3D_REQUIRE(h && wpacked_x3 && w_fc && att && R > 0 && C > 0 && H > 0);
   DH3D_SUPPORTED(C % HKC == 0 && H % HTN == 0);
   const size_t lds = (size_t)2 * A_STAGE * 2 + (size_t)2 * B_STAGE * 16 + sizeof(float) * 4 * HTM;
-  if (g_head_wc == 2) {
-    auto kern = mlp_head_x6_kernel<2>;
-    DH3D_ALLOW_BIG_LDS(kern);
-    hipLaunchKernelGGL(kern, dim3(dh3d_cdiv(R, HTM)), dim3(256), lds, (hipStream_t)stream, h, C,
-                       static_cast<const uint4 *>(wpacked_x3), H, dh3d_ep(ep), w_fc, b_fc, (long long)R, att);
-  } else {
-    auto kern = mlp_head_x6_kernel<4>;
-    DH3D_ALLOW_BIG_LDS(kern);
-    hipLaunchKernelGGL(kern, dim3(dh3d_cdiv(R, HTM)), dim3(512), lds, (hipStream_t)stream, h, C,
-                       static_cast<const uint4 *>(wpacked_x3), H, dh3d_ep(ep), w_fc, b_fc, (long long)R, att);
-  }
+  auto kern = mlp_head_x6_kernel<4>;
+  DH3D_ALLOW_BIG_LDS(kern);
+  hipLaunchKernelGGL(kern, dim3(dh3d_cdiv(R, HTM)), dim3(512), lds, (hipStream_t)stream, h, C,
+                     static_cast<const uint4 *>(wpacked_x3), H, dh3d_ep(ep), w_fc, b_fc, (long long)R, att);
   return dh3d_launch_status();
 }
 
@@ -703,10 +689,7 @@ static int linear_x6_launch(const float *x1, int C1, const float *x2, int C2, co
   const dim3 grid(dh3d_cdiv(R, HTM), slices), block(512);
   const uint4 *wp = static_cast<const uint4 *>(wpacked_x3);
   if (C1 == 64 && C2 == 0 && Dout == 128 && slices == 1 && !up.points && !l2.out && !sc.x3) {
-#ifndef DH3D_K64_NCB
-#define DH3D_K64_NCB 4
-#endif
-    constexpr int kNcb = DH3D_K64_NCB;  // column blocks per wave
+    constexpr int kNcb = 4;  // column blocks per wave
     const dim3 g64(dh3d_cdiv(R, 32 * kNcb));
 #define DH3D_K64_LAUNCH(RES, ACT) \
   hipLaunchKernelGGL((linear_k64_x6_kernel<RES, kNcb, ACT>), g64, dim3(256), 0, s, x1, wp, e, residual, (long long)R, out)
@@ -891,7 +874,7 @@ __device__ __forceinline__ Row4 idw_mix_pk(const Row4 a, const Row4 b, const Row
 // The block's SLOT TABLE (first kIHPlan dwords of the workgroup's LDS: s_slot | s_w | s_orig | s_bits | s_pre | s_row | lists), built
 // from the three_nn result: bitmap of the coarse rows the block's 128 points touch -> prefix popcounts -> slot = rank of the
 // row.  Three dependent global round trips (order -> idx / dist -> ...) and five barriers: 17 us of the walk when built in
-// the walk's own launch (round 5, tools/walk_phases.sh) -- round 6: walk_plan_kernel builds it once behind three_nn, off the
+// the walk's own launch (round 5) -- round 6: walk_plan_kernel builds it once behind three_nn, off the
 // critical chain, and the walk copies the image in (dh3d_walk_plan / dh3d_global_walk_planned_fwd).
 // LISTS (the plan kernel): also the references to every staged row, slot-major -- s_loff[slot] .. s_loff[slot + 1] index
 // entries `point * 4 + t` of s_lst (within a list in (point, t) order, ranked from a per-slot bitmap: sorting each list by
@@ -1075,7 +1058,7 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
   // sl are worked on and parked in registers until the buffer is free (staging and per-point work took about the same
   // time when they ran one after the other).  The parked rows are ONE 32-float vector value: as a float4 array the
   // compiler kept them in scratch, stored behind every load and reloaded -- which is why the first attempt at this
-  // double buffer measured slower (139 vs 100 us).  Measured by compiling parts out (tools/walk_phases.sh, 32 x 4096):
+  // double buffer measured slower (139 vs 100 us).  Measured by compiling parts out (32 x 4096):
   // slot table 17 us, the slices 39 (per-point work 36: LDS reads of 3 KB per point and slice are ~20 of it), |x| 9,
   // soft assignment 7, MFMA scatter + atomics 17.
   typedef float f32park __attribute__((ext_vector_type(4 * (kIHCap / kIHW))));
@@ -1121,9 +1104,7 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
       const bool more = sl + 1 < NS;
       const float *nb = more ? H + (size_t)(sl + 1) * SS : (VLAD ? vt.coarse : H + (size_t)sl * SS);
       const int nrs = (more || !VLAD) ? RS : 256;
-#if !defined(DH3D_IH_SKIP) || !(DH3D_IH_SKIP & 2)
       DH3D_IH_REQUEST(nb, nrs)
-#endif
     }
     __builtin_amdgcn_sched_barrier(0);
     if (!ep.pre_bias) pb = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1167,9 +1148,7 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
         }
       }
     };
-#if !defined(DH3D_IH_SKIP) || !(DH3D_IH_SKIP & 1)   // dev timing knob (tools/walk_phases.sh): results wrong when set
     if (overflow) slice_points(std::true_type{}); else slice_points(std::false_type{});
-#endif
     __syncthreads();  // the rows are overwritten by the next slice
   }
   if (tid < kIHP) {
@@ -1216,9 +1195,7 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
         }
       }
     };
-#if !defined(DH3D_GT_SKIP) || !(DH3D_GT_SKIP & 2)   // dev timing knob (tools/gt_bench.py): results wrong when set
     if (overflow) norm_points(std::true_type{}); else norm_points(std::false_type{});
-#endif
     __syncthreads();
   }
   // ---- (b, c): cw rows (64 floats each) at the head of the row buffer, A' behind them
@@ -1276,12 +1253,9 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
         }
       }
     };
-#if !defined(DH3D_GT_SKIP) || !(DH3D_GT_SKIP & 1)
     if (overflow) assign_points(std::true_type{}); else assign_points(std::false_type{});
-#endif
     unsafeAtomicAdd(&s_asum[lane], asum_acc);
     __syncthreads();
-#if !defined(DH3D_GT_SKIP) || !(DH3D_GT_SKIP & 4)
     if (vt.plan) {
       // Planned walk (round 6): the plan carries, per staged row, the list of the (point, t) references to it.  Wave w owns
       // slots 8w .. 8w + 7 = ONE contiguous run of the slot-major list (~48 references): lane l fetches entry l and its
@@ -1340,10 +1314,7 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
     {
       // (of the eight waves the first four -- one per SIMD -- take the four tiles; splitting the points over two copies of
       // the tiles halved each wave's MFMA chain but doubled the atomics: 233 -> 228 us for the whole tail with ONE copy)
-#ifndef DH3D_IH_SCATTER_COPIES
-#define DH3D_IH_SCATTER_COPIES 1
-#endif
-      constexpr int kCopies = DH3D_IH_SCATTER_COPIES;
+      constexpr int kCopies = 1;
       const int w4 = wave & 3, half = wave >> 2;
       const int ti = w4 >> 1, tj = w4 & 1;
       if (ti * 32 < nd && half < kCopies) {  // block-uniform per wave pair
@@ -1363,15 +1334,10 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int j = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;  // 32x32 accumulator layout
-#if !defined(DH3D_GT_SKIP) || !(DH3D_GT_SKIP & 8)
           if (j < nd) unsafeAtomicAdd(&Ab[(size_t)s_row[j] * 64 + tj * 32 + (lane & 31)], acc[r]);
-#else
-          if (j < nd && acc[r] == 123.456f) Ab[0] = acc[r];
-#endif
         }
       }
     }
-#endif
     if (tid < 64) unsafeAtomicAdd(&vt.asum[(size_t)bi * 64 + tid], s_asum[tid]);
   }
 }
@@ -1418,53 +1384,6 @@ DH3D_API int dh3d_interp_head_sorted_fwd_dev(const float *H, int Hd, int row_maj
   return dh3d_launch_status();
 }
 
-// Attention head + NetVLAD soft assignment in one walk over the fine points (see VladTail above).  Outputs: att
-// [B,n] (may be NULL) and `accum` = [ apart B*m*64 | asum B*64 | V B*64*256 ] floats, zeroed here in one fill: apart =
-// A', asum its column sums, V[b] = apart[b]^T coarse[b] (exact-f32 MFMA GEMM, accumulating).  The caller finishes
-// with dh3d_netvlad_tail_fwd(V, asum, ...).
-static int global_tail_launch(const float *H, int Hd, const float *coarse, const float *cw, const int32_t *idx,
-                              const float *dist, const float *order, int B, int n, int m, const dh3d_epilogue *ep,
-                              const float *w_fc, float b_fc, const float *cl_scale, const float *cl_shift, float *att,
-                              float *accum, bool zero_here, hipStream_t s, bool with_gemm = true,
-                              const int *plan = nullptr) {
-  DH3D_REQUIRE(H && coarse && cw && idx && dist && w_fc && cl_scale && cl_shift && accum);
-  DH3D_REQUIRE(B > 0 && n > 0 && m > 0 && Hd > 0);
-  DH3D_SUPPORTED(Hd % 256 == 0 && Hd <= 1024 && m <= 1024 && (!ep || ep->act != DH3D_ACT_SIGMOID) &&
-                 (long long)B * m * Hd < (1ll << 30) /* 32-bit byte offsets of the row requests */);
-  float *apart = accum, *asum = apart + (size_t)B * m * 64, *V = asum + (size_t)B * 64;
-  if (zero_here &&
-      hipMemsetAsync(accum, 0, sizeof(float) * ((size_t)B * m * 64 + (size_t)B * 64 + (with_gemm ? (size_t)B * 64 * 256 : 0)), s) != hipSuccess)
-    return DH3D_ERR_LAUNCH;
-  const int nblk = dh3d_cdiv(n, kIHP);
-  const int per_xcd = dh3d_cdiv(B, 8) * nblk;
-  DH3D_ALLOW_BIG_LDS(interp_head_lds_kernel<true>);
-  hipLaunchKernelGGL(interp_head_lds_kernel<true>, dim3(8 * per_xcd), dim3(kIHT), interp_head_lds_bytes(), s, H, Hd / 256,
-                     (long long)B * m, idx, dist, reinterpret_cast<const float4 *>(order), B, n, m, nblk, dh3d_ep(ep),
-                     w_fc, b_fc, att, VladTail{coarse, cw, cl_scale, cl_shift, apart, asum, nullptr, 0, 0, plan});
-  const int st = dh3d_launch_status();
-  if (st != DH3D_OK || !with_gemm) return st;
-  return dh3d_internal_gemm_tn_batched(apart, coarse, B, m, 64, 256, V, true, s);
-}
-
-DH3D_API int dh3d_global_tail_fwd(const float *H, int Hd, const float *coarse, const float *cw, const int32_t *idx,
-                                  const float *dist, const float *order, int B, int n, int m, const dh3d_epilogue *ep,
-                                  const float *w_fc, float b_fc, const float *cl_scale, const float *cl_shift, float *att,
-                                  float *accum, void *stream) {
-  return global_tail_launch(H, Hd, coarse, cw, idx, dist, order, B, n, m, ep, w_fc, b_fc, cl_scale, cl_shift, att, accum,
-                            true, (hipStream_t)stream);
-}
-
-// the walk alone: accum = [ apart B*m*64 | asum B*64 ] floats; zero_accum != 0: cleared here, else ZEROED BY THE CALLER (a
-// fill issued off the critical chain).  dh3d_netvlad_tail_assign_fwd(apart, coarse, asum, m, ...) finishes (it forms
-// V = apart^T coarse inside its finalize kernel).
-DH3D_API int dh3d_global_walk_fwd(const float *H, int Hd, const float *coarse, const float *cw, const int32_t *idx,
-                                  const float *dist, const float *order, int B, int n, int m, const dh3d_epilogue *ep,
-                                  const float *w_fc, float b_fc, const float *cl_scale, const float *cl_shift, float *att,
-                                  float *accum, int zero_accum, void *stream) {
-  return global_tail_launch(H, Hd, coarse, cw, idx, dist, order, B, n, m, ep, w_fc, b_fc, cl_scale, cl_shift, att, accum,
-                            zero_accum != 0, (hipStream_t)stream, false);
-}
-
 // The walk's slot tables built ahead of it (round 6): one image of kIHPlan dwords per 128-point block of the Morton order,
 // written behind three_nn (off the global step's critical chain) and copied into the walk's LDS with one coalesced read.
 // plan: dh3d_walk_plan_bytes(B, n) bytes; valid for the (idx, dist, order) it was built from.
@@ -1483,13 +1402,31 @@ DH3D_API int dh3d_walk_plan(const int32_t *idx, const float *dist, const float *
   return dh3d_launch_status();
 }
 
-// dh3d_global_walk_fwd with the slot tables of dh3d_walk_plan (plan may be NULL: built inside the walk as before).
+// Attention head + NetVLAD soft assignment in one walk over the fine points (see VladTail above).  Outputs: att [B,n]
+// (may be NULL) and accum = [ apart B*m*64 | asum B*64 ] floats: apart = A', asum its column sums.  zero_accum != 0:
+// cleared here, else ZEROED BY THE CALLER (a fill issued off the critical chain).  dh3d_netvlad_tail_assign_fwd(apart,
+// coarse, asum, m, ...) finishes (it forms V = apart^T coarse inside its finalize kernel).  plan: the slot tables of
+// dh3d_walk_plan, or NULL (built inside the walk).
 DH3D_API int dh3d_global_walk_planned_fwd(const float *H, int Hd, const float *coarse, const float *cw, const int32_t *idx,
                                           const float *dist, const float *order, const void *plan, int B, int n, int m,
                                           const dh3d_epilogue *ep, const float *w_fc, float b_fc, const float *cl_scale,
                                           const float *cl_shift, float *att, float *accum, int zero_accum, void *stream) {
-  return global_tail_launch(H, Hd, coarse, cw, idx, dist, order, B, n, m, ep, w_fc, b_fc, cl_scale, cl_shift, att, accum,
-                            zero_accum != 0, (hipStream_t)stream, false, static_cast<const int *>(plan));
+  DH3D_REQUIRE(H && coarse && cw && idx && dist && w_fc && cl_scale && cl_shift && accum);
+  DH3D_REQUIRE(B > 0 && n > 0 && m > 0 && Hd > 0);
+  DH3D_SUPPORTED(Hd % 256 == 0 && Hd <= 1024 && m <= 1024 && (!ep || ep->act != DH3D_ACT_SIGMOID) &&
+                 (long long)B * m * Hd < (1ll << 30) /* 32-bit byte offsets of the row requests */);
+  hipStream_t s = (hipStream_t)stream;
+  float *apart = accum, *asum = apart + (size_t)B * m * 64;
+  if (zero_accum && hipMemsetAsync(accum, 0, sizeof(float) * ((size_t)B * m * 64 + (size_t)B * 64), s) != hipSuccess)
+    return DH3D_ERR_LAUNCH;
+  const int nblk = dh3d_cdiv(n, kIHP);
+  const int per_xcd = dh3d_cdiv(B, 8) * nblk;
+  DH3D_ALLOW_BIG_LDS(interp_head_lds_kernel<true>);
+  hipLaunchKernelGGL(interp_head_lds_kernel<true>, dim3(8 * per_xcd), dim3(kIHT), interp_head_lds_bytes(), s, H, Hd / 256,
+                     (long long)B * m, idx, dist, reinterpret_cast<const float4 *>(order), B, n, m, nblk, dh3d_ep(ep),
+                     w_fc, b_fc, att,
+                     VladTail{coarse, cw, cl_scale, cl_shift, apart, asum, nullptr, 0, 0, static_cast<const int *>(plan)});
+  return dh3d_launch_status();
 }
 
 DH3D_API int dh3d_interp_head_fwd(const float *H, int Hd, const int32_t *idx, const float *dist, int B, int n, int m,

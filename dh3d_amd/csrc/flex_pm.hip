@@ -34,24 +34,12 @@ struct FlexCfg {
   static_assert(NT >= 1 && NB * MB % 4 == 0, "tile must split over 4 waves");
 };
 
-#ifdef DH3D_FLEX_PROBE  // dev instrumentation (tools/flex_probe.py): cycle stamps of a few workgroups
-__device__ long long g_fprobe[64 * 8];
-#define FPROBE(i) do { if (threadIdx.x == 0 && blockIdx.x < 64) g_fprobe[blockIdx.x * 8 + (i)] = clock64(); } while (0)
-#else
-#define FPROBE(i) do { } while (0)
-#endif
-
 // KT = compile-time neighbourhood size (8 on the DH3D path) or 0 for a run-time K.
-// POST: the finished output tile goes through one more linear layer [DOUT -> 64] (wpost = dh3d_pack_weight of [DOUT, 64], no
-// bias / activation) before it leaves the chip, both results stored: the cluster logits `coarse @ cluster_weights` of
-// NetVLAD behind the global flex_conv (core/backbones.py:213-216 on the commuted form) -- a 17 us launch + its gap on
-// the global step's critical chain become ~12 % more MFMA work in this kernel.
-template <int DIN, int DOUT, int KT, int TMSEL = 0, bool POST = false>
+template <int DIN, int DOUT, int KT, int TMSEL = 0>
 __global__ __launch_bounds__(256) void flex_conv_pm_kernel(
     const float *__restrict__ feat, const float *__restrict__ xyz, const int32_t *__restrict__ nbr,
     const float *__restrict__ wpacked, long long R, int N, int K, EpilogueArgs ep,
-    float *__restrict__ out, const int32_t *__restrict__ remap, int Nsrc, const float *__restrict__ wpost = nullptr,
-    float *__restrict__ out2 = nullptr) {
+    float *__restrict__ out, const int32_t *__restrict__ remap, int Nsrc) {
   // remap (may be NULL): the features are rows of a LARGER per-cloud map [B, Nsrc, DIN] and point j of this level is
   // row remap[b*N + j] of it -- group_point (the sampled level's feature gather, core/tf_utils.py:92-95) fused into the
   // neighbour gather: one more dependent index load instead of a kernel + its dependency gap
@@ -61,7 +49,6 @@ __global__ __launch_bounds__(256) void flex_conv_pm_kernel(
   const long long grow0 = (long long)dh3d_xcd_remap(blockIdx.x, gridDim.x) * C::TM;
 
   // ---- phase A: gather-reduce S = [S0|Sx|Sy|Sz] for TM points
-  FPROBE(0);
   const int r4 = (tid % C::LPR) * 4;
   if (KT > 0) {
     // Two dependent memory round trips for the whole tile instead of ~5 per round: (1) every round's
@@ -157,9 +144,7 @@ __global__ __launch_bounds__(256) void flex_conv_pm_kernel(
       *reinterpret_cast<float4 *>(row + 3 * DIN) = sz;
     }
   }
-  FPROBE(1);
   __syncthreads();
-  FPROBE(2);
 
   // ---- phase B: S @ Wcat on the f32 MFMA pipe, epilogue in the store
   const int wave = tid >> 6;
@@ -172,29 +157,12 @@ __global__ __launch_bounds__(256) void flex_conv_pm_kernel(
 #pragma unroll
   for (int j = 0; j < C::NT; ++j) er[j] = epilogue_prefetch(ep, (cb0 + j * cbstride) * 32 + (tid & 31));
   wave_gemm_f32<C::NT>(s_S, C::LD, row0, wpacked, C::KD / 8, cb0, cbstride, acc);
-#ifdef DH3D_FLEX_PROBE
-  asm volatile("" :: "v"(acc[0][0]));
-#endif
-  FPROBE(3);
   // wide epilogue through the (now dead) S tile: LD = 4*Din + 4 >= Dout + 4 for every supported shape
   static_assert(C::LD >= DOUT + 4, "output tile must fit the S tile");
   __syncthreads();
   wave_tiles_to_lds<C::NT>(acc, er, ep.act, s_S, C::LD, row0, cb0, cbstride);
   __syncthreads();
   block_store_rows(s_S, C::LD, C::TM, grow0, R, DOUT, nullptr, out);
-  if (POST) {
-    static_assert(!POST || (C::TM == 32 && C::LD >= DOUT + 64 + 4), "POST: 32-point tiles, room for 64 more columns");
-    if (wave < 2) {  // [32, DOUT] x [DOUT, 64]: one 32-column block per wave, the tile in LDS is the A operand
-      f32x16 pacc[1];
-      zero_acc<1>(pacc);
-      wave_gemm_f32<1>(s_S, C::LD, 0, wpost, DOUT / 8, wave, 1, pacc);
-      const EpilogueRegs none[1] = {EpilogueRegs{0.f, 1.f, 0.f}};
-      wave_tiles_to_lds<1>(pacc, none, DH3D_ACT_NONE, s_S + DOUT, C::LD, 0, wave, 1);  // columns [DOUT, DOUT + 64) of the rows
-    }
-    __syncthreads();
-    block_store_rows(s_S + DOUT, C::LD, C::TM, grow0, R, 64, nullptr, out2);
-  }
-  FPROBE(4);
 }
 
 template <int DIN, int DOUT>
@@ -210,7 +178,7 @@ int flex_conv_pm_launch(const float *feat, const float *xyz, const int32_t *nbr,
       auto kern = flex_conv_pm_kernel<DIN, DOUT, 8, 32>;
       DH3D_ALLOW_BIG_LDS(kern);
       hipLaunchKernelGGL(kern, dim3(dh3d_cdiv(R, 32)), dim3(256), sizeof(float) * 32 * C32::LD, s, feat, xyz, nbr,
-                         wpacked, R, N, K, ep, out, remap, Nsrc, (const float *)nullptr, (float *)nullptr);
+                         wpacked, R, N, K, ep, out, remap, Nsrc);
       return dh3d_launch_status();
     }
   }
@@ -219,17 +187,17 @@ int flex_conv_pm_launch(const float *feat, const float *xyz, const int32_t *nbr,
   if (K == 8) {
     auto kern = flex_conv_pm_kernel<DIN, DOUT, 8>;
     DH3D_ALLOW_BIG_LDS(kern);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, feat, xyz, nbr, wpacked, R, N, K, ep, out, remap, Nsrc, (const float *)nullptr, (float *)nullptr);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, feat, xyz, nbr, wpacked, R, N, K, ep, out, remap, Nsrc);
   } else if (K == 12 && DIN == 128 && DOUT == 128) {
     // BASELINE config 5's stress kernel (localdesc_extract.py:146,166: K = 12 on 128-d features): the two-round-trip
     // gather with a compile-time K instead of the run-time-K loop (a dependent id -> row load chain per neighbour)
     auto kern = flex_conv_pm_kernel<DIN, DOUT, 12>;
     DH3D_ALLOW_BIG_LDS(kern);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, feat, xyz, nbr, wpacked, R, N, K, ep, out, remap, Nsrc, (const float *)nullptr, (float *)nullptr);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, feat, xyz, nbr, wpacked, R, N, K, ep, out, remap, Nsrc);
   } else {
     auto kern = flex_conv_pm_kernel<DIN, DOUT, 0>;
     DH3D_ALLOW_BIG_LDS(kern);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, feat, xyz, nbr, wpacked, R, N, K, ep, out, remap, Nsrc, (const float *)nullptr, (float *)nullptr);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, feat, xyz, nbr, wpacked, R, N, K, ep, out, remap, Nsrc);
   }
   return dh3d_launch_status();
 }
@@ -497,20 +465,6 @@ DH3D_API int dh3d_flex_conv_pm_gather_fwd(const float *features, const int32_t *
   return DH3D_ERR_UNSUPPORTED;
 }
 
-DH3D_API int dh3d_flex_conv_pm_post_fwd(const float *features, const float *xyz, const int32_t *nbr, const float *wpacked,
-                                        int B, int N, int K, int Din, int Dout, const dh3d_epilogue *ep, float *out,
-                                        const float *wpost_packed, int Dpost, float *out2, void *stream) {
-  DH3D_REQUIRE(features && xyz && nbr && wpacked && out && wpost_packed && out2 && B > 0 && N > 0);
-  DH3D_SUPPORTED(Din == 128 && Dout == 256 && K == 8 && Dpost == 64);
-  using C = FlexCfg<128, 256>;
-  const long long R = (long long)B * N;
-  auto kern = flex_conv_pm_kernel<128, 256, 8, 0, true>;
-  DH3D_ALLOW_BIG_LDS(kern);
-  hipLaunchKernelGGL(kern, dim3(dh3d_cdiv(R, C::TM)), dim3(256), sizeof(float) * C::TM * C::LD, (hipStream_t)stream, features,
-                     xyz, nbr, wpacked, R, N, K, dh3d_ep(ep), out, (const int32_t *)nullptr, 0, wpost_packed, out2);
-  return dh3d_launch_status();
-}
-
 DH3D_API int dh3d_flex_conv_pm_fwd(const float *features, const float *xyz, const int32_t *nbr,
                                    const float *wpacked, int B, int N, int K, int Din, int Dout,
                                    const dh3d_epilogue *ep, float *out, void *stream) {
@@ -584,9 +538,3 @@ DH3D_API int dh3d_conv_pointset_pool_pm_fwd(const float *xyz, const int32_t *nbr
     hipLaunchKernelGGL(pointset_pool_kernel<32>, grid, block, 0, s, S, nbr, theta, bias, (int)R, N, e, out);
   return dh3d_launch_status();
 }
-
-#ifdef DH3D_FLEX_PROBE
-DH3D_API int dh3d_flex_probe_read(long long *host, int n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fprobe), sizeof(long long) * n) == hipSuccess ? 0 : 3;
-}
-#endif

@@ -2,7 +2,7 @@
 // sampled levels' shapes (Din 64 / 128 -> Dout 128 / 256, K = 8) and BASELINE config 5's 128 -> 128, K = 12.
 //
 // flex_conv_pm_kernel (flex_pm.hip) spends its time like this on 8 x 1024 points, 128 -> 128 (clock stamps of 64
-// workgroups, tools/flex_probe_n8.py): gather 9.3 k cycles, GEMM 20.4 k, store 2.9 k -- and the GEMM phase IS the f32 matrix
+// workgroups): gather 9.3 k cycles, GEMM 20.4 k, store 2.9 k -- and the GEMM phase IS the f32 matrix
 // pipe's floor for one 32-point tile per CU (256 v_mfma_f32_32x32x2_f32 of 64 cycles per SIMD = 16.4 k).  The same
 // product as six v_mfma_f32_32x32x16_bf16 per 16 k (32 cycles each) is 2.7x less pipe time.  Same factorisation, same
 // gather (two dependent round trips per tile, no load under a branch); the S tile goes to LDS as three bf16 planes
@@ -14,13 +14,6 @@
 #include "mfma_gemm.h"
 
 namespace {
-
-#ifdef DH3D_FLEX_PROBE  // dev instrumentation (tools/flex_probe_n8.py): cycle stamps of a few workgroups
-__device__ long long g_tprobe[64 * 8];
-#define TPROBE(i) do { if (threadIdx.x == 0 && blockIdx.x < 64) g_tprobe[blockIdx.x * 8 + (i)] = clock64(); } while (0)
-#else
-#define TPROBE(i) do { } while (0)
-#endif
 
 template <int DIN, int DOUT>
 struct TileCfg {
@@ -36,7 +29,8 @@ struct TileCfg {
 };
 
 // POST: the finished tile goes through one more linear layer [DOUT -> 64] on the f32 pipe (wpost = dh3d_pack_weight of
-// [DOUT, 64]) before it leaves the chip, both results stored (see flex_conv_pm_kernel).
+// [DOUT, 64]) before it leaves the chip, both results stored: the cluster logits `coarse @ cluster_weights` of NetVLAD
+// behind the global flex_conv (core/backbones.py:213-216 on the commuted form).
 // HALF: the planes hold one half of K at a time -- [S0|Sx], then [Sy|Sz], which wait in the registers of the threads that
 // reduced them: 51 KB of LDS instead of 100 at Din = 128, so that TWO workgroups share a CU and one's gather runs under the
 // other's products.  For launches with more tiles than CUs (cfg 5's 512 tiles, the global step's sampled level).
@@ -59,7 +53,6 @@ __global__ __launch_bounds__(256) void flex_conv_tx6_kernel(const float *__restr
   const long long grow0 = (long long)dh3d_xcd_remap(blockIdx.x, gridDim.x) * C::TM;
 
   // ---- phase A: gather-reduce S for TM points (two dependent round trips for the whole tile), split, planes
-  TPROBE(0);
   const int r4 = (tid % C::LPR) * 4;
   float4 keep[HALF ? C::ROUNDS : 1][2];  // HALF: [Sy|Sz] of this thread's rows until the planes are free again
   auto to_planes = [&](const float4 v, unsigned short *dst) __attribute__((always_inline)) {
@@ -129,9 +122,7 @@ __global__ __launch_bounds__(256) void flex_conv_tx6_kernel(const float *__restr
       }
     }
   }
-  TPROBE(1);
   __syncthreads();
-  TPROBE(2);
 
   // ---- phase B: S @ Wcat, six bf16 products per f32 product, weight fragments four K-steps ahead
   f32x16 acc[C::NT];
@@ -208,10 +199,6 @@ __global__ __launch_bounds__(256) void flex_conv_tx6_kernel(const float *__restr
       }
     }
   }
-#ifdef DH3D_FLEX_PROBE
-  asm volatile("" :: "v"(acc[0][0]));
-#endif
-  TPROBE(3);
   // ---- epilogue through the (now dead) planes
   __syncthreads();
   wave_tiles_to_lds<C::NT>(acc, er, ep.act, s_out, LDO, 0, wave, 4);
@@ -228,7 +215,6 @@ __global__ __launch_bounds__(256) void flex_conv_tx6_kernel(const float *__restr
     __syncthreads();
     block_store_rows(s_out + DOUT, LDO, C::TM, grow0, R, 64, nullptr, out2);
   }
-  TPROBE(4);
 }
 
 template <int DIN, int DOUT, int KT, bool POST, bool HALF>
@@ -247,10 +233,8 @@ template <int DIN, int DOUT, int KT, bool POST>
 int tx6_launch(const float *feat, const float *xyz, const int32_t *nbr, const void *wp3, int B, int N,
                const EpilogueArgs &ep, float *out, const float *wpost, float *out2, hipStream_t s) {
   // more tiles than CUs: half-K planes, two workgroups per CU (Din = 128: 51 KB each instead of 100)
-#ifndef DH3D_TX6_HALF_TILES
-#define DH3D_TX6_HALF_TILES 256
-#endif
-  if (DIN == 128 && (long long)B * N > 32ll * DH3D_TX6_HALF_TILES)
+  constexpr int kHalfTiles = 256;
+  if (DIN == 128 && (long long)B * N > 32ll * kHalfTiles)
     return tx6_launch_h<DIN, DOUT, KT, POST, true>(feat, xyz, nbr, wp3, B, N, ep, out, wpost, out2, s);
   return tx6_launch_h<DIN, DOUT, KT, POST, false>(feat, xyz, nbr, wp3, B, N, ep, out, wpost, out2, s);
 }
@@ -275,9 +259,3 @@ DH3D_API int dh3d_flex_conv_pm_tile_x6_fwd(const float *features, const float *x
 #undef DH3D_TX6_CASE
   return DH3D_ERR_UNSUPPORTED;
 }
-
-#ifdef DH3D_FLEX_PROBE
-DH3D_API int dh3d_flex_tprobe_read(long long *host, int n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_tprobe), sizeof(long long) * n) == hipSuccess ? 0 : 3;
-}
-#endif

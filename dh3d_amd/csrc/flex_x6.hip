@@ -48,29 +48,8 @@ struct X6Cfg {
   static_assert(DOUT == 64 && (VEC == 2 || VEC == 4) && KBH % 2 == 0 && LDS_BYTES <= 159 * 1024, "shape");
 };
 
-#ifdef DH3D_X6_PROBE  // dev instrumentation (tools/x6_probe.py): cycle stamps of one workgroup's two roles
-__device__ long long g_x6probe[2][64][8];
-#define XPROBE(role, it, k)                                                                     \
-  do {                                                                                          \
-    if (blockIdx.x == 8 && (threadIdx.x == 0 || threadIdx.x == kProducers) && (it) < 64) g_x6probe[role][it][k] = clock64(); \
-  } while (0)
-#else
-#define XPROBE(role, it, k) do { } while (0)
-#endif
-
 // LDS traffic of this wave done, then workgroup barrier.  Global loads stay in flight across it.
-#if defined(DH3D_X6_PROBE) && DH3D_X6_PROBE == 5  // probe 5: arrival / departure time of every wave at every barrier
-__device__ long long g_x6bar[12][16][2];
-__device__ __forceinline__ void wg_barrier(int k = 0) {
-  const int w = threadIdx.x >> 6;
-  const bool rec = blockIdx.x == 8 && (threadIdx.x & 63) == 0 && k < 16;
-  if (rec) g_x6bar[w][k][0] = clock64();
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  if (rec) g_x6bar[w][k][1] = clock64();
-}
-#else
 __device__ __forceinline__ void wg_barrier(int = 0) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#endif
 
 // value of lane K of the caller's 16-lane row (v_mov_b32_dpp row_newbcast: an integer-class VALU op)
 template <int K>
@@ -121,10 +100,7 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
     // FP32 VALU work only issues in the gaps of the consumers' MFMA stream: with the producers ahead in the issue
     // arbitration those gaps open as soon as an FP instruction is ready instead of at the end of a GEMM burst
     // (measured 26.9 -> 25.9 us per launch)
-#ifndef DH3D_X6_PRIO
-#define DH3D_X6_PRIO 1
-#endif
-    if (DH3D_X6_PRIO & 1) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     const int prow = tid >> 4, lj = tid & 15;
     const int c0 = lj * C::VEC;  // first channel of this lane
     const unsigned mrec = (unsigned)(0x100000000ULL / N);
@@ -260,12 +236,7 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
           const int gg = g + s;
           issue_feat(s ^ 1, gg + 1);
           issue_ids(s ^ 1, gg + 3);
-#if !(defined(DH3D_X6_EXP) && (DH3D_X6_EXP & 4))
           compute(s, gg);
-#else
-          asm volatile("" :: "v"(reinterpret_cast<const float *>(&fv[s][0])[0]), "v"(reinterpret_cast<const float *>(&fv[s][7])[1]),
-                       "v"(qd[s][0]), "v"(pcd[s]));
-#endif
           if (gg % C::ROUNDS == C::ROUNDS - 1 && gg < G) wg_barrier(gg / C::ROUNDS);
         }
       }
@@ -280,30 +251,16 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const int gg = g + s;
-          XPROBE(0, gg, 0);
-#if defined(DH3D_X6_PROBE) && DH3D_X6_PROBE == 2
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-          XPROBE(0, gg, 1);
-#if (!defined(DH3D_X6_PROBE) || DH3D_X6_PROBE != 3) && !(defined(DH3D_X6_EXP) && (DH3D_X6_EXP & 4))   // probe 3 / exp 4: producers only load (timing experiment)
           compute(s, gg);
-#else
-          asm volatile("" :: "v"(reinterpret_cast<const float *>(&fv[s][0])[0]), "v"(reinterpret_cast<const float *>(&fv[s][7])[1]),
-                       "v"(qd[s][0]), "v"(pcd[s]));
-#endif
-          XPROBE(0, gg, 2);
           issue_feat(s, gg + 2);
           issue_ids(s, gg + 4);
-          XPROBE(0, gg, 3);
           if (gg % C::ROUNDS == C::ROUNDS - 1 && gg < G) wg_barrier(gg / C::ROUNDS);  // tile gg / ROUNDS is staged
-          XPROBE(0, gg, 4);
         }
       }
     }
     wg_barrier(cnt);  // the consumers' last partial tiles
   } else {
     // ------------------------------------------------------------------ consumers
-    if (DH3D_X6_PRIO & 2) __builtin_amdgcn_s_setprio(3);
     const int cw = wave - kProducers / 64, lane = tid & 63;
     const int cb = cw & 1, kh = cw >> 1;
     // Weights: the two large bf16 planes of this wave's (K-half, column block) quarter live in registers for the
@@ -372,7 +329,6 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
             a[(kb + 1) & 1][p] = *reinterpret_cast<const bf16x8 *>(abase + p * kTM * C::LD + (kb + 1) * 16);
           b3r[(kb + 1) & 1] = s_b3[(size_t)(kb + 1) * 64];
         }
-#if !((defined(DH3D_X6_PROBE) && DH3D_X6_PROBE == 4) || (defined(DH3D_X6_EXP) && (DH3D_X6_EXP & 8)))  // probe 4 / exp 8: no MFMAs (timing experiment)
         const bf16x8 a1 = a[kb & 1][0], a2 = a[kb & 1][1], a3 = a[kb & 1][2];
         const bf16x8 b1 = __builtin_bit_cast(bf16x8, breg[kb][0]), b2 = __builtin_bit_cast(bf16x8, breg[kb][1]),
                      b3 = __builtin_bit_cast(bf16x8, b3r[kb & 1]);
@@ -382,8 +338,6 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc1, 0, 0, 0);
         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc1, 0, 0, 0);
-#endif
-#if !(defined(DH3D_X6_EXP) && (DH3D_X6_EXP & 2))   // exp 2: no partial exchange / epilogue / store (timing experiment, results wrong)
         if (PREV) {
 #pragma unroll
           for (int jj = 0; jj < 8 / C::KBH; ++jj) {
@@ -394,7 +348,6 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
             if (!RAGGED || grow_prev + rowoff < R) reinterpret_cast<int *>(orow)[rowoff * DOUT] = vi;
           }
         }
-#endif
         // the order above within the k-block: loads first, then MFMAs with one independent instruction behind each
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
@@ -405,7 +358,6 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-#if !(defined(DH3D_X6_EXP) && (DH3D_X6_EXP & 2))
       // K-half sum of the two chains; own half stays in registers, the other half goes to the partner
       float sum[16];
 #pragma unroll
@@ -414,25 +366,15 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
       for (int j = 0; j < 8; ++j) keep[j] = kh ? sum[8 + j] : sum[j];
       p_mine[(size_t)(i & 1) * 512] = kh ? make_float4(sum[0], sum[1], sum[2], sum[3]) : make_float4(sum[8], sum[9], sum[10], sum[11]);
       p_mine[(size_t)(i & 1) * 512 + 64] = kh ? make_float4(sum[4], sum[5], sum[6], sum[7]) : make_float4(sum[12], sum[13], sum[14], sum[15]);
-#else
-      asm volatile("" :: "v"(acc0), "v"(acc1));
-#endif
     };
 
     wg_barrier(0);  // tile 0 staged
-    XPROBE(1, 0, 0);
     tile(0, std::false_type{});
-    XPROBE(1, 0, 1);
     wg_barrier(1);  // halves of tile 0 exchanged, tile 1 staged
-    XPROBE(1, 0, 2);
     for (int i = 1; i < cnt; ++i) {
-      XPROBE(1, i, 0);
       tile(i, std::true_type{});
-      XPROBE(1, i, 1);
       wg_barrier(i + 1);  // halves of tile i exchanged, tile i+1 staged
-      XPROBE(1, i, 2);
     }
-#if !(defined(DH3D_X6_EXP) && (DH3D_X6_EXP & 2))
     {  // the last tile's epilogue
       const int i = cnt;
       const float4 pp0 = p_partner[(size_t)((i - 1) & 1) * 512], pp1 = p_partner[(size_t)((i - 1) & 1) * 512 + 64];
@@ -446,7 +388,6 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
         if (!RAGGED || grow_prev + rowoff < R) reinterpret_cast<int *>(orow)[rowoff * DOUT] = vi;
       }
     }
-#endif
   }
 }
 
@@ -512,17 +453,6 @@ int flex_conv_x6_launch(const float *feat, const float *xyz, const int32_t *nbr,
 }
 
 }  // namespace
-
-#if defined(DH3D_X6_PROBE) && DH3D_X6_PROBE == 5
-DH3D_API int dh3d_x6_bar_read(long long *host, int n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_x6bar), sizeof(long long) * n) == hipSuccess ? 0 : 3;
-}
-#endif
-#ifdef DH3D_X6_PROBE
-DH3D_API int dh3d_x6_probe_read(long long *host, int n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_x6probe), sizeof(long long) * n) == hipSuccess ? 0 : 3;
-}
-#endif
 
 DH3D_API int dh3d_pack_flex_weight_x3(const float *theta, const float *bias, int Din, int Dout, void *packed,
                                       void *stream) {

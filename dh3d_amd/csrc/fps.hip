@@ -28,16 +28,6 @@ namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifdef DH3D_FPS_PROBE  // dev instrumentation (tools/fps_list_phases.py): per-phase cycle sums of one wave of cloud 0
-__device__ long long g_probe[32];
-#ifndef DH3D_FPS_PROBE_WAVE
-#define DH3D_FPS_PROBE_WAVE 0
-#endif
-#define STAMP(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); pt[i] = clock64(); } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-
 __device__ __forceinline__ int fps_key(int k) { return ((k & 511) << 16) | (k >> 9); }
 __device__ __forceinline__ int fps_unkey(int key) { return ((key & 0xffff) << 9) | (key >> 16); }
 
@@ -271,11 +261,7 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
   float delta = 0.05f;                                      // listing margin, relative to the wave maximum
   int npick = 1, r = 1;
   constexpr unsigned long long kPickMask = PPT == 64 ? ~0ull : ((1ull << (PPT & 63)) - 1ull);
-#ifdef DH3D_FPS_PROBE
-  long long pt[12];
-#endif
   while (r < m) {
-    STAMP(0);
     // 1. box tests, PP picks per pass: can pick p change anything in group g?  Then the updates.
     bool touched = false;
     for (int p0 = 0; p0 < npick; p0 += PP) {
@@ -307,7 +293,6 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
         }
       }
     }
-    STAMP(1);
     if (touched) {  // wave-uniform: new arg-max, list and bound (an untouched wave's published state stays valid)
       float b1 = -2.f, b2 = -2.f;
       int lkey = INT_MAX;
@@ -373,9 +358,7 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
       }
       delta = cnt > HI ? delta * 0.7f : (cnt < LO ? fminf(delta * 1.3f, 0.5f) : delta);
     }
-    STAMP(2);
     __syncthreads();
-    STAMP(3);
     // 2. the judge: sequential FPS on the pool
     if (wave == 0) {
       const float2 e = s_list[lane];
@@ -392,7 +375,6 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
       int kl = 0, k = 0;  // lane k of kl: the pool lane of pick k
       int rbe = -1;  // the first pick of a sync is unconditional
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(cx), "+v"(cy), "+v"(cz), "+v"(cv));
-      STAMP(7);
       while (true) {
         // One pick per trip, hand-scheduled (compiled: 57 instructions and three taken branches, 375 cycles per pick).
         // The pool lane of pick k goes into lane k of kl with v_writelane; its record is fetched after the loop.
@@ -453,7 +435,6 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
         cv = __builtin_fminf(d, cv);
         if (++k == cap) break;
       }
-      STAMP(8);
       {  // lane k fetches pick k's record from its pool lane (ds_bpermute: no LDS memory involved)
         const float kx = __int_as_float(__builtin_amdgcn_ds_bpermute(kl << 2, __float_as_int(cx)));
         const float ky = __int_as_float(__builtin_amdgcn_ds_bpermute(kl << 2, __float_as_int(cy)));
@@ -466,20 +447,9 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
       }
       if (lane == 0) s_np[0] = k;
     }
-    STAMP(4);
     __syncthreads();
-    STAMP(5);
     npick = s_np[0];
     r += npick;
-#ifdef DH3D_FPS_PROBE
-    if (tid == 64 * DH3D_FPS_PROBE_WAVE && blockIdx.x == 0) {
-      for (int i = 0; i < 5; ++i) g_probe[i] += pt[i + 1] - pt[i];
-      if (wave == 0) { g_probe[6] += pt[7] - pt[3]; g_probe[7] += pt[8] - pt[7]; g_probe[8] += pt[4] - pt[8]; }
-      g_probe[13] += npick;
-      g_probe[14] += touched;
-      g_probe[15] += 1;
-    }
-#endif
   }
   __syncthreads();
   for (int i = tid; i < m; i += 64 * WAVES) out[(size_t)b * m + i] = s_out[i];
@@ -765,9 +735,3 @@ DH3D_API int dh3d_fps_sorted_ordered(const float *sorted, const float *gbox, con
   oo.occ_min = (int)(0.6 * 4096.0 * (1.0 - exp(-(double)m / 4096.0)));  // spatial.hip sort_launch's rule for m points
   return fps_sorted_dispatch(sorted, gbox, B, N, m, out, xyz_out, nullptr, stream, oo);
 }
-
-#ifdef DH3D_FPS_PROBE
-DH3D_API int dh3d_fps_probe_read(long long *host32) {
-  return hipMemcpyFromSymbol(host32, HIP_SYMBOL(g_probe), sizeof(long long) * 32) == hipSuccess ? 0 : 3;
-}
-#endif

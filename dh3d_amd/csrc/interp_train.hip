@@ -121,12 +121,9 @@ __global__ __launch_bounds__(256) void interp_bn_kernel(const InterpBnArgs a) {
   }
   // (not in MODE 2: 64 more registers would leave one wave per SIMD there)
   constexpr bool PREFETCH = MODE != 2 && MODE != 4;
-#if !defined(DH3D_IB_EXP) || !(DH3D_IB_EXP & 16)   // exp 16: no staging (results wrong)
   if (MODE != 3 && PREFETCH) rg = request_rows<CAP / 4>(a.G, rowoff);
-#endif
   for (int sl = 0; sl < a.NS; ++sl) {
     const float *Gs = MODE == 3 ? nullptr : a.G + (size_t)sl * a.SS + (size_t)bi * m * a.RS;
-#if !defined(DH3D_IB_EXP) || !(DH3D_IB_EXP & 16)
     if (MODE != 3) {
       if (!PREFETCH) rg = request_rows<CAP / 4>(a.G + (size_t)sl * a.SS, rowoff);
 #pragma unroll
@@ -138,7 +135,6 @@ __global__ __launch_bounds__(256) void interp_bn_kernel(const InterpBnArgs a) {
       // (unconditional -- the last slice once more: a load under a branch would be merged through memory)
       if (PREFETCH) rg = request_rows<CAP / 4>(a.G + (size_t)(sl + 1 < a.NS ? sl + 1 : sl) * a.SS, rowoff);
     }
-#endif
     const int c = sl * 256 + lane * 4;
     float4 q0 = {}, q1 = {}, q2 = {}, q3 = {}, wf = {};
     if (MODE == 1 || MODE == 2) {
@@ -181,9 +177,7 @@ __global__ __launch_bounds__(256) void interp_bn_kernel(const InterpBnArgs a) {
           }
         }
       };
-#if !defined(DH3D_IB_EXP) || !(DH3D_IB_EXP & 32)   // exp 32: no per-point work (results wrong)
       if (overflow) points(std::true_type{}); else points(std::false_type{});
-#endif
       // the four waves hold different points of the same channels: through LDS (the row buffer is dead by now), then
       // one f64 atomic per channel
       __syncthreads();
@@ -198,11 +192,7 @@ __global__ __launch_bounds__(256) void interp_bn_kernel(const InterpBnArgs a) {
         for (int k = 0; k < (MODE == 1 ? 3 : 2); ++k) {
           const double v = ((double)red[(k * 4 + 0) * 256 + tid] + red[(k * 4 + 1) * 256 + tid]) +
                            ((double)red[(k * 4 + 2) * 256 + tid] + red[(k * 4 + 3) * 256 + tid]);
-#if defined(DH3D_IB_EXP) && (DH3D_IB_EXP & 8)   // timing experiment: no statistics atomics (results wrong)
-          if (v == 123.456) a.s0[0] = v;
-#else
           unsafeAtomicAdd((k == 0 ? a.s0 : k == 1 ? a.s1 : a.s2) + ch, v);
-#endif
         }
       }
       __syncthreads();  // rows and partial sums are overwritten by the next slice
@@ -292,12 +282,8 @@ __global__ __launch_bounds__(256) void interp_bn_kernel(const InterpBnArgs a) {
             if (rt < nrt) {
               const int jrow = rt * 32 + (lane & 31);
               const float sv = (si.x == jrow ? sw.x : 0.f) + (si.y == jrow ? sw.y : 0.f) + (si.z == jrow ? sw.z : 0.f);
-#if defined(DH3D_IB_EXP) && (DH3D_IB_EXP & 1)   // timing experiment: no MFMAs (results wrong)
-              asm volatile("" :: "v"(sv), "v"(b0), "v"(b1));
-#else
               acc[rt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(sv, b0, acc[rt][0], 0, 0, 0);
               acc[rt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(sv, b1, acc[rt][1], 0, 0, 0);
-#endif
             }
           }
         }
@@ -311,13 +297,7 @@ __global__ __launch_bounds__(256) void interp_bn_kernel(const InterpBnArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int j = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);  // 32x32 accumulator layout
-#if defined(DH3D_IB_EXP) && (DH3D_IB_EXP & 2)   // timing experiment: plain stores instead of atomics (results wrong)
-              if (j < nd) dGs[(size_t)s_row[j] * a.RS + wave * 64 + ct * 32 + (lane & 31)] = acc[rt][ct][r];
-#elif defined(DH3D_IB_EXP) && (DH3D_IB_EXP & 4)   // timing experiment: no flush at all
-              if (j < nd && acc[rt][ct][r] == 123.456f) dGs[0] = 1.f;
-#else
               if (j < nd) unsafeAtomicAdd(dGs + (size_t)s_row[j] * a.RS + wave * 64 + ct * 32 + (lane & 31), acc[rt][ct][r]);
-#endif
             }
         }
       }

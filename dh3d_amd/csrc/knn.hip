@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__re
     // 32 candidates per iteration: 24 broadcast LDS reads + 48 packed ops with nothing between them that
     // depends on the lane's list, so they pipeline; ONE wave-uniform test decides whether anybody needs the
     // slow path (a per-8 branch serialised every step behind its own LDS latency: 650-800 cycles/step
-    // measured with one wave per SIMD, tools/knn_probe.py).
+    // measured with one wave per SIMD).
     const int len32 = (len8 + 31) & ~31;  // the image is padded with +inf up to a multiple of 32
     for (int j = 0; j < len32; j += 32) {
       f32x2 s[4][4];
@@ -290,9 +290,6 @@ __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__re
 constexpr int kSortedWaves = 4;
 constexpr int kCellInts = 4112;  // ints per cloud of the cell table (spatial.hip)
 constexpr int kCellFlag = 4106;  // ... [kCellFlag]: 1 = not a cloud for cell lists (dense cells), the pruned scan takes it
-#ifdef DH3D_KNN_PROBE  // dev instrumentation (tools/knn_probe.py): per-wave cycle / event counters
-__device__ long long g_kprobe[8 * 4096];
-#endif
 
 template <int KMAX>
 __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const float4 *__restrict__ sorted,
@@ -329,15 +326,7 @@ __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const flo
   int cnt = 0;
   float wave_bound = INFINITY;  // max over the wave's valid lanes of st.bound (refreshed after each drain)
 
-#ifdef DH3D_KNN_PROBE
-  long long pr_t0 = clock64(), pr_drain = 0;
-  int pr_ndrain = 0, pr_nslots = 0, pr_ngroups = 0;
-#endif
   auto drain = [&]() {
-#ifdef DH3D_KNN_PROBE
-    const long long d0 = clock64();
-    ++pr_ndrain;
-#endif
     // ONE copy of the (long) insertion per drain site, the next slot requested from LDS while this one is inserted.
     // Unrolled over the 16 slots the kernel was > 100 KB of code (the drain is inlined at every site of the scan); the
     // instruction cache coped with that in the shipped build (0.2 % misses, profiles/r03_d_pmc_knn.txt) but not in the
@@ -348,23 +337,14 @@ __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const flo
     for (int i = 0; i < deepest; ++i) {  // wave-uniform trip count
       const uint2 e = nxt;
       if (i + 1 < deepest) nxt = my_q[(i + 1) * 64 + lane];
-#ifdef DH3D_KNN_PROBE
-      ++pr_nslots;
-#endif
       if (i < cnt) knn_offer<KMAX>(st, __uint_as_float(e.x), (int)e.y, lad);
     }
     cnt = 0;
     wave_bound = wave_max_f32(valid ? st.bound : 0.f);
-#ifdef DH3D_KNN_PROBE
-    pr_drain += clock64() - d0;
-#endif
   };
 
   // evaluate the 64 candidates of group gcc (records already in `cr`, one per lane)
   auto scan_group = [&](int gcc, const float4 cr) {
-#ifdef DH3D_KNN_PROBE
-    ++pr_ngroups;
-#endif
     my_c[cand_slot(lane, 0)] = cr.x;
     my_c[cand_slot(lane, 1)] = cr.y;
     my_c[cand_slot(lane, 2)] = cr.z;
@@ -460,12 +440,6 @@ __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const flo
     }
   }
   if (__any(cnt > 0)) drain();
-#ifdef DH3D_KNN_PROBE
-  if (lane == 0 && b == 0) {
-    long long *o = g_kprobe + (size_t)g * 8;
-    o[0] = clock64() - pr_t0; o[1] = pr_drain; o[2] = pr_ndrain; o[3] = pr_nslots; o[4] = pr_ngroups;
-  }
-#endif
 
   if (valid) {
     const int y = __float_as_int(qr.w);  // original index of this query
@@ -543,10 +517,6 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
   s_share[wave][lane] = INFINITY;
   s_kth[wave][lane] = INFINITY;
   __syncthreads();
-#ifdef DH3D_KNN_PROBE
-  long long pr_t0 = clock64(), pr_drain = 0, pr_scan = 0;
-  int pr_ndrain = 0, pr_nslots = 0, pr_ngroups = 0, pr_hits = 0, pr_sparse = 0, pr_sparse_slots = 0, pr_entries = 0, pr_halfskip = 0, pr_steps = 0;
-#endif
 
   // everyone's progress -> my screen: the true K-th distance is at most any wave's own K-th, and at most the largest
   // of the S R-th distances
@@ -562,28 +532,12 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
   };
 
   auto drain = [&]() {
-#ifdef DH3D_KNN_PROBE
-    const long long d0 = clock64();
-    ++pr_ndrain;
-#endif
     const int deepest = -wave_min_i32(-cnt);
-#ifdef DH3D_KNN_PROBE
-    {
-      const int deep = __popcll(__ballot(cnt > 4));
-      int tot = cnt;
-      for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
-      pr_entries += tot;
-      if (deep <= 3) { ++pr_sparse; pr_sparse_slots += deepest; }
-    }
-#endif
     uint2 nxt = my_q[lane];
 #pragma unroll 1
     for (int i = 0; i < deepest; ++i) {  // one copy of the insertion per site (code size, see knn_sorted_kernel)
       const uint2 e = nxt;
       if (i + 1 < deepest) nxt = my_q[(i + 1) * 64 + lane];
-#ifdef DH3D_KNN_PROBE
-      ++pr_nslots;
-#endif
       if (i < cnt) knn_offer<KMAX, true>(st, __uint_as_float(e.x), (int)e.y, lad);
     }
     cnt = 0;
@@ -601,16 +555,9 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
       s_kth[wave][lane] = __fmul_rn(__fmul_rn(dk, dk), 1.000001f);
     }
     adopt(mx);
-#ifdef DH3D_KNN_PROBE
-    pr_drain += clock64() - d0;
-#endif
   };
 
   auto scan_group = [&](int gcc, const float4 cr) {
-#ifdef DH3D_KNN_PROBE
-    ++pr_ngroups;
-    const long long s0 = clock64(), dr0 = pr_drain;
-#endif
     my_c[cand_slot(lane, 0)] = cr.x;
     my_c[cand_slot(lane, 1)] = cr.y;
     my_c[cand_slot(lane, 2)] = cr.z;
@@ -618,24 +565,6 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
     __builtin_amdgcn_wave_barrier();
     const int clen = min(64, N - gcc * 64);
     for (int j = 0; j < clen; j += 32) {
-#ifdef DH3D_KNN_PROBE  // would a per-query test against the box of these 32 candidates have skipped the step?
-      {
-        const bool mine = (lane >> 5) == (j >> 5);   // the half-group's candidates sit in lanes 32*(j/32)..
-        float lo[3] = {mine ? cr.x : INFINITY, mine ? cr.y : INFINITY, mine ? cr.z : INFINITY};
-        float hi[3] = {mine ? cr.x : -INFINITY, mine ? cr.y : -INFINITY, mine ? cr.z : -INFINITY};
-        if (cr.x == INFINITY) { hi[0] = hi[1] = hi[2] = -INFINITY; }  // padding records
-#pragma unroll
-        for (int c3 = 0; c3 < 3; ++c3)
-          for (int off = 32; off > 0; off >>= 1) {
-            lo[c3] = fminf(lo[c3], __shfl_xor(lo[c3], off, 64));
-            hi[c3] = fmaxf(hi[c3], __shfl_xor(hi[c3], off, 64));
-          }
-        const float px = fmaxf(fmaxf(lo[0] - qr.x, qr.x - hi[0]), 0.f), py = fmaxf(fmaxf(lo[1] - qr.y, qr.y - hi[1]), 0.f),
-                    pz = fmaxf(fmaxf(lo[2] - qr.z, qr.z - hi[2]), 0.f);
-        if (!__any(valid && (px * px + py * py + pz * pz) * 0.99999f <= st.bound)) ++pr_halfskip;
-        ++pr_steps;
-      }
-#endif
       f32x2 sq[4][4];
       float mn[4];
 #pragma unroll
@@ -645,9 +574,6 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
       }
       const float m = fminf(fminf(mn[0], mn[1]), fminf(mn[2], mn[3]));
       if (__any(valid && m <= st.bound)) {
-#ifdef DH3D_KNN_PROBE
-        ++pr_hits;
-#endif
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           if (valid && mn[u] <= st.bound) {
@@ -665,9 +591,6 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
       }
     }
     __builtin_amdgcn_wave_barrier();
-#ifdef DH3D_KNN_PROBE
-    pr_scan += (clock64() - s0) - (pr_drain - dr0);
-#endif
   };
   auto load_group = [&](int gcc) { const int ci = gcc * 64 + lane; return ci < N ? sc[ci] : pad; };
 
@@ -769,14 +692,6 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
     }
   }
   if (__any(cnt > 0)) drain();
-#ifdef DH3D_KNN_PROBE
-  if (lane == 0 && ((b * NG + g) * S + wave) < 4096) {
-    long long *o = g_kprobe + (size_t)((b * NG + g) * S + wave) * 8;
-    o[7] = pr_halfskip * 1000 + pr_steps;
-    o[0] = clock64() - pr_t0; o[1] = pr_drain; o[2] = pr_ndrain; o[3] = pr_nslots; o[4] = pr_ngroups;
-    o[5] = pr_scan; o[6] = pr_hits + 1000 * pr_sparse + 1000000ll * pr_sparse_slots + 1000000000ll * pr_entries;
-  }
-#endif
 
   // merge the S lists (tree: w <- w + step), keys are unique so plain insertion
   for (int step = S / 2; step >= 1; step >>= 1) {
@@ -1024,13 +939,6 @@ DH3D_API int dh3d_knn_bruteforce_xyz(const float *xyz, int B, int N, int K, int3
   return knn_launch<true>(xyz, B, N, K, nn, dist, (hipStream_t)stream);
 }
 
-#ifdef DH3D_DEV  // dev builds only (tools/geo_bench.py): waves per query group of the ordered search; -1 = default
-static int g_knn_split = -1;
-DH3D_API void dh3d_dev_set_knn_split(int s) { g_knn_split = s; }
-#else
-static constexpr int g_knn_split = -1;
-#endif
-
 static int knn_sorted_launch(const float *sorted, const float *gbox, int B, int N, int K, int32_t *nn, float *dist,
                              const int *gate, void *stream) {
   DH3D_REQUIRE(sorted && gbox && nn && dist && B > 0 && N > 0 && K > 0);
@@ -1043,7 +951,7 @@ static int knn_sorted_launch(const float *sorted, const float *gbox, int B, int 
   // waves per query group (0 = the one-wave kernel): as many as keep the chip at <= ~4 waves per SIMD, where the
   // search turns from latency- to issue-bound (MI355X: 8x8192 0.194 -> 0.109 ms at 4; 32x4096 0.178 -> 0.147 at 2)
   const long long groups = (long long)NG * B;
-  const int S = g_knn_split >= 0 ? g_knn_split : groups <= 256 ? 8 : groups <= 1280 ? 4 : groups <= 4096 ? 2 : 0;
+  const int S = groups <= 256 ? 8 : groups <= 1280 ? 4 : groups <= 4096 ? 2 : 0;
   if (S > 0 && K <= 16) {
     dim3 sgrid(NG, B);
 #define DH3D_SPLIT_CASE(KM, SS)                                                                               \
@@ -1129,13 +1037,6 @@ __device__ __forceinline__ void knn_merge_sublanes(KnnState<8> &st) {
     st.bound = __fmul_rn(__fmul_rn(dk, dk), 1.000001f);
   }
 }
-
-#ifdef DH3D_GRID_PROBE  // dev instrumentation (tools/knn_grid_probe.py): cycle stamps of the first wave of 64 workgroups
-__device__ long long g_gprobe[64 * 8];
-#define GPROBE(i) do { if (threadIdx.x == 0 && blockIdx.x < 64 && blockIdx.y == 0) g_gprobe[blockIdx.x * 8 + (i)] = clock64(); } while (0)
-#else
-#define GPROBE(i) do { } while (0)
-#endif
 
 // L = lanes per query (2, 4 or 8): fewer lanes = longer private candidate streams, but an insertion round serves 64 / L
 // queries and the merge has log2(L) steps.
@@ -1369,17 +1270,13 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   };
   // The columns are dealt DENSELY: walking all 25 with the other pass's columns skipped cost the wave the full body in
   // nearly every iteration (some lane always had a live column) -- clock stamps: the first pass's 27 cells took as long
-  // as the second's 98 (tools/knn_grid_probe.py), and the two together two thirds of the kernel.
-  GPROBE(0);
+  // as the second's 98, and the two together two thirds of the kernel.
   // pass 0: shells 0-1 = the nine inner columns at dx in -1..1
   begin_pass();
 #pragma unroll 1
   for (int ci = sub; ci < 9; ci += L) column(std::integral_constant<int, 0b01110>{}, 1 + ci % 3, 1 + ci / 3);
-  GPROBE(1);
   drain();
-  GPROBE(2);
   knn_merge_sublanes<L>(st);
-  GPROBE(3);
   // pass 1: every other cell the ball of the merged bound meets.  The K nearest neighbours all lie within the K-th distance
   // seen so far, so the cells to look at are a BOX with its own radius per axis -- two cells each way in a uniform cloud
   // (the 5 x 5 x 5 block of the first versions of this kernel), one cell in x / y and four thin layers in z on the ground
@@ -1413,11 +1310,8 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     if (abs(dy) <= 1 && abs(dz) <= 1) column(std::integral_constant<int, 0b10001>{}, dy + 2, dz + 2);  // (dx in -1..1: pass 0)
     else column(std::integral_constant<int, 0b11111>{}, dy + 2, dz + 2);
   }
-  GPROBE(4);
   drain();
-  GPROBE(5);
   knn_merge_sublanes<L>(st);
-  GPROBE(6);
   // What is left -- sparse corners, outliers, clusters that put everything into a few cells -- restarts against the bound
   // it has, over the 64-point groups of the Morton order whose box the search ball meets (the sort's group boxes): exact
   // (the list is emptied first, every point within the bound is offered again, nothing twice) and bounded: N / 64 box
@@ -1476,10 +1370,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   }
 }
 
-#ifndef DH3D_GRID_LANES
-#define DH3D_GRID_LANES 4
-#endif
-constexpr int kGridLanes = DH3D_GRID_LANES;  // per query
+constexpr int kGridLanes = 4;  // per query
 
 // The launch plan of dh3d_knn_grid -- the one place its thresholds live (dh3d_knn_grid, dh3d_knn_grid_plan).
 //   sf: how a crowded cloud is served.  4 / 2 = the pruned scan inside knn_grid_kernel<4, sf> (one launch); 0 =
@@ -1493,9 +1384,6 @@ static KnnGridPlan knn_grid_plan(int B, int N) {
   // one to two points per cell: all 4096 cells down to 4096 points (measured: 32 x 4096 77 us against 83 with half the
   // cells), one bit of the cell code less for every halving below that
   while (p.drop < 6 && ((long long)N << p.drop) <= 3072) ++p.drop;
-#ifdef DH3D_GRID_DROP_BIAS
-  p.drop = p.drop + (DH3D_GRID_DROP_BIAS) < 0 ? 0 : p.drop + (DH3D_GRID_DROP_BIAS);
-#endif
   // The clouds whose points crowd into few cells (the sort's verdict, cells[kCellFlag]) go to the pruned scan -- in the SAME
   // launch (four waves per query group = the cell lists' 256-thread workgroup) up to 4096 query groups, as a second launch
   // (whose workgroups leave at once for the other clouds) for the one-wave scan beyond that.
@@ -1535,15 +1423,3 @@ DH3D_API int dh3d_knn_grid(const float *sorted, const float *gbox, const int32_t
   if (dh3d_launch_status() != DH3D_OK) return DH3D_ERR_LAUNCH;
   return knn_sorted_launch(sorted, gbox, B, N, K, nn, dist, cells, stream);
 }
-
-#ifdef DH3D_GRID_PROBE
-DH3D_API int dh3d_grid_probe_read(long long *host, int n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gprobe), sizeof(long long) * n) == hipSuccess ? 0 : 3;
-}
-#endif
-
-#ifdef DH3D_KNN_PROBE
-DH3D_API int dh3d_knn_probe_read(long long *host, int n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_kprobe), sizeof(long long) * n) == hipSuccess ? 0 : 3;
-}
-#endif

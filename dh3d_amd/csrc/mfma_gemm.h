@@ -177,7 +177,7 @@ __device__ __forceinline__ void wave_store_f32(const f32x16 (&acc)[NT], long lon
 // ---------------------------------------------------------------------------------------------------------
 // Wide epilogue.  Storing an accumulator tile straight from registers is 16 global_store_dword per tile per
 // lane (256 B per instruction); measured on the flex_conv tile that store phase took as long as the GEMM
-// itself (store-issue bound, tools/flex_probe.py).  Instead: epilogue in registers -> tile into LDS (the A
+// itself (store-issue bound).  Instead: epilogue in registers -> tile into LDS (the A
 // tile is dead by then) -> the whole workgroup writes full rows with one 16-byte store per lane.
 struct EpilogueRegs {
   float pb, sc, sh;

@@ -28,14 +28,6 @@ constexpr int kThreads = 1024;
 constexpr int kWaves = 16;
 constexpr int kCellInts = 4112;  // ints per cloud of the cell table (dh3d_spatial_sort_cells)
 
-#ifdef DH3D_SORT_PROBE  // dev instrumentation (tools/sort_probe.py): s_memtime stamps of wave 0 / wave 15 of a few clouds
-__device__ long long g_sprobe[8 * 2 * 16];
-#define SPROBE(i) do { if ((threadIdx.x == 0 || threadIdx.x == 960) && blockIdx.x < 8) \
-  g_sprobe[(blockIdx.x * 2 + (threadIdx.x != 0)) * 16 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define SPROBE(i) do { } while (0)
-#endif
-
 __device__ __forceinline__ unsigned spread6(unsigned v) {  // 6 bits -> every third bit
   v &= 63u;
   v = (v | (v << 8)) & 0x300Fu;
@@ -94,7 +86,6 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
   // steps of 64: the arrangement the stable radix passes below need.
   const int SEG = npad / kWaves;  // = 64 * PPT
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  SPROBE(0);
   float px[PPT], py[PPT], pz[PPT];
   // every load of the thread is requested before the first one is used: no load sits under a branch (a padding lane
   // re-reads the last point) -- with `if (k < N) load` the compiler waited for each of the PPT loads in turn
@@ -110,7 +101,6 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
     lo[1] = fminf(lo[1], py[j]); hi[1] = fmaxf(hi[1], py[j]);
     lo[2] = fminf(lo[2], pz[j]); hi[2] = fmaxf(hi[2], pz[j]);
   }
-  SPROBE(1);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const float wl = wave_min_f32(lo[a]), wh = wave_max_f32(hi[a]);
@@ -187,7 +177,6 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
   // ---- three stable counting passes over 6-bit digits of the cell.  Per pass: every wave ranks its keys digit by
   // digit (same-digit lanes found with 6 ballots; the running per-(wave, digit) count lives in LDS), one block scan
   // of the 64 x 16 counts in (digit, wave) order gives the bases, and the keys move to their places.
-  SPROBE(2);
   unsigned *src = s_raw, *dst = s_raw + npad;
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   for (int pass = 0; pass < 3; ++pass) {
@@ -211,9 +200,7 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
       local[j] = before + rank;
       if (rank == 0) whist[d] = before + (unsigned)__popcll(same);  // one lane per digit; reads above precede it
     }
-    if (pass == 0) SPROBE(3);
     __syncthreads();
-    if (pass == 0) SPROBE(4);
     // exclusive scan over (digit, wave): thread t <-> digit t / 16, wave t % 16
     {
       const int d = tid >> 4, w = tid & 15;
@@ -232,21 +219,17 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
       s_hist[w * 64 + d] = base + inc - v;
     }
     __syncthreads();
-    if (pass == 0) SPROBE(5);
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
       const unsigned d = (key[j] >> shift) & 63u;
       dst[whist[d] + local[j]] = key[j];
     }
     __syncthreads();
-    if (pass == 0) SPROBE(6);
     // reload in the wave-contiguous arrangement for the next pass
 #pragma unroll
     for (int j = 0; j < PPT; ++j) key[j] = dst[wave * SEG + j * 64 + lane];
     unsigned *t = src; src = dst; dst = t;
-    if (pass == 0) SPROBE(7);
   }
-  SPROBE(8);
   const unsigned *s_keys = src;  // sorted
   // ---- sorted records + one box per 64: lane l of wave w owns positions (w + 16 j) * 64 + l.  Gather first (all PPT
   // rows requested together, padding lanes re-read the cloud's last sorted point), then store and reduce.
@@ -261,7 +244,6 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
   for (int j = 0; j < PPT; ++j) {
     gx[j] = pc[(size_t)gk[j] * 3]; gy[j] = pc[(size_t)gk[j] * 3 + 1]; gz[j] = pc[(size_t)gk[j] * 3 + 2];
   }
-  SPROBE(9);
 #pragma unroll
   for (int j = 0; j < PPT; ++j) {
     const int g = wave + kWaves * j;
@@ -314,7 +296,6 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
     __syncthreads();
     if (tid == 0) ct[4106] = s_occupied < occ_min ? 1 : 0;   // (the grid's header was written at the top)
   }
-  SPROBE(10);
 }
 
 template <int PPT>
@@ -332,12 +313,6 @@ int sort_launch(const float *xyz, int B, int N, float4 *sorted, float *gbox, int
 }
 
 }  // namespace
-
-#ifdef DH3D_SORT_PROBE
-DH3D_API int dh3d_sort_probe_read(long long *host, int n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sprobe), sizeof(long long) * n) == hipSuccess ? 0 : 3;
-}
-#endif
 
 static int spatial_sort_any(const float *xyz, int B, int N, float *sorted, float *gbox, int *cells, void *stream) {
   DH3D_REQUIRE(xyz && sorted && gbox && B > 0 && N > 0);

@@ -12,7 +12,6 @@ The forward is launch-bound when driven op by op from Python (about 30 short ker
 `DH3D.graphed(example)` captures it into one hipGraph (two streams: feature path + geometry path)
 and replays it with static buffers.
 """
-import os
 
 import torch
 from torch import nn
@@ -29,9 +28,6 @@ def tf_variable_name(state_dict_key):
     return name
 
 
-KNN_GRID = pm.KNN_GRID
-
-
 def _copy_in(src, dst):
     """dst (a graph's static input) <- src: device tensors by copy_, pinned host tensors by the staging kernel."""
     if (not src.is_cuda and src.is_pinned() and src.is_contiguous() and src.dtype == dst.dtype
@@ -39,12 +35,6 @@ def _copy_in(src, dst):
         pm.stage_copy(src, dst)
     else:
         dst.copy_(src, non_blocking=True)
-
-
-# Development A/B knobs (tools/single_stream_ab.py, the placement-hint sweeps): read only when DH3D_DEBUG_KNOBS=1, so a
-# production process cannot pick one up from a stray environment variable.
-_DEBUG_KNOBS = os.environ.get("DH3D_DEBUG_KNOBS") == "1"
-_DEV_RESERVE = int(os.environ["DH3D_DEV_RESERVE"]) if _DEBUG_KNOBS and os.environ.get("DH3D_DEV_RESERVE") else None
 
 
 class DH3D(nn.Module):
@@ -239,10 +229,10 @@ class DH3D(nn.Module):
         if points.shape[1] <= 16384 and (knn_inds is None or (4096 <= points.shape[1] and self.config.fps_contract is None)):
             # Morton order + group boxes: shared by the kNN (side) and the pruned FPS (here); + the cell table when the
             # kNN is the cell-list search
-            geo.ordered(cells=knn_inds is None and self.knn_num <= 8 and KNN_GRID)
+            geo.ordered(cells=knn_inds is None and self.knn_num <= 8)
         if self._geo_stream is None:
             self._geo_stream = torch.cuda.Stream(device=points.device)
-        side = main if (_DEBUG_KNOBS and getattr(self, "_single_stream", False)) else self._geo_stream  # (dev: tools/single_stream_ab.py)
+        side = self._geo_stream
         fork = torch.cuda.Event()
         fork.record()  # the side stream needs the input (and the ordering) only
         geo._side = side
@@ -268,8 +258,6 @@ class DH3D(nn.Module):
             # the persistent flex_conv kernels of stage 1 run -- they leave those CUs out (placement hint, speed only)
             # (steps_in_flight: a serving loop that overlaps consecutive batches has that many FPS kernels on the chip)
             geo.busy_cus_per_xcd = min(8, getattr(self, "steps_in_flight", 1) * ((points.shape[0] + 7) // 8))
-        if _DEV_RESERVE is not None:  # dev A/B (DH3D_DEV_RESERVE=n: the placement hint of the persistent kernels)
-            geo.busy_cus_per_xcd = _DEV_RESERVE
         side.wait_event(fork)
         with torch.cuda.stream(side):
             if knn_inds is not None:
@@ -287,20 +275,6 @@ class DH3D(nn.Module):
                     geo.nbr, _ = pm.knn_sorted(srt, gbox, self.knn_num)
             geo.nbr.record_stream(main)
         return geo
-
-    def _stage1_tails(self, n_per_cloud):
-        """(tail on stage 1's output, tail on before_stage2_conv1d's output) for FlexConvDilate.forward(post_tails=...), or
-        None where the separate launches are what applies (the same rules as Conv2D1x1.forward / commuted_partial: the
-        points per cloud only, never the batch)."""
-        sc = self.local_stage1_shortcut.tfconv0
-        cc = self.stage2.concat_conv1d.tfconv0 if self.stage2.concat else None
-        if (cc is None or n_per_cloud <= 4096 or not (self.stage2.upsample and self.stage2.dilate > 1)
-                or not cc.commuted_supported(self.stage2.outdims[-1]) or sc.cin != 64 or sc.cout != 128):
-            return None
-        ps, pc = sc._prep or sc.prepare(), cc._prep or cc.prepare()
-        if "wp3" not in ps or "wp3_bot" not in pc or pc["W2"].shape[0] - pc.get("c_top", 0) != 64 or cc.cout != 128:
-            return None
-        return ((ps["wp3"], ps["b"], ps["scale"], ps["shift"], pm.ACT_RELU), (pc["wp3_bot"], None, None, None, pm.ACT_NONE))
 
     def _three_nn_before_sampled_level(self, points):
         """Where three_nn (+ the sampled set's sort) is enqueued: on the MAIN stream between the sampled set's kNN and its
@@ -339,16 +313,9 @@ class DH3D(nn.Module):
             else:   # other init_feat_dim (e.g. 16): the fused pair covers Dout 32 / 64 / 128 -- the two operators apart
                 init = pm.flex_pool(pm.conv_pointset_xyz(geo.xyz, nn_8, p["theta"], p["bias"], scale=p["scale"],
                                                          shift=p["shift"], act=pm.ACT_RELU), nn_8)
-            # larger clouds: the shortcut conv (on stage 1's output) and the lower block of stage 2's commuted concat conv
-            # (on before_stage2_conv1d's output) ride in stage 1's SE kernel -- two launches over tiles it already holds
             fuse_sc = points.shape[1] <= 4096 and self.stage2.shortcut_fusable(points.shape[1])
-            tails = None if fuse_sc else self._stage1_tails(points.shape[1])
-            r = self.stage1(geo, init, nbr=nn_8, post_conv=self.before_stage2_conv1d, post_tails=tails)
-            shortcut = lower = None
-            if isinstance(r, tuple) and len(r) == 4:
-                x1, x2, shortcut, lower = r
-            else:
-                x1, x2 = r if isinstance(r, tuple) else (r, self.before_stage2_conv1d(r, act=pm.ACT_RELU))
+            r = self.stage1(geo, init, nbr=nn_8, post_conv=self.before_stage2_conv1d)
+            x1, x2 = r if isinstance(r, tuple) else (r, self.before_stage2_conv1d(r, act=pm.ACT_RELU))
             # BNReLU(conv(x1)) + stage2 (backbones.py:123).  Large clouds: the shortcut conv runs INSIDE stage 2's last
             # conv (its input x1 is just more K for that GEMM, with its own accumulators and epilogue), so its
             # [Bt,N,128] result is never written or read back.  Otherwise it runs here, beside the FPS chain, and its
@@ -363,18 +330,18 @@ class DH3D(nn.Module):
             # sampled level -- their two [Bt,N,128] maps (67 MB written and read back at 8 x 8192) never exist
             cconv = self.stage2.concat_conv1d.tfconv0 if getattr(self.stage2, "concat", False) else None
             small = points.shape[1] <= 4096
-            fused_tail = ((_l2cat_eps is not None or small) and shortcut is None and lower is None and cconv is not None
+            fused_tail = ((_l2cat_eps is not None or small) and cconv is not None
                           and self._local.featdim == 128 and cconv.commuted_supported(128)
                           and cconv.tail_fusable(self.local_stage1_shortcut.tfconv0, points.shape[1],
                                                  in_flight=getattr(self, "steps_in_flight", 1) > 1))
             if fused_tail:
                 fuse_sc = False   # (the one-launch tail replaces the K = 256 GEMM with the shortcut fused into it)
-            if shortcut is None and not fuse_sc and not fused_tail:
+            shortcut = lower = None
+            if not fuse_sc and not fused_tail:
                 shortcut = self.local_stage1_shortcut(x1, act=pm.ACT_RELU)
-            # larger clouds: stage 2's concat conv is commuted through its up-sampling -- its lower weight block meets
-            # x2 here, beside the sampling chain; behind the sampled level only a GEMM on the N/8 rows and one
-            # gather / epilogue kernel are left (backbones.Conv2D1x1.forward_commuted)
-            if lower is None and not fuse_sc and not fused_tail:
+                # larger clouds: stage 2's concat conv is commuted through its up-sampling -- its lower weight block meets
+                # x2 here, beside the sampling chain; behind the sampled level only a GEMM on the N/8 rows and one
+                # gather / epilogue kernel are left (backbones.Conv2D1x1.forward_commuted)
                 lower = self.stage2.commuted_partial(x2)
             stage1_done = torch.cuda.Event()
             stage1_done.record()

@@ -3,7 +3,6 @@
 Thin, allocation-only wrappers: each function validates shapes, allocates the output with torch and
 enqueues one C-ABI call on the current stream.  No function here has a CPU or eager-torch fallback.
 """
-import os
 
 import torch
 
@@ -37,10 +36,6 @@ def spatial_sort(xyz):
 
 
 CELL_INTS = 4112  # include/dh3d_hip.h DH3D_CELL_INTS
-
-
-# dev A/B switch (DH3D_KNN_GRID=0: the Morton-pruned shared scan / brute force for every K); identical ids either way
-KNN_GRID = os.environ.get("DH3D_KNN_GRID", "1") != "0"
 
 
 def spatial_sort_cells(xyz):
@@ -245,25 +240,6 @@ def flex_conv(features, xyz, nbr, wpacked, Dout, pre_bias=None, scale=None, shif
     return out
 
 
-def flex_conv_post(features, xyz, nbr, wpacked, Dout, wpost_packed, Dpost, pre_bias=None, scale=None, shift=None,
-                   act=ACT_NONE):
-    """flex_conv() and, from the same launch, out2 = out @ Wpost (a packed [Dout, Dpost] weight, no bias / activation).
-    Returns (out [B,N,Dout], out2 [B,N,Dpost]).  128 -> 256 with Dpost = 64, K = 8 (the global path's sampled level)."""
-    f = L.require_cuda_f32(features, "features", 3)
-    x = L.require_cuda_f32(xyz, "xyz", 3)
-    nb = L.require_cuda_i32(nbr, "nbr", 3)
-    B, N, Din = f.shape
-    if tuple(x.shape) != (B, N, 3) or tuple(nb.shape[:2]) != (B, N):
-        raise ValueError("flex_conv_post: xyz/nbr do not match features [B,N,*]")
-    out = torch.empty((B, N, Dout), dtype=torch.float32, device=f.device)
-    out2 = torch.empty((B, N, Dpost), dtype=torch.float32, device=f.device)
-    ep = _ep(pre_bias, scale, shift, act)
-    L.check(L.lib().dh3d_flex_conv_pm_post_fwd(L.ptr(f), L.ptr(x), L.ptr(nb), L.ptr(wpacked), B, N, nb.shape[2], Din, Dout, ep,
-                                               L.ptr(out), L.ptr(wpost_packed), Dpost, L.ptr(out2), L.stream_ptr()),
-            "flex_conv_pm_post")
-    return out, out2
-
-
 def flex_tile_x6_supported(Din, Dout, K):
     """Shapes served by the 32-point-tile bf16x6 flex_conv (csrc/flex_tx6.hip): the sampled levels, cfg 5's K = 12."""
     return (Din, Dout, K) in ((64, 128, 8), (128, 128, 8), (128, 256, 8), (128, 128, 12))
@@ -272,7 +248,7 @@ def flex_tile_x6_supported(Din, Dout, K):
 def flex_conv_tile_x6(features, xyz, nbr, wpacked_x3, Dout, pre_bias=None, scale=None, shift=None, act=ACT_NONE,
                       wpost_packed=None, Dpost=0):
     """flex_conv on 32-point tiles, tile GEMM on the bf16 matrix pipe at f32 accuracy.  With wpost_packed (a packed
-    [Dout, 64] weight): returns (out, out @ Wpost) from the same launch, like flex_conv_post."""
+    [Dout, 64] weight; 128 -> 256, K = 8): returns (out, out @ Wpost) from the same launch."""
     f = L.require_cuda_f32(features, "features", 3)
     x = L.require_cuda_f32(xyz, "xyz", 3)
     nb = L.require_cuda_i32(nbr, "nbr", 3)
@@ -286,10 +262,6 @@ def flex_conv_tile_x6(features, xyz, nbr, wpacked_x3, Dout, pre_bias=None, scale
                                                   Dout, ep, L.ptr(out), L.ptr(wpost_packed), int(Dpost), L.ptr(out2),
                                                   L.stream_ptr()), "flex_conv_pm_tile_x6")
     return out if wpost_packed is None else (out, out2)
-
-
-def flex_post_supported(Din, Dout, K, Dpost):
-    return Din == 128 and Dout == 256 and K == 8 and Dpost == 64
 
 
 def flex_x6_supported(Din, Dout, K):
@@ -462,29 +434,6 @@ def se_res_pool_conv(x, nbr, w1packed, b1pad, w2packed, b2, conv_wp, conv_b, con
                                                  L.ptr(w2packed), L.ptr(b2), C, L.ptr(out), L.ptr(conv_wp), ep, C,
                                                  L.ptr(out2), L.stream_ptr()), "se_res_pool_conv_pm")
     return out, out2
-
-
-def se_res_pool_conv_tails(x, nbr, w1packed, b1pad, w2packed, b2, conv_wp, conv_b, conv_scale, conv_shift, tail_a, tail_b,
-                           act=ACT_RELU, store_y=True):
-    """se_res_pool_conv (C = 64) with two more 1x1 convs 64 -> 128 in the launch (bf16x6): tail_a on the block's output y,
-    tail_b on z = conv(y); a tail = (pack_weight_x3 of [64, 128], pre_bias, scale, shift, act) with act NONE or RELU.
-    Returns (y or None, z, out_a [B,N,128], out_b [B,N,128])."""
-    a = L.require_cuda_f32(x, "x", 3)
-    nb = L.require_cuda_i32(nbr, "nbr", 3)
-    B, N, C = a.shape
-    if C != 64:
-        raise ValueError("se_res_pool_conv_tails: C == 64")
-    y = torch.empty_like(a) if store_y else None
-    z = torch.empty((B, N, C), dtype=torch.float32, device=a.device)
-    oa = torch.empty((B, N, 128), dtype=torch.float32, device=a.device)
-    ob = torch.empty((B, N, 128), dtype=torch.float32, device=a.device)
-    ep = _ep(conv_b, conv_scale, conv_shift, act)
-    ea, eb = _ep(*tail_a[1:5]), _ep(*tail_b[1:5])
-    L.check(L.lib().dh3d_se_res_pool_conv_tails_pm_fwd(L.ptr(a), L.ptr(nb), B, N, nb.shape[2], L.ptr(w1packed), L.ptr(b1pad),
-                                                       L.ptr(w2packed), L.ptr(b2), L.ptr(y), L.ptr(conv_wp), ep, L.ptr(z),
-                                                       L.ptr(tail_a[0]), ea, L.ptr(oa), L.ptr(tail_b[0]), eb, L.ptr(ob),
-                                                       L.stream_ptr()), "se_res_pool_conv_tails_pm")
-    return y, z, oa, ob
 
 
 def three_interpolate_idw(points, idx, dist):
@@ -774,7 +723,7 @@ def global_tail(coarse, idx, dist, order, wslices_x3, Hd, w_fc, b_fc, att_ep, wc
     H = torch.empty((ns, B * m, 256), dtype=torch.float32, device=x.device)
     L.check(L.lib().dh3d_linear_slices_pm_x6_fwd(L.ptr(x), C, L.ptr(wslices_x3), B * m, ns, L.ptr(H), L.stream_ptr()),
             "linear_slices_pm_x6")
-    if cw is None:   # (the caller may have it already: pm.flex_conv_post computes it in the flex_conv's launch)
+    if cw is None:   # (the caller may have it already: pm.flex_conv_tile_x6 computes it in the flex_conv's launch)
         cw = linear(x, wc_packed, 64)                                              # coarse @ cluster_weights
     att = torch.empty((B, n, 1), dtype=torch.float32, device=x.device) if want_att else None
     zero_here = accum is None

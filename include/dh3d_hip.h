@@ -326,17 +326,13 @@ int dh3d_flex_conv_pm_fwd(const float *features, const float *xyz, const int32_t
                           const float *wpacked, int B, int N, int K, int Din, int Dout,
                           const dh3d_epilogue *ep, float *out, void *stream);
 
-/* dh3d_flex_conv_pm_fwd with one more linear layer applied to the finished output tile before it leaves the chip:
- * out [B,N,Dout] as above AND out2 [B,N,Dpost] = out @ Wpost (wpost_packed = dh3d_pack_weight of [Dout, Dpost], no bias /
- * activation).  The global step uses it for NetVLAD's cluster logits on the sampled rows (core/backbones.py:213-216,
- * commuted through the up-sampling).  Din == 128, Dout == 256, K == 8, Dpost == 64. */
-int dh3d_flex_conv_pm_post_fwd(const float *features, const float *xyz, const int32_t *nbr, const float *wpacked, int B,
-                               int N, int K, int Din, int Dout, const dh3d_epilogue *ep, float *out,
-                               const float *wpost_packed, int Dpost, float *out2, void *stream);
 /* The same operator on 32-point tiles with the tile GEMM on the bf16 matrix pipe at f32 accuracy (six bf16 products per
  * f32 product, like dh3d_flex_conv_pm_x6_fwd; csrc/flex_tx6.hip): the sampled levels' layers, whose f32-MFMA GEMM phase
  * sits at the f32 pipe's floor for one tile per CU.  wpacked_x3 from dh3d_pack_flex_weight_x3.  wpost_packed (may be
- * NULL; then Dpost / out2 are ignored) as in dh3d_flex_conv_pm_post_fwd (Din == 128, Dout == 256, Dpost == 64).
+ * NULL; then Dpost / out2 are ignored): one more linear layer on the finished output tile before it leaves the chip,
+ * out2 [B,N,Dpost] = out @ Wpost (dh3d_pack_weight of [Dout, Dpost], no bias / activation) -- NetVLAD's cluster logits on
+ * the sampled rows of the global step (core/backbones.py:213-216, commuted through the up-sampling); Din == 128,
+ * Dout == 256, Dpost == 64.
  * (Din, Dout, K) in {(64,128,8), (128,128,8), (128,256,8), (128,128,12)}. */
 int dh3d_flex_conv_pm_tile_x6_fwd(const float *features, const float *xyz, const int32_t *nbr, const void *wpacked_x3,
                                   int B, int N, int K, int Din, int Dout, const dh3d_epilogue *ep, float *out,
@@ -421,17 +417,6 @@ int dh3d_se_res_pool_pm_packed_fwd(const float *x, const int32_t *nbr, int B, in
 int dh3d_se_res_pool_conv_pm_fwd(const float *x, const int32_t *nbr, int B, int N, int K, const float *w1packed,
                                  const float *b1pad, const float *w2packed, const float *b2, int C, float *out,
                                  const float *wconv_packed, const dh3d_epilogue *ep, int Dout, float *out2, void *stream);
-
-/* dh3d_se_res_pool_conv_pm_fwd for C = Dout = 64 with two more 1x1 convs 64 -> 128 riding in the launch, on the bf16 pipe at
- * f32 accuracy: out_a = act_a(bn_a(y @ Wa)) on the block's output y (out), out_b = act_b(bn_b(z @ Wb)) on z = the 64 -> 64
- * conv's output (out2).  wa_x3 / wb_x3 = dh3d_pack_weight_x3 of [64, 128]; act NONE or RELU.  out may be NULL (y is not
- * stored).  The local step: stage 1's SE block + before_stage2_conv1d + local_stage1_shortcut + the lower block of stage 2's
- * commuted concat conv (core/backbones.py:115-123) -- one launch instead of three over the same tiles. */
-int dh3d_se_res_pool_conv_tails_pm_fwd(const float *x, const int32_t *nbr, int B, int N, int K, const float *w1packed,
-                                       const float *b1pad, const float *w2packed, const float *b2, float *out,
-                                       const float *wconv_packed, const dh3d_epilogue *ep, float *out2, const void *wa_x3,
-                                       const dh3d_epilogue *ep_a, float *out_a, const void *wb_x3,
-                                       const dh3d_epilogue *ep_b, float *out_b, void *stream);
 
 /* three_nn + inverse-distance weights + three_interpolate (core/backbones.py:90-96) fused:
  * weight = (1/max(d,1e-10)) / sum(1/max(d,1e-10)).  idx/dist from dh3d_three_nn.
@@ -567,7 +552,7 @@ int dh3d_flex_conv_pm_bwd(const float *features, const float *xyz, const int32_t
 
 /* f32 GEMMs of the backward passes (csrc/gemm.hip), all row-major; f32-accurate: the exact-f32 matrix pipe for small
  * products, the bf16 pipe with a three-way split of BOTH operands (six products, ~2^-23 relative) from 2^26
- * multiply-adds when K % 4 == 0 (environment DH3D_GEMM_F32=1 keeps everything on the exact-f32 kernel):
+ * multiply-adds when K % 4 == 0:
  *   tn: C[M,N] (+)= A[K,M]^T B[K,N]  (weight gradients: reduction over rows, split over workgroups + f32 atomics)
  *   nn: C[M,N] (+)= A[M,K]   B[K,N] (+ colbias[N], may be NULL; not with accumulate)  (linear layers of the
  *       training step, input gradients with W^T materialised)
@@ -746,40 +731,26 @@ int dh3d_gemm_nn_f32_batched(const float *A, const float *B, const float *colbia
                              float *C, void *stream);
 
 /* The global-descriptor tail with the up-sampling commuted through BOTH consumers of the up-sampled map (attention MLP
- * and NetVLAD; csrc/dense_x6.hip VladTail): dh3d_global_tail_fwd walks the fine points once (Morton order of `order`,
- * coarse rows staged in LDS) from H = the 256-column slices of coarse @ W_att (dh3d_linear_slices_pm_x6_fwd), coarse
- * [B,m,256] and cw = coarse @ cluster_weights [B,m,64], and produces att [B,n] (may be NULL) and
- * accum = [ apart B*m*64 | asum B*64 | V B*64*256 ] floats (zeroed by the call): apart = A' (softmax * attention
- * scattered onto the coarse rows, f32 atomics), asum its per-cluster sums, V[b] = apart[b]^T coarse[b].
- * dh3d_netvlad_tail_fwd(V, asum, ...) finishes (subtract asum*W2, intra-normalise, project, gate).  Same function as
- * three_interpolate -> attention head -> dh3d_netvlad_fused_fwd, reassociated; m <= 1024. */
-int dh3d_global_tail_fwd(const float *H, int Hd, const float *coarse, const float *cw, const int32_t *idx,
-                         const float *dist, const float *order, int B, int n, int m, const dh3d_epilogue *ep,
-                         const float *w_fc, float b_fc, const float *cl_scale, const float *cl_shift, float *att,
-                         float *accum, void *stream);
-size_t dh3d_netvlad_tail_workspace_bytes(int B, int D, int Cl, int O);
-int dh3d_netvlad_tail_fwd(const float *V, const float *asum, const float *W2, const float *Wh, const float *bn1_scale,
-                          const float *bn1_shift, const float *Wg, const float *bn2_scale, const float *bn2_shift, int B,
-                          int D, int Cl, int O, float l2_eps, void *workspace, size_t workspace_bytes, float *out,
-                          void *stream);
-/* The two-call form the model uses since round 4: dh3d_global_walk_fwd = the walk alone, accum = [ apart B*m*64 | asum B*64 ]
- * floats (zero_accum != 0: cleared by the call; 0: zeroed by the CALLER, e.g. by a fill issued beside the sampling chain),
- * and dh3d_netvlad_tail_assign_fwd, which forms V = apart^T coarse inside its finalize kernel (no batched GEMM launch, a
- * fixed summation order) and then projects and gates as dh3d_netvlad_tail_fwd.  m <= 1024; workspace:
+ * and NetVLAD; csrc/dense_x6.hip VladTail), two calls.  dh3d_global_walk_planned_fwd walks the fine points once (Morton
+ * order of `order`, coarse rows staged in LDS) from H = the 256-column slices of coarse @ W_att
+ * (dh3d_linear_slices_pm_x6_fwd), coarse [B,m,256] and cw = coarse @ cluster_weights [B,m,64], and produces att [B,n]
+ * (may be NULL) and accum = [ apart B*m*64 | asum B*64 ] floats (zero_accum != 0: cleared by the call; 0: zeroed by the
+ * CALLER, e.g. by a fill issued beside the sampling chain): apart = A' (softmax * attention scattered onto the coarse
+ * rows, f32 atomics), asum its per-cluster sums.  dh3d_netvlad_tail_assign_fwd finishes: it forms V = apart^T coarse
+ * inside its finalize kernel (a fixed summation order), subtracts asum*W2, intra-normalises, projects and gates.  Same
+ * function as three_interpolate -> attention head -> dh3d_netvlad_fused_fwd, reassociated; m <= 1024; workspace:
  * dh3d_netvlad_tail_workspace_bytes. */
-int dh3d_global_walk_fwd(const float *H, int Hd, const float *coarse, const float *cw, const int32_t *idx, const float *dist,
-                         const float *order, int B, int n, int m, const dh3d_epilogue *ep, const float *w_fc, float b_fc,
-                         const float *cl_scale, const float *cl_shift, float *att, float *accum, int zero_accum, void *stream);
 /* Round 6: the walk's slot tables built AHEAD of it.  Inside the walk the table of a 128-point block (bitmap of the coarse
  * rows its points touch -> prefix popcounts -> slots; three dependent global round trips + five barriers) was 17 of the
  * launch's ~95 us at 32 x 4096.  dh3d_walk_plan builds every block's table from the three_nn result (idx, dist [B,n,3], order =
  * dh3d_spatial_sort records of the fine cloud, may be NULL) into `plan` (dh3d_walk_plan_bytes(B, n) bytes, opaque:
  * per block the slot table and the slot-major lists of the references to every staged row, which the planned walk's
- * NetVLAD scatter follows instead of forming a selection matrix on the matrix pipe) -- launched behind dh3d_three_nn_*, off the critical chain -- and dh3d_global_walk_planned_fwd is
- * dh3d_global_walk_fwd reading it (plan == NULL: the table is built inside the walk as before).  Same results bit for bit
- * up to the order of the f32 atomics (as dh3d_global_walk_fwd).  m <= 1024. */
+ * NetVLAD scatter follows instead of forming a selection matrix on the matrix pipe) -- launched behind dh3d_three_nn_*, off the critical chain -- and dh3d_global_walk_planned_fwd
+ * reads it (plan == NULL: the table is built inside the walk).  Same results bit for bit either way, up to the order of
+ * the f32 atomics.  m <= 1024. */
 size_t dh3d_walk_plan_bytes(int B, int n);
 int dh3d_walk_plan(const int32_t *idx, const float *dist, const float *order, int B, int n, int m, void *plan, void *stream);
+size_t dh3d_netvlad_tail_workspace_bytes(int B, int D, int Cl, int O);
 int dh3d_global_walk_planned_fwd(const float *H, int Hd, const float *coarse, const float *cw, const int32_t *idx,
                                  const float *dist, const float *order, const void *plan, int B, int n, int m,
                                  const dh3d_epilogue *ep, const float *w_fc, float b_fc, const float *cl_scale,

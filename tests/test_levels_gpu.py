@@ -75,22 +75,16 @@ CASES = {
     "npoint_17000": (1, 34000, 2, 8, None, None, "uniform", ("any_n", "brute", "plain"), set()),
     # three_nn on the plain kernel below 256 sampled points (a sorted cloud all the same)
     "m128_sorted": (4, 4096, 32, 8, "sort", None, "uniform", ("ordered", "brute", "plain"), set()),
-    # the dev switches off, on a shipped shape each
-    "no_fps_ordered": (8, 8192, 8, 8, "cells", None, "uniform", ("sorted", "brute", "sorted"), {"FPS_ORDERED"}),
-    "no_sampled_grid": (32, 4096, 8, 8, "cells", None, "blob", ("ordered", "brute", "sorted"), {"SAMPLED_GRID"}),
 }
 
 
 @pytest.mark.parametrize("case", list(CASES))
-def test_level_matches_oracle(dev, oracle, monkeypatch, case):
+def test_level_matches_oracle(dev, oracle, case):
     from dh3d_amd import backbones as bb
     from dh3d_amd import pm
     B, N, dilate, knn, sort, contract, kind, want, extras = CASES[case]
     if isinstance(N, str):
         N = _edge_n(N.startswith("ordered")) + N.endswith("+1")
-    for switch in ("FPS_ORDERED", "SAMPLED_GRID"):
-        if switch in extras:
-            monkeypatch.setattr(bb, switch, False)
     xyz = _cloud(kind, B, N, seed=N * 31 + dilate * 7 + B)
     t = T(xyz, dev)
     geo = bb.Geometry(t, knn, fps_contract=contract)

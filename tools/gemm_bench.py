@@ -1,6 +1,6 @@
-"""Time the training GEMM shapes on the bf16x6 kernel and (DH3D_GEMM_F32=1, separate process) the exact-f32 one.
-usage: python tools/gemm_bench.py            (runs itself twice)"""
-import os, subprocess, sys, time
+"""Time the training GEMM shapes (bf16x6 or exact-f32 kernel, as gemm_launch picks).
+usage: python tools/gemm_bench.py"""
+import os, sys
 
 SHAPES = [("nn", 11264, 256, 1024), ("nn", 11264, 1024, 256), ("tn", 11264, 256, 1024), ("nn", 90112, 256, 64),
           ("nn", 90112, 64, 256), ("tn", 90112, 256, 64), ("tn", 11264, 512, 256), ("bnn", 4096, 256, 64),
@@ -40,12 +40,4 @@ def main():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "run":
-        main()
-    else:
-        envs = ({}, {"DH3D_GEMM_KC": "16"}, {"DH3D_GEMM_KC": "32"}, {"DH3D_GEMM_F32": "1"})
-        if len(sys.argv) > 1 and sys.argv[1] == "wgs":
-            envs = tuple({"DH3D_GEMM_WGS": w} for w in ("256", "384", "512", "768", "1024", "1536"))
-        for env in envs:
-            print(env, flush=True)
-            subprocess.run([sys.executable, os.path.abspath(__file__), "run"], env=dict(os.environ, **env), timeout=120)
+    main()

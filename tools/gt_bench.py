@@ -1,6 +1,4 @@
-"""Dev: time pm.global_tail pieces at cfg 3 (32 x 4096).  Build variants:
-  for k in 1 2 4 7; do (cd dh3d_amd/csrc && hipcc ... -DDH3D_GT_SKIP=$k -c dense_x6.hip -o /tmp/dx6_$k.o && hipcc -shared ... ); done
-and run with DH3D_HIP_LIB=tools/libgt_skip$k.so."""
+"""Dev: time pm.global_tail pieces at cfg 3 (32 x 4096)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
