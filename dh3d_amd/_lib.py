@@ -56,6 +56,18 @@ _SIGNATURES = {
     "dh3d_conv_pointset_fwd_f64": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp],
     "dh3d_conv_pointset_bwd_f64": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp,
                                    c_fp],
+    "dh3d_flex_deconv_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp],
+    "dh3d_flex_deconv_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp,
+                             c_fp, c_fp, c_fp],
+    "dh3d_flex_deconv_fwd_f64": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp],
+    "dh3d_flex_deconv_bwd_f64": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp,
+                                 c_fp, c_fp, c_fp],
+    "dh3d_flex_deconv_fwd_workspace_bytes": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "dh3d_flex_deconv_fwd_ws": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp,
+                                c_size_t, c_fp],
+    "dh3d_flex_deconv_bwd_workspace_bytes": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "dh3d_flex_deconv_bwd_ws": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp,
+                                c_fp, c_fp, c_fp, c_size_t, c_fp],
     "dh3d_flex_conv_fwd_workspace_bytes": [c_int, c_int, c_int, c_int, c_int, c_int],
     "dh3d_flex_conv_fwd_ws": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp,
                               c_size_t, c_fp],
@@ -224,6 +236,8 @@ _RESTYPES = {
     "dh3d_flex_conv_bwd_workspace_bytes": c_size_t,
     "dh3d_flex_pool_fwd_workspace_bytes": c_size_t,
     "dh3d_flex_conv_pm_bwd_workspace_bytes": c_size_t,
+    "dh3d_flex_deconv_fwd_workspace_bytes": c_size_t,
+    "dh3d_flex_deconv_bwd_workspace_bytes": c_size_t,
     "dh3d_keypoint_nms_workspace_bytes": c_size_t,
 }
 

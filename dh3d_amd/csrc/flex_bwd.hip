@@ -86,6 +86,12 @@ inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
+int dh3d_internal_flex_S(const float *feat, const float *xyz, const int32_t *nbr, long long R, int N, int K, int D,
+                         int rank0, float *S, hipStream_t s) {
+  hipLaunchKernelGGL(flex_S_kernel, dim3(flat_grid256(R * (D / 4))), dim3(256), 0, s, feat, xyz, nbr, R, N, K, D, rank0, S);
+  return dh3d_launch_status();
+}
+
 DH3D_API size_t dh3d_flex_conv_pm_bwd_workspace_bytes(int B, int N, int Din, int Dout) {
   if (B <= 0 || N <= 0 || Din <= 0 || Dout <= 0 || Din % 4 || Dout % 4) return 0;
   const size_t R = (size_t)B * N;

@@ -1,6 +1,7 @@
 """Layer wrappers in the reference's channels-first convention (mirrors core/layers.py).
 
 KnnBruteforce (core/layers.py:49-107), FlexPooling (:110-175), FlexConvolution (:178-339, :439-461),
+FlexConvolutionTranspose (:483-561),
 Flex_Avg (:342-436, :464-480), ConvolutionPointset (:564-707): same constructor arguments that matter, same weight names
 (position_theta / position_bias / feature_bias), same tensor layouts ([B, C, N] features,
 [B, K, N] neighbourhoods).  They call the drop-in operators of dh3d_amd.ops and are differentiable
@@ -14,7 +15,7 @@ from torch import nn
 from . import ops
 
 __all__ = ["KnnBruteforce", "knn_bruteforce", "FlexPooling", "flex_pooling", "FlexConvolution",
-           "ConvolutionPointset", "Flex_Avg", "flex_avg"]
+           "FlexConvolutionTranspose", "flex_convolution_transpose", "ConvolutionPointset", "Flex_Avg", "flex_avg"]
 
 
 class KnnBruteforce(nn.Module):
@@ -64,6 +65,8 @@ def flex_pooling(features, neighborhoods, data_format="simple"):
 class FlexConvolution(nn.Module):
     """Weights: position_theta [Dp, Din, Dout], position_bias [Din, Dout], feature_bias [Dout, 1]."""
 
+    _op = staticmethod(ops.flex_convolution)
+
     def __init__(self, in_channels, filters, dp=3, activation=None, use_feature_bias=True,
                  data_format="simple"):
         super().__init__()
@@ -80,7 +83,7 @@ class FlexConvolution(nn.Module):
     def forward(self, features, positions, neighborhoods):
         if self.data_format == "expanded":
             features, positions, neighborhoods = features.squeeze(2), positions.squeeze(2), neighborhoods.squeeze(2)
-        y = ops.flex_convolution(features, positions, neighborhoods, self.position_theta, self.position_bias)
+        y = self._op(features, positions, neighborhoods, self.position_theta, self.position_bias)
         if self.feature_bias is not None:
             y = y + self.feature_bias
         if self.activation is not None:
@@ -88,6 +91,22 @@ class FlexConvolution(nn.Module):
         if self.data_format == "expanded":
             y = y.unsqueeze(2)
         return y
+
+
+class FlexConvolutionTranspose(FlexConvolution):
+    """core/layers.py:483-537: FlexConvolution's parameters and initialisers (position_theta [Dp, Din, Dout],
+    position_bias [Din, Dout], feature_bias [Dout, 1]) on the transposed operator."""
+
+    _op = staticmethod(ops.flex_convolution_transpose)
+
+
+def flex_convolution_transpose(features, positions, neighborhoods, filters, activation=None, use_feature_bias=True,
+                               data_format="simple"):
+    """core/layers.py:540-561 (a fresh layer per call, as there)."""
+    cin = features.shape[1]
+    layer = FlexConvolutionTranspose(cin, filters, dp=positions.shape[1], activation=activation,
+                                     use_feature_bias=use_feature_bias, data_format=data_format)
+    return layer.to(device=features.device, dtype=features.dtype)(features, positions, neighborhoods)
 
 
 class ConvolutionPointset(nn.Module):

@@ -1,7 +1,7 @@
 """Drop-in operator API: the reference's op names, argument orders and tensor layouts.
 
-Mirrors user_ops/__init__.py (knn_bruteforce :50, flex_convolution :63-89, flex_pooling :115-135,
-convolution_pointset :205-225) and tf_ops/{sampling,grouping,interpolation}/tf_*.py
+Mirrors user_ops/__init__.py (knn_bruteforce :50, flex_convolution :63-89, flex_convolution_transpose,
+flex_pooling :115-135, convolution_pointset :205-225) and tf_ops/{sampling,grouping,interpolation}/tf_*.py
 (farthest_point_sample tf_sampling.py:63-71, group_point tf_grouping.py:48-56, three_nn / three_interpolate
 tf_interpolate.py:8-34), with torch.autograd.Function standing in for the RegisterGradient hooks
 (user_ops/__init__.py:95-111,141-151,231-246; tf_grouping.py:57-61; tf_interpolate.py:29-34).
@@ -13,7 +13,7 @@ import torch
 from . import _lib as L
 
 __all__ = [
-    "knn_bruteforce", "flex_convolution", "flex_pooling", "convolution_pointset",
+    "knn_bruteforce", "flex_convolution", "flex_convolution_transpose", "flex_pooling", "convolution_pointset",
     "farthest_point_sample", "group_point", "three_nn", "three_interpolate",
 ]
 
@@ -111,6 +111,76 @@ def flex_convolution(features, position, neighborhood, theta, bias, name=None):
     """features [B,Din,N], position [B,Dp,N], neighborhood [B,K,N] int32, theta [Dp,Din,Dout],
     bias [Din,Dout] -> [B,Dout,N]   (user_ops/__init__.py:63-89; note its argument re-order)."""
     return _FlexConv.apply(features, theta, bias, neighborhood, position)
+
+
+# --------------------------------------------------------------------------- flex_conv transpose (FlexDeconv)
+class _FlexDeconv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, theta, bias, neighborhood, position):
+        f = L.require_cuda_float(features, "features", 3)
+        t = L.require_cuda_float(theta, "theta", 3, like=f)
+        bi = L.require_cuda_float(bias, "bias", 2, like=f)
+        nb = L.require_cuda_i32(neighborhood, "neighborhood", 3)
+        p = L.require_cuda_float(position, "position", 3, like=f)
+        f64 = f.dtype == torch.float64
+        B, Din, N = f.shape
+        Dp, Din_t, Dout = t.shape
+        K = nb.shape[1]
+        # shape function of user_ops/ops/flex_deconv.cc (FlexDeconv)
+        _same((nb.shape[0], p.shape[0]), (B, B), "batch(features/neighborhood/position)")
+        _same((nb.shape[2], p.shape[2]), (N, N), "N(features/neighborhood/position)")
+        _same(p.shape[1], Dp, "Dp(theta/position)")
+        _same(bi.shape[1], Dout, "Dout(theta/bias)")
+        _same((Din_t, bi.shape[0]), (Din, Din), "Din(features/theta/bias)")
+        out = torch.empty((B, Dout, N), dtype=f.dtype, device=f.device)
+        with torch.cuda.device(f.device):
+            ws_bytes = L.lib().dh3d_flex_deconv_fwd_workspace_bytes(B, N, K, Dp, Din, Dout) if FAST_PATH and not f64 else 0
+            if f64:
+                L.check(L.lib().dh3d_flex_deconv_fwd_f64(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
+                                                         Din, Dout, L.ptr(out), L.stream_ptr()), "flex_convolution_transpose")
+            elif ws_bytes:  # inverted neighbour lists + GEMM (section A', csrc/flex_deconv.hip)
+                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=f.device)
+                L.check(L.lib().dh3d_flex_deconv_fwd_ws(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
+                                                        Din, Dout, L.ptr(out), L.ptr(ws), ws_bytes, L.stream_ptr()),
+                        "flex_convolution_transpose")
+            else:       # any other shape: the reference formulation
+                L.check(L.lib().dh3d_flex_deconv_fwd(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
+                                                     Din, Dout, L.ptr(out), L.stream_ptr()), "flex_convolution_transpose")
+        ctx.save_for_backward(f, t, bi, nb, p)
+        return out
+
+    @staticmethod
+    def backward(ctx, topdiff):
+        f, t, bi, nb, p = ctx.saved_tensors
+        td = topdiff.contiguous()
+        B, Din, N = f.shape
+        Dp, _, Dout = t.shape
+        K = nb.shape[1]
+        gf, gt, gb = torch.empty_like(f), torch.empty_like(t), torch.empty_like(bi)
+        with torch.cuda.device(f.device):
+            f64 = f.dtype == torch.float64
+            ws_bytes = L.lib().dh3d_flex_deconv_bwd_workspace_bytes(B, N, K, Dp, Din, Dout) if FAST_PATH and not f64 else 0
+            if f64:
+                L.check(L.lib().dh3d_flex_deconv_bwd_f64(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td),
+                                                         B, N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb),
+                                                         L.stream_ptr()), "flex_convolution_transpose_grad")
+            elif ws_bytes:
+                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=f.device)
+                L.check(L.lib().dh3d_flex_deconv_bwd_ws(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td), B,
+                                                        N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb), L.ptr(ws),
+                                                        ws_bytes, L.stream_ptr()), "flex_convolution_transpose_grad")
+            else:
+                L.check(L.lib().dh3d_flex_deconv_bwd(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td), B,
+                                                     N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb),
+                                                     L.stream_ptr()), "flex_convolution_transpose_grad")
+        return gf, gt, gb, None, None
+
+
+def flex_convolution_transpose(features, position, neighborhood, theta, bias, name=None):
+    """features [B,Din,N], position [B,Dp,N], neighborhood [B,K,N] int32, theta [Dp,Din,Dout], bias [Din,Dout]
+    -> [B,Dout,N]: every point spreads the features of its rank-0 neighbour to its whole list (FlexDeconv,
+    user_ops.flex_convolution_transpose; the argument re-order of flex_convolution)."""
+    return _FlexDeconv.apply(features, theta, bias, neighborhood, position)
 
 
 # --------------------------------------------------------------------------- flex_pool

@@ -143,6 +143,27 @@ int dh3d_conv_pointset_bwd_f64(const double *features, const double *theta, cons
                                const double *topdiff, int B, int N, int K, int Din, int Dout, double *grad_features,
                                double *grad_theta, double *grad_bias, void *stream);
 
+/* FlexDeconv -- replaces FlexDeconvFunctor / FlexDeconvGrad (op user_ops/ops/flex_deconv.cc; exposed as
+ * user_ops.flex_convolution_transpose).  Argument order and layouts are FlexConv's: features [B,Din,N], theta
+ * [Dp,Din,Dout], bias [Din,Dout], neighborhood [B,K,N] int32, positions [B,Dp,N] -> output [B,Dout,N].  Every source point
+ * n spreads its centre s = nbr[b,0,n] to its targets m = nbr[b,k,n] (k = 0 included):
+ *   out[b,:,m] += sum_din f[b,din,s] (bias[din,:] + sum_dp theta[dp,din,:] (p[b,dp,m] - p[b,dp,s])).
+ * A point no list names gets 0.  The reference formulation (csrc/flex_deconv.hip), any shape, Dp <= 4; f32 / f64 atomics
+ * into the outputs, which the library zeroes first.  The backward returns the gradients of all three parameters. */
+int dh3d_flex_deconv_fwd(const float *features, const float *theta, const float *bias, const int32_t *neighborhood,
+                         const float *positions, int B, int N, int K, int Dp, int Din, int Dout, float *output,
+                         void *stream);
+int dh3d_flex_deconv_bwd(const float *features, const float *theta, const float *bias, const int32_t *neighborhood,
+                         const float *positions, const float *topdiff, int B, int N, int K, int Dp, int Din, int Dout,
+                         float *grad_features, float *grad_theta, float *grad_bias, void *stream);
+int dh3d_flex_deconv_fwd_f64(const double *features, const double *theta, const double *bias,
+                             const int32_t *neighborhood, const double *positions, int B, int N, int K, int Dp, int Din,
+                             int Dout, double *output, void *stream);
+int dh3d_flex_deconv_bwd_f64(const double *features, const double *theta, const double *bias,
+                             const int32_t *neighborhood, const double *positions, const double *topdiff, int B, int N,
+                             int K, int Dp, int Din, int Dout, double *grad_features, double *grad_theta,
+                             double *grad_bias, void *stream);
+
 /* FarthestPointSample -- replaces farthestpointsamplingLauncher (tf_ops/sampling/tf_sampling.cpp:94,
  * tf_sampling_g.cu:105-170,203-205).  inp [B,N,3] -> out [B,m] int32, first pick 0, bit-exact tie
  * order.  `temp` is the reference's scratch (tf_sampling.cpp:115 allocates [32,N]): for N <= 16384 the
@@ -202,6 +223,23 @@ int dh3d_flex_conv_bwd_ws(const float *features, const float *theta, const float
 size_t dh3d_flex_pool_fwd_workspace_bytes(int B, int N, int K, int D);
 int dh3d_flex_pool_fwd_ws(const float *features, const int32_t *neighborhood, int B, int N, int K, int D,
                           float *output, int32_t *argmax, void *workspace, size_t workspace_bytes, void *stream);
+
+/* FlexDeconv / its gradient on the fast kernels, signatures of section A + (workspace, workspace_bytes).  Shapes:
+ * Dp = 3, Din % 4 == 0, Dout % 4 == 0 (else, or when a buffer would overflow, *_workspace_bytes returns 0: use section A).
+ * The factorised form of FlexConv read through INVERTED neighbour lists (a CSR per cloud, built in the workspace, every
+ * list in ascending edge order n*K + k): forward out = S' @ [bias; theta] with S' = flex_conv's S summed over each
+ * point's inverted list; backward Q = flex_conv's S of the upstream gradient centred on rank 0, summed over the rank-0
+ * inverted lists, then two GEMMs.  No atomics but the weight gradients' split-K GEMM: the output and grad_features are
+ * bitwise reproducible (for 4*Din resp. 4*Dout <= 256, where the GEMM's reduction is not split). */
+size_t dh3d_flex_deconv_fwd_workspace_bytes(int B, int N, int K, int Dp, int Din, int Dout);
+int dh3d_flex_deconv_fwd_ws(const float *features, const float *theta, const float *bias,
+                            const int32_t *neighborhood, const float *positions, int B, int N, int K, int Dp,
+                            int Din, int Dout, float *output, void *workspace, size_t workspace_bytes, void *stream);
+size_t dh3d_flex_deconv_bwd_workspace_bytes(int B, int N, int K, int Dp, int Din, int Dout);
+int dh3d_flex_deconv_bwd_ws(const float *features, const float *theta, const float *bias,
+                            const int32_t *neighborhood, const float *positions, const float *topdiff, int B, int N,
+                            int K, int Dp, int Din, int Dout, float *grad_features, float *grad_theta,
+                            float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ===================================================================================== *
  * B. Fused point-major kernels (model path)
