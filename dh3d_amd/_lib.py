@@ -310,41 +310,28 @@ def make_epilogue(pre_bias=None, scale=None, shift=None, act=ACT_NONE):
     return ep
 
 
-def require_cuda_f32(t, name, ndim=None):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("%s must be a torch.Tensor" % name)
-    if t.dtype != torch.float32:
-        raise ValueError("%s must be float32, got %s" % (name, t.dtype))
-    if not t.is_cuda:
-        raise ValueError("%s must live on the GPU (the HIP path has no CPU fallback)" % name)
-    if ndim is not None and t.dim() != ndim:
-        raise ValueError("%s must have rank %d, got shape %s" % (name, ndim, tuple(t.shape)))
-    return t.contiguous()
+def _require_cuda(dtypes):
+    """The argument check of every op: a contiguous CUDA tensor of one of `dtypes`, of rank `ndim` if given, and of the
+    dtype of `like` if given (the six reference-layout flex operators accept float32 and float64, as the reference's
+    registrations do, with one dtype across their arguments).  A closure per dtype set rather than wrappers round one
+    function: pm.py checks every argument of every launch, and a wrapper would add a call to each check."""
+    allowed = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+
+    def require(t, name, ndim=None, like=None):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a torch.Tensor" % name)
+        if t.dtype not in dtypes:
+            raise ValueError("%s must be %s, got %s" % (name, allowed, t.dtype))
+        if like is not None and t.dtype != like.dtype:
+            raise ValueError("%s must have the dtype of the features (%s), got %s" % (name, like.dtype, t.dtype))
+        if not t.is_cuda:
+            raise ValueError("%s must live on the GPU (the HIP path has no CPU fallback)" % name)
+        if ndim is not None and t.dim() != ndim:
+            raise ValueError("%s must have rank %d, got shape %s" % (name, ndim, tuple(t.shape)))
+        return t.contiguous()
+    return require
 
 
-def require_cuda_float(t, name, ndim=None, like=None):
-    """float32 or float64 (the six reference-layout flex operators accept both, as the reference's registrations do);
-    `like`: a tensor whose dtype this one has to share."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("%s must be a torch.Tensor" % name)
-    if t.dtype not in (torch.float32, torch.float64):
-        raise ValueError("%s must be float32 or float64, got %s" % (name, t.dtype))
-    if like is not None and t.dtype != like.dtype:
-        raise ValueError("%s must have the dtype of the features (%s), got %s" % (name, like.dtype, t.dtype))
-    if not t.is_cuda:
-        raise ValueError("%s must live on the GPU (the HIP path has no CPU fallback)" % name)
-    if ndim is not None and t.dim() != ndim:
-        raise ValueError("%s must have rank %d, got shape %s" % (name, ndim, tuple(t.shape)))
-    return t.contiguous()
-
-
-def require_cuda_i32(t, name, ndim=None):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("%s must be a torch.Tensor" % name)
-    if t.dtype != torch.int32:
-        raise ValueError("%s must be int32, got %s" % (name, t.dtype))
-    if not t.is_cuda:
-        raise ValueError("%s must live on the GPU (the HIP path has no CPU fallback)" % name)
-    if ndim is not None and t.dim() != ndim:
-        raise ValueError("%s must have rank %d, got shape %s" % (name, ndim, tuple(t.shape)))
-    return t.contiguous()
+require_cuda_f32 = _require_cuda((torch.float32,))
+require_cuda_float = _require_cuda((torch.float32, torch.float64))
+require_cuda_i32 = _require_cuda((torch.int32,))

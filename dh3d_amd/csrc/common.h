@@ -45,6 +45,19 @@ __device__ __forceinline__ int dh3d_xcd_remap(int bid, int nblk) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
+// Sum of v over a block of 256 threads (four waves), returned to every thread; s_red: 4 elements of LDS.  The
+// barrier on entry lets a caller reuse s_red from one call to the next.
+template <typename T>
+__device__ __forceinline__ T block_sum_256(T v, T *s_red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_red[wave] = v;
+  __syncthreads();
+  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
+}
+
 // Epilogue y = act(scale*(x+pre_bias)+shift), by value for kernels.
 struct EpilogueArgs {
   const float *pre_bias;

@@ -86,17 +86,6 @@ __global__ __launch_bounds__(kPts) void flex_conv_bwd_feat_generic(
   }
 }
 
-template <typename T>
-__device__ __forceinline__ T block_sum_256(T v, T *s_red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[wave] = v;
-  __syncthreads();
-  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
-
 // d theta / d bias: one block per (din j, dout l) pair as gpu.cu.cc:168-248, reduced over (b,n,k).
 template <typename T>
 __global__ __launch_bounds__(256) void flex_conv_bwd_theta_generic(

@@ -45,135 +45,83 @@ def knn_bruteforce(positions, k, name=None):
     return nn, dist
 
 
-# --------------------------------------------------------------------------- flex_conv
-class _FlexConv(torch.autograd.Function):
-    @staticmethod
+# --------------------------------------------------------------------------- reference-layout dispatch
+def _run(stem, like, args, what, ws_shape=None):
+    """Enqueue dh3d_<stem>[_f64|_ws](*args, ...) on the device of `like` and the current stream:
+      float64                                 -> dh3d_<stem>_f64 (flex_conv_op.cc:97-106 registers double too);
+      float32, FAST_PATH, workspace_bytes > 0 -> dh3d_<stem>_ws, given a uint8 workspace of dh3d_<stem>_workspace_bytes(
+                                                 *ws_shape) bytes (section A': csrc/flex_bwd.hip, csrc/flex_deconv.hip);
+      otherwise                               -> dh3d_<stem> (section A, the reference formulation).
+    ws_shape None: the operator has no section A' entry point."""
+    lib, f64 = L.lib(), like.dtype == torch.float64
+    fast = FAST_PATH and ws_shape is not None and not f64
+    with torch.cuda.device(like.device):
+        ws_bytes = getattr(lib, "dh3d_%s_workspace_bytes" % stem)(*ws_shape) if fast else 0
+        if ws_bytes:
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=like.device)
+            L.check(getattr(lib, "dh3d_%s_ws" % stem)(*args, L.ptr(ws), ws_bytes, L.stream_ptr()), what)
+        else:
+            L.check(getattr(lib, "dh3d_" + stem + ("_f64" if f64 else ""))(*args, L.stream_ptr()), what)
+
+
+# --------------------------------------------------------------------------- flex_conv and its transpose
+def _flex_conv_shapes(f, t, bi, nb, p):
+    (B, Din, N), (Dp, Din_t, Dout) = f.shape, t.shape
+    # shape function of user_ops/ops/flex_conv.cc:41-82
+    _same(Din_t, Din, "Din(theta/features)")
+    _same(tuple(bi.shape), (Din, Dout), "bias shape")
+    _same((nb.shape[0], nb.shape[2]), (B, N), "neighborhood [B,_,N]")
+    _same(tuple(p.shape), (B, Dp, N), "position shape")
+
+
+def _flex_deconv_shapes(f, t, bi, nb, p):
+    (B, Din, N), (Dp, Din_t, Dout) = f.shape, t.shape
+    # shape function of user_ops/ops/flex_deconv.cc (FlexDeconv)
+    _same((nb.shape[0], p.shape[0]), (B, B), "batch(features/neighborhood/position)")
+    _same((nb.shape[2], p.shape[2]), (N, N), "N(features/neighborhood/position)")
+    _same(p.shape[1], Dp, "Dp(theta/position)")
+    _same(bi.shape[1], Dout, "Dout(theta/bias)")
+    _same((Din_t, bi.shape[0]), (Din, Din), "Din(features/theta/bias)")
+
+
+def _flex_function(name, stem, what, check_shapes):
+    """The autograd.Function of flex_convolution (stem "flex_conv") or flex_convolution_transpose ("flex_deconv"): the
+    same arguments, layouts and entry-point signatures; check_shapes(f, t, bi, nb, p) is the operator's own."""
+
     def forward(ctx, features, theta, bias, neighborhood, position):
         f = L.require_cuda_float(features, "features", 3)
         t = L.require_cuda_float(theta, "theta", 3, like=f)
         bi = L.require_cuda_float(bias, "bias", 2, like=f)
         nb = L.require_cuda_i32(neighborhood, "neighborhood", 3)
         p = L.require_cuda_float(position, "position", 3, like=f)
-        f64 = f.dtype == torch.float64   # (flex_conv_op.cc:97-106 registers double too: the reference formulation)
-        B, Din, N = f.shape
-        Dp, Din_t, Dout = t.shape
-        K = nb.shape[1]
-        # shape function of user_ops/ops/flex_conv.cc:41-82
-        _same(Din_t, Din, "Din(theta/features)")
-        _same(tuple(bi.shape), (Din, Dout), "bias shape")
-        _same((nb.shape[0], nb.shape[2]), (B, N), "neighborhood [B,_,N]")
-        _same(tuple(p.shape), (B, Dp, N), "position shape")
+        check_shapes(f, t, bi, nb, p)
+        (B, Din, N), (Dp, _, Dout) = f.shape, t.shape
+        ctx.dims = d = (B, N, nb.shape[1], Dp, Din, Dout)  # the sizes every entry point and workspace query takes
         out = torch.empty((B, Dout, N), dtype=f.dtype, device=f.device)
-        with torch.cuda.device(f.device):
-            ws_bytes = L.lib().dh3d_flex_conv_fwd_workspace_bytes(B, N, K, Dp, Din, Dout) if FAST_PATH and not f64 else 0
-            if f64:
-                L.check(L.lib().dh3d_flex_conv_fwd_f64(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
-                                                       Din, Dout, L.ptr(out), L.stream_ptr()), "flex_convolution")
-            elif ws_bytes:  # the DH3D shapes: fused MFMA kernels behind the reference signature (section A' of the ABI)
-                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=f.device)
-                L.check(L.lib().dh3d_flex_conv_fwd_ws(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
-                                                      Din, Dout, L.ptr(out), L.ptr(ws), ws_bytes, L.stream_ptr()),
-                        "flex_convolution")
-            else:       # any other shape: the reference formulation (csrc/flex_generic.hip)
-                L.check(L.lib().dh3d_flex_conv_fwd(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
-                                                   Din, Dout, L.ptr(out), L.stream_ptr()), "flex_convolution")
+        _run(stem + "_fwd", f, (L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p)) + d + (L.ptr(out),), what, d)
         ctx.save_for_backward(f, t, bi, nb, p)
         return out
 
-    @staticmethod
     def backward(ctx, topdiff):
         f, t, bi, nb, p = ctx.saved_tensors
         td = topdiff.contiguous()
-        B, Din, N = f.shape
-        Dp, _, Dout = t.shape
-        K = nb.shape[1]
         gf, gt, gb = torch.empty_like(f), torch.empty_like(t), torch.empty_like(bi)
-        with torch.cuda.device(f.device):
-            f64 = f.dtype == torch.float64
-            ws_bytes = L.lib().dh3d_flex_conv_bwd_workspace_bytes(B, N, K, Dp, Din, Dout) if FAST_PATH and not f64 else 0
-            if f64:
-                L.check(L.lib().dh3d_flex_conv_bwd_f64(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td), B,
-                                                       N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb),
-                                                       L.stream_ptr()), "flex_convolution_grad")
-            elif ws_bytes:  # factorised backward on the MFMA pipe + atomics scatter (csrc/flex_bwd.hip)
-                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=f.device)
-                L.check(L.lib().dh3d_flex_conv_bwd_ws(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td), B,
-                                                      N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb), L.ptr(ws),
-                                                      ws_bytes, L.stream_ptr()), "flex_convolution_grad")
-            else:
-                L.check(L.lib().dh3d_flex_conv_bwd(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td), B,
-                                                   N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb),
-                                                   L.stream_ptr()), "flex_convolution_grad")
+        _run(stem + "_bwd", f, (L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td)) + ctx.dims
+             + (L.ptr(gf), L.ptr(gt), L.ptr(gb)), what + "_grad", ctx.dims)
         return gf, gt, gb, None, None
+
+    # (a named class: autograd shows its nodes as _FlexConvBackward / _FlexDeconvBackward)
+    return type(name, (torch.autograd.Function,), dict(forward=staticmethod(forward), backward=staticmethod(backward)))
+
+
+_FlexConv = _flex_function("_FlexConv", "flex_conv", "flex_convolution", _flex_conv_shapes)
+_FlexDeconv = _flex_function("_FlexDeconv", "flex_deconv", "flex_convolution_transpose", _flex_deconv_shapes)
 
 
 def flex_convolution(features, position, neighborhood, theta, bias, name=None):
     """features [B,Din,N], position [B,Dp,N], neighborhood [B,K,N] int32, theta [Dp,Din,Dout],
     bias [Din,Dout] -> [B,Dout,N]   (user_ops/__init__.py:63-89; note its argument re-order)."""
     return _FlexConv.apply(features, theta, bias, neighborhood, position)
-
-
-# --------------------------------------------------------------------------- flex_conv transpose (FlexDeconv)
-class _FlexDeconv(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, features, theta, bias, neighborhood, position):
-        f = L.require_cuda_float(features, "features", 3)
-        t = L.require_cuda_float(theta, "theta", 3, like=f)
-        bi = L.require_cuda_float(bias, "bias", 2, like=f)
-        nb = L.require_cuda_i32(neighborhood, "neighborhood", 3)
-        p = L.require_cuda_float(position, "position", 3, like=f)
-        f64 = f.dtype == torch.float64
-        B, Din, N = f.shape
-        Dp, Din_t, Dout = t.shape
-        K = nb.shape[1]
-        # shape function of user_ops/ops/flex_deconv.cc (FlexDeconv)
-        _same((nb.shape[0], p.shape[0]), (B, B), "batch(features/neighborhood/position)")
-        _same((nb.shape[2], p.shape[2]), (N, N), "N(features/neighborhood/position)")
-        _same(p.shape[1], Dp, "Dp(theta/position)")
-        _same(bi.shape[1], Dout, "Dout(theta/bias)")
-        _same((Din_t, bi.shape[0]), (Din, Din), "Din(features/theta/bias)")
-        out = torch.empty((B, Dout, N), dtype=f.dtype, device=f.device)
-        with torch.cuda.device(f.device):
-            ws_bytes = L.lib().dh3d_flex_deconv_fwd_workspace_bytes(B, N, K, Dp, Din, Dout) if FAST_PATH and not f64 else 0
-            if f64:
-                L.check(L.lib().dh3d_flex_deconv_fwd_f64(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
-                                                         Din, Dout, L.ptr(out), L.stream_ptr()), "flex_convolution_transpose")
-            elif ws_bytes:  # inverted neighbour lists + GEMM (section A', csrc/flex_deconv.hip)
-                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=f.device)
-                L.check(L.lib().dh3d_flex_deconv_fwd_ws(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
-                                                        Din, Dout, L.ptr(out), L.ptr(ws), ws_bytes, L.stream_ptr()),
-                        "flex_convolution_transpose")
-            else:       # any other shape: the reference formulation
-                L.check(L.lib().dh3d_flex_deconv_fwd(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), B, N, K, Dp,
-                                                     Din, Dout, L.ptr(out), L.stream_ptr()), "flex_convolution_transpose")
-        ctx.save_for_backward(f, t, bi, nb, p)
-        return out
-
-    @staticmethod
-    def backward(ctx, topdiff):
-        f, t, bi, nb, p = ctx.saved_tensors
-        td = topdiff.contiguous()
-        B, Din, N = f.shape
-        Dp, _, Dout = t.shape
-        K = nb.shape[1]
-        gf, gt, gb = torch.empty_like(f), torch.empty_like(t), torch.empty_like(bi)
-        with torch.cuda.device(f.device):
-            f64 = f.dtype == torch.float64
-            ws_bytes = L.lib().dh3d_flex_deconv_bwd_workspace_bytes(B, N, K, Dp, Din, Dout) if FAST_PATH and not f64 else 0
-            if f64:
-                L.check(L.lib().dh3d_flex_deconv_bwd_f64(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td),
-                                                         B, N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb),
-                                                         L.stream_ptr()), "flex_convolution_transpose_grad")
-            elif ws_bytes:
-                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=f.device)
-                L.check(L.lib().dh3d_flex_deconv_bwd_ws(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td), B,
-                                                        N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb), L.ptr(ws),
-                                                        ws_bytes, L.stream_ptr()), "flex_convolution_transpose_grad")
-            else:
-                L.check(L.lib().dh3d_flex_deconv_bwd(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), L.ptr(p), L.ptr(td), B,
-                                                     N, K, Dp, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb),
-                                                     L.stream_ptr()), "flex_convolution_transpose_grad")
-        return gf, gt, gb, None, None
 
 
 def flex_convolution_transpose(features, position, neighborhood, theta, bias, name=None):
@@ -189,24 +137,13 @@ class _FlexPool(torch.autograd.Function):
     def forward(ctx, features, neighborhood):
         f = L.require_cuda_float(features, "features", 3)
         nb = L.require_cuda_i32(neighborhood, "neighborhood", 3)
-        f64 = f.dtype == torch.float64
         B, D, N = f.shape
         K = nb.shape[1]
         _same((nb.shape[0], nb.shape[2]), (B, N), "neighborhood [B,_,N]")  # ops/flex_pool.cc:35-56
         out = torch.empty_like(f)
         argmax = torch.empty((B, D, N), dtype=torch.int32, device=f.device)
-        with torch.cuda.device(f.device):
-            ws_bytes = L.lib().dh3d_flex_pool_fwd_workspace_bytes(B, N, K, D) if FAST_PATH and not f64 else 0
-            if f64:
-                L.check(L.lib().dh3d_flex_pool_fwd_f64(L.ptr(f), L.ptr(nb), B, N, K, D, L.ptr(out), L.ptr(argmax),
-                                                       L.stream_ptr()), "flex_pooling")
-            elif ws_bytes:
-                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=f.device)
-                L.check(L.lib().dh3d_flex_pool_fwd_ws(L.ptr(f), L.ptr(nb), B, N, K, D, L.ptr(out), L.ptr(argmax),
-                                                      L.ptr(ws), ws_bytes, L.stream_ptr()), "flex_pooling")
-            else:
-                L.check(L.lib().dh3d_flex_pool_fwd(L.ptr(f), L.ptr(nb), B, N, K, D, L.ptr(out), L.ptr(argmax),
-                                                   L.stream_ptr()), "flex_pooling")
+        _run("flex_pool_fwd", f, (L.ptr(f), L.ptr(nb), B, N, K, D, L.ptr(out), L.ptr(argmax)), "flex_pooling",
+             (B, N, K, D))
         ctx.save_for_backward(argmax)
         ctx.mark_non_differentiable(argmax)
         return out, argmax
@@ -217,9 +154,7 @@ class _FlexPool(torch.autograd.Function):
         td = topdiff.contiguous()
         B, D, N = td.shape
         gf = torch.empty_like(td)
-        with torch.cuda.device(td.device):
-            fn = L.lib().dh3d_flex_pool_bwd_f64 if td.dtype == torch.float64 else L.lib().dh3d_flex_pool_bwd
-            L.check(fn(L.ptr(td), L.ptr(argmax), B, N, D, L.ptr(gf), L.stream_ptr()), "flex_pooling_grad")
+        _run("flex_pool_bwd", td, (L.ptr(td), L.ptr(argmax), B, N, D, L.ptr(gf)), "flex_pooling_grad")
         return gf, None
 
 
@@ -237,17 +172,14 @@ class _ConvPointset(torch.autograd.Function):
         t = L.require_cuda_float(theta, "theta", 2, like=f)
         bi = L.require_cuda_float(bias, "bias", 1, like=f)
         nb = L.require_cuda_i32(neighborhood, "neighborhood", 3)
-        B, Din, N = f.shape
-        Din_t, Dout = t.shape
-        K = nb.shape[1]
+        (B, Din, N), (Din_t, Dout) = f.shape, t.shape
         _same(Din_t, Din, "Din(theta/features)")  # ops/conv_pointset.cc:38-73
         _same(bi.shape[0], Dout, "bias length")
         _same((nb.shape[0], nb.shape[2]), (B, N), "neighborhood [B,_,N]")
+        ctx.dims = d = (B, N, nb.shape[1], Din, Dout)
         out = torch.empty((B, Dout, N), dtype=f.dtype, device=f.device)
-        with torch.cuda.device(f.device):
-            fn = L.lib().dh3d_conv_pointset_fwd_f64 if f.dtype == torch.float64 else L.lib().dh3d_conv_pointset_fwd
-            L.check(fn(L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb), B, N, K, Din, Dout, L.ptr(out), L.stream_ptr()),
-                    "convolution_pointset")
+        _run("conv_pointset_fwd", f, (L.ptr(f), L.ptr(t), L.ptr(bi), L.ptr(nb)) + d + (L.ptr(out),),
+             "convolution_pointset")
         ctx.save_for_backward(f, t, nb)
         return out
 
@@ -255,15 +187,10 @@ class _ConvPointset(torch.autograd.Function):
     def backward(ctx, topdiff):
         f, t, nb = ctx.saved_tensors
         td = topdiff.contiguous()
-        B, Din, N = f.shape
-        Dout = t.shape[1]
-        K = nb.shape[1]
         gf, gt = torch.empty_like(f), torch.empty_like(t)
-        gb = torch.empty((Dout,), dtype=f.dtype, device=f.device)
-        with torch.cuda.device(f.device):
-            fn = L.lib().dh3d_conv_pointset_bwd_f64 if f.dtype == torch.float64 else L.lib().dh3d_conv_pointset_bwd
-            L.check(fn(L.ptr(f), L.ptr(t), L.ptr(nb), L.ptr(td), B, N, K, Din, Dout, L.ptr(gf), L.ptr(gt), L.ptr(gb),
-                       L.stream_ptr()), "convolution_pointset_grad")
+        gb = torch.empty((t.shape[1],), dtype=f.dtype, device=f.device)
+        _run("conv_pointset_bwd", f, (L.ptr(f), L.ptr(t), L.ptr(nb), L.ptr(td)) + ctx.dims
+             + (L.ptr(gf), L.ptr(gt), L.ptr(gb)), "convolution_pointset_grad")
         return gf, gt, gb, None
 
 

@@ -11,10 +11,6 @@ from . import _lib as L
 ACT_NONE, ACT_RELU, ACT_SIGMOID = L.ACT_NONE, L.ACT_RELU, L.ACT_SIGMOID
 
 
-def _ep(pre_bias, scale, shift, act):
-    return L.make_epilogue(pre_bias, scale, shift, act)
-
-
 def knn_xyz(xyz, k):
     """xyz [B,N,3] -> (nbr [B,N,K] int32, dist [B,N,K]); same function as ops.knn_bruteforce."""
     x = L.require_cuda_f32(xyz, "xyz", 3)
@@ -234,7 +230,7 @@ def flex_conv(features, xyz, nbr, wpacked, Dout, pre_bias=None, scale=None, shif
     if tuple(x.shape) != (B, N, 3) or tuple(nb.shape[:2]) != (B, N):
         raise ValueError("flex_conv: xyz/nbr do not match [B,N,*]")
     out = torch.empty((B, N, Dout), dtype=torch.float32, device=f.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_flex_conv_pm_gather_fwd(L.ptr(f), L.ptr(rm), f.shape[1], L.ptr(x), L.ptr(nb), L.ptr(wpacked), B,
                                                  N, K, Din, Dout, ep, L.ptr(out), L.stream_ptr()), "flex_conv_pm")
     return out
@@ -257,7 +253,7 @@ def flex_conv_tile_x6(features, xyz, nbr, wpacked_x3, Dout, pre_bias=None, scale
         raise ValueError("flex_conv_tile_x6: xyz/nbr do not match features [B,N,*]")
     out = torch.empty((B, N, Dout), dtype=torch.float32, device=f.device)
     out2 = torch.empty((B, N, Dpost), dtype=torch.float32, device=f.device) if wpost_packed is not None else None
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_flex_conv_pm_tile_x6_fwd(L.ptr(f), L.ptr(x), L.ptr(nb), L.ptr(wpacked_x3), B, N, nb.shape[2], Din,
                                                   Dout, ep, L.ptr(out), L.ptr(wpost_packed), int(Dpost), L.ptr(out2),
                                                   L.stream_ptr()), "flex_conv_pm_tile_x6")
@@ -294,7 +290,7 @@ def flex_conv_x6(features, xyz, nbr, wpacked_x3, Dout, pre_bias=None, scale=None
     if tuple(x.shape) != (B, N, 3) or tuple(nb.shape[:2]) != (B, N):
         raise ValueError("flex_conv_x6: xyz/nbr do not match features [B,N,*]")
     out = torch.empty((B, N, Dout), dtype=torch.float32, device=f.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_flex_conv_pm_x6_fwd_r(L.ptr(f), L.ptr(x), L.ptr(nb), L.ptr(wpacked_x3), B, N, K, Din, Dout, ep,
                                                int(reserve_cus_per_xcd), L.ptr(out), L.stream_ptr()), "flex_conv_pm_x6")
     return out
@@ -330,7 +326,7 @@ def conv_pointset_xyz(xyz, nbr, theta, bias, pre_bias=None, scale=None, shift=No
     K = nb.shape[2]
     Dout = theta.shape[1]
     out = torch.empty((B, N, Dout), dtype=torch.float32, device=x.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_conv_pointset_pm_fwd(L.ptr(x), L.ptr(nb), L.ptr(theta), L.ptr(bias), B, N, K, Dout, ep,
                                               L.ptr(out), L.stream_ptr()), "conv_pointset_pm")
     return out
@@ -345,7 +341,7 @@ def conv_pointset_pool_xyz(xyz, nbr, theta, bias, pre_bias=None, scale=None, shi
     Dout = theta.shape[1]
     out = torch.empty((B, N, Dout), dtype=torch.float32, device=x.device)
     scratch = torch.empty((B, N, 4), dtype=torch.float32, device=x.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_conv_pointset_pool_pm_fwd(L.ptr(x), L.ptr(nb), L.ptr(theta), L.ptr(bias), B, N, nb.shape[2], Dout,
                                                    ep, L.ptr(scratch), L.ptr(out), L.stream_ptr()), "conv_pointset_pool_pm")
     return out
@@ -368,7 +364,7 @@ def linear(x1, wpacked, Dout, x2=None, pre_bias=None, scale=None, shift=None, ac
     if residual is not None:
         res = L.require_cuda_f32(residual, "residual")
     out = torch.empty(lead + (Dout,), dtype=torch.float32, device=a.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_linear_pm_fwd(L.ptr(a), C1, L.ptr(b), C2, L.ptr(wpacked), R, Dout, ep, L.ptr(res),
                                        L.ptr(out), L.stream_ptr()), "linear_pm")
     return out
@@ -429,7 +425,7 @@ def se_res_pool_conv(x, nbr, w1packed, b1pad, w2packed, b2, conv_wp, conv_b, con
     nb = L.require_cuda_i32(nbr, "nbr", 3)
     B, N, C = a.shape
     out, out2 = torch.empty_like(a), torch.empty((B, N, C), dtype=torch.float32, device=a.device)
-    ep = _ep(conv_b, conv_scale, conv_shift, act)
+    ep = L.make_epilogue(conv_b, conv_scale, conv_shift, act)
     L.check(L.lib().dh3d_se_res_pool_conv_pm_fwd(L.ptr(a), L.ptr(nb), B, N, nb.shape[2], L.ptr(w1packed), L.ptr(b1pad),
                                                  L.ptr(w2packed), L.ptr(b2), C, L.ptr(out), L.ptr(conv_wp), ep, C,
                                                  L.ptr(out2), L.stream_ptr()), "se_res_pool_conv_pm")
@@ -468,7 +464,7 @@ def mlp_head(h, wpacked, H, w_fc, b_fc, pre_bias=None, scale=None, shift=None, a
     C = a.shape[-1]
     R = a.numel() // C
     out = torch.empty(a.shape[:-1] + (1,), dtype=torch.float32, device=a.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_mlp_head_pm_fwd(L.ptr(a), R, C, L.ptr(wpacked), H, ep, L.ptr(w_fc), float(b_fc),
                                          L.ptr(out), L.stream_ptr()), "mlp_head_pm")
     return out
@@ -491,7 +487,7 @@ def linear_x6(x1, wpacked_x3, Dout, x2=None, pre_bias=None, scale=None, shift=No
     if residual is not None:
         res = L.require_cuda_f32(residual, "residual")
     out = torch.empty(lead + (Dout,), dtype=torch.float32, device=a.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_linear_pm_x6_fwd(L.ptr(a), C1, L.ptr(b), C2, L.ptr(wpacked_x3), R, Dout, ep, L.ptr(res),
                                           L.ptr(out), L.stream_ptr()), "linear_pm_x6")
     return out
@@ -517,7 +513,7 @@ def upsample_linear_x6(points, idx, dist, wpacked_x3, Dout, x2=None, pre_bias=No
     res = None
     if residual is not None:
         res = L.require_cuda_f32(residual, "residual", 3)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     if l2cat is not None:
         pf = L.require_cuda_f32(l2cat[0], "prefix", 3)
         if tuple(pf.shape) != (B, n, 3):
@@ -555,7 +551,7 @@ def upsample_linear_shortcut_x6(points, idx, dist, wstacked_x3, Dout, x2, x3, ep
             raise ValueError("upsample_linear_shortcut_x6: prefix must be [B,n,3]")
         width = 3 + Dout
     out = torch.empty((B, n, width), dtype=torch.float32, device=p.device)
-    e1, e2 = _ep(*ep_main), _ep(*ep_shortcut)
+    e1, e2 = L.make_epilogue(*ep_main), L.make_epilogue(*ep_shortcut)
     L.check(L.lib().dh3d_upsample_linear_shortcut_pm_x6_fwd(
         L.ptr(p), L.ptr(ix), L.ptr(d), B, n, m, C1, L.ptr(b), b.shape[-1], L.ptr(c), c.shape[-1], L.ptr(wstacked_x3),
         Dout, e1, e2, L.ptr(pf), float(l2cat[1]) if l2cat is not None else 0.0, L.ptr(out), L.stream_ptr()),
@@ -574,7 +570,7 @@ def interp_combine(coarse_w, idx, dist, partial=None, pre_bias=None, scale=None,
     N = ix.shape[1]
     pf, eps = (L.require_cuda_f32(l2cat[0], "prefix", 3), float(l2cat[1])) if l2cat is not None else (None, 0.0)
     out = torch.empty((B, N, C + (3 if pf is not None else 0)), dtype=torch.float32, device=cw.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_interp_combine_fwd(L.ptr(cw), L.ptr(ix), L.ptr(d), L.ptr(partial), B, N, M, C, ep,
                                             L.ptr(residual), L.ptr(pf), eps, L.ptr(out), L.stream_ptr()),
             "interp_combine")
@@ -595,7 +591,7 @@ def local_tail_fused(x1, x2, wp3_shortcut, wp3_lower, ep_shortcut, ep_concat, co
     if C != 64 or b.shape != a.shape or cw.shape[2] != 128 or N % 32:
         raise ValueError("local_tail_fused: x1 / x2 [B,N,64], coarse_w [B,M,128], N % 32 == 0")
     out = torch.empty((B, N, 131 if pf is not None else 128), dtype=torch.float32, device=a.device)
-    e1, e2 = _ep(*ep_shortcut, ACT_RELU), _ep(*ep_concat, ACT_RELU)
+    e1, e2 = L.make_epilogue(*ep_shortcut, ACT_RELU), L.make_epilogue(*ep_concat, ACT_RELU)
     L.check(L.lib().dh3d_local_tail_fused_fwd(L.ptr(a), L.ptr(b), L.ptr(wp3_shortcut), L.ptr(wp3_lower), e1, e2, L.ptr(cw),
                                               L.ptr(ix), L.ptr(d), L.ptr(pf), float(l2_eps), B, N, cw.shape[1], L.ptr(out),
                                               L.stream_ptr()), "local_tail_fused")
@@ -617,7 +613,7 @@ def mlp_head_x6(h, wpacked_x3, H, w_fc, b_fc, pre_bias=None, scale=None, shift=N
     C = a.shape[-1]
     R = a.numel() // C
     out = torch.empty(a.shape[:-1] + (1,), dtype=torch.float32, device=a.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     L.check(L.lib().dh3d_mlp_head_pm_x6_fwd(L.ptr(a), R, C, L.ptr(wpacked_x3), H, ep, L.ptr(w_fc), float(b_fc),
                                             L.ptr(out), L.stream_ptr()), "mlp_head_pm_x6")
     return out
@@ -640,7 +636,7 @@ def interp_head(coarse, idx, dist, wslices_x3, Hd, w_fc, b_fc, pre_bias=None, sc
     L.check(L.lib().dh3d_linear_slices_pm_x6_fwd(L.ptr(x), C, L.ptr(wslices_x3), B * m, ns, L.ptr(H), L.stream_ptr()),
             "linear_slices_pm_x6")
     out = torch.empty((B, n, 1), dtype=torch.float32, device=x.device)
-    ep = _ep(pre_bias, scale, shift, act)
+    ep = L.make_epilogue(pre_bias, scale, shift, act)
     if order is not None and m <= 1024:
         # fine points in Morton order (`order` = spatial_sort records of the fine cloud), coarse rows staged in LDS
         L.check(L.lib().dh3d_interp_head_sorted_fwd(L.ptr(H), Hd, L.ptr(ix), L.ptr(d), L.ptr(order), B, n, m, ep,
@@ -731,7 +727,7 @@ def global_tail(coarse, idx, dist, order, wslices_x3, Hd, w_fc, b_fc, att_ep, wc
         accum = torch.empty((global_tail_accum_size(B, m),), dtype=torch.float32, device=x.device)
     elif accum.numel() != global_tail_accum_size(B, m) or accum.dtype != torch.float32 or not accum.is_cuda:
         raise ValueError("global_tail: accum must be a zeroed float32 GPU tensor of global_tail_accum_size(B, m) elements")
-    ep = _ep(*att_ep)
+    ep = L.make_epilogue(*att_ep)
     if plan is not None and (plan.dtype != torch.int32 or plan.numel() * 4 != L.lib().dh3d_walk_plan_bytes(B, n)):
         raise ValueError("global_tail: plan is not walk_plan(idx, dist, order, m) of these shapes")
     L.check(L.lib().dh3d_global_walk_planned_fwd(L.ptr(H), Hd, L.ptr(x), L.ptr(cw), L.ptr(ix), L.ptr(d), L.ptr(order), L.ptr(plan),
@@ -1091,7 +1087,7 @@ def interp_head_rows(G, idx, dist, order, scale, shift, w_fc, b_fc_dev):
     Hd, rm, m = _g_layout(G, idx)
     B, n = idx.shape[0], idx.shape[1]
     out = torch.empty((B * n,), dtype=torch.float32, device=G.device)
-    ep = _ep(None, scale, shift, ACT_RELU)
+    ep = L.make_epilogue(None, scale, shift, ACT_RELU)
     L.check(L.lib().dh3d_interp_head_sorted_fwd_dev(L.ptr(G), Hd, rm, L.ptr(idx), L.ptr(dist), L.ptr(order), B, n, m, ep,
                                                     L.ptr(w_fc), L.ptr(b_fc_dev), L.ptr(out), L.stream_ptr()),
             "interp_head_sorted_dev")
