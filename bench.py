@@ -2,7 +2,12 @@
 """Benchmark of the DH3D hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload local|global|cfg5|train] [--scaling weak|strong]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full [--extras]]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  `--full` adds
+what the headline does not need (one step at a time, further timed blocks, the other K, the serving loop, the global
+forward in a fresh process, the multi-GPU global lines, the roofline kernel with live PMC, the CPU baseline, the side
+file); `--extras` (implies `--full`) adds the evidence tables on top.
 
 A "step" is one pass of the hot path over one batch of synthetic clouds already resident in HBM:
   local  (default, BASELINE config[1]): local-descriptor forward, basic_config, N=8192 K=8, batch 8
@@ -919,18 +924,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     # K = 100 by default since round 6: with steps in flight the K timed steps include the fill and the drain of the pipeline
     # (four slots for the local forward), which weighed ~5 % at the K = 20 of rounds 1-5 (and of the driver's command line,
-    # `--steps 20 --warmup 5`); the line carries the other K's figure as `at_20_steps` / `at_100_steps`
+    # `--steps 20 --warmup 5`); a --full line carries the other K's figure as `at_20_steps` / `at_100_steps`
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="local")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--batch", type=int, default=0, help="override the workload's batch (clouds)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: one step at a time, --repeats further blocks, the "
+                         "other K, the serving loop, the global forward in a fresh process (or with --gpus N > 1 the global "
+                         "path's weak / strong lines), the roofline kernel, the CPU baseline; the full record goes to the "
+                         "side file (--extras-file).  The --no-* options below trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the roofline of the named kernel too (headline only)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the roofline of the named kernel and the global line too")
     ap.add_argument("--extras", action="store_true",
                     help="also measure the evidence tables (step-level roofline, other workloads, sweeps in fresh processes, "
-                         "data sensitivity): minutes of wall time; they go to the side file named by the line's `extras` key, "
-                         "never onto the stdout line")
+                         "data sensitivity; implies --full): minutes of wall time; they go to the side file named by the "
+                         "line's `extras` key, never onto the stdout line")
     ap.add_argument("--extras-file", default=None,
                     help="where the full record goes (default gpurun_out/bench_extras[_<workload>].json under the repo)")
     ap.add_argument("--no-global-scaling", action="store_true",
@@ -941,8 +952,9 @@ def main():
     ap.add_argument("--no-global-line", action="store_true",
                     help="default workload at one GPU: do not measure the global-descriptor forward (the other half of "
                          "BASELINE.json's metric) in a fresh process for the line's `global` block")
-    ap.add_argument("--repeats", type=int, default=7,
-                    help="further blocks of K timed steps after the contract block (median / min / max as extra keys)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="further blocks of K timed steps after the contract block (median / min / max as extra keys); "
+                         "default 7 with --full, 0 without")
     ap.add_argument("--inflight", type=int, default=0,
                     help="independent steps in flight (graph instances on separate streams, each with its own batch "
                          "buffers, every step one full pass over one batch).  Default 0 = the workload's own (local 4, "
@@ -960,6 +972,9 @@ def main():
     if args.dump_outputs and args.workload in ("train", "train_local"):
         ap.error("--dump-outputs: a training step's results depend on every step before it, including the time-based "
                  "clock ramp; only the forward workloads have reproducible outputs")
+    args.full = args.full or args.extras
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 0
     explicit_inflight = args.inflight > 0
     if not explicit_inflight:
         args.inflight = WORKLOADS[args.workload]["inflight"]
@@ -1034,14 +1049,16 @@ def main():
         pts = synthetic_clouds(wl["B"], wl["N"], wl["seed"], dev, 0)  # same role-ordered batch on every rank
         # (the loss stays on the device: nothing in the timed loop waits for the GPU but the closing synchronize)
         dt = time_steps(resident_step(trainer), pts, args.steps, args.warmup, dev)
+        extra = {"head_implementation": trainer.impl, "step_graphed": bool(trainer._step_graphs),
+                 "frozen_backbone_batchnorm": "moving averages (fused inference path); the reference graph uses batch "
+                                              "statistics there -- QuadrupletTrainer(backbone_bn='batch'), DESIGN.md 6"}
+        if not args.full:
+            return wl["B"] * args.steps / dt, dt / args.steps * 1e3, extra
         trainer.time_phases(True)   # five more (untimed) steps with events around the phases
         D.COLLECTIVE_CALLS[0] = 0
         for _ in range(5):
             trainer.step(pts)
-        extra = {"phases_ms": trainer.phase_times_ms(), "head_implementation": trainer.impl,
-                 "step_graphed": bool(trainer._step_graphs), "collectives_per_step": D.COLLECTIVE_CALLS[0] / 5.0,
-                 "frozen_backbone_batchnorm": "moving averages (fused inference path); the reference graph uses batch "
-                                              "statistics there -- QuadrupletTrainer(backbone_bn='batch'), DESIGN.md 6"}
+        extra.update({"phases_ms": trainer.phase_times_ms(), "collectives_per_step": D.COLLECTIVE_CALLS[0] / 5.0})
         trainer.time_phases(False)
         if world == 1:
             extra["sharded_path"] = sharded_path_at_one_rank(model, pts, dt / args.steps * 1e3)
@@ -1188,7 +1205,7 @@ def main():
             dt = time_steps(step, pts, nsteps, args.warmup, dev, align=lambda: (depth - pipe.next_slot) % depth)
             if args.dump_outputs and workload == args.workload and not steps and strong_ is None:
                 _LAST_OUTPUTS["in_flight"] = {k: host_output(v) for k, v in pipe.result(last[0], wait="host").items()}
-            if workload == args.workload and not steps:
+            if args.full and workload == args.workload and not steps:
                 # the same pipeline over the OTHER K: 20 = the K of rounds 1-5 and of the driver's command line, 100 = this
                 # file's default (the timed region includes the fill and the drain of the slots: ~5 % at K = 20)
                 ko = 100 if nsteps == 20 else 20
@@ -1313,16 +1330,23 @@ def main():
                                "resident_batches_ms_per_step": dz / long_n * 1e3, "ratio_to_resident": dz / dl}
         return rec
 
+    def one_step_at_a_time():
+        value, ms, info = measure(args.workload)  # the definition of rounds 1-2; `value` for train
+        serial = {"value": value, "unit": "point-clouds/sec", "ms_per_step": ms,
+                  "note": "each step finishes before the next one starts (rounds 1-2 reported this as `value`)"}
+        if "repeats" in info:
+            serial["repeats"] = info.pop("repeats")
+        return value, ms, info, serial
+
     pipelined = args.inflight > 1 and args.workload not in ("train", "train_local")
-    value, ms, info = measure(args.workload)  # one step at a time (the definition of rounds 1-2; `value` for train)
-    serial = {"value": value, "unit": "point-clouds/sec", "ms_per_step": ms,
-              "note": "each step finishes before the next one starts (rounds 1-2 reported this as `value`)"}
-    if "repeats" in info:
-        serial["repeats"] = info.pop("repeats")
+    serial, info = None, {}   # a plain run with steps in flight does not measure one step at a time
+    if args.full or not pipelined:
+        value, ms, info, serial = one_step_at_a_time()
     in_flight_error = None
     if pipelined:
         try:
-            value, ms, rep = measure_in_flight(args.workload, args.inflight, args.repeats, streaming=not args.no_streaming)
+            value, ms, rep = measure_in_flight(args.workload, args.inflight, args.repeats,
+                                               streaming=args.full and not args.no_streaming)
             if rep:
                 info["repeats"] = rep
         except Exception as e:  # noqa: BLE001 -- the line must not be lost: fall back to the one-at-a-time measurement
@@ -1330,6 +1354,8 @@ def main():
                 raise
             in_flight_error = repr(e)[:300]
             pipelined = False
+            if serial is None:
+                value, ms, info, serial = one_step_at_a_time()
     wl = WORKLOADS[args.workload]
     per, total = per_rank_batch(args.batch or wl["B"])
     line = {
@@ -1351,7 +1377,7 @@ def main():
         line["at_%d_steps" % _AT20[args.workload]["steps"]] = {k: _AT20[args.workload][k] for k in ("value", "ms_per_step")}
     if pipelined and args.workload in _STREAMING:
         line["value_streaming"] = _STREAMING[args.workload]
-    if args.workload not in ("train", "train_local"):
+    if serial is not None and args.workload not in ("train", "train_local"):
         line["one_step_at_a_time"] = serial
     if args.workload == "train_local":
         line["config"]["execution"] = ("whole step (local backbone fwd/bwd in training mode, loss, weight decay, fused Adam) "
@@ -1377,8 +1403,8 @@ def main():
         informational numbers get that state too."""
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", workload, "--inflight", str(depth),
-               "--steps", str(steps), "--warmup", str(args.warmup), "--no-extras", "--no-cpu-baseline", "--repeats", "0",
-               "--no-streaming", "--extras-file", os.devnull]
+               "--steps", str(steps), "--warmup", str(args.warmup), "--full", "--no-extras", "--no-cpu-baseline",
+               "--repeats", "0", "--no-streaming", "--extras-file", os.devnull]
         if batch:
             cmd += ["--batch", str(batch)]
         try:
@@ -1390,13 +1416,13 @@ def main():
             return v, ms
 
     def fresh_process_line(workload):
-        """The compact record of `bench.py --workload w` (its own steps in flight AND one step at a time) measured in a
-        process of its own, for the default line's `global` block: BASELINE.json's metric names both forwards, the driver
-        runs this file once without flags."""
+        """The compact record of `bench.py --full --workload w` (its own steps in flight AND one step at a time) measured
+        in a process of its own, for the --full line's `global` block: BASELINE.json's metric names both forwards."""
         import subprocess
         wl_ = WORKLOADS[workload]
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", workload, "--steps", str(args.steps),
-               "--warmup", str(args.warmup), "--no-extras", "--no-cpu-baseline", "--repeats", "0", "--extras-file", os.devnull]
+               "--warmup", str(args.warmup), "--full", "--no-extras", "--no-cpu-baseline", "--repeats", "0",
+               "--extras-file", os.devnull]
         try:
             t0 = time.time()
             out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300).stdout.decode()
@@ -1411,12 +1437,12 @@ def main():
         except Exception as e:  # noqa: BLE001 -- the headline must not be lost with it
             return {"workload": wl_["name"], "error": repr(e)[:200]}
 
-    if rank == 0 and world == 1 and args.workload == "local" and not args.no_extras and not args.no_global_line:
+    if args.full and rank == 0 and world == 1 and args.workload == "local" and not args.no_extras and not args.no_global_line:
         line["global"] = fresh_process_line("global")
 
     # --- N > 1, default workload: the GLOBAL path's weak and strong figures ride on the same line (BASELINE's ">= 6.5x at 8
     # GPUs on the global-descriptor path" is read both ways; every rank takes part: the timed regions hold barriers)
-    if world > 1 and args.workload == "local" and not args.no_global_scaling:
+    if args.full and world > 1 and args.workload == "local" and not args.no_global_scaling:
         gw = WORKLOADS["global"]
         gs = {"workload": gw["name"], "steps_in_flight": gw["inflight"]}
         for tag, st in (("weak", False), ("strong", True)):
@@ -1441,7 +1467,7 @@ def main():
                       "1-GPU batch sweep (DESIGN.md 6)")
         line["global_scaling"] = gs
 
-    roof = rank == 0 and not args.no_extras and args.workload in ("local", "global")
+    roof = args.full and rank == 0 and not args.no_extras and args.workload in ("local", "global")
     extras = roof and args.extras
     if roof:
         with torch.no_grad():
@@ -1568,7 +1594,7 @@ def main():
                         "construction, minus whatever eight processes on one host cost; strong scaling of ONE 32-cloud batch "
                         "(4 clouds per GPU) is bounded by the per-cloud latency chain, not by communication.  UNMEASURED on "
                         "more than one GPU in rounds 1-5 (no 8-GPU node was available to the driver)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("local", "global"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("local", "global"):
         line["cpu_baseline"] = cpu_baseline(args.workload)
     if rank == 0 and args.dump_outputs:
         outs = _LAST_OUTPUTS["in_flight" if pipelined else "serial"]
@@ -1576,7 +1602,7 @@ def main():
                                   "arrays": dump_outputs(outs, args.dump_outputs)}
     D.barrier()
     if rank == 0:
-        path = write_side_file(line, args.extras_file, args.workload)
+        path = write_side_file(line, args.extras_file, args.workload) if args.full else None
         out = compact_line(line, extras_path=path)
         sys.stdout.flush()
         os.write(json_fd, (out + "\n").encode())

@@ -155,3 +155,13 @@ def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
     again = tmp_path / "again"
     bench.dump_outputs({"big": big, "small": small}, str(again), limit=64 << 10)
     assert np.array_equal(np.load(again / "big_rows.npy"), rows)   # the same sample every run
+
+
+def test_plain_line_holds_the_contract_alone():
+    """A run without --full measures the headline alone: its record is the contract's keys and `config`, no side file."""
+    full = {k: v for k, v in _canned(1).items() if k in (
+        "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+        "dtype", "data", "ranks_seen", "config")}
+    rec = json.loads(bench.compact_line(full, extras_path=None))
+    assert set(rec) == set(full) | {"extras"} and rec["extras"] is None
+    assert rec["value"] == pytest.approx(31416.123) and rec["ms_per_step"] == pytest.approx(0.25471235)

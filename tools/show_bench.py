@@ -1,4 +1,4 @@
-"""Dev: print the headline numbers and the roofline_step tables of a bench.py JSON line.  usage: python tools/show_bench.py file"""
+"""Dev: print the headline numbers and the roofline_step tables of a `bench.py --full` JSON line.  usage: python tools/show_bench.py file"""
 import json, sys
 d = None
 for l in open(sys.argv[1]):
