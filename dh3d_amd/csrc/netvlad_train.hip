@@ -6,7 +6,7 @@
 //     s[n]  = r[n] sum_t w_t cw[i_t]                         V[b] = A'^T c,   A'[j,k] = sum_{(n,t): i_t = j} a[n,k] r[n] w_t
 // and, given dV and dasum (E = c dV^T, a GEMM on the sampled rows; e = interp(E)),
 //     da = r e + dasum;   datt = sum_k da p;   dz = p (da att - sum_k da att p);   ds = BN backward of dz;
-//     dcw[j] = sum_{(n,t)} w_t r ds;   dWc = c^T dcw;   q[n] = r^2 sum_k ds s + r^3 sum_k a e;
+//     dcw[j] = sum_{(n,t)} w_t r ds;   dWc = c^T dcw;   q[n] = r^2 sum_k ds s + r^3 sum_k a e (0 where |x|^2 <= 1e-12);
 //     dc = A' dV + dcw Wc^T - interp^T(q x)
 // (algebra checked against float64 autograd by tools/netvlad_commute_check.py and tests/test_host_logic.py).  Nothing
 // 256 wide is ever written for the B*n fine points: the materialised form moved x, xn, dxn, dx (92 MB each at 22 x
@@ -36,6 +36,10 @@ using dh3d_walk::mix3;
 constexpr int kPW = kP / 4;
 constexpr int kCap0 = 56;  // staged rows in MODE 0 (c and cw rows: 71.7 KB; blocks touching more read the excess from L2)
 constexpr int kCap = 64;   // slots in the other modes
+// MODE 3 recognises a row held by the l2 clamp (|x|^2 <= 1e-12, where l2norm_rows_bwd drops the norm's gradient) by
+// the rinv MODE 0 wrote: rsqrtf(1e-12f) = 1e6 within the rsqrt's 1 ulp (2^-4 here), while a live norm gives
+// rsqrtf(|x|^2) < 1e6 - 2^-3 once |x|^2 > 1e-12 (1 + 4e-7).  Rows in that sliver above 1e-12 count as clamped.
+constexpr float kRinvClamped = 1e6f - 0.125f;
 
 struct NvArgs {
   const float *c;        // [B*m, 256] sampled rows (MODE 0)
@@ -349,7 +353,8 @@ __global__ __launch_bounds__(256) void nv_walk_kernel(const NvArgs a) {
         s_d[pt * 64 + lane] = ds[h];
         if (o >= 0 && lane == 0) {
           const float rv = s_f1[pt];
-          a.q[rbase + o] = rv * rv * (bcast(rg, h == 0 ? 16 : 48) + rv * s_f2[pt]);  // r^2 sum ds s + r^3 sum a e
+          // r^2 sum ds s + r^3 sum a e; 0 where the l2 clamp held the row (r constant: no gradient through it)
+          a.q[rbase + o] = rv >= kRinvClamped ? 0.f : rv * rv * (bcast(rg, h == 0 ? 16 : 48) + rv * s_f2[pt]);
         }
         if (overflow) {
           const int4 si = *reinterpret_cast<const int4 *>(s_slot + pt * 4);

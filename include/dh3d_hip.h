@@ -725,8 +725,8 @@ int dh3d_three_interpolate_bwd_sorted(int b, int n, int c, int m, const float *g
  *               by the CALLER; V[b] = Ap[b]^T c[b])
  *   bwd_sums  : da = rinv*interp(E) + dasum; datt = sum_k da p (0 for masked clouds); dz = softmax backward of da*att;
  *               t2 = sum_k p att interp(E); part [2][B][64] f64 (zeroed by the CALLER) = per-cloud sums of dz and dz*(s - mean)*rstd
- *   bwd_apply : ds = k1*dz - k2 - k3*s (dh3d_bn_bwd_finalize); q = rinv^2 sum_k ds s + rinv^3 t2; dcw [B*m,64] =
- *               interp^T(rinv*ds) (zeroed by the CALLER)
+ *   bwd_apply : ds = k1*dz - k2 - k3*s (dh3d_bn_bwd_finalize); q = rinv^2 sum_k ds s + rinv^3 t2, 0 on rows the l2
+ *               clamp held (rinv = rsqrt(1e-12): no gradient through it); dcw [B*m,64] = interp^T(rinv*ds) (zeroed by the CALLER)
  * dh3d_interp_scatter_scaled: dc [B*m,256] += interp^T(-q * interp(c)) (dc NOT zeroed: it holds Ap dV + dcw Wc^T). */
 int dh3d_netvlad_commuted_fwd_stats(const float *c, const float *cw, const int32_t *idx, const float *dist,
                                     const float *order, int B, int n, int m, const unsigned char *mask, float *s,

@@ -461,6 +461,17 @@ def test_commuted_attention_head_matches_the_materialised_one(dev, N, use_mask):
 @pytest.mark.parametrize("N,use_mask,scrambled", [(4096, False, False), (4096, True, False), (5000, False, False),
                                                   (4096, False, True)])
 def test_commuted_netvlad_assignment_matches_the_materialised_one(dev, N, use_mask, scrambled):
+    _commuted_netvlad_vs_materialised(dev, N, use_mask, scrambled)
+
+
+def test_commuted_netvlad_assignment_matches_on_rows_the_l2_clamp_holds(dev):
+    """The same with fine points whose interpolated row has 0 < |x|^2 <= 1e-12 (all three neighbours on sampled rows
+    of norm 7e-7): the l2 normalisation's clamp holds their norm, so it passes no gradient -- the materialised
+    backward (l2norm_rows_bwd) drops the term there and the commuted one (q = 0 in netvlad_commuted_bwd_apply) must too."""
+    _commuted_netvlad_vs_materialised(dev, 4096, True, False, clamped=True)
+
+
+def _commuted_netvlad_vs_materialised(dev, N, use_mask, scrambled, clamped=False):
     """train_ops.netvlad_assign_commuted (NetVLAD's rows commuted through three_interpolate, nothing 256 wide written
     for the fine points, csrc/netvlad_train.hip + interp_train.hip MODE 4) == train_ops.netvlad_assign on the
     materialised up-sampled rows (core/backbones.py:202-256): V, asum, the gradients of the sampled rows, the
@@ -476,6 +487,14 @@ def test_commuted_netvlad_assignment_matches_the_materialised_one(dev, N, use_ma
     d3, i3 = ops.three_nn(pts, cxyz)
     if scrambled:
         i3 = torch.randint(0, M, (Bt, N, 3), generator=g, dtype=torch.int32).to(dev)
+    rows = None
+    if clamped:   # sampled rows of norm 7e-7, and every other fine point whose nearest one they are uses only them
+        rows = torch.unique(i3[:, ::97, 0].reshape(-1))[:8].long()
+        i3 = i3.clone()
+        for b in range(Bt):
+            sel = torch.isin(i3[b, :, 0].long(), rows).nonzero().reshape(-1)[::2]
+            i3[b, sel, 1:] = i3[b, sel, :1]
+        assert int(torch.isin(i3[:, :, 2].long(), rows).sum()) >= 20
     order = pm.spatial_sort(pts)[0]
     mask = torch.tensor([True, False, True], device=dev) if use_mask else None
     dV = torch.randn(Bt, 64, Dm, generator=torch.Generator().manual_seed(11)).to(dev)
@@ -489,7 +508,10 @@ def test_commuted_netvlad_assignment_matches_the_materialised_one(dev, N, use_ma
         with torch.no_grad():
             nv.cluster_bn.gamma.copy_(0.5 + torch.rand(64, generator=torch.Generator().manual_seed(1)).to(dev))
             nv.cluster_bn.beta.copy_(0.3 * torch.randn(64, generator=torch.Generator().manual_seed(2)).to(dev))
-        coarse = torch.randn(Bt, M, Dm, generator=torch.Generator().manual_seed(7)).to(dev).requires_grad_(True)
+        coarse = torch.randn(Bt, M, Dm, generator=torch.Generator().manual_seed(7)).to(dev)
+        if rows is not None:
+            coarse[:, rows] *= 7e-7 / coarse[:, rows].norm(dim=-1, keepdim=True)
+        coarse.requires_grad_(True)
         att = torch.rand(Bt * N, generator=torch.Generator().manual_seed(8)).to(dev).requires_grad_(True)
         if commuted:
             V, asum = T.netvlad_assign_commuted(coarse, att, nv.cluster_weights, nv.cluster_bn, i3, d3, order, False, mask)

@@ -9,7 +9,8 @@ Backward (dV, dasum given):
            E = c dV^T (GEMM);  e = interp(E);  da = r e + dasum;  datt = sum_k da p;  dz = p (da att - sum_k da att p);
            ds = BN backward of dz (needs S1 = sum dz, S2 = sum dz s_hat: one 64-wide walk);
            dcw[j] = sum_{(n,t)} w_t r ds   (64-wide scatter);   dWc = c^T dcw;
-           q[n] = r^3 (sum_k ds u + sum_k a e);   dc = A' dV + dcw Wc^T - interp^T(q x)   (the last term: ONE 256-wide walk).
+           q[n] = r^3 (sum_k ds u + sum_k a e), 0 where the clamp holds the norm (|x|^2 <= eps: r has no gradient);
+           dc = A' dV + dcw Wc^T - interp^T(q x)   (the last term: ONE 256-wide walk).
 usage: python tools/netvlad_commute_check.py   (prints the largest relative deviations; exits non-zero above 1e-9)"""
 import sys
 import torch
@@ -24,6 +25,11 @@ gamma = (0.5 + torch.rand(K, dtype=dt)).requires_grad_()
 beta = torch.randn(K, dtype=dt, requires_grad=True)
 att = torch.rand(Bt, N, dtype=dt, requires_grad=True)
 idx = torch.stack([torch.stack([torch.randperm(M)[:3] for _ in range(N)]) for _ in range(Bt)])      # [Bt,N,3]
+# rows held by the l2 clamp: two sampled rows of norm 7e-7, and fine points whose three neighbours are only those
+with torch.no_grad():
+    c[:, :2] *= 7e-7 / c[:, :2].norm(dim=-1, keepdim=True)
+idx[:, 5:9, :] = 0
+idx[:, 9:11, :] = torch.tensor([0, 1, 1])
 w = torch.rand(Bt, N, 3, dtype=dt); w = w / w.sum(2, keepdim=True)
 dV = torch.randn(Bt, K, D, dtype=dt)
 dasum = torch.randn(Bt, K, dtype=dt)
@@ -84,7 +90,9 @@ with torch.no_grad():
     dcw = interp_t(ds * r[..., None])
     dWc2 = (cd.reshape(-1, D).t() @ dcw.reshape(-1, K))
     q = r ** 3 * ((ds * u).sum(2) + (a2 * e).sum(2))
-    # (rows clamped by eps_l2 would have dr = 0: none here)
+    clamped = (xx * xx).sum(2) <= eps_l2              # r is a constant there: no gradient through the norm
+    assert bool(clamped.any())
+    q = torch.where(clamped, torch.zeros_like(q), q)
     dc2 = Ap @ dV + dcw @ Wd.t() - interp_t(q[..., None] * xx)
 
 
