@@ -22,6 +22,8 @@ c_int = ctypes.c_int
 c_size_t = ctypes.c_size_t
 c_float = ctypes.c_float
 c_ll = ctypes.c_longlong
+c_double = ctypes.c_double
+c_u64 = ctypes.c_uint64
 
 
 class Epilogue(ctypes.Structure):
@@ -222,6 +224,9 @@ _SIGNATURES = {
     "dh3d_keypoint_nms": [c_fp, c_ll, c_int, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_fp,
                           c_fp, c_fp, c_size_t, c_fp],
     "dh3d_gather_rows": [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_int, c_fp, c_fp],
+    "dh3d_match_descriptors": [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp],
+    "dh3d_ransac_rigid": [c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_int, c_int, c_int, c_double, c_double, c_int, c_u64,
+                          c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
 }
 _RESTYPES = {
     "dh3d_arch": ctypes.c_char_p,

@@ -1,0 +1,453 @@
+// Keypoint matching and RANSAC rigid registration of cloud pairs for gfx950 (evaluate/local_eval/matlab_code:
+// eval_align.m's pdist2(pos_desc, anc_desc, 'smallest', 1) followed by ransacfitRt.m / ransac.m / estimateRigidTransform.m,
+// run there one pair at a time on the host).  Two launches per batch of P pairs, no atomics on global memory, no workspace,
+// no host sync (graph-capturable):
+//   match_kernel   one thread per anchor keypoint, 256 per block, (ceil(Ma / 256), P) blocks: the positives' descriptors
+//                  pass through LDS 32 rows at a time and every thread keeps 32 running f32 sums of squared differences
+//                  (d ascending, the same order for every pair: a pair's ids do not depend on the batch); the first
+//                  smallest sum wins, ties to the lowest positive id;
+//   ransac_kernel  one 256-lane workgroup per pair: the valid correspondences are compacted (anchor order kept) into LDS as
+//                  f32 coordinates; every round each lane evaluates one trial k (splitmix64 sample, float64 3-point
+//                  estimateRigidTransform with a cyclic Jacobi eigen-solve, float64 inlier count over all n matches); lane
+//                  0 then replays ransac.m's serial stop rule over the round's 256 counts.  The winning trial's model is
+//                  recomputed by every lane (same code, same bits), gives the inlier mask, and the inliers are refitted
+//                  with float64 block sums in a fixed order.
+// Compiled without contraction (csrc/Makefile EXACT): the ids and the inlier sets depend on every rounding.
+#include "common.h"
+
+namespace {
+
+constexpr int kMatchThreads = 256;
+constexpr int kMatchTile = 32;     // positive rows per LDS tile
+constexpr int kMaxDim = 256;       // descriptor length limit (LDS tile: 32 x 256 f32 = 32 KB)
+constexpr int kMaxKp = 4096;       // keypoints per cloud (pm.KEYPOINT_MAX)
+constexpr int kRansacThreads = 256;
+constexpr int kRansacWaves = kRansacThreads / 64;
+
+__device__ __forceinline__ int clamp_count(const int32_t *count, int p, int M) {
+  const int n = count[p];
+  return n < 0 ? 0 : (n > M ? M : n);
+}
+
+__global__ __launch_bounds__(kMatchThreads) void match_kernel(const float *__restrict__ a, long long a_stride, int Ma,
+                                                              const int32_t *__restrict__ a_count,
+                                                              const float *__restrict__ b, long long b_stride, int Mb,
+                                                              const int32_t *__restrict__ b_count, int D,
+                                                              int32_t *__restrict__ match, float *__restrict__ dist) {
+  __shared__ __align__(16) float s_b[kMatchTile * kMaxDim];
+  const int p = blockIdx.y, i = blockIdx.x * kMatchThreads + threadIdx.x;
+  const int na = clamp_count(a_count, p, Ma), nb = clamp_count(b_count, p, Mb);
+  const bool live = i < na;
+  const float *arow = a + ((long long)p * Ma + (live ? i : 0)) * a_stride;
+  const float *bp = b + (long long)p * Mb * b_stride;
+  float best = INFINITY;
+  int best_j = -1;
+  for (int j0 = 0; j0 < nb; j0 += kMatchTile) {
+    const int rows = nb - j0 < kMatchTile ? nb - j0 : kMatchTile;
+    __syncthreads();  // the previous tile has been read
+    for (int e = threadIdx.x; e < rows * D; e += kMatchThreads) {
+      const int r = e / D, c = e - r * D;
+      s_b[r * D + c] = bp[(long long)(j0 + r) * b_stride + c];  // (rows may not be 16-byte aligned: column 3 of 132)
+    }
+    __syncthreads();
+    if (!live) continue;
+    float acc[kMatchTile];
+#pragma unroll
+    for (int r = 0; r < kMatchTile; ++r) acc[r] = 0.f;
+    for (int c = 0; c < D; c += 4) {
+      const float a0 = arow[c], a1 = arow[c + 1], a2 = arow[c + 2], a3 = arow[c + 3];
+#pragma unroll
+      for (int r = 0; r < kMatchTile; ++r) {
+        const float4 v = *reinterpret_cast<const float4 *>(&s_b[r * D + c]);  // (D % 4 == 0: 16-byte aligned, broadcast)
+        float d0 = a0 - v.x, d1 = a1 - v.y, d2 = a2 - v.z, d3 = a3 - v.w;
+        float s = acc[r];
+        s = s + d0 * d0;
+        s = s + d1 * d1;
+        s = s + d2 * d2;
+        s = s + d3 * d3;
+        acc[r] = s;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kMatchTile; ++r) {
+      if (r < rows && acc[r] < best) {  // strict: the lowest id keeps a tie
+        best = acc[r];
+        best_j = j0 + r;
+      }
+    }
+  }
+  if (i < Ma) {
+    const long long o = (long long)p * Ma + i;
+    match[o] = live ? best_j : -1;
+    dist[o] = live && best_j >= 0 ? sqrtf(best) : INFINITY;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------- RANSAC
+
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// three distinct ids in [0, n), n >= 4, of trial k (include/dh3d_hip.h dh3d_ransac_rigid)
+__device__ __forceinline__ void sample3(unsigned long long seed_h, unsigned long long k, int n, int &i0, int &i1, int &i2) {
+  const unsigned long long h = splitmix64(seed_h ^ k);
+  const unsigned long long u0 = splitmix64(h), u1 = splitmix64(h + 1), u2 = splitmix64(h + 2);
+  i0 = (int)(u0 % (unsigned long long)n);
+  i1 = (int)(u1 % (unsigned long long)(n - 1));
+  if (i1 >= i0) ++i1;
+  i2 = (int)(u2 % (unsigned long long)(n - 2));
+  const int lo = i0 < i1 ? i0 : i1, hi = i0 < i1 ? i1 : i0;
+  if (i2 >= lo) ++i2;
+  if (i2 >= hi) ++i2;
+}
+
+// B += A^T A for one centred pair (X anchor, Y positive): A = [0, (Y-X)^T; X-Y, crossTimesMatrix(Y+X)]
+// (estimateRigidTransform.m); B holds the upper triangle b00 b01 b02 b03 b11 b12 b13 b22 b23 b33
+__device__ __forceinline__ void accumulate_b(double *B, double x0, double x1, double x2, double y0, double y1, double y2) {
+  const double d0 = x0 - y0, d1 = x1 - y1, d2 = x2 - y2;
+  const double s0 = y0 + x0, s1 = y1 + x1, s2 = y2 + x2;
+  // columns of A
+  const double c0[4] = {0.0, d0, d1, d2};
+  const double c1[4] = {-d0, 0.0, s2, -s1};
+  const double c2[4] = {-d1, -s2, 0.0, s0};
+  const double c3[4] = {-d2, s1, -s0, 0.0};
+  const double *cols[4] = {c0, c1, c2, c3};
+  int e = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int c = r; c < 4; ++c) {
+      double v = 0.0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v = v + cols[r][q] * cols[c][q];
+      B[e++] += v;
+    }
+  }
+}
+
+// R (row-major 3x3) from the unit eigenvector of B's smallest eigenvalue (cyclic Jacobi, float64), quat2rot.m
+__device__ void rotation_from_b(const double *Bu, double *R) {
+  double a[4][4], v[4][4];
+  int e = 0;
+  for (int r = 0; r < 4; ++r)
+    for (int c = r; c < 4; ++c) a[r][c] = a[c][r] = Bu[e++];
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) v[r][c] = r == c ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 32; ++sweep) {  // (converges in 5-6 sweeps)
+    double off = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = r + 1; c < 4; ++c) off += a[r][c] * a[r][c];
+    if (!(off > 0.0)) break;  // (also stops on NaN)
+#pragma unroll
+    for (int pp = 0; pp < 3; ++pp) {
+#pragma unroll
+      for (int qq = pp + 1; qq < 4; ++qq) {
+        const double apq = a[pp][qq];
+        if (fabs(apq) <= 1e-18 * (fabs(a[pp][pp]) + fabs(a[qq][qq]))) {  // negligible: drop it
+          a[pp][qq] = a[qq][pp] = 0.0;
+          continue;
+        }
+        // the rotation that zeroes a[pp][qq], in the rounding-friendly form of Numerical Recipes' jacobi (tau = s / (1 + c))
+        const double theta = (a[qq][qq] - a[pp][pp]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+        a[pp][pp] -= t * apq;
+        a[qq][qq] += t * apq;
+        a[pp][qq] = a[qq][pp] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (k != pp && k != qq) {
+            const double g = a[k][pp], h = a[k][qq];
+            a[k][pp] = a[pp][k] = g - s * (h + g * tau);
+            a[k][qq] = a[qq][k] = h + s * (g - h * tau);
+          }
+          const double g = v[k][pp], h = v[k][qq];
+          v[k][pp] = g - s * (h + g * tau);
+          v[k][qq] = h + s * (g - h * tau);
+        }
+      }
+    }
+  }
+  double lam = a[0][0], q0 = v[0][0], q1 = v[1][0], q2 = v[2][0], q3 = v[3][0];  // (the first smallest; no dynamic index)
+#pragma unroll
+  for (int k = 1; k < 4; ++k) {
+    if (a[k][k] < lam) {
+      lam = a[k][k];
+      q0 = v[0][k]; q1 = v[1][k]; q2 = v[2][k]; q3 = v[3][k];
+    }
+  }
+  R[0] = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3;
+  R[1] = 2.0 * (q1 * q2 - q0 * q3);
+  R[2] = 2.0 * (q1 * q3 + q0 * q2);
+  R[3] = 2.0 * (q1 * q2 + q0 * q3);
+  R[4] = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3;
+  R[5] = 2.0 * (q2 * q3 - q0 * q1);
+  R[6] = 2.0 * (q1 * q3 - q0 * q2);
+  R[7] = 2.0 * (q2 * q3 + q0 * q1);
+  R[8] = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3;
+}
+
+struct Corr {  // the compacted correspondences in LDS (f32, exact in f64)
+  float *x0, *x1, *x2, *y0, *y1, *y2;
+  int *id;
+};
+
+// t = xc - R yc
+__device__ __forceinline__ void translation(const double *R, const double *xc, const double *yc, double *t) {
+  for (int r = 0; r < 3; ++r) t[r] = xc[r] - (R[3 * r] * yc[0] + R[3 * r + 1] * yc[1] + R[3 * r + 2] * yc[2]);
+}
+
+// the model of the sample (j0, j1, j2): centroid = (sum in sample order) / 3, B over the centred points in sample order
+__device__ void fit3(const Corr &s, int j0, int j1, int j2, double *R, double *t) {
+  const int js[3] = {j0, j1, j2};
+  double x[3][3], y[3][3], xc[3] = {0.0, 0.0, 0.0}, yc[3] = {0.0, 0.0, 0.0};
+  for (int q = 0; q < 3; ++q) {
+    const int j = js[q];
+    x[q][0] = s.x0[j]; x[q][1] = s.x1[j]; x[q][2] = s.x2[j];
+    y[q][0] = s.y0[j]; y[q][1] = s.y1[j]; y[q][2] = s.y2[j];
+    for (int r = 0; r < 3; ++r) {
+      xc[r] += x[q][r];
+      yc[r] += y[q][r];
+    }
+  }
+  for (int r = 0; r < 3; ++r) {
+    xc[r] = xc[r] / 3.0;
+    yc[r] = yc[r] / 3.0;
+  }
+  double B[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int q = 0; q < 3; ++q)
+    accumulate_b(B, x[q][0] - xc[0], x[q][1] - xc[1], x[q][2] - xc[2], y[q][0] - yc[0], y[q][1] - yc[1], y[q][2] - yc[2]);
+  rotation_from_b(B, R);
+  translation(R, xc, yc, t);
+}
+
+// sqrt(|x - (R y + t)|^2) < thr (ransacfitRt.m euc3Ddist)
+__device__ __forceinline__ bool is_inlier(const Corr &s, int j, const double *R, const double *t, double thr) {
+  const double y0 = s.y0[j], y1 = s.y1[j], y2 = s.y2[j];
+  const double e0 = (double)s.x0[j] - ((R[0] * y0 + R[1] * y1 + R[2] * y2) + t[0]);
+  const double e1 = (double)s.x1[j] - ((R[3] * y0 + R[4] * y1 + R[5] * y2) + t[1]);
+  const double e2 = (double)s.x2[j] - ((R[6] * y0 + R[7] * y1 + R[8] * y2) + t[2]);
+  return sqrt(e0 * e0 + e1 * e1 + e2 * e2) < thr;
+}
+
+__device__ __forceinline__ unsigned long long lanes_below() {
+  const unsigned lane = threadIdx.x & 63;
+  return lane ? (~0ull >> (64 - lane)) : 0ull;
+}
+
+__global__ __launch_bounds__(kRansacThreads) void ransac_kernel(
+    const float *__restrict__ axyz, long long a_stride, int Ma, const int32_t *__restrict__ a_count,
+    const float *__restrict__ bxyz, long long b_stride, int Mb, const int32_t *__restrict__ match, double thr, double conf,
+    int max_trials, unsigned long long seed, double *__restrict__ Rt, int32_t *__restrict__ valid,
+    uint8_t *__restrict__ inliers, int32_t *__restrict__ num_inliers, int32_t *__restrict__ trials,
+    int32_t *__restrict__ num_corr) {
+  extern __shared__ float s_dyn[];
+  __shared__ int s_wave[kRansacWaves];
+  __shared__ int s_cnt[kRansacThreads];
+  __shared__ int s_done, s_win, s_kstar;
+  __shared__ double s_red[kRansacWaves];
+  const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+  Corr s;
+  s.x0 = s_dyn;
+  s.x1 = s.x0 + Ma;
+  s.x2 = s.x1 + Ma;
+  s.y0 = s.x2 + Ma;
+  s.y1 = s.y0 + Ma;
+  s.y2 = s.y1 + Ma;
+  s.id = reinterpret_cast<int *>(s.y2 + Ma);
+
+  // (1) compact the valid correspondences (i < a_count, 0 <= match < Mb) in anchor order; clear the mask row
+  const int na = clamp_count(a_count, p, Ma);
+  int n = 0;
+  for (int base = 0; base < Ma; base += kRansacThreads) {
+    const int i = base + tid;
+    int m = -1;
+    if (i < Ma) {
+      inliers[(long long)p * Ma + i] = 0;
+      if (i < na) m = match[(long long)p * Ma + i];
+    }
+    const bool ok = m >= 0 && m < Mb;
+    const unsigned long long bal = __ballot(ok);
+    if ((tid & 63) == 0) s_wave[w] = __popcll(bal);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int q = 0; q < kRansacWaves; ++q) {
+      const int v = s_wave[q];
+      off += q < w ? v : 0;
+      tot += v;
+    }
+    if (ok) {
+      const int slot = n + off + __popcll(bal & lanes_below());
+      const float *xa = axyz + ((long long)p * Ma + i) * a_stride;
+      const float *xb = bxyz + ((long long)p * Mb + m) * b_stride;
+      s.x0[slot] = xa[0]; s.x1[slot] = xa[1]; s.x2[slot] = xa[2];
+      s.y0[slot] = xb[0]; s.y1[slot] = xb[1]; s.y2[slot] = xb[2];
+      s.id[slot] = i;
+    }
+    n += tot;
+    __syncthreads();
+  }
+  if (tid == 0 && num_corr) num_corr[p] = n;
+  double *rt = Rt + (long long)p * 12;
+  if (n < 3) {  // ransacfitRt.m: no model
+    if (tid < 12) rt[tid] = __longlong_as_double(0x7ff8000000000000ll);
+    if (tid == 0) {
+      valid[p] = 0;
+      num_inliers[p] = 0;
+      trials[p] = 0;
+    }
+    return;
+  }
+
+  // (2) ransac.m's loop, 256 trials per round; lane 0 replays the serial stop rule over the round's counts
+  int win = 0, kstar = -1;
+  if (n > 3) {
+    const unsigned long long seed_h = splitmix64(seed);
+    const double log_fail = log(1.0 - conf);
+    const double eps = 2.220446049250313e-16;
+    int best = 0;     // (lane 0's state across rounds: ransac.m's bestscore and N)
+    double N = 1.0;
+    if (tid == 0) s_done = 0;
+    for (int base = 0;; base += kRansacThreads) {
+      const int k = base + tid;
+      int c = -1;
+      if (k <= max_trials) {
+        int j0, j1, j2;
+        sample3(seed_h, (unsigned long long)k, n, j0, j1, j2);
+        double R[9], t[3];
+        fit3(s, j0, j1, j2, R, t);
+        c = 0;
+        for (int j = 0; j < n; ++j) c += is_inlier(s, j, R, t, thr) ? 1 : 0;
+      }
+      s_cnt[tid] = c;
+      __syncthreads();
+      if (tid == 0) {
+        for (int q = 0; q < kRansacThreads; ++q) {
+          const int kk = base + q, ck = s_cnt[q];
+          if (ck >= best) {  // ransac.m accepts on >=: the last trial with the best count wins
+            best = ck;
+            win = kk;
+            const double frac = (double)best / (double)n;
+            double pno = 1.0 - frac * frac * frac;
+            pno = pno < eps ? eps : pno;
+            pno = pno > 1.0 - eps ? 1.0 - eps : pno;
+            N = log_fail / log(pno);
+            N = N < 10.0 ? 10.0 : N;
+          }
+          if (N <= (double)(kk + 1) || kk + 1 > max_trials) {  // ransac.m: while N > trialcount ... > maxTrials
+            s_done = 1;
+            s_win = win;
+            s_kstar = kk;
+            break;
+          }
+        }
+      }
+      __syncthreads();
+      if (s_done) break;
+    }
+    win = s_win;
+    kstar = s_kstar;
+  }
+
+  // (3) the winning model (recomputed: the same bits as in its round), its inlier mask and count
+  int j0 = 0, j1 = 1, j2 = 2;
+  if (n > 3) sample3(splitmix64(seed), (unsigned long long)win, n, j0, j1, j2);
+  double R[9], t[3];
+  fit3(s, j0, j1, j2, R, t);
+  int cnt = 0;
+  for (int j = tid; j < n; j += kRansacThreads) {
+    const bool in = n == 3 || is_inlier(s, j, R, t, thr);  // (n == 3: ransacfitRt.m takes all three)
+    if (in) {
+      inliers[(long long)p * Ma + s.id[j]] = 1;
+      ++cnt;
+    }
+  }
+  const int count = (int)block_sum_256<double>((double)cnt, s_red);
+  if (tid == 0) {
+    num_inliers[p] = count;
+    trials[p] = n > 3 ? kstar + 1 : 0;
+    valid[p] = count >= 3;
+  }
+  if (count < 3) {
+    if (tid < 12) rt[tid] = __longlong_as_double(0x7ff8000000000000ll);
+    return;
+  }
+
+  // (4) least-squares refit on the inliers: float64 sums, each lane over its slots in order, then a fixed tree
+  double sx[3] = {0.0, 0.0, 0.0}, sy[3] = {0.0, 0.0, 0.0};
+  for (int j = tid; j < n; j += kRansacThreads) {
+    if (n == 3 || is_inlier(s, j, R, t, thr)) {
+      sx[0] += s.x0[j]; sx[1] += s.x1[j]; sx[2] += s.x2[j];
+      sy[0] += s.y0[j]; sy[1] += s.y1[j]; sy[2] += s.y2[j];
+    }
+  }
+  double xc[3], yc[3];
+  for (int r = 0; r < 3; ++r) {
+    xc[r] = block_sum_256<double>(sx[r], s_red) / (double)count;
+    yc[r] = block_sum_256<double>(sy[r], s_red) / (double)count;
+  }
+  double B[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = tid; j < n; j += kRansacThreads) {
+    if (n == 3 || is_inlier(s, j, R, t, thr))
+      accumulate_b(B, s.x0[j] - xc[0], s.x1[j] - xc[1], s.x2[j] - xc[2], s.y0[j] - yc[0], s.y1[j] - yc[1],
+                   s.y2[j] - yc[2]);
+  }
+  for (int e = 0; e < 10; ++e) B[e] = block_sum_256<double>(B[e], s_red);
+  if (tid == 0) {
+    double Rf[9], tf[3];
+    rotation_from_b(B, Rf);
+    translation(Rf, xc, yc, tf);
+    for (int r = 0; r < 3; ++r) {
+      rt[4 * r] = Rf[3 * r];
+      rt[4 * r + 1] = Rf[3 * r + 1];
+      rt[4 * r + 2] = Rf[3 * r + 2];
+      rt[4 * r + 3] = tf[r];
+    }
+  }
+}
+
+size_t ransac_lds_bytes(int Ma) { return (size_t)Ma * (6 * sizeof(float) + sizeof(int)); }
+
+}  // namespace
+
+DH3D_API int dh3d_match_descriptors(const float *anchor_desc, long long anchor_stride, const int32_t *anchor_count,
+                                    const float *positive_desc, long long positive_stride, const int32_t *positive_count,
+                                    int P, int Ma, int Mb, int D, int32_t *match, float *dist, void *stream) {
+  DH3D_REQUIRE(anchor_desc && anchor_count && positive_desc && positive_count && match && dist);
+  DH3D_REQUIRE(P > 0 && Ma > 0 && Mb > 0 && D > 0 && anchor_stride >= D && positive_stride >= D);
+  DH3D_SUPPORTED(D <= kMaxDim && D % 4 == 0 && Ma <= kMaxKp && Mb <= kMaxKp && P <= 65535);
+  hipLaunchKernelGGL(match_kernel, dim3(dh3d_cdiv(Ma, kMatchThreads), P), dim3(kMatchThreads), 0, (hipStream_t)stream,
+                     anchor_desc, anchor_stride, Ma, anchor_count, positive_desc, positive_stride, Mb, positive_count, D,
+                     match, dist);
+  return dh3d_launch_status();
+}
+
+DH3D_API int dh3d_ransac_rigid(const float *anchor_xyz, long long anchor_stride, const float *positive_xyz,
+                               long long positive_stride, const int32_t *match, const int32_t *anchor_count, int P, int Ma,
+                               int Mb, double threshold, double confidence, int max_trials, unsigned long long seed,
+                               double *Rt, int32_t *valid, uint8_t *inliers, int32_t *num_inliers, int32_t *trials,
+                               int32_t *num_corr, void *stream) {
+  DH3D_REQUIRE(anchor_xyz && positive_xyz && match && anchor_count && Rt && valid && inliers && num_inliers && trials);
+  DH3D_REQUIRE(P > 0 && Ma > 0 && Mb > 0 && anchor_stride >= 3 && positive_stride >= 3);
+  DH3D_REQUIRE(threshold > 0.0 && confidence > 0.0 && confidence < 1.0 && max_trials >= 0);
+  DH3D_SUPPORTED(Ma <= kMaxKp && Mb <= kMaxKp && P <= 65535 && max_trials < (1 << 30));
+  // the dynamic-LDS cap for the largest staging (4096 correspondences: 112 KB) once per process, out of the steady state.
+  // (Not DH3D_ALLOW_BIG_LDS: its 159 KB plus this kernel's 1 KB of static LDS is beyond the CU's 160 KB, and the refused
+  // call would be reported as this launch's status.)
+  static bool lds_cap_set = false;
+  if (!lds_cap_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ransac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)ransac_lds_bytes(kMaxKp));
+    lds_cap_set = true;
+  }
+  hipLaunchKernelGGL(ransac_kernel, dim3(P), dim3(kRansacThreads), ransac_lds_bytes(Ma), (hipStream_t)stream, anchor_xyz,
+                     anchor_stride, Ma, anchor_count, positive_xyz, positive_stride, Mb, match, threshold, confidence,
+                     max_trials, seed, Rt, valid, inliers, num_inliers, trials, num_corr);
+  return dh3d_launch_status();
+}

@@ -1,0 +1,181 @@
+"""Registration of cloud pairs from keypoints: descriptor matching and RANSAC rigid fits on the device, for many pairs per
+call (csrc/registration.hip), plus the reference evaluation's error metrics on the host.
+
+The reference does this step in MATLAB, one pair at a time (evaluate/local_eval/matlab_code: local_align_demo.m,
+eval_align.m): pdist2(pos_desc, anc_desc, 'smallest', 1), ransacfitRt with a 1.0 m threshold, then compareTransform /
+GetEulerAngles and a success / inlier-ratio / trial / RTE / RRE summary.  Here a batch of pairs stays on the GPU until a
+[P, 3, 4] pose and a few counts per pair come out; include/dh3d_hip.h dh3d_ransac_rigid states every rule (the splitmix64
+sampler replaces randsample, whose stream cannot be reproduced).
+
+    match, dist = match_descriptors(anchor_desc, anchor_count, positive_desc, positive_count)
+    res = ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count)       # Rt, valid, inliers, ... (no host sync)
+    res = register(anchor_rows, anchor_count, positive_rows, positive_count)  # rows as xyz_feat_att_nms / _nms_res.bin
+    res = register_clouds(model, anchor_points, positive_points)              # forward (config.detection) + register
+    dt, ddeg = transform_errors(T_gt, res["Rt"], res["valid"])                # compareTransform, host float64
+    summary = summarize_registration(dt, ddeg, res["inlier_ratio"], res["trials"])
+"""
+import numpy as np
+import torch
+
+from . import _lib as L
+from .pm import KEYPOINT_MAX
+
+DESC_MAX = 256  # descriptor length limit of dh3d_match_descriptors
+
+
+def _rows(t, name, min_cols):
+    """A float32 [P, M, C] GPU tensor whose rows can be read with one element stride (a column slice of a contiguous map is
+    read in place); anything else is made contiguous."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.dim() != 3:
+        raise ValueError("%s must be a float32 [P, M, C] tensor on the GPU" % name)
+    if t.shape[2] < min_cols:
+        raise ValueError("%s needs at least %d columns, got shape %s" % (name, min_cols, tuple(t.shape)))
+    if t.shape[0] == 0 or t.shape[1] == 0:
+        raise ValueError("%s must not be empty, got shape %s" % (name, tuple(t.shape)))
+    if t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1) or t.stride(1) < t.shape[2]:
+        t = t.contiguous()
+    return t
+
+
+def _count(c, name, P, device):
+    c = L.require_cuda_i32(c, name, 1)
+    if c.shape[0] != P or c.device != device:
+        raise ValueError("%s must be int32 [%d] on %s, got %s on %s" % (name, P, device, tuple(c.shape), c.device))
+    return c
+
+
+def _check_m(M, name):
+    if M > KEYPOINT_MAX:
+        raise ValueError("%s: at most %d keypoints per cloud, got %d" % (name, KEYPOINT_MAX, M))
+
+
+def match_descriptors(anchor_desc, anchor_count, positive_desc, positive_count):
+    """Nearest positive descriptor of every anchor keypoint (pdist2(pos, anc, 'smallest', 1)): anchor_desc [P, Ma, D] and
+    positive_desc [P, Mb, D] float32 (column views such as rows[:, :, 3:131] are read in place), counts [P] int32 ->
+    (match [P, Ma] int32, the lowest positive id at the smallest distance, -1 past anchor_count or when the pair has no
+    positive; dist [P, Ma] float32, +inf there).  D <= 256, a multiple of 4; Ma, Mb <= 4096."""
+    a = _rows(anchor_desc, "anchor_desc", 1)
+    b = _rows(positive_desc, "positive_desc", 1)
+    P, Ma, D = a.shape
+    if b.shape[0] != P or b.shape[2] != D or b.device != a.device:
+        raise ValueError("positive_desc must be [%d, Mb, %d] on %s, got %s" % (P, D, a.device, tuple(b.shape)))
+    Mb = b.shape[1]
+    if D > DESC_MAX or D % 4:
+        raise ValueError("descriptor length must be a multiple of 4 up to %d, got %d" % (DESC_MAX, D))
+    _check_m(Ma, "anchor_desc")
+    _check_m(Mb, "positive_desc")
+    ac = _count(anchor_count, "anchor_count", P, a.device)
+    bc = _count(positive_count, "positive_count", P, a.device)
+    match = torch.empty((P, Ma), dtype=torch.int32, device=a.device)
+    dist = torch.empty((P, Ma), dtype=torch.float32, device=a.device)
+    L.check(L.lib().dh3d_match_descriptors(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(b), b.stride(1), L.ptr(bc), P, Ma, Mb, D,
+                                           L.ptr(match), L.ptr(dist), L.stream_ptr()), "match_descriptors")
+    return match, dist
+
+
+def ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=1.0, confidence=0.99, max_trials=10000, seed=0):
+    """ransacfitRt on every pair: correspondences anchor_xyz[p, i] <-> positive_xyz[p, match[p, i]] for i < anchor_count[p]
+    with 0 <= match < Mb; the model maps positive into anchor coordinates (anchor ~ R positive + t).  anchor_xyz [P, Ma, >=3]
+    and positive_xyz [P, Mb, >=3] float32 (the first three columns are read; keypoint rows are read in place).  Returns a
+    dict of device tensors: Rt [P, 3, 4] float64 (NaN where not valid), valid [P] bool, inliers [P, Ma] bool (the winning
+    hypothesis' mask), num_inliers [P] int32, inlier_ratio [P] float64 (num_inliers / n, 0 when n = 0), trials [P] int32,
+    num_corr [P] int32 (n).  No host sync: graph-capturable."""
+    ax = _rows(anchor_xyz, "anchor_xyz", 3)
+    bx = _rows(positive_xyz, "positive_xyz", 3)
+    P, Ma = ax.shape[:2]
+    if bx.shape[0] != P or bx.device != ax.device:
+        raise ValueError("positive_xyz must be [%d, Mb, >=3] on %s, got %s" % (P, ax.device, tuple(bx.shape)))
+    Mb = bx.shape[1]
+    _check_m(Ma, "anchor_xyz")
+    _check_m(Mb, "positive_xyz")
+    m = L.require_cuda_i32(match, "match", 2)
+    if tuple(m.shape) != (P, Ma) or m.device != ax.device:
+        raise ValueError("match must be int32 [%d, %d] on %s, got %s" % (P, Ma, ax.device, tuple(m.shape)))
+    ac = _count(anchor_count, "anchor_count", P, ax.device)
+    threshold, confidence, max_trials, seed = float(threshold), float(confidence), int(max_trials), int(seed)
+    if not threshold > 0.0 or not 0.0 < confidence < 1.0 or not 0 <= max_trials < (1 << 30):
+        raise ValueError("need threshold > 0, 0 < confidence < 1 and 0 <= max_trials < 2^30, got %r, %r, %r"
+                         % (threshold, confidence, max_trials))
+    if not 0 <= seed < (1 << 64):
+        raise ValueError("seed must be a uint64, got %r" % seed)
+    dev = ax.device
+    Rt = torch.empty((P, 3, 4), dtype=torch.float64, device=dev)
+    valid = torch.empty((P,), dtype=torch.int32, device=dev)
+    inliers = torch.empty((P, Ma), dtype=torch.bool, device=dev)
+    num_inliers = torch.empty((P,), dtype=torch.int32, device=dev)
+    trials = torch.empty((P,), dtype=torch.int32, device=dev)
+    num_corr = torch.empty((P,), dtype=torch.int32, device=dev)
+    L.check(L.lib().dh3d_ransac_rigid(L.ptr(ax), ax.stride(1), L.ptr(bx), bx.stride(1), L.ptr(m), L.ptr(ac), P, Ma, Mb,
+                                      threshold, confidence, max_trials, seed, L.ptr(Rt), L.ptr(valid), L.ptr(inliers),
+                                      L.ptr(num_inliers), L.ptr(trials), L.ptr(num_corr), L.stream_ptr()), "ransac_rigid")
+    ratio = num_inliers.to(torch.float64) / num_corr.clamp(min=1).to(torch.float64)
+    return dict(Rt=Rt, valid=valid.bool(), inliers=inliers, num_inliers=num_inliers, inlier_ratio=ratio, trials=trials,
+                num_corr=num_corr)
+
+
+def register(anchor_rows, anchor_count, positive_rows, positive_count, desc_dim=128, **ransac_kw):
+    """Keypoint rows in, poses out: rows [P, M, C >= 3 + desc_dim] float32 as the model's xyz_feat_att_nms (C = 132) or a
+    _nms_res.bin (utils.load_descriptor_bin) give them -- [x, y, z, descriptor(, score)] -- with counts [P] int32.  Matches
+    every anchor keypoint to its nearest positive descriptor, then ransac_rigid (keyword arguments threshold, confidence,
+    max_trials, seed).  Returns ransac_rigid's dict plus match / dist; everything stays on the device, no host sync."""
+    a = _rows(anchor_rows, "anchor_rows", 3 + int(desc_dim))
+    b = _rows(positive_rows, "positive_rows", 3 + int(desc_dim))
+    match, dist = match_descriptors(a[:, :, 3:3 + desc_dim], anchor_count, b[:, :, 3:3 + desc_dim], positive_count)
+    out = ransac_rigid(a, b, match, anchor_count, **ransac_kw)
+    out["match"], out["dist"] = match, dist
+    return out
+
+
+def register_clouds(model, anchor_points, positive_points, num_valid=None, **kw):
+    """Both batches of clouds [P, N, 3] through model.forward(fetch=("kp_count", "xyz_feat_att_nms")) (config.detection),
+    then register on the keypoints.  num_valid: None, one int32 [P] tensor for both batches, or a pair (anchor, positive)."""
+    if not getattr(model.config, "detection", False):
+        raise ValueError("register_clouds needs a model with config.detection (the keypoint outputs)")
+    nv_a, nv_b = num_valid if isinstance(num_valid, (tuple, list)) else (num_valid, num_valid)
+    fetch = ("kp_count", "xyz_feat_att_nms")
+    oa = model.forward(anchor_points, fetch=fetch, num_valid=nv_a)
+    ob = model.forward(positive_points, fetch=fetch, num_valid=nv_b)
+    return register(oa["xyz_feat_att_nms"], oa["kp_count"], ob["xyz_feat_att_nms"], ob["kp_count"], **kw)
+
+
+def _host64(t):
+    return t.detach().cpu().numpy().astype(np.float64) if isinstance(t, torch.Tensor) else np.asarray(t, np.float64)
+
+
+def transform_errors(T_gt, T_est, valid=None):
+    """compareTransform (common/Utils.m) with GetEulerAngles, float64 on the host.  T_gt, T_est [P, 3 or 4, 4] (tensors or
+    arrays), valid [P] (None: all).  delta_t = |t_gt - t_est|; dR = R_gt^T R_est, ry = asin(dR[0, 2]), rz = acos(dR[0, 0] /
+    cos ry), rx = acos(dR[2, 2] / cos ry) evaluated in complex128 with abs taken, as MATLAB does when rounding pushes an
+    argument past +-1; delta_deg = (|rx| + |ry| + |rz|) * 180 / pi.  Pairs without an estimate get (3, 6), eval_align.m's
+    catch.  Returns (delta_t [P], delta_deg [P]) float64."""
+    G = _host64(T_gt)[:, :3, :]
+    E = _host64(T_est)[:, :3, :]
+    if G.shape != E.shape or G.shape[1:] != (3, 4):
+        raise ValueError("T_gt and T_est must be [P, 3 or 4, 4], got %s / %s" % (G.shape, E.shape))
+    ok = np.ones(len(G), bool) if valid is None else _host64(valid).astype(bool)
+    ok &= np.isfinite(E).all(axis=(1, 2))
+    dt = np.linalg.norm(G[:, :, 3] - E[:, :, 3], axis=1)
+    dR = np.einsum("pki,pkj->pij", G[:, :, :3], E[:, :, :3]).astype(np.complex128)
+    with np.errstate(invalid="ignore", divide="ignore"):  # (pairs without an estimate are NaN here; replaced below)
+        ry = np.arcsin(dR[:, 0, 2])
+        rz = np.arccos(dR[:, 0, 0] / np.cos(ry))
+        rx = np.arccos(dR[:, 2, 2] / np.cos(ry))
+    ddeg = (np.abs(rx) + np.abs(ry) + np.abs(rz)) * 180.0 / np.pi
+    return np.where(ok, dt, 3.0), np.where(ok, ddeg, 6.0)
+
+
+def summarize_registration(delta_t, delta_deg, inlier_ratio, trials):
+    """eval_align.m's summary: a pair fails when delta_t > 2 or delta_deg > 5; over the successful pairs only, the mean
+    inlier ratio, the mean trial count and mean / std (N - 1) of RTE (delta_t) and RRE (delta_deg)."""
+    dt, dd = _host64(delta_t), _host64(delta_deg)
+    ir, tr = _host64(inlier_ratio), _host64(trials)
+    ok = ~((dt > 2) | (dd > 5))
+    n_ok = int(ok.sum())
+
+    def std(v):
+        return float(np.std(v, ddof=1)) if len(v) > 1 else float("nan")
+    return dict(num_pairs=len(dt), num_failed=len(dt) - n_ok, success_rate=100.0 * n_ok / max(len(dt), 1),
+                mean_inlier_ratio=float(ir[ok].mean()) if n_ok else float("nan"),
+                mean_trials=float(tr[ok].mean()) if n_ok else float("nan"),
+                rte_mean=float(dt[ok].mean()) if n_ok else float("nan"), rte_std=std(dt[ok]),
+                rre_mean=float(dd[ok].mean()) if n_ok else float("nan"), rre_std=std(dd[ok]))

@@ -831,6 +831,49 @@ int dh3d_keypoint_nms(const float *score, long long score_stride, int invert, co
 int dh3d_gather_rows(const float *src, int B, int N, int C, const int32_t *inds, const int32_t *count, int M, float *dst,
                      void *stream);
 
+/* Descriptor matching of P cloud pairs (eval_align.m: pdist2(pos_desc, anc_desc, 'euclidean', 'smallest', 1), run there one
+ * pair at a time; csrc/registration.hip).  Anchor descriptors: row (p, i) at anchor_desc + (p*Ma + i) * anchor_stride, D floats;
+ * positive descriptors likewise with positive_stride (strides in elements: xyz_feat_att_nms + 3 with stride 132 is read in
+ * place).  For every pair p and anchor i < a = clamp(anchor_count[p], 0, Ma):
+ *   match [P, Ma] = argmin over j < b = clamp(positive_count[p], 0, Mb) of the Euclidean distance, ties to the lowest j;
+ *   dist  [P, Ma] = that distance (float32: sqrt of the f32 sum over d ascending of (a_d - b_d)^2, no fma contraction).
+ * Rows i >= a, and every row when b = 0, get match -1 and dist +inf.  A pair's result does not depend on the batch.
+ * D <= 256 and a multiple of 4, Ma, Mb <= 4096 (else DH3D_ERR_UNSUPPORTED); NULL pointers, P / Ma / Mb / D <= 0 or a stride
+ * below D: DH3D_ERR_INVALID_ARGUMENT.  No workspace. */
+int dh3d_match_descriptors(const float *anchor_desc, long long anchor_stride, const int32_t *anchor_count,
+                           const float *positive_desc, long long positive_stride, const int32_t *positive_count, int P, int Ma,
+                           int Mb, int D, int32_t *match, float *dist, void *stream);
+/* RANSAC rigid registration of P cloud pairs (ransacfitRt.m over ransac.m and estimateRigidTransform.m with isdegenerate = 0,
+ * batched; csrc/registration.hip).  One workgroup per pair; no workspace (the correspondences are staged in LDS).
+ * Coordinates: anchor point i of pair p at anchor_xyz + (p*Ma + i) * anchor_stride (3 floats), positive point j at
+ * positive_xyz + (p*Mb + j) * positive_stride (strides in elements, >= 3).  The correspondences are the anchors
+ * i < clamp(anchor_count[p], 0, Ma) with 0 <= match[p, i] < Mb, in ascending i; n = their number (num_corr [P], may be NULL).
+ * The model maps positive into anchor coordinates, anchor ~ R * positive + t; everything below is float64 on the exact
+ * float64 values of the float32 inputs.
+ *   fit of a point set: centroids (sums in set order / count), B = sum over the set of A^T A with
+ *     A = [0, (Y - X)^T; X - Y, [Y + X]x] on the centred points (crossTimesMatrix sign convention), q = the unit eigenvector
+ *     of B's smallest eigenvalue (cyclic Jacobi), R = quat2rot(q), t = x_centroid - R * y_centroid;
+ *   inlier: sqrt(|x - (R y + t)|^2) < threshold;
+ *   sample of trial k: splitmix64(z) = { z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z>>27) * 0x94D049BB133111EB; return z ^ z>>31 } (uint64 wrap-around); h = splitmix64(splitmix64(seed) ^ k),
+ *     u_j = splitmix64(h + j); i0 = u0 mod n; i1 = u1 mod (n-1), + 1 if i1 >= i0; i2 = u2 mod (n-2), then + 1 if i2 >= min(i0,
+ *     i1), then + 1 if i2 >= max(i0, i1); the fit sums in the order i0, i1, i2.  The same sequence for every pair (ransac.m
+ *     resets its stream on every call; it replaces randsample, whose stream cannot be reproduced);
+ *   stop rule: c_k = the inlier count of trial k's model, best_k = max(c_0..c_k), N_k = max(log(1 - confidence) /
+ *     log(clamp(1 - (best_k / n)^3, eps, 1 - eps)), 10) with eps = 2^-52; the loop stops after trial k*, the first k with
+ *     N_k <= k + 1 or k + 1 > max_trials (at most max_trials + 1 trials); trials[p] = k* + 1; the winner is the LAST trial
+ *     in 0..k* whose count equals best_k* (ransac.m accepts on >=);
+ *   n < 3: no model, trials 0; n == 3: the fit of the three, all three inliers, trials 0.
+ * Outputs: inliers [P, Ma] uint8 (1 at the anchor rows of the winner's inliers, the winner's mask, not recomputed after the
+ * refit), num_inliers [P], trials [P], Rt [P, 3, 4] float64 = [R | t] of the fit over the winner's inliers (sums of each lane
+ * in ascending order, then a fixed tree), valid [P] = n >= 3 and num_inliers >= 3; Rt is NaN where valid is 0.
+ * threshold > 0, 0 < confidence < 1, max_trials >= 0, NULL pointers (num_corr excepted), P / Ma / Mb <= 0 or a stride below
+ * 3: DH3D_ERR_INVALID_ARGUMENT; Ma or Mb > 4096: DH3D_ERR_UNSUPPORTED. */
+int dh3d_ransac_rigid(const float *anchor_xyz, long long anchor_stride, const float *positive_xyz, long long positive_stride,
+                      const int32_t *match, const int32_t *anchor_count, int P, int Ma, int Mb, double threshold,
+                      double confidence, int max_trials, unsigned long long seed, double *Rt, int32_t *valid,
+                      uint8_t *inliers, int32_t *num_inliers, int32_t *trials, int32_t *num_corr, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
