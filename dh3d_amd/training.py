@@ -787,14 +787,18 @@ class LocalTrainer(object):
                 with torch.cuda.graph(graph):
                     loss = self._body(arena, *static)
                     self.opt.step()
-                ent = (graph, static, loss, arena)
+                ent = (graph, static, loss, arena, [p.grad for p in self.params])
                 self._graphs[key] = ent
-            graph, static, loss, _ = ent
+            graph, static, loss, _, grads = ent
             for dst, src in zip(static, (points, R, sample_idx)):
                 if dst.data_ptr() != src.data_ptr():
                     dst.copy_(src)
             self._set_lr()
             graph.replay()
+            # the replay wrote its gradients into the tensors its capture created; `p.grad` may still name another
+            # shape's (that graph's capture or eager step came later): point it at this step's
+            for p, g in zip(self.params, grads):
+                p.grad = g
         else:
             self._eager_seen[key] = self._eager_seen.get(key, 0) + 1
             self._set_lr()
