@@ -37,6 +37,22 @@ def _copy_in(src, dst):
         dst.copy_(src, non_blocking=True)
 
 
+def _capture_warmed(body, warmup, device):
+    """Run `body` `warmup` times on a side stream, synchronise, then capture it into a hipGraph:
+    (graph, what body returned inside the capture)."""
+    s = torch.cuda.Stream(device=device)
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(warmup):
+            body()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        outs = body()
+    return graph, outs
+
+
 class DH3D(nn.Module):
     def __init__(self, config=None):
         super().__init__()
@@ -555,16 +571,8 @@ class DH3D(nn.Module):
         static_knn = example_knn.clone() if example_knn is not None else None
         static_nv = example_num_valid.clone() if example_num_valid is not None else None
         keep = outputs
-        s = torch.cuda.Stream(device=example_points.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.forward(static_in, static_knn, fetch=keep, num_valid=static_nv)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            outs = self.forward(static_in, static_knn, fetch=keep, num_valid=static_nv)
+        graph, outs = _capture_warmed(lambda: self.forward(static_in, static_knn, fetch=keep, num_valid=static_nv),
+                                     warmup, example_points.device)
         if keep is not None:
             outs = {k: v for k, v in outs.items() if k in keep}
         version = self.weights_version

@@ -1,7 +1,8 @@
 """Siamese training step of the global-descriptor stage (BASELINE config 4; core/model.py:135-255 with
 core/configs.py:104-144 global_config), sharded over GPUs by cloud, and the stage-1 step of the local backbone
-(LocalTrainer) -- both on the hand-written HIP kernels of dh3d_amd.train_ops in BOTH directions, each replayed as one
-hipGraph per step.
+(LocalTrainer) -- both on the hand-written HIP kernels of dh3d_amd.train_ops in BOTH directions.  The two trainers
+share ONE step loop (_StepLoop): staircase learning rate, L2 weight decay on '.*/W', Adam, three eager steps per batch
+shape and then the whole step replayed as one hipGraph; a trainer adds its forward + backward and a few hooks.
 
 global_config freezes the local backbone (configs.py:112-113), so a quadruplet step is:
   1. frozen backbone + geometry on the fused HIP inference path (dh3d_amd.model, no autograd) -- or, with
@@ -14,8 +15,7 @@ global_config freezes the local backbone (configs.py:112-113), so a quadruplet s
      and [Bt, 256]-sized element-wise glue, no GEMM,
   3. all-gather of the [clouds_per_rank, 256] descriptors over RCCL (differentiable: backward keeps the rank's own
      slice, every rank evaluates the identical full loss), lazy quadruplet loss (core/losses.py:173-200) on the device,
-     backward, ONE SUM all-reduce of the flat gradient arena, fused Adam with the staircase exponential learning rate
-     (core/model.py:248-255) and L2 weight decay on '.*/W' (model.py:239-243).
+     backward, weight decay by rank 0, ONE SUM all-reduce of the flat gradient arena, Adam.
 
 BatchNorm statistics under sharding: `sync_bn=True` (default) all-reduces (sum, sum of squares, count) so the
 statistics equal the reference's single-GPU whole-batch statistics; `sync_bn=False` uses per-rank statistics.
@@ -29,6 +29,7 @@ import torch.distributed as dist
 from . import backbones as bb
 from . import dist as D
 from . import losses, ops, pm
+from .model import _capture_warmed
 
 
 class _AllGatherKeepOwn(torch.autograd.Function):
@@ -274,68 +275,195 @@ def trainable_head_parameters(model):
     return out
 
 
-class QuadrupletTrainer(object):
+class _StepLoop(object):
+    """The optimisation step both trainers run: staircase learning rate, Adam, L2 weight decay on '.*/W', and "three
+    eager steps per batch shape, then the whole step -- ~500-600 launches, about as much host time as GPU time --
+    captured into one hipGraph and replayed".  A subclass supplies `_body` (forward + backward) and the hooks below.
+
+      learning rate  start_lr * decay_rate ** (steps_done // decay_step) (core/model.py:248-255), written before a step
+                     only when it changed.  Which Adam is decided ONCE, at construction (`device_lr`): fused capturable
+                     Adam reading a device scalar (`_lr`; replayable), or fused-iff-CUDA Adam with the rate in its param
+                     group.  Setting `graph_step = False` later only stops capturing; the optimiser stays.
+      eager or not   eager for the first three steps ON EVERY BATCH SHAPE (allocator / autograd / lazily built
+                     constants warm up before the capture; `_eager_seen`, keyed by (input shapes, device)), while
+                     `graph_step` is off, and while `_force_eager()` says so (something of the step is kept for
+                     inspection).  The graph table `_graphs` is keyed by `_graph_key` of the same tuple; an entry is
+                     (graph, static inputs, loss, its ZeroArena, the gradient tensors of its capture).
+      arenas         the eager steps share `_zarena`; a graph gets its OWN accumulator arena, sized by its shape's eager
+                     steps (`_shape_demand`) and never reallocated: the eager arena grows (and frees its old buffer)
+                     whenever a larger shape comes along, and a graph replaying into a freed buffer would corrupt
+                     whatever owns that memory by then.
+      inputs         a replay reads the graph's static inputs; a caller's tensor is copied in only when it is a
+                     different one (each copy is a launch in front of the replay, ~10 us of queue latency).
+      capture fails  (RuntimeError) outside a collective: warn, switch `graph_step` off and go on with eager steps --
+                     the parameters are untouched, a capture records, it does not run.  In a sharded run the ranks must
+                     not diverge (one replaying captured collectives, one issuing them eagerly), and a capture that died
+                     inside a collective leaves the communicator undefined: there it is re-raised.
+      p.grad         after a replay names the tensors that graph's capture left there (the replay wrote into those;
+                     `p.grad` may still name another shape's, whose capture or eager step came later)."""
+
+    def __init__(self, model, params, start_lr, decay_step, decay_rate, weight_decay, fallback, graph_step, device_lr):
+        """Schedule / weight decay default to the model's config (core/configs.py:50-54,115-117), then to
+        `fallback` = (decay_step, decay_rate)."""
+        self.model, self.cfg = model, model.config
+        c = self.cfg
+        start_lr = start_lr if start_lr is not None else (c.start_lr or 5e-4)
+        decay_step = decay_step if decay_step is not None else (c.decay_step or fallback[0])
+        decay_rate = decay_rate if decay_rate is not None else (c.decay_rate or fallback[1])
+        if weight_decay is None:
+            weight_decay = (c.train_weight_decay or 1e-5) if c.add_weight_decay is not False else 0.0
+        self.weight_decay = weight_decay
+        self.params = params
+        self.wd_params = [p for n, p in model.named_parameters() if n.endswith(".W") and any(p is q for q in params)]
+        self.graph_step = graph_step
+        self._sched = (float(start_lr), int(decay_step), float(decay_rate))
+        self._steps_done, self._graphs, self._eager_seen, self._shape_demand = 0, {}, {}, {}
+        self._zarena = pm.ZeroArena()   # the step's accumulators: one fill per step (pm.ZeroArena)
+        self.keep_grads, self.last_grads = False, None
+        self._grads_of = None   # the graph entry whose gradient tensors `p.grad` names (None: an eager step's)
+        self._lr, self._lr_value = None, self._sched[0]
+        if device_lr:
+            self._lr = torch.tensor(self._lr_value, dtype=torch.float32, device=params[0].device)
+            # (fused: one multi-tensor kernel per step instead of ~8 foreach passes over the parameter tensors)
+            self.opt = torch.optim.Adam(params, lr=self._lr, capturable=True, fused=True)
+        else:
+            self.opt = torch.optim.Adam(params, lr=self._lr_value, fused=bool(params[0].is_cuda))
+
+    # hooks
+    def _body(self, *inputs):
+        """Forward + backward (+ whatever else precedes Adam) on `inputs`; returns the loss."""
+        raise NotImplementedError
+
+    def _graph_key(self, shape):
+        return shape
+
+    def _force_eager(self):
+        return self.keep_grads
+
+    def _before_capture(self):
+        pass
+
+    def _after_step(self, replayed):
+        pass
+
+    def _lr_now(self):
+        lr0, dstep, drate = self._sched
+        return lr0 * drate ** (self._steps_done // dstep)
+
+    def _set_lr(self):
+        lr = self._lr_now()
+        if lr != self._lr_value:  # (staircase schedule: changes every decay_step steps)
+            if self._lr is None:
+                for group in self.opt.param_groups:
+                    group["lr"] = lr
+            else:
+                self._lr.fill_(lr)
+            self._lr_value = lr
+
+    def _add_weight_decay(self, rank0_only=False):
+        """L2 weight decay on '.*/W' (regularize_cost, core/model.py:239-243): d/dp [wd/2 * sum p^2] = wd * p, added to the
+        gradients directly (one multi-tensor launch).  rank0_only: a SUM all-reduce follows and must count it once."""
+        if not (self.wd_params and self.weight_decay) or (rank0_only and D.collectives_active() and dist.get_rank() != 0):
+            return
+        gs = [p.grad for p in self.wd_params if p.grad is not None]
+        ps = [p.detach() for p in self.wd_params if p.grad is not None]
+        if gs:
+            torch._foreach_add_(gs, ps, alpha=self.weight_decay)
+
+    def _arena_body(self, arena, inputs):
+        with pm.zero_arena(arena):
+            arena.begin(inputs[0].device)   # ONE fill for every accumulator of the step
+            return self._body(*inputs)
+
+    def _capture(self, key, shape, inputs):
+        static = tuple(t.clone() for t in inputs)
+        arena = pm.ZeroArena(fixed_bytes=self._shape_demand.get(shape, self._zarena.peak), device=inputs[0].device)
+        self.opt.zero_grad(set_to_none=True)
+        self._before_capture()
+        graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(graph):
+                loss = self._arena_body(arena, static)
+                self.opt.step()
+        except RuntimeError as e:
+            if D.collectives_active():
+                raise
+            import warnings
+            warnings.warn("dh3d_amd: the training step for inputs of shape %s could not be captured into a hipGraph "
+                          "(%s: %s); continuing with eager steps" % (shape[0], type(e).__name__, e), RuntimeWarning)
+            self.graph_step = False
+            self.opt.zero_grad(set_to_none=True)
+            return None
+        ent = (graph, static, loss, arena, [p.grad for p in self.params])
+        self._graphs[key] = ent
+        return ent
+
+    def _step(self, *inputs):
+        """One optimisation step on `inputs`; returns the loss as a device scalar (a replayed step overwrites it)."""
+        shape = (tuple(tuple(t.shape) for t in inputs), inputs[0].device)
+        ent = None
+        if self.graph_step and self._eager_seen.get(shape, 0) >= 3 and not self._force_eager():
+            key = self._graph_key(shape)
+            ent = self._graphs.get(key) or self._capture(key, shape, inputs)
+        if ent is None:
+            self._eager_seen[shape] = self._eager_seen.get(shape, 0) + 1
+            self._grads_of = None
+            self._set_lr()
+            self.opt.zero_grad(set_to_none=True)
+            loss = self._arena_body(self._zarena, inputs)
+            self._shape_demand[shape] = max(self._shape_demand.get(shape, 0), self._zarena.demand)
+            if self.keep_grads:  # tests: the gradient Adam is about to see (Adam's m/sqrt(v) is sign-like in the first
+                # steps, so the parameters themselves are ill-conditioned witnesses)
+                self.last_grads = [None if p.grad is None else p.grad.detach().clone() for p in self.params]
+            self.opt.step()
+        else:
+            graph, static, loss, _, grads = ent
+            for dst, src in zip(static, inputs):
+                if dst.data_ptr() != src.data_ptr():
+                    dst.copy_(src)
+            self._set_lr()
+            graph.replay()
+            if self._grads_of is not ent:  # (not on every replay: ~0.4 us of host time per parameter)
+                for p, g in zip(self.params, grads):
+                    p.grad = g
+                self._grads_of = ent
+        self._steps_done += 1
+        self._after_step(ent is not None)
+        return loss.detach()
+
+
+class QuadrupletTrainer(_StepLoop):
     """One process per GPU.  `step(points)` takes the role-ordered batch [B*(1+P+Ng+1), N, 3] (identical on
     every rank, e.g. generated from a shared seed), runs this rank's block and returns the loss."""
 
     def __init__(self, model, start_lr=None, decay_step=None, decay_rate=None, weight_decay=None, sync_bn=True,
                  graph_backbone=True, graph_step=None, backbone_bn="ema"):
-        """Schedule / weight decay default to the model's config (core/configs.py:50-54,115-117).  sync_bn=True (the
-        default) reproduces the reference's whole-batch BatchNorm statistics under sharding -- and keeps the running
-        buffers identical on every rank; sync_bn=False normalises with per-rank statistics (a few clouds of one role
-        each under the contiguous role-ordered partition) and lets the buffers diverge.
+        """Schedule, weight decay and the step loop are _StepLoop's (the device-scalar Adam iff graph_step).
+        sync_bn=True (the default) reproduces the reference's whole-batch BatchNorm statistics under sharding -- and
+        keeps the running buffers identical on every rank; sync_bn=False normalises with per-rank statistics (a few
+        clouds of one role each under the contiguous role-ordered partition) and lets the buffers diverge.
         backbone_bn: "ema" (default) -- the frozen backbone runs the fused inference path on its moving averages;
         "batch" -- it normalises with batch statistics and updates its moving averages, which is what the reference
         graph does while global_config trains (backbone_local_batch_stats_hip; slower, un-fused)."""
         if backbone_bn not in ("ema", "batch"):
             raise ValueError("backbone_bn must be 'ema' or 'batch'")
-        self.model = model
-        self.cfg = model.config
+        # Sharded (RCCL), the collectives of a step -- sync-BN statistics, the descriptor all-gather, ONE all-reduce of
+        # the flat gradient arena -- are captured with the kernels between them (torch's NCCL process group enqueues on
+        # the capturing stream); gloo's host-staged collectives cannot be captured, so the CPU-test path stays eager.
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        capturable = world == 1 and not D.collectives_active() or (D.collectives_active() and dist.get_backend() == "nccl")
+        graph_step = capturable if graph_step is None else (bool(graph_step) and capturable)
+        super().__init__(model, trainable_head_parameters(model), start_lr, decay_step, decay_rate, weight_decay,
+                         (20000, 0.9), graph_step, device_lr=graph_step)
         self.impl = "hip"         # (reported by bench.py; the tensor-op subclass of the tests says "torch")
         self.backbone_bn = backbone_bn
         self.graph_backbone = graph_backbone and backbone_bn == "ema"
         self._bb_graphs = {}
-        self.keep_grads, self.last_grads = False, None
+        self._step_graphs = self._graphs
         self._ev = None
-        c = self.cfg
-        start_lr = start_lr if start_lr is not None else (c.start_lr or 5e-4)
-        decay_step = decay_step if decay_step is not None else (c.decay_step or 20000)
-        decay_rate = decay_rate if decay_rate is not None else (c.decay_rate or 0.9)
-        if weight_decay is None:
-            weight_decay = (c.train_weight_decay or 1e-5) if c.add_weight_decay is not False else 0.0
         self.sync_bn = sync_bn
-        self.params = trainable_head_parameters(model)
-        self.wd_params = [p for n, p in model.named_parameters() if n.endswith(".W")
-                          and any(p is q for q in self.params)]
-        self.weight_decay = weight_decay
-        # Whole-step hipGraph (forward, loss, backward, weight decay, gradient all-reduce, Adam): a 22-cloud step is ~600
-        # launches, about as much host time as GPU time.  The first steps on a batch shape run eagerly (allocator /
-        # autograd warm-up), then the step is captured once per shape and replayed.  The learning rate is a device
-        # scalar the staircase schedule writes into.  Sharded (RCCL): the collectives -- sync-BN statistics, the
-        # descriptor all-gather, ONE all-reduce of the flat gradient arena -- are captured with the kernels between
-        # them (torch's NCCL process group enqueues on the capturing stream); gloo's host-staged collectives cannot be
-        # captured, so the CPU-test path stays eager.
-        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-        capturable = world == 1 and not D.collectives_active() or (D.collectives_active() and dist.get_backend() == "nccl")
-        self.graph_step = capturable if graph_step is None else (bool(graph_step) and capturable)
-        self._zarena = pm.ZeroArena()   # the step's accumulators: one fill per step (pm.ZeroArena)
         self._garena = None     # flat gradient arena of the sharded step (all-reduced in place, .grad are views of it)
-        self._sched = (float(start_lr), int(decay_step), float(decay_rate))
-        self._steps_done = 0
-        self._step_graphs = {}
-        self._shape_demand = {}  # batch shape -> accumulator bytes one step of it takes from the ZeroArena
-        self._eager_seen = {}   # batch shape -> eager steps run on it (every shape warms up before its capture)
         self.keep_desc, self.last_desc = False, None
-        if self.graph_step:
-            dev = self.params[0].device
-            self._lr = torch.tensor(float(start_lr), dtype=torch.float32, device=dev)
-            self._lr_value = float(start_lr)
-            # (fused: one multi-tensor kernel per step instead of ~8 foreach passes over the 20 parameter tensors)
-            self.opt = torch.optim.Adam(self.params, lr=self._lr, capturable=True, fused=True)
-            self.sched = None
-        else:
-            self.opt = torch.optim.Adam(self.params, lr=start_lr, fused=bool(self.params[0].is_cuda))
-            self.sched = torch.optim.lr_scheduler.LambdaLR(self.opt, lambda s: decay_rate ** (s // decay_step))
 
     def forward_loss(self, points):
         cfg = self.cfg
@@ -407,16 +535,7 @@ class QuadrupletTrainer(object):
                 keep = {k: v for k, v in lv.items() if torch.is_tensor(v) or k == "_ordered"}  # no capture-time events
                 return localdesc, keep
 
-            s = torch.cuda.Stream(device=block.device)
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    body()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                outs = body()
+            graph, outs = _capture_warmed(body, 2, block.device)
             ent = (graph, static_in, outs)
             self._bb_graphs[key] = ent
         graph, static_in, outs = ent
@@ -447,23 +566,13 @@ class QuadrupletTrainer(object):
                 cnt[k0] += 1
         return {n: (t / c if c else None) for n, t, c in zip(names, tot, cnt)}
 
-    def _lr_now(self):
-        lr0, dstep, drate = self._sched
-        return lr0 * drate ** (self._steps_done // dstep)
-
-    def _set_lr(self):
-        lr = self._lr_now()
-        if lr != self._lr_value:  # (staircase schedule: changes every decay_step steps)
-            self._lr.fill_(lr)
-            self._lr_value = lr
-
     def input_buffer(self, shape, device=None):
         """The replayed step's own input tensor for batches of `shape` (None until that shape has been captured): a
         loader that writes the next batch straight into it and passes it to `step` saves the copy into the graph's
         input (the graph reads this buffer; any other tensor is copied into it first)."""
-        for (shp, dev, _), ent in self._step_graphs.items():
-            if tuple(shp) == tuple(shape) and (device is None or dev == device):
-                return ent[1]
+        for (shapes, dev, _), ent in self._graphs.items():
+            if shapes[0] == tuple(shape) and (device is None or dev == device):
+                return ent[1][0]
         return None
 
     def _reduce_gradients(self):
@@ -490,108 +599,41 @@ class QuadrupletTrainer(object):
                 self._gviews.append(self._garena[off:off + p.numel()].view(p.shape))
                 off += p.numel()
 
-    def _step_graphed(self, points):
-        key = (tuple(points.shape), points.device, getattr(self.model, "_backbone_version", 0))
-        ent = self._step_graphs.get(key)
-        if ent is None:
-            for k in [k for k in self._step_graphs if k[2] != key[2]]:  # graphs of an older backbone are stale
-                del self._step_graphs[k]
-            static_in = points.clone()
-            # the graph's OWN accumulator arena, sized by this shape's eager steps and never reallocated: the eager
-            # arena grows (and frees its old buffer) whenever a larger shape comes along, and a graph replaying into a
-            # freed buffer would corrupt whatever owns that memory by then
-            arena = pm.ZeroArena(fixed_bytes=self._shape_demand.get(key[:2], self._zarena.peak), device=points.device)
-            self.opt.zero_grad(set_to_none=True)
-            if D.collectives_active():
-                self._ensure_arena()
-            graph = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(graph), pm.zero_arena(arena):
-                    arena.begin(static_in.device)   # ONE fill for every accumulator of the step
-                    loss = self.forward_loss(static_in)
-                    loss.backward()
-                    if self.wd_params and self.weight_decay and (not D.collectives_active() or dist.get_rank() == 0):
-                        gs = [p.grad for p in self.wd_params if p.grad is not None]
-                        ps = [p.detach() for p in self.wd_params if p.grad is not None]
-                        if gs:
-                            torch._foreach_add_(gs, ps, alpha=self.weight_decay)
-                    if D.collectives_active():
-                        self._reduce_gradients()
-                    self.opt.step()
-            except RuntimeError as e:
-                # something in this shape's step cannot be captured: stay eager for good (the parameters are untouched --
-                # a capture records, it does not run) -- and say so.  In a sharded run the ranks must not diverge (one
-                # replaying captured collectives, one issuing them eagerly), and a capture that died inside a
-                # collective leaves the communicator undefined: that is an error, not a fallback.
-                if D.collectives_active():
-                    raise
-                import warnings
-                warnings.warn("dh3d_amd: the training step for batches of shape %s could not be captured into a "
-                              "hipGraph (%s: %s); continuing with eager steps" % (tuple(points.shape), type(e).__name__, e),
-                              RuntimeWarning)
-                self.graph_step = False
-                self.opt.zero_grad(set_to_none=True)
-                return None
-            ent = (graph, static_in, loss, arena)
-            self._step_graphs[key] = ent
-        graph, static_in, loss = ent[:3]
-        # (each of these two is a launch of its own in front of the replay -- ~10 us of queue latency apiece: skipped
-        # when the batch already sits in the step's input buffer (`input_buffer`) / the rate has not changed)
-        if points.data_ptr() != static_in.data_ptr():
-            static_in.copy_(points)
-        self._set_lr()
-        graph.replay()
-        self._steps_done += 1
-        self.model.invalidate(head_only=True)
-        if self.backbone_bn == "batch":   # the replay moved the backbone's moving averages on the device
+    def _body(self, points):
+        loss = self.forward_loss(points)
+        self._mark(2)
+        loss.backward()
+        self._add_weight_decay(rank0_only=True)
+        self._mark(3)
+        if D.collectives_active():
+            self._reduce_gradients()
+        return loss
+
+    def _graph_key(self, shape):
+        key = shape + (getattr(self.model, "_backbone_version", 0),)
+        for k in [k for k in self._graphs if k[2] != key[2]]:  # graphs of an older backbone are stale
+            del self._graphs[k]
+        return key
+
+    def _force_eager(self):  # phases are timed, or gradients / descriptors are kept for inspection
+        return self._ev is not None or self.keep_grads or self.keep_desc
+
+    def _before_capture(self):
+        if D.collectives_active():
+            self._ensure_arena()
+
+    def _after_step(self, replayed):
+        self.model.invalidate(head_only=True)  # the packed / folded weight copies of the fused inference path are stale now
+        if replayed and self.backbone_bn == "batch":   # the replay moved the backbone's moving averages on the device
             self.model._bn_stale = True
-        return loss.detach()
 
     def step(self, points, sync=True):
         """One optimisation step; returns the loss -- as a float (sync=True: one host round trip per step) or as the
         device scalar the step wrote (sync=False: nothing waits for the GPU; a replayed step overwrites it)."""
-        loss = self._step(points)
-        return float(loss) if sync else loss
-
-    def _step(self, points):
-        # eager for the first steps ON EVERY BATCH SHAPE (allocator / autograd / lazily built constants warm up before
-        # the capture), while phases are timed or gradients / descriptors are kept for inspection
-        shape = (tuple(points.shape), points.device)
-        if (self.graph_step and self._eager_seen.get(shape, 0) >= 3 and self._ev is None and not self.keep_grads
-                and not self.keep_desc):
-            out = self._step_graphed(points)
-            if out is not None:
-                return out
-        self._eager_seen[shape] = self._eager_seen.get(shape, 0) + 1
-        if self.graph_step:
-            self._set_lr()
-        self.opt.zero_grad(set_to_none=True)
         self._mark(0)
-        with pm.zero_arena(self._zarena):
-            self._zarena.begin(points.device)
-            loss = self.forward_loss(points)
-            self._mark(2)
-            loss.backward()
-        self._shape_demand[shape] = max(self._shape_demand.get(shape, 0), self._zarena.demand)
-        # L2 weight decay on '.*/W' (regularize_cost, core/model.py:239-243): d/dp [wd/2 * sum p^2] = wd * p, added to the
-        # gradients directly (one multi-tensor launch) by rank 0 only -- the SUM all-reduce below then counts it once
-        if self.wd_params and self.weight_decay and (not dist.is_initialized() or dist.get_rank() == 0):
-            gs = [p.grad for p in self.wd_params if p.grad is not None]
-            ps = [p.detach() for p in self.wd_params if p.grad is not None]
-            if gs:
-                torch._foreach_add_(gs, ps, alpha=self.weight_decay)
-        self._mark(3)
-        if D.collectives_active():
-            self._reduce_gradients()
-        if self.keep_grads:  # tests: the reduced gradient of this step (Adam's m/sqrt(v) is sign-like in the first
-            self.last_grads = [p.grad.detach().clone() for p in self.params]  # steps: parameters are ill-conditioned)
-        self.opt.step()
-        if self.sched is not None:
-            self.sched.step()
-        self._steps_done += 1
+        loss = self._step(points)
         self._mark(4)
-        self.model.invalidate(head_only=True)  # the packed / folded weight copies of the fused inference path are stale now
-        return loss.detach()
+        return float(loss) if sync else loss
 
 
 # ======================================================================================================================
@@ -711,46 +753,20 @@ def local_trainable_parameters(model):
     return out
 
 
-class LocalTrainer(object):
+class LocalTrainer(_StepLoop):
     """Stage 1-2 training step on ONE GPU: forward of the whole local backbone in training mode (local_backbone_train),
     desc_local_loss (+ local_detection_loss_nn x det_loss_weight with detection_config) through losses.compute_loss as
-    core/model.py:212-237 assembles them, backward, L2 weight decay on '.*/W', Adam with the staircase learning rate
-    (model.py:238-255).  After three eager steps on a batch shape the whole step -- ~500 launches -- is captured into one
-    hipGraph and replayed from its own input buffers."""
+    core/model.py:212-237 assembles them, backward; weight decay, Adam, the learning rate and the eager / captured /
+    replayed step are _StepLoop's (the Adam reading the device scalar; inputs (points, R, sample_idx))."""
 
     def __init__(self, model, start_lr=None, decay_step=None, decay_rate=None, weight_decay=None, graph_step=True):
-        self.model, self.cfg = model, model.config
-        c = self.cfg
-        if c.extract_global:
+        if model.config.extract_global:
             raise ValueError("LocalTrainer trains basic_config / detection_config (extract_global False); the global "
                              "stage is QuadrupletTrainer")
-        start_lr = start_lr if start_lr is not None else (c.start_lr or 5e-4)
-        decay_step = decay_step if decay_step is not None else (c.decay_step or 10000)
-        decay_rate = decay_rate if decay_rate is not None else (c.decay_rate or 0.5)
-        if weight_decay is None:
-            weight_decay = (c.train_weight_decay or 1e-5) if c.add_weight_decay is not False else 0.0
-        self.weight_decay = weight_decay
-        self.params = local_trainable_parameters(model)
-        self.wd_params = [p for n, p in model.named_parameters() if n.endswith(".W") and any(p is q for q in self.params)]
-        self.graph_step = bool(graph_step) and self.params[0].is_cuda
-        self._sched = (float(start_lr), int(decay_step), float(decay_rate))
-        self._steps_done, self._graphs, self._eager_seen, self._shape_demand = 0, {}, {}, {}
-        self._zarena = pm.ZeroArena()
-        dev = self.params[0].device
-        self._lr = torch.tensor(float(start_lr), dtype=torch.float32, device=dev)
-        self._lr_value = float(start_lr)
-        if self.params[0].is_cuda:
-            self.opt = torch.optim.Adam(self.params, lr=self._lr, capturable=True, fused=True)
-        else:
-            self.opt = torch.optim.Adam(self.params, lr=float(start_lr))
-        self.keep_grads, self.last_grads, self.last_outs = False, None, None
-
-    def _set_lr(self):
-        lr0, dstep, drate = self._sched
-        lr = lr0 * drate ** (self._steps_done // dstep)
-        if lr != self._lr_value:
-            self._lr.fill_(lr)
-            self._lr_value = lr
+        params = local_trainable_parameters(model)
+        super().__init__(model, params, start_lr, decay_step, decay_rate, weight_decay, (10000, 0.5),
+                         bool(graph_step) and params[0].is_cuda, device_lr=params[0].is_cuda)
+        self.last_outs = None
 
     def forward_loss(self, points, R, sample_idx):
         outs = local_training_outputs(self.model, points, R, sample_idx)
@@ -758,57 +774,19 @@ class LocalTrainer(object):
             self.last_outs = outs
         return losses.compute_loss(outs, self.cfg)
 
-    def _body(self, arena, points, R, sample_idx):
-        with pm.zero_arena(arena):
-            arena.begin(points.device)
-            loss = self.forward_loss(points, R, sample_idx)
-            loss.backward()
-        if self.wd_params and self.weight_decay:
-            gs = [p.grad for p in self.wd_params if p.grad is not None]
-            ps = [p.detach() for p in self.wd_params if p.grad is not None]
-            if gs:
-                torch._foreach_add_(gs, ps, alpha=self.weight_decay)   # d/dp [wd/2 * sum p^2] (model.py:239-243)
+    def _body(self, points, R, sample_idx):
+        loss = self.forward_loss(points, R, sample_idx)
+        loss.backward()
+        self._add_weight_decay()
         return loss
+
+    def _after_step(self, replayed):
+        # moving averages and weights moved: the inference path re-folds on its next forward; older replays refuse to run
+        self.model.mark_weights_changed(bn_stale=True)
 
     def step(self, points, R, sample_idx, sync=True):
         """One optimisation step on (points [2B,N,3], R [B,3,3], sample_idx [2B,M] int32); returns the loss (a float, or
         the device scalar with sync=False)."""
         self.model.eval()  # (the module flag: the training-mode graph is built explicitly, the fused path stays usable)
-        sample_idx = sample_idx.to(torch.int32)
-        key = (tuple(points.shape), tuple(R.shape), tuple(sample_idx.shape), points.device)
-        graphed = self.graph_step and self._eager_seen.get(key, 0) >= 3 and not self.keep_grads
-        if graphed:
-            ent = self._graphs.get(key)
-            if ent is None:
-                static = (points.clone(), R.clone(), sample_idx.clone())
-                arena = pm.ZeroArena(fixed_bytes=self._shape_demand.get(key, self._zarena.peak), device=points.device)
-                self.opt.zero_grad(set_to_none=True)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    loss = self._body(arena, *static)
-                    self.opt.step()
-                ent = (graph, static, loss, arena, [p.grad for p in self.params])
-                self._graphs[key] = ent
-            graph, static, loss, _, grads = ent
-            for dst, src in zip(static, (points, R, sample_idx)):
-                if dst.data_ptr() != src.data_ptr():
-                    dst.copy_(src)
-            self._set_lr()
-            graph.replay()
-            # the replay wrote its gradients into the tensors its capture created; `p.grad` may still name another
-            # shape's (that graph's capture or eager step came later): point it at this step's
-            for p, g in zip(self.params, grads):
-                p.grad = g
-        else:
-            self._eager_seen[key] = self._eager_seen.get(key, 0) + 1
-            self._set_lr()
-            self.opt.zero_grad(set_to_none=True)
-            loss = self._body(self._zarena, points, R, sample_idx)
-            self._shape_demand[key] = max(self._shape_demand.get(key, 0), self._zarena.demand)
-            if self.keep_grads:
-                self.last_grads = [None if p.grad is None else p.grad.detach().clone() for p in self.params]
-            self.opt.step()
-        self._steps_done += 1
-        self.model.mark_weights_changed(bn_stale=True)   # moving averages and weights moved: the inference path re-folds on its next forward; older replays refuse to run
-        loss = loss.detach()
+        loss = self._step(points, R, sample_idx.to(torch.int32))
         return float(loss) if sync else loss

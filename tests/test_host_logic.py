@@ -213,3 +213,19 @@ def test_unknown_fetch_name_is_an_error():
     with pytest.raises(ValueError, match="unknown output name"):
         m.forward(torch.zeros(1, 64, 3), fetch=("global_desc",))
     assert "globaldesc" in DH3D.OUTPUT_NAMES and "xyz_feat" in DH3D.OUTPUT_NAMES
+
+
+def test_host_learning_rate_follows_the_staircase_exactly():
+    """A trainer built without the device scalar (graph_step off) carries the rate in Adam's param group: before every
+    step it must be start_lr * decay_rate ** (steps_done // decay_step), to the bit, across decay boundaries."""
+    from dh3d_amd import ConfigFactory
+    from dh3d_amd.model import DH3D
+    from dh3d_amd.training import QuadrupletTrainer
+    m = DH3D(ConfigFactory("global_config").getconfig()).init_synthetic(0)
+    start_lr, decay_step, decay_rate = 3e-4, 4, 0.9
+    tr = QuadrupletTrainer(m, start_lr=start_lr, decay_step=decay_step, decay_rate=decay_rate, graph_step=False)
+    assert tr._lr is None and not hasattr(tr, "sched") and tr.opt.param_groups[0]["lr"] == start_lr
+    for s in range(3 * decay_step + 2):  # two decay boundaries and into the third stair
+        tr._steps_done = s
+        tr._set_lr()  # what the step does before it runs
+        assert tr.opt.param_groups[0]["lr"] == start_lr * decay_rate ** (s // decay_step), s
