@@ -2,7 +2,8 @@
 
 Mirrors user_ops/__init__.py (knn_bruteforce :50, flex_convolution :63-89, flex_convolution_transpose,
 flex_pooling :115-135, convolution_pointset :205-225) and tf_ops/{sampling,grouping,interpolation}/tf_*.py
-(farthest_point_sample tf_sampling.py:63-71, group_point tf_grouping.py:48-56, three_nn / three_interpolate
+(farthest_point_sample tf_sampling.py:63-71, query_ball_point / query_ball_point2 tf_grouping.py:9-36, group_point
+tf_grouping.py:48-56, three_nn / three_interpolate
 tf_interpolate.py:8-34), with torch.autograd.Function standing in for the RegisterGradient hooks
 (user_ops/__init__.py:95-111,141-151,231-246; tf_grouping.py:57-61; tf_interpolate.py:29-34).
 Where TF raised InvalidArgument these raise ValueError.  Every op runs on the HIP library; there is no
@@ -14,7 +15,7 @@ from . import _lib as L
 
 __all__ = [
     "knn_bruteforce", "flex_convolution", "flex_convolution_transpose", "flex_pooling", "convolution_pointset",
-    "farthest_point_sample", "group_point", "three_nn", "three_interpolate",
+    "farthest_point_sample", "group_point", "three_nn", "three_interpolate", "query_ball_point", "query_ball_point2",
 ]
 
 
@@ -224,6 +225,34 @@ def farthest_point_sample(npoint, inp, contract=None):
                                                             1 if contract is None else int(bool(contract)),
                                                             L.stream_ptr()), "farthest_point_sample")
     return out
+
+
+def _query_ball(radius, nsample, xyz1, xyz2):
+    from . import pm
+    with torch.no_grad():  # ops.NoGradient('QueryBallPoint') (tf_grouping.py:22)
+        n, m = (xyz1.shape[1], xyz2.shape[1]) if isinstance(xyz1, torch.Tensor) and xyz1.dim() == 3 and \
+            isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 else (0, 0)
+        # one rule on (n, m, nsample) alone -- never the batch or the data: a cloud gives the same rows in any batch
+        if pm.ball_query_plan(n, m, int(nsample)) == 1:
+            return pm.ball_query_grid(radius, nsample, xyz1, xyz2)
+        return pm.ball_query_scan(radius, nsample, xyz1, xyz2)
+
+
+def query_ball_point(radius, nsample, xyz1, xyz2):
+    """radius float, nsample int, xyz1 [b,n,3] dataset, xyz2 [b,m,3] queries -> (idx [b,m,nsample] int32, pts_cnt [b,m]
+    int32) (tf_grouping.py:9-22): per query the nsample lowest indices with d < radius in ascending order, then the first
+    repeated; an empty ball's row is its nearest point, pts_cnt 0.  Not differentiable."""
+    if isinstance(radius, torch.Tensor) or not float(radius) > 0.0:
+        raise ValueError("QueryBallPoint expects positive radius")  # tf_grouping.cpp:90
+    return _query_ball(float(radius), nsample, xyz1, xyz2)
+
+
+def query_ball_point2(radii, nsample, xyz1, xyz2):
+    """radii [b,m] float32, one per query (a radius <= 0 or NaN has no hits); otherwise query_ball_point
+    (tf_grouping.py:23-36).  Not differentiable."""
+    if not isinstance(radii, torch.Tensor):
+        raise ValueError("QueryBallPoint2 expects radii as a (batch_size,npoint) tensor")
+    return _query_ball(radii, nsample, xyz1, xyz2)
 
 
 class _GroupPoint(torch.autograd.Function):

@@ -82,6 +82,83 @@ def knn_sorted(srt, gbox, k):
     return nn, dist
 
 
+def _ball_args(radius, nsample, xyz1, xyz2, what):
+    """The checks both ball-query kernels share -> (x1, x2, radii tensor or None, b, n, m)."""
+    # the operator's own refusals first (tf_grouping.cpp:90-104), then where the tensors live: the two kinds of error do
+    # not mask each other
+    if int(nsample) <= 0:
+        raise ValueError("%s expects positive nsample" % what)
+    if not isinstance(radius, torch.Tensor) and not float(radius) > 0.0:
+        raise ValueError("%s expects positive radius" % what)
+    if all(isinstance(t, torch.Tensor) and t.dim() == 3 for t in (xyz1, xyz2)):
+        if xyz1.shape[2] != 3 or xyz2.shape[2] != 3:
+            raise ValueError("%s expects (batch_size,ndataset,3) xyz1 and (batch_size,npoint,3) xyz2" % what)
+        if xyz1.shape[0] != xyz2.shape[0]:
+            raise ValueError("%s: batch(xyz1/xyz2) mismatch: %d vs %d" % (what, xyz1.shape[0], xyz2.shape[0]))
+    x1 = L.require_cuda_f32(xyz1, "xyz1", 3)
+    x2 = L.require_cuda_f32(xyz2, "xyz2", 3)
+    if x1.device != x2.device:
+        raise ValueError("%s: xyz1 and xyz2 live on different devices" % what)
+    b, n, m = x1.shape[0], x1.shape[1], x2.shape[1]
+    if b <= 0 or n <= 0 or m <= 0:
+        raise ValueError("%s: empty xyz1 %s or xyz2 %s" % (what, tuple(x1.shape), tuple(x2.shape)))
+    if isinstance(radius, torch.Tensor):
+        rad = L.require_cuda_f32(radius, "radii", 2)
+        if tuple(rad.shape) != (b, m) or rad.device != x1.device:
+            raise ValueError("%s: radii must be [%d, %d] on %s, got %s on %s" % (what, b, m, x1.device, tuple(rad.shape),
+                                                                             rad.device))
+    else:
+        rad = None
+    return x1, x2, rad, b, n, m
+
+
+def ball_query_scan(radius, nsample, xyz1, xyz2):
+    """query_ball_point by the scan kernel (any shape): xyz1 [b,n,3] dataset, xyz2 [b,m,3] queries -> (idx [b,m,nsample]
+    int32, pts_cnt [b,m] int32).  radius: a positive float, or a float32 tensor [b,m] of per-query radii
+    (query_ball_point2; a radius <= 0 or NaN has no hits).  Row format: include/dh3d_hip.h dh3d_query_ball_point."""
+    x1, x2, rad, b, n, m = _ball_args(radius, nsample, xyz1, xyz2, "ball_query_scan")
+    idx = torch.empty((b, m, int(nsample)), dtype=torch.int32, device=x1.device)
+    cnt = torch.empty((b, m), dtype=torch.int32, device=x1.device)
+    with torch.cuda.device(x1.device):
+        if rad is None:
+            st = L.lib().dh3d_query_ball_point(b, n, m, float(radius), int(nsample), L.ptr(x1), L.ptr(x2), L.ptr(idx),
+                                               L.ptr(cnt), L.stream_ptr())
+        else:
+            st = L.lib().dh3d_query_ball_point2(b, n, m, int(nsample), L.ptr(x1), L.ptr(x2), L.ptr(rad), L.ptr(idx),
+                                                L.ptr(cnt), L.stream_ptr())
+    L.check(st, "ball_query_scan")
+    return idx, cnt
+
+
+def ball_query_grid(radius, nsample, xyz1, xyz2, sort=None):
+    """The same (idx, pts_cnt) bit for bit by cell lists (n <= 16384).  sort: the (sorted, gbox, cells) of
+    spatial_sort_cells(xyz1) when the caller holds them already; None: sorted here."""
+    x1, x2, rad, b, n, m = _ball_args(radius, nsample, xyz1, xyz2, "ball_query_grid")
+    if n > 16384:
+        raise ValueError("ball_query_grid: n = %d is beyond the spatial sort (16384)" % n)
+    with torch.cuda.device(x1.device):
+        srt, gbox, cells = spatial_sort_cells(x1) if sort is None else sort
+        if tuple(srt.shape) != (b, n, 4) or tuple(cells.shape) != (b, CELL_INTS) or tuple(gbox.shape) != (b, (n + 63) // 64, 8):
+            raise ValueError("ball_query_grid: sort is not spatial_sort_cells() of a [%d, %d, 3] cloud" % (b, n))
+        r = rad if rad is not None else torch.full((1,), float(radius), dtype=torch.float32, device=x1.device)
+        idx = torch.empty((b, m, int(nsample)), dtype=torch.int32, device=x1.device)
+        cnt = torch.empty((b, m), dtype=torch.int32, device=x1.device)
+        L.check(L.lib().dh3d_query_ball_point_grid(b, n, m, L.ptr(r), int(rad is not None), int(nsample), L.ptr(srt),
+                                                   L.ptr(gbox), L.ptr(cells), L.ptr(x2), L.ptr(idx), L.ptr(cnt),
+                                                   L.stream_ptr()), "ball_query_grid")
+    return idx, cnt
+
+
+BALL_GRID_MIN_N, BALL_GRID_MAX_N = 1 << 30, 16384  # csrc/ball_query.hip kGridMinN (no shape yet: not measured), the sort's limit
+
+
+def ball_query_plan(n, m, nsample):
+    """The dispatcher's one rule, on shapes alone (= dh3d_query_ball_point_plan): 1 sort + cell lists, 0 the scan."""
+    if n <= 0 or m <= 0 or nsample <= 0:
+        return -1
+    return 1 if BALL_GRID_MIN_N <= n <= BALL_GRID_MAX_N else 0
+
+
 KEYPOINT_MAX = 4096  # include/dh3d_hip.h dh3d_keypoint_nms: M limit
 
 

@@ -187,6 +187,36 @@ int dh3d_group_point_fwd(int b, int n, int c, int m, int nsample, const float *p
 int dh3d_group_point_bwd(int b, int n, int c, int m, int nsample, const float *grad_out,
                          const int32_t *idx, float *grad_points, void *stream);
 
+/* QueryBallPoint / QueryBallPoint2 -- replace queryBallPointLauncher / queryBallPoint2Launcher
+ * (tf_ops/grouping/tf_grouping.cpp:86-165, tf_grouping_g.cu:3-92,179-186; CPU twin test/query_ball_point.cpp:19-47).
+ * xyz1 [b,n,3] (dataset), xyz2 [b,m,3] (queries) -> idx [b,m,nsample], pts_cnt [b,m].
+ * ROW FORMAT: per query, over the dataset points in index order, d = max(sqrtf(dx*dx + dy*dy + dz*dz), 1e-20f) and a hit is
+ * d < radius (strict); the row holds the min(hits, nsample) SMALLEST hit indices in ascending order, then the first of them
+ * repeated; pts_cnt = min(hits, nsample).
+ * EMPTY BALL: the row is nsample copies of the index of the point nearest to this query (same d, strict <, lowest index on
+ * ties), pts_cnt = 0 -- the twin leaves such a row unwritten, the CUDA kernel writes a nearest point that queries
+ * j >= 256 inherit from other queries.
+ * ROUNDING: the twin's, ((dx*dx + dy*dy) + dz*dz) in f32 without fma contraction and an IEEE sqrtf.
+ * dh3d_query_ball_point: one radius > 0.  dh3d_query_ball_point2: radii [b,m], one per query; a radius <= 0 or NaN has no
+ * hits.  Both run the scan kernel (lane = query, the cloud staged through LDS in index order, a wave leaves when all its
+ * balls are full): any n, m, nsample. */
+int dh3d_query_ball_point(int b, int n, int m, float radius, int nsample, const float *xyz1, const float *xyz2,
+                          int32_t *idx, int32_t *pts_cnt, void *stream);
+int dh3d_query_ball_point2(int b, int n, int m, int nsample, const float *xyz1, const float *xyz2, const float *radii,
+                           int32_t *idx, int32_t *pts_cnt, void *stream);
+/* The same rows bit for bit by cell lists: sorted1 / gbox1 / cells1 are the three outputs of dh3d_spatial_sort_cells(xyz1),
+ * n <= 16384.  radius_or_radii is DEVICE memory: one float (per_query = 0) or radii [b,m] (per_query = 1).  One wave per
+ * query tests the records of the cells that the ball's axis-aligned box meets and marks the hits in a bit set over original
+ * indices in LDS, whose nsample lowest bits are the row.  A box of more than 512 cells and a cloud the sort flagged as
+ * crowded (cells[4106]) go over the 64-point groups whose box (gbox1) the ball meets; an empty ball scans the cloud for
+ * its nearest point. */
+int dh3d_query_ball_point_grid(int b, int n, int m, const float *radius_or_radii, int per_query, int nsample,
+                               const float *sorted1, const float *gbox1, const int32_t *cells1, const float *xyz2,
+                               int32_t *idx, int32_t *pts_cnt, void *stream);
+/* Which of the two serves (n, m, nsample) in the operator: 0 the scan, 1 sort + cell lists, -1 a shape both refuse.  Host
+ * only; looks at the shape alone, never at the batch or the data. */
+int dh3d_query_ball_point_plan(int n, int m, int nsample);
+
 /* ThreeNN -- replaces threenn_cpu (tf_ops/interpolation/tf_interpolate.cpp:60-103).
  * xyz1 [b,n,3], xyz2 [b,m,3] -> dist [b,n,3] (SQUARED, ascending), idx [b,n,3]. */
 int dh3d_three_nn(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist,
