@@ -119,6 +119,9 @@ _SIGNATURES = {
     "dh3d_query_ball_point2": [c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_query_ball_point_grid": [c_int, c_int, c_int, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_query_ball_point_plan": [c_int, c_int, c_int],
+    "dh3d_select_top_k": [c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_knn_point": [c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_knn_point_plan": [c_int, c_int, c_int, c_int],
     "dh3d_three_nn": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_three_interpolate_fwd": [c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_three_interpolate_bwd": [c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp],

@@ -2,8 +2,9 @@
 
 Mirrors user_ops/__init__.py (knn_bruteforce :50, flex_convolution :63-89, flex_convolution_transpose,
 flex_pooling :115-135, convolution_pointset :205-225) and tf_ops/{sampling,grouping,interpolation}/tf_*.py
-(farthest_point_sample tf_sampling.py:63-71, query_ball_point / query_ball_point2 tf_grouping.py:9-36, group_point
-tf_grouping.py:48-56, three_nn / three_interpolate
+(farthest_point_sample tf_sampling.py:63-71, gather_point tf_sampling.py:38-61, query_ball_point / query_ball_point2
+tf_grouping.py:9-36, select_top_k / knn_point tf_grouping.py:37-47,63-88, group_point tf_grouping.py:48-56,
+three_nn / three_interpolate
 tf_interpolate.py:8-34), with torch.autograd.Function standing in for the RegisterGradient hooks
 (user_ops/__init__.py:95-111,141-151,231-246; tf_grouping.py:57-61; tf_interpolate.py:29-34).
 Where TF raised InvalidArgument these raise ValueError.  Every op runs on the HIP library; there is no
@@ -16,6 +17,7 @@ from . import _lib as L
 __all__ = [
     "knn_bruteforce", "flex_convolution", "flex_convolution_transpose", "flex_pooling", "convolution_pointset",
     "farthest_point_sample", "group_point", "three_nn", "three_interpolate", "query_ball_point", "query_ball_point2",
+    "knn_point", "select_top_k", "gather_point",
 ]
 
 
@@ -287,6 +289,35 @@ class _GroupPoint(torch.autograd.Function):
 def group_point(points, idx):
     """points [b,n,c], idx [b,m,nsample] int32 -> [b,m,nsample,c] (tf_grouping.py:48-61)."""
     return _GroupPoint.apply(points, idx)
+
+
+def select_top_k(k, dist):
+    """k int, dist [b,m,n] float32 -> (idx [b,m,n] int32, dist_out [b,m,n]) (tf_grouping.py:37-47, the SelectionSort op):
+    every row the partial selection sort of its first k entries -- strict <, first minimum, swap -- and the WHOLE row is
+    returned; ties come out in the swap walk's order, not lowest id first.  1 <= k <= n.  Not differentiable."""
+    from . import pm
+    with torch.no_grad():  # ops.NoGradient('SelectionSort') (tf_grouping.py:47)
+        return pm.select_top_k(k, dist)
+
+
+def knn_point(k, xyz1, xyz2):
+    """k int, xyz1 [b,n,c] dataset, xyz2 [b,m,c] queries -> (val [b,m,k] SQUARED distances, idx [b,m,k] int32)
+    (tf_grouping.py:63-88): the first k columns of select_top_k on the matrix of squared distances, which the fused kernel
+    never forms.  Not differentiable."""
+    from . import pm
+    with torch.no_grad():
+        return pm.knn_point(k, xyz1, xyz2)
+
+
+def gather_point(inp, idx):
+    """inp [b,n,3], idx [b,m] int32 -> [b,m,3] (tf_sampling.py:38-61); the gradient is GatherPointGrad's scatter-add.
+    group_point with nsample = 1 on the same entry points."""
+    if isinstance(inp, torch.Tensor) and (inp.dim() != 3 or inp.shape[2] != 3):
+        raise ValueError("GatherPoint expects (batch_size,num_points,3) inp shape")  # tf_sampling.cpp:131
+    if isinstance(inp, torch.Tensor) and isinstance(idx, torch.Tensor) and (idx.dim() != 2 or idx.shape[0] != inp.shape[0]):
+        raise ValueError("GatherPoint expects (batch_size,num_result) idx shape")  # tf_sampling.cpp:135
+    ix = L.require_cuda_i32(idx, "idx", 2)
+    return _GroupPoint.apply(inp, ix.unsqueeze(2)).squeeze(2)
 
 
 def three_nn(xyz1, xyz2):

@@ -159,6 +159,72 @@ def ball_query_plan(n, m, nsample):
     return 1 if BALL_GRID_MIN_N <= n <= BALL_GRID_MAX_N else 0
 
 
+KNN_POINT_FUSED_MAX_K, KNN_POINT_MAX_K = 64, 1024  # csrc/knn_point.hip kFusedMaxK, kRowMaxK
+
+
+def knn_point_plan(n, m, c, k):
+    """The kernel dh3d_knn_point runs for a shape (= dh3d_knn_point_plan): 1 the fused kernel (c = 3, k <= 64), 0 the
+    generic one (a workgroup per query, any c, k <= 1024), -1 a shape it refuses.  Never the batch or the data."""
+    if n <= 0 or m <= 0 or c <= 0 or k <= 0 or k > n:
+        return -1
+    if c == 3 and k <= KNN_POINT_FUSED_MAX_K:
+        return 1
+    return 0 if k <= KNN_POINT_MAX_K else -1
+
+
+def select_top_k(k, dist):
+    """dist [b,m,n] float32 -> (idx [b,m,n] int32, dist_out [b,m,n]): every row the reference's partial selection sort of
+    its first k entries, whole row returned (include/dh3d_hip.h dh3d_select_top_k: ROW FORMAT, TIE ORDER)."""
+    k = int(k)
+    if k < 1 or (isinstance(dist, torch.Tensor) and dist.dim() == 3 and k > dist.shape[2]):
+        raise ValueError("SelectionSort expects 1 <= k <= n")
+    if isinstance(dist, torch.Tensor) and dist.dim() != 3:
+        raise ValueError("SelectionSort expects rank 3: (b,m,n) dist shape")  # tf_grouping.cpp:181
+    d = L.require_cuda_f32(dist, "dist", 3)
+    b, m, n = d.shape
+    if b <= 0 or m <= 0:
+        raise ValueError("SelectionSort: empty dist %s" % (tuple(d.shape),))
+    idx = torch.empty((b, m, n), dtype=torch.int32, device=d.device)
+    out = torch.empty((b, m, n), dtype=torch.float32, device=d.device)
+    with torch.cuda.device(d.device):
+        L.check(L.lib().dh3d_select_top_k(b, n, m, k, L.ptr(d), L.ptr(idx), L.ptr(out), L.stream_ptr()), "select_top_k")
+    return idx, out
+
+
+def knn_point(k, xyz1, xyz2):
+    """xyz1 [b,n,c] dataset, xyz2 [b,m,c] queries -> (val [b,m,k] squared distances, idx [b,m,k] int32): the first k columns
+    of select_top_k on the squared-distance matrix, which is never formed (include/dh3d_hip.h dh3d_knn_point)."""
+    k = int(k)
+    # the operator's own refusals first, then where the tensors live (as _ball_args)
+    if k < 1:
+        raise ValueError("SelectionSort expects 1 <= k <= n")
+    if all(isinstance(t, torch.Tensor) for t in (xyz1, xyz2)):
+        if xyz1.dim() == 3 and xyz2.dim() == 3:
+            if k > xyz1.shape[1]:
+                raise ValueError("SelectionSort expects 1 <= k <= n")
+            if xyz1.shape[0] != xyz2.shape[0]:
+                raise ValueError("knn_point: batch(xyz1/xyz2) mismatch: %d vs %d" % (xyz1.shape[0], xyz2.shape[0]))
+            if xyz1.shape[2] != xyz2.shape[2] or xyz1.shape[2] < 1:
+                raise ValueError("knn_point: c(xyz1/xyz2) mismatch: %d vs %d" % (xyz1.shape[2], xyz2.shape[2]))
+        else:
+            raise ValueError("knn_point expects rank 3: (batch_size,ndataset,c) xyz1 and (batch_size,npoint,c) xyz2")
+    x1 = L.require_cuda_f32(xyz1, "xyz1", 3)
+    x2 = L.require_cuda_f32(xyz2, "xyz2", 3)
+    if x1.device != x2.device:
+        raise ValueError("knn_point: xyz1 and xyz2 live on different devices")
+    (b, n, c), m = x1.shape, x2.shape[1]
+    if b <= 0 or m <= 0:
+        raise ValueError("knn_point: empty xyz1 %s or xyz2 %s" % (tuple(x1.shape), tuple(x2.shape)))
+    if knn_point_plan(n, m, c, k) < 0:
+        raise ValueError("knn_point: k = %d is beyond the kernels (%d)" % (k, KNN_POINT_MAX_K))
+    val = torch.empty((b, m, k), dtype=torch.float32, device=x1.device)
+    idx = torch.empty((b, m, k), dtype=torch.int32, device=x1.device)
+    with torch.cuda.device(x1.device):
+        L.check(L.lib().dh3d_knn_point(b, n, m, c, k, L.ptr(x1), L.ptr(x2), L.ptr(val), L.ptr(idx), L.stream_ptr()),
+                "knn_point")
+    return val, idx
+
+
 KEYPOINT_MAX = 4096  # include/dh3d_hip.h dh3d_keypoint_nms: M limit
 
 

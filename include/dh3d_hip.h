@@ -217,6 +217,33 @@ int dh3d_query_ball_point_grid(int b, int n, int m, const float *radius_or_radii
  * only; looks at the shape alone, never at the batch or the data. */
 int dh3d_query_ball_point_plan(int n, int m, int nsample);
 
+/* SelectionSort (select_top_k) and KnnPoint -- replace selectionSortLauncher and the tile + reduce_sum + SelectionSort
+ * composition of knn_point (tf_ops/grouping/tf_grouping.py:37-47,63-88, tf_grouping.cpp:50-58,175-206,
+ * tf_grouping_g.cu:134-177).
+ * dh3d_select_top_k: dist [b,m,n] -> outi [b,m,n] int32, out [b,m,n], 1 <= k <= n; out / outi must not overlap dist.
+ * dh3d_knn_point: xyz1 [b,n,c] (dataset), xyz2 [b,m,c] (queries), c >= 1 -> val [b,m,k] (SQUARED distances, no root is
+ * ever taken), idx [b,m,k] int32: the first k columns of dh3d_select_top_k on D[b,j,i] = sum_c (xyz1[b,i,c] - xyz2[b,j,c])^2,
+ * which is never written to memory.
+ * ROW FORMAT: a row is the reference's partial selection sort of that row, and the WHOLE row is the result: start from
+ * out = dist, outi = 0 .. n-1; for s = 0 .. k-1 find the first position t >= s holding the smallest value (strict <) and
+ * swap positions s and t of both arrays.  Entries from k on are the inputs where no swapped-out entry landed.
+ * TIE ORDER: the swap walk's, reproduced exactly -- NOT lowest id first: a swapped-out entry re-enters at a higher
+ * position and is then met later than entries of the same value with a higher id.  -0 and +0 are one value.  The kernels
+ * scan a row once for the min(k, n-k) smallest (value, position) keys over the positions >= k and replay the walk on them
+ * and the positions 0 .. k-1: nothing else ever moves (tests/test_knn_point_reference.py proves that on tie-heavy rows).
+ * ROUNDING: every difference and every square is rounded to f32 on its own, without fma contraction, and the squares are
+ * added left to right over c.  For c = 3 that is what the reference's reduce_sum of three elements does; for larger c the
+ * order of its Eigen reduction cannot be read from the source: left to right is INFERRED there.
+ * NaN and infinite inputs are outside the contract.  Both take the caller's stream, synchronise nothing and allocate
+ * nothing.  dh3d_select_top_k serves every k <= n; dh3d_knn_point refuses k > 1024 (status 2). */
+int dh3d_select_top_k(int b, int n, int m, int k, const float *dist, int32_t *outi, float *out, void *stream);
+int dh3d_knn_point(int b, int n, int m, int c, int k, const float *xyz1, const float *xyz2, float *val, int32_t *idx,
+                   void *stream);
+/* Which kernel serves (n, m, c, k) in dh3d_knn_point: 1 the fused kernel (c = 3, k <= 64: the dataset streamed through
+ * LDS past 16 queries per workgroup), 0 the generic one (any c, k <= 1024: a workgroup per query), -1 a shape it refuses.
+ * Host only; looks at these four numbers alone, never at the batch or the data. */
+int dh3d_knn_point_plan(int n, int m, int c, int k);
+
 /* ThreeNN -- replaces threenn_cpu (tf_ops/interpolation/tf_interpolate.cpp:60-103).
  * xyz1 [b,n,3], xyz2 [b,m,3] -> dist [b,n,3] (SQUARED, ascending), idx [b,n,3]. */
 int dh3d_three_nn(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist,
