@@ -225,6 +225,52 @@ def knn_point(k, xyz1, xyz2):
     return val, idx
 
 
+PREPARE_MAX_N, PREPARE_MAX_TARGET = 131072, 1 << 20  # csrc/prepare.hip kMaxN, kMaxTarget
+
+
+def prepare_clouds(raw, num_raw, targetnum, voxel_size=0.2, radius=1.0, nb_points=4, sortby_dis=True):
+    """raw [B,Nraw,3] float32, num_raw [B] int32 -> (points [B,targetnum,3], num_valid [B] int32, counts [B,3] int32,
+    centroid [B,3] float64): voxel grid, radius-outlier removal and crop / pad of every cloud on the device, no host sync
+    (dh3d_prepare_clouds in include/dh3d_hip.h holds the semantics).  voxel_size / radius None: that stage is skipped."""
+    targetnum, nb_points = int(targetnum), int(nb_points)
+    vox = 0.0 if voxel_size is None else float(voxel_size)
+    rad = 0.0 if radius is None else float(radius)
+    if targetnum < 1:
+        raise ValueError("prepare_clouds expects targetnum >= 1")
+    if (voxel_size is not None and not 0.0 < vox < float("inf")) or (radius is not None and not 0.0 < rad < float("inf")):
+        raise ValueError("prepare_clouds expects a positive finite voxel_size and radius (or None to skip the stage)")
+    if nb_points < 0:
+        raise ValueError("prepare_clouds expects nb_points >= 0")
+    if all(isinstance(t, torch.Tensor) for t in (raw, num_raw)):
+        if raw.dtype != torch.float32 or num_raw.dtype != torch.int32:
+            raise ValueError("prepare_clouds expects float32 raw and int32 num_raw, got %s and %s" % (raw.dtype, num_raw.dtype))
+        if raw.dim() != 3 or raw.shape[2] != 3 or raw.shape[0] < 1 or raw.shape[1] < 1:
+            raise ValueError("prepare_clouds expects (batch_size,nraw,3) raw, got %s" % (tuple(raw.shape),))
+        if num_raw.dim() != 1 or num_raw.shape[0] != raw.shape[0]:
+            raise ValueError("prepare_clouds expects (batch_size) num_raw = (%d,), got %s" % (raw.shape[0], tuple(num_raw.shape)))
+        if raw.shape[1] > PREPARE_MAX_N or targetnum > PREPARE_MAX_TARGET:
+            raise ValueError("prepare_clouds: nraw = %d / targetnum = %d is beyond the kernels (%d / %d)"
+                             % (raw.shape[1], targetnum, PREPARE_MAX_N, PREPARE_MAX_TARGET))
+    x = L.require_cuda_f32(raw, "raw", 3)
+    n = L.require_cuda_i32(num_raw, "num_raw", 1)
+    if x.device != n.device:
+        raise ValueError("prepare_clouds: raw and num_raw live on different devices")
+    B, N, _ = x.shape
+    points = torch.empty((B, targetnum, 3), dtype=torch.float32, device=x.device)
+    num_valid = torch.empty((B,), dtype=torch.int32, device=x.device)
+    counts = torch.empty((B, 3), dtype=torch.int32, device=x.device)
+    centroid = torch.empty((B, 3), dtype=torch.float64, device=x.device)
+    nbytes = L.lib().dh3d_prepare_clouds_workspace(B, N, targetnum)
+    if nbytes == 0:
+        raise ValueError("prepare_clouds: shape B = %d, nraw = %d, targetnum = %d is beyond the kernels" % (B, N, targetnum))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().dh3d_prepare_clouds(B, N, targetnum, L.ptr(x), L.ptr(n), vox, rad, nb_points, int(bool(sortby_dis)),
+                                            L.ptr(points), L.ptr(num_valid), L.ptr(counts), L.ptr(centroid), L.ptr(ws),
+                                            nbytes, L.stream_ptr()), "prepare_clouds")
+    return points, num_valid, counts, centroid
+
+
 KEYPOINT_MAX = 4096  # include/dh3d_hip.h dh3d_keypoint_nms: M limit
 
 

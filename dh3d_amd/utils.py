@@ -91,8 +91,9 @@ def write_to_bin(points, filename):
 
 def get_fixednum_pcd(cloud, targetnum, randsample=True, sortby_dis=True, rng=None):
     """Crop (nearest to the centroid first, then a random permutation) or pad (random re-draws, or far-away
-    dummies) a cloud to exactly `targetnum` points; returns (cloud, number of original points kept).
-    The optional voxel down-sampling / outlier removal of the reference live in open3d and are out of scope."""
+    dummies) a cloud to exactly `targetnum` points; returns (cloud, number of original points kept).  One cloud, on the
+    host, without the voxel down-sampling / outlier removal the reference runs first (open3d): prepare_clouds() below does
+    those two steps and the randsample=False crop / pad for a batch of raw clouds on the device."""
     rng = np.random.default_rng() if rng is None else rng
     cloud = np.asarray(cloud)
     n = cloud.shape[0]
@@ -108,3 +109,33 @@ def get_fixednum_pcd(cloud, targetnum, randsample=True, sortby_dis=True, rng=Non
     else:
         extra = np.full((pad, 3), 100000.0, dtype=np.float32)
     return np.concatenate([cloud, extra], axis=0), n
+
+
+def prepare_clouds(raw, num_raw, targetnum, voxel_size=0.2, radius=1.0, nb_points=4, randsample=False, sortby_dis=True,
+                   check=False):
+    """get_fixednum_pcd(need_downsample=True, randsample=False) of the reference (core/utils.py:87-110, the test-set reader
+    core/datasets.py:85) for B raw clouds of different sizes, on the GPU, no host sync, graph-capturable (HIP:
+    dh3d_prepare_clouds; include/dh3d_hip.h holds the exact semantics, DESIGN.md the points INFERRED from open3d).
+
+    raw [B,Nraw,3] float32 and num_raw [B] int32 on the GPU: cloud b is raw[b, :num_raw[b]], finite rows, Nraw <= 131072.
+      1. voxel grid of `voxel_size` (None: skipped): a voxel's point is the float32 mean of its members; the voxels come in
+         the order of their first member.
+      2. radius outliers (radius None: skipped): a point stays iff more than `nb_points` points, itself included, lie
+         strictly inside `radius`.
+      3. m survivors: m <= targetnum pads with rows of 100000.0 (num_valid = m); m > targetnum keeps the targetnum points
+         nearest the centroid (sortby_dis) or the first targetnum.  The reference then shuffles the kept points with an
+         unseeded random permutation; here they stay in index order, which nothing downstream depends on.
+    Returns (points [B,targetnum,3], num_valid [B] int32, counts [B,3] int32 = raw points / voxels / survivors, centroid
+    [B,3] float64): points and num_valid are what DH3D.forward(num_valid=...), batched_nms and register_clouds take.
+
+    randsample=True (padding by re-drawn points) is not on the device: get_fixednum_pcd does it on the host.  A cloud
+    wider than 2^21 cells on an axis comes back void (num_valid 0, counts [b, 1:] = -1); check=True reads counts back (a
+    host sync, not capturable) and raises ValueError for it."""
+    if randsample:
+        raise NotImplementedError("prepare_clouds pads with far-away dummies only (randsample=False); padding by re-drawn "
+                                  "points is utils.get_fixednum_pcd(randsample=True) on the host")
+    out = pm.prepare_clouds(raw, num_raw, targetnum, voxel_size=voxel_size, radius=radius, nb_points=nb_points,
+                            sortby_dis=sortby_dis)
+    if check and bool((out[2][:, 1] < 0).any()):
+        raise ValueError("prepare_clouds: a cloud spans 2^21 cells or more on an axis (voxel_size / radius too small for it)")
+    return out

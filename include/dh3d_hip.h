@@ -931,6 +931,40 @@ int dh3d_ransac_rigid(const float *anchor_xyz, long long anchor_stride, const fl
                       double confidence, int max_trials, unsigned long long seed, double *Rt, int32_t *valid,
                       uint8_t *inliers, int32_t *num_inliers, int32_t *trials, int32_t *num_corr, void *stream);
 
+/* Preparation of raw clouds (csrc/prepare.hip) -- get_fixednum_pcd(need_downsample = True, randsample = False)
+ * (core/utils.py:87-110: open3d voxel_down_sample, remove_radius_outlier(nb_points, radius), crop to the points nearest the
+ * centroid or pad), batched, for clouds of different sizes, with every size kept on the device.
+ * raw [B, Nraw, 3], num_raw [B]: cloud b is raw[b, :n], n = clamp(num_raw[b], 0, Nraw); its rows must be finite.
+ * STAGE 1, voxel grid (voxel_size > 0; voxel_size == 0 skips it: the stage-1 points are the raw ones).  lo = the per-axis
+ *   minimum of the cloud; origin = double(lo) - voxel_size / 2 (INFERRED); cell = floor((double(p) - origin) / voxel_size)
+ *   per axis, in double, by a true division.  Points of equal cell triples form one voxel; its point is
+ *   float32((sum of double(p)) / count), the sum starting from 0 and running over the members in ascending index
+ *   (INFERRED: point order); the voxels come out in the order of their lowest member index.  (open3d returns float64
+ *   points in its hash map's order; nothing downstream depends on either.)
+ * STAGE 2, radius outliers (radius > 0; radius == 0 skips it), on the stage-1 points: i is kept iff
+ *   #{j : d2(i, j) < r2} > nb_points, j over all points of the cloud, i included (INFERRED: the strict <; INFERRED: more
+ *   than nb_points with the point itself counted); d2 = (dx*dx + dy*dy) + dz*dz in double on the float32 coordinates, no
+ *   contraction; r2 = radius * radius in double.  The kept points stay in order.
+ * STAGE 3, fixed size, m = the number of survivors.  centroid [B, 3] float64 = their mean (a fixed summation tree: within
+ *   m * 2^-52 * max|coordinate| of any other order; zeros when m = 0).  m <= targetnum: the survivors, then rows of 100000.0,
+ *   num_valid = m.  m > targetnum: num_valid = targetnum and the rows are, in their stage-2 order, the targetnum points with
+ *   the smallest (d2 to the centroid, index) (sortby_dis != 0, d2 as in stage 2 with the returned centroid), or the first
+ *   targetnum points (sortby_dis == 0).  The reference then shuffles the kept points with an unseeded permutation; here they
+ *   keep their order.  Padding by re-drawn points (randsample = True) is not on the device.
+ * Outputs: points [B, targetnum, 3], num_valid [B], counts [B, 3] = (n, voxels, survivors), centroid [B, 3]; every element
+ *   is written.  A result does not depend on the batch, on the workspace's content or on the run.
+ * LIMITS: Nraw <= 131072, targetnum <= 2^20, B <= 65535 (else DH3D_ERR_UNSUPPORTED); B, Nraw, targetnum <= 0, NULL pointers,
+ *   a negative or non-finite voxel_size / radius, nb_points < 0, a workspace smaller than dh3d_prepare_clouds_workspace() or
+ *   not 16-byte aligned: DH3D_ERR_INVALID_ARGUMENT.  A cell index of 2^21 or more on an axis (stage 1, or the stage-2 cells
+ *   of edge radius) is beyond the 63-bit keys.  It depends on the data, which the host never reads (no synchronisation), so
+ *   it cannot be this call's status: that cloud comes back void -- num_valid 0, every row 100000.0, counts (n, -1, -1) -- and
+ *   a caller that wants DH3D_ERR_UNSUPPORTED for it tests counts[b][1] < 0 where it next synchronises.
+ * Caller's stream, no allocation, no synchronisation, graph-capturable; the workspace needs no clearing. */
+size_t dh3d_prepare_clouds_workspace(int B, int Nraw, int targetnum); /* bytes; 0 for a shape the call refuses.  Host only. */
+int dh3d_prepare_clouds(int B, int Nraw, int targetnum, const float *raw, const int32_t *num_raw, double voxel_size,
+                        double radius, int nb_points, int sortby_dis, float *points, int32_t *num_valid, int32_t *counts,
+                        double *centroid, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
