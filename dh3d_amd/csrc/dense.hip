@@ -5,6 +5,7 @@
 // kernel on [R, C] rows (R = B*N points): rows staged through LDS once, exact-f32 MFMA GEMM against a
 // fragment-packed weight, and bias + BatchNorm + activation (+ residual) applied in the store.
 #include "mfma_gemm.h"
+#include "interp_walk.h"
 #include "wave_ops.h"
 
 namespace {
@@ -464,11 +465,7 @@ __global__ __launch_bounds__(256) void interp_combine_kernel(const float *__rest
     const int r = min(row0 + (lane & (RPW - 1)), n - 1);
     const long long g = (cloud * n + r) * 3;
     o1 = idx[g] * C; o2 = idx[g + 1] * C; o3 = idx[g + 2] * C;
-    // the inverse-distance weights of core/backbones.py:92-95, same arithmetic as three_interp_fwd_kernel<true>
-    const float r1 = 1.0f / fmaxf(dist[g], 1e-10f), r2 = 1.0f / fmaxf(dist[g + 1], 1e-10f),
-                r3 = 1.0f / fmaxf(dist[g + 2], 1e-10f);
-    const float norm = (r1 + r2) + r3;
-    w1 = r1 / norm; w2 = r2 / norm; w3 = r3 / norm;
+    dh3d_walk::idw3(dist[g], dist[g + 1], dist[g + 2], w1, w2, w3);
   }
   const float *cwb = cw + cloud * m * C + c4;
   const long long base = cloud * n;
@@ -482,7 +479,7 @@ __global__ __launch_bounds__(256) void interp_combine_kernel(const float *__rest
     const float4 a = *reinterpret_cast<const float4 *>(cwb + a1);
     const float4 bq = *reinterpret_cast<const float4 *>(cwb + a2);
     const float4 cq = *reinterpret_cast<const float4 *>(cwb + a3);
-    float4 v;
+    float4 v;  // (not mix3_fma: the default contraction fuses these lines its own way, and the outputs follow it)
     v.x = (a.x * u1 + bq.x * u2) + cq.x * u3; v.y = (a.y * u1 + bq.y * u2) + cq.y * u3;
     v.z = (a.z * u1 + bq.z * u2) + cq.z * u3; v.w = (a.w * u1 + bq.w * u2) + cq.w * u3;
     if (PART) {

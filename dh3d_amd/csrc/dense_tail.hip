@@ -14,6 +14,7 @@
 // leave no room for one).  Per-row interpolation operands (three row offsets, three inverse-distance weights) are
 // computed once per row by lane = row and handed over through LDS.
 #include "bf16x3.h"
+#include "interp_walk.h"
 #include "wave_ops.h"
 
 namespace {
@@ -72,15 +73,8 @@ __global__ __launch_bounds__(kTailWaves * 64) void local_tail_fused_kernel(TailA
   {
     const long long g = (rowc + lr) * 3;
     const int i1 = a.idx[g], i2 = a.idx[g + 1], i3 = a.idx[g + 2];
-    // the inverse-distance weights of core/backbones.py:92-95, same arithmetic as three_interp_fwd_kernel<true>
     float w1, w2, w3;
-    {
-#pragma clang fp contract(off)
-      const float r1 = 1.0f / fmaxf(a.dist[g], 1e-10f), r2 = 1.0f / fmaxf(a.dist[g + 1], 1e-10f),
-                  r3 = 1.0f / fmaxf(a.dist[g + 2], 1e-10f);
-      const float norm = (r1 + r2) + r3;
-      w1 = r1 / norm; w2 = r2 / norm; w3 = r3 / norm;
-    }
+    dh3d_walk::idw3(a.dist[g], a.dist[g + 1], a.dist[g + 2], w1, w2, w3);
     if (half == 0) {
       float *q = s_rw + ((size_t)wave * 32 + lr) * 8;
       *reinterpret_cast<float4 *>(q) = make_float4(__int_as_float(i1 * kTailD), __int_as_float(i2 * kTailD),
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(kTailWaves * 64) void local_tail_fused_kernel(TailA
 #pragma unroll
       for (int cb = 0; cb < kTailNCB; ++cb) {
         // (the same association as interp_combine_kernel: ((a w1 + b w2) + c w3) + partial, then BN with the bias folded)
-        float v = fmaf(g[u][2][cb], w[u][2], fmaf(g[u][1][cb], w[u][1], g[u][0][cb] * w[u][0])) + acc_l[cb][r];
+        float v = dh3d_walk::mix3_fma(g[u][0][cb], g[u][1][cb], g[u][2][cb], w[u][0], w[u][1], w[u][2]) + acc_l[cb][r];
         v = fmaxf(fmaf(v, scc[cb], shc[cb]), 0.f) + acc_s[cb][r];
         y[cb] = v;
         ss = fmaf(v, v, ss);

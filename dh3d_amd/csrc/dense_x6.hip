@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "bf16x3.h"
+#include "interp_walk.h"
 #include "wave_ops.h"
 #include "internal.h"
 
@@ -23,6 +24,9 @@
 
 namespace {
 
+using dh3d_walk::idw3;
+using dh3d_walk::mix3;
+using dh3d_walk::row4;
 
 // W [Kd, Dout] f32 -> packed[((nb*KB + kb)*3 + plane)*64 + lane][8 bf16],
 //   element j = chunk_plane( W[16*kb + 8*(lane>>5) + j][32*nb + (lane&31)] )
@@ -223,38 +227,10 @@ __global__ __launch_bounds__(128 * WC) void mlp_head_x6_kernel(const float *__re
 // and staging as the head above; NC = 32-column blocks per wave (1: Dout = 128, 2: Dout = 256).  The finished
 // 128 x Dout tile goes through LDS (the stage buffers are dead by then) so that every lane stores 16 bytes of
 // a full output row, residual added on the way.
-// The interpolation arithmetic must round exactly like three_interp_fwd_kernel<IDW> (pointnet2.hip is compiled
-// without contraction): no fused multiply-adds in these two helpers.
-#pragma clang fp contract(off)
-__device__ __forceinline__ void idw_weights(float d1, float d2, float d3, float &w1, float &w2, float &w3) {
-  const float r1 = 1.0f / fmaxf(d1, 1e-10f), r2 = 1.0f / fmaxf(d2, 1e-10f), r3 = 1.0f / fmaxf(d3, 1e-10f);
-  const float norm = (r1 + r2) + r3;
-  w1 = r1 / norm; w2 = r2 / norm; w3 = r3 / norm;
-}
-__device__ __forceinline__ float4 idw_mix(const float4 a, const float4 b, const float4 c, float w1, float w2, float w3) {
-  float4 r;
-  r.x = (a.x * w1 + b.x * w2) + c.x * w3;
-  r.y = (a.y * w1 + b.y * w2) + c.y * w3;
-  r.z = (a.z * w1 + b.z * w2) + c.z * w3;
-  r.w = (a.w * w1 + b.w * w2) + c.w * w3;
-  return r;
-}
-#pragma clang fp contract(fast)
-// the same mix with fused multiply-adds (3 instructions per channel instead of 5): for the COMMUTED walks, whose
-// arithmetic is not the reference's association anyway (the interpolation there runs on rows a linear layer has
-// already been applied to)
-__device__ __forceinline__ float4 idw_mix_fma(const float4 a, const float4 b, const float4 c, float w1, float w2, float w3) {
-  float4 r;
-  r.x = fmaf(c.x, w3, fmaf(b.x, w2, a.x * w1));
-  r.y = fmaf(c.y, w3, fmaf(b.y, w2, a.y * w1));
-  r.z = fmaf(c.z, w3, fmaf(b.z, w2, a.z * w1));
-  r.w = fmaf(c.w, w3, fmaf(b.w, w2, a.w * w1));
-  return r;
-}
 
 // Up-sampling source for the x1 half (three_interpolate with inverse-distance weights, core/backbones.py:91-95,
-// fused into the A staging): x1[r, :] = sum_t w[r,t] * points[cloud(r), idx[r,t], :], exactly the arithmetic of
-// three_interp_fwd_kernel<IDW> (unfused, same association), so the fused and the two-kernel paths agree bit for bit.
+// fused into the A staging): x1[r, :] = sum_t w[r,t] * points[cloud(r), idx[r,t], :], with the idw3 / mix3 of
+// three_interp_fwd_kernel<IDW> (interp_walk.h), so the fused and the two-kernel paths agree bit for bit.
 struct UpsampleSrc {
   const float *points;   // [B, m, C1]   (null: x1 is read directly)
   const int32_t *idx;    // [R, 3]
@@ -314,7 +290,7 @@ __global__ __launch_bounds__(512) void linear_x6_kernel(const float *__restrict_
   if (up.points) {
     const long long bi = arow / up.n;
     const int i1 = up.idx[arow * 3], i2 = up.idx[arow * 3 + 1], i3 = up.idx[arow * 3 + 2];
-    idw_weights(up.dist[arow * 3], up.dist[arow * 3 + 1], up.dist[arow * 3 + 2], w1, w2, w3);
+    idw3(up.dist[arow * 3], up.dist[arow * 3 + 1], up.dist[arow * 3 + 2], w1, w2, w3);
     ip1 = up.points + (bi * up.m + i1) * C1;
     ip2 = up.points + (bi * up.m + i2) * C1;
     ip3 = up.points + (bi * up.m + i3) * C1;
@@ -324,8 +300,8 @@ __global__ __launch_bounds__(512) void linear_x6_kernel(const float *__restrict_
     if (up.points && k0 < C1) {  // uniform per chunk
       const float4 *a = reinterpret_cast<const float4 *>(ip1 + k0), *b = reinterpret_cast<const float4 *>(ip2 + k0),
                    *c = reinterpret_cast<const float4 *>(ip3 + k0);
-      pa[0] = idw_mix(a[0], b[0], c[0], w1, w2, w3);
-      pa[1] = idw_mix(a[1], b[1], c[1], w1, w2, w3);
+      pa[0] = mix3(a[0], b[0], c[0], w1, w2, w3);
+      pa[1] = mix3(a[1], b[1], c[1], w1, w2, w3);
     } else {
       const float *src = k0 < C1 ? x1 + arow * C1 + k0
                          : (!SC || k0 < C1 + C2) ? x2 + arow * C2 + (k0 - C1)
@@ -625,7 +601,7 @@ __global__ __launch_bounds__(256) void interp_head_kernel(const float *__restric
     const float *p2 = H + ((long long)bi * m + i2) * 256 + lane * 4;
     const float *p3 = H + ((long long)bi * m + i3) * 256 + lane * 4;
     float w1, w2, w3;
-    idw_weights(d1, d2, d3, w1, w2, w3);
+    idw3(d1, d2, d3, w1, w2, w3);
     float4 a[MAXS], b[MAXS], c[MAXS];
 #pragma unroll
     for (int j = 0; j < MAXS; ++j)
@@ -642,7 +618,7 @@ __global__ __launch_bounds__(256) void interp_head_kernel(const float *__restric
 #pragma unroll
     for (int j = 0; j < MAXS; ++j)
       if (j < NS) {
-        const float4 v = idw_mix(a[j], b[j], c[j], w1, w2, w3);
+        const float4 v = mix3(a[j], b[j], c[j], w1, w2, w3);
         z = fmaf(dh3d_act((v.x + pb[j].x) * sc[j].x + sh[j].x, ep.act), wf[j].x, z);
         z = fmaf(dh3d_act((v.y + pb[j].y) * sc[j].y + sh[j].y, ep.act), wf[j].y, z);
         z = fmaf(dh3d_act((v.z + pb[j].z) * sc[j].z + sh[j].z, ep.act), wf[j].z, z);
@@ -820,7 +796,8 @@ constexpr int kIHW = 8;             // waves per workgroup (two workgroups per C
 constexpr int kIHT = kIHW * 64;      // threads
 constexpr int kIHPW = kIHP / kIHW;   // points per wave
 constexpr int kIHLst = kIHCap + 1 + 3 * kIHP;  // slot-major reference lists: [kIHCap + 1] offsets, [3 * kIHP] entries (point * 4 + t)
-constexpr int kIHPlan = (kIHP * 4 * 2 + kIHP + 32 + 33 + kIHCap + kIHLst + 3) / 4 * 4;  // dwords of the plan image (1732)
+constexpr int kIHPlan = (kIHP * 4 * 2 + 32 + 33 + kIHCap + kIHLst + 3) / 4 * 4;  // dwords of the plan image (1604)
+static_assert(kIHP == dh3d_walk::kP, "the walks share build_slot_table");
 constexpr int kIHTab = kIHPlan + (kIHP /*s_z*/ + kIHP /*s_inv*/ + 64 + 3) / 4 * 4;  // floats of tables
 
 // VLAD (the global descriptor path): the same walk continues into NetVLAD's soft assignment
@@ -834,14 +811,7 @@ constexpr int kIHTab = kIHPlan + (kIHP /*s_z*/ + kIHP /*s_inv*/ + 64 + 3) / 4 * 
 // the caller finishes with a [m x 64]^T [m x 256] GEMM per cloud on the COARSE rows.  Replaces three_interpolate (134
 // MB written and read back at cfg 3) and the per-point part of netvlad_assign_accumulate; the f32 atomics make the
 // global descriptor reproducible to ~1e-7 instead of bit for bit.
-// a staged row (slot >= 0) from LDS, or -- only in blocks that exceeded the slot capacity (OVF) -- row -1-slot from
-// global memory.  The common case has no branch at all: a taken scalar branch costs ~35 cycles and there would be
-// three per point and slice.
-template <bool OVF>
-__device__ __forceinline__ float4 ih_row4(const float *s_rows, const float *gbase, int slot, int lane, int rs = 256) {
-  if (OVF && slot < 0) return *reinterpret_cast<const float4 *>(gbase + (size_t)(-1 - slot) * rs + lane * 4);
-  return *reinterpret_cast<const float4 *>(s_rows + (size_t)slot * 256 + lane * 4);
-}
+// (The rows come through row4<OVF> of interp_walk.h: staged in LDS, or -- overflow blocks only -- from global memory.)
 
 // Row requests go through buffer loads: a scalar resource (base of the slice) + ONE 32-bit byte offset per row in a VGPR.
 // (As flat 64-bit addresses the eight row offsets took sixteen registers and were spilled around the slice loop.)
@@ -856,14 +826,14 @@ template <bool OVF>
 __device__ __forceinline__ int ih_uniform(int v) { return OVF ? __builtin_amdgcn_readfirstlane(v) : v; }
 
 // The same row as two packed-f32 pairs, and the inverse-distance mix on them: v_pk_mul_f32 / v_pk_fma_f32 do two lanes'
-// worth of idw_mix_fma per issue slot with the same association (bit-equal results).  Only for phases WITHOUT matrix
+// worth of mix3_fma per issue slot with the same association (bit-equal results).  Only for phases WITHOUT matrix
 // work beside them: packed f32 occupies the matrix pipe on gfx950.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct Row4 { f32x2 lo, hi; };
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 template <bool OVF>
 __device__ __forceinline__ Row4 ih_row4p(const float *s_rows, const float *gbase, int slot, int lane, int rs = 256) {
-  const float4 v = ih_row4<OVF>(s_rows, gbase, slot, lane, rs);
+  const float4 v = row4<OVF>(s_rows, gbase, slot, lane, rs);
   return Row4{f32x2{v.x, v.y}, f32x2{v.z, v.w}};
 }
 __device__ __forceinline__ Row4 idw_mix_pk(const Row4 a, const Row4 b, const Row4 c, float w1, float w2, float w3) {
@@ -871,121 +841,67 @@ __device__ __forceinline__ Row4 idw_mix_pk(const Row4 a, const Row4 b, const Row
   return Row4{pk_fma(c.lo, W3, pk_fma(b.lo, W2, a.lo * W1)), pk_fma(c.hi, W3, pk_fma(b.hi, W2, a.hi * W1))};
 }
 
-// The block's SLOT TABLE (first kIHPlan dwords of the workgroup's LDS: s_slot | s_w | s_orig | s_bits | s_pre | s_row | lists), built
-// from the three_nn result: bitmap of the coarse rows the block's 128 points touch -> prefix popcounts -> slot = rank of the
-// row.  Three dependent global round trips (order -> idx / dist -> ...) and five barriers: 17 us of the walk when built in
-// the walk's own launch (round 5) -- round 6: walk_plan_kernel builds it once behind three_nn, off the
-// critical chain, and the walk copies the image in (dh3d_walk_plan / dh3d_global_walk_planned_fwd).
-// LISTS (the plan kernel): also the references to every staged row, slot-major -- s_loff[slot] .. s_loff[slot + 1] index
-// entries `point * 4 + t` of s_lst (within a list in (point, t) order, ranked from a per-slot bitmap: sorting each list by
-// one thread cost the plan 68 us) -- for the NetVLAD scatter of the walk.
-template <bool LISTS>
-__device__ __forceinline__ void ih_build_table(float *s_ih, const int32_t *__restrict__ idx, const float *__restrict__ dist,
-                                               const float4 *__restrict__ order, int bi, int blk, int n, int m) {
-  int *s_slot = reinterpret_cast<int *>(s_ih);
-  float *s_w = reinterpret_cast<float *>(s_slot + kIHP * 4);
-  int *s_orig = reinterpret_cast<int *>(s_w + kIHP * 4);
-  unsigned *s_bits = reinterpret_cast<unsigned *>(s_orig + kIHP);
-  int *s_pre = reinterpret_cast<int *>(s_bits + 32);
-  int *s_row = s_pre + 33;
+// The block's SLOT TABLE (first kIHPlan dwords of the workgroup's LDS: s_slot | s_w | s_bits | s_pre | s_row | lists) is the one
+// of the training walks (dh3d_walk::build_slot_table, interp_walk.h; a point's original index is 4th slot word - 1, the
+// per-point scalar stays 0).  Three dependent global round trips (order -> idx / dist -> ...) and five barriers: 17 us of
+// the walk when built in the walk's own launch (round 5) -- round 6: walk_plan_kernel builds it once behind three_nn,
+// off the critical chain, and the walk copies the image in (dh3d_walk_plan / dh3d_global_walk_planned_fwd).
+__device__ __forceinline__ dh3d_walk::SlotTable ih_table(float *s_ih) {
+  int *slot = reinterpret_cast<int *>(s_ih);                    // [kIHP][4] slot (or -1 - coarse row), .w = 1 + original index (0: none)
+  float *w = reinterpret_cast<float *>(slot + kIHP * 4);        // [kIHP][4] interpolation weights (.w = 0)
+  unsigned *bits = reinterpret_cast<unsigned *>(w + kIHP * 4);  // [32] bitmap over the cloud's coarse rows
+  int *pre = reinterpret_cast<int *>(bits + 32);                // [33] popcount prefix
+  return {slot, w, bits, pre, pre + 33};                        // [kIHCap] slot -> coarse row; the lists behind it
+}
+
+// The plan's REFERENCE LISTS behind a built table: the references to every staged row, slot-major -- s_loff[slot] ..
+// s_loff[slot + 1] index entries `point * 4 + t` of s_lst (within a list in (point, t) order, ranked from a per-slot
+// bitmap: sorting each list by one thread cost the plan 68 us) -- for the NetVLAD scatter of the walk.
+__device__ __forceinline__ void ih_build_lists(const int *s_slot, int *s_loff) {
+  int *s_lst = s_loff + kIHCap + 1;
   const int tid = threadIdx.x;
-  if (tid < 32) s_bits[tid] = 0u;
+  // a list holds its references in (point, t) order, not in the order the LDS atomics land in (which varies from run to
+  // run): each slot's references are a bitmap over q = point * 3 + t, and an entry's place is the number of bits below it
+  constexpr int kQW = 3 * kIHP / 32;
+  __shared__ int s_cnt[kIHCap];
+  __shared__ unsigned s_ref[kIHCap * kQW];
+  for (int i = tid; i < kIHCap * kQW; i += kIHT) s_ref[i] = 0u;
+  if (tid < kIHCap) s_cnt[tid] = 0;
   __syncthreads();
-  // ---- the block's points, their neighbours and weights; mark the coarse rows they touch
-  int my_i[3] = {0, 0, 0};
-  if (tid < kIHP) {
-    const int q = blk * kIHP + tid;
-    int orig = -1;
-    if (q < n) {
-      orig = order ? __float_as_int(order[(size_t)bi * n + q].w) : q;
-      const long long r = (long long)bi * n + orig;
-      float w1, w2, w3;
-      idw_weights(dist[r * 3], dist[r * 3 + 1], dist[r * 3 + 2], w1, w2, w3);
-      *reinterpret_cast<float4 *>(s_w + tid * 4) = make_float4(w1, w2, w3, 0.f);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        my_i[t] = idx[r * 3 + t];
-        atomicOr(&s_bits[my_i[t] >> 5], 1u << (my_i[t] & 31));
-      }
-    }
-    s_orig[tid] = orig;
-    if (orig < 0) {  // padding point of the last block: harmless reads of slot 0 with zero weights
-      *reinterpret_cast<float4 *>(s_w + tid * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<int4 *>(s_slot + tid * 4) = make_int4(0, 0, 0, 0);
-    }
-  }
-  __syncthreads();
-  if (tid < 64) {  // exclusive prefix of the 32 word popcounts (one wave, shuffle scan)
-    int c = tid < 32 ? __popc(s_bits[tid]) : 0, v = c;
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-      const int o = __shfl_up(v, off, 64);
-      if ((tid & 63) >= off) v += o;
-    }
-    if (tid < 32) s_pre[tid] = v - c;
-    if (tid == 31) s_pre[32] = v;
-  }
-  __syncthreads();
-  if (tid < kIHP && s_orig[tid] >= 0) {
+  int sl3[3] = {-1, -1, -1};
+  if (tid < kIHP && s_slot[tid * 4 + 3] != 0) {  // a live point
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
-      const int j = my_i[t];
-      const int slot = s_pre[j >> 5] + __popc(s_bits[j >> 5] & ((1u << (j & 31)) - 1u));
-      s_slot[tid * 4 + t] = slot < kIHCap ? slot : -1 - j;
-    }
-  }
-  for (int j = tid; j < m; j += kIHT) {  // slot -> coarse row
-    if ((s_bits[j >> 5] >> (j & 31)) & 1u) {
-      const int slot = s_pre[j >> 5] + __popc(s_bits[j >> 5] & ((1u << (j & 31)) - 1u));
-      if (slot < kIHCap) s_row[slot] = j;
-    }
-  }
-  if (LISTS) {
-    int *s_loff = s_row + kIHCap, *s_lst = s_loff + kIHCap + 1;
-    // a list holds its references in (point, t) order, not in the order the LDS atomics land in (which varies from run to
-    // run): each slot's references are a bitmap over q = point * 3 + t, and an entry's place is the number of bits below it
-    constexpr int kQW = 3 * kIHP / 32;
-    __shared__ int s_cnt[kIHCap];
-    __shared__ unsigned s_ref[kIHCap * kQW];
-    for (int i = tid; i < kIHCap * kQW; i += kIHT) s_ref[i] = 0u;
-    if (tid < kIHCap) s_cnt[tid] = 0;
-    __syncthreads();
-    int sl3[3] = {-1, -1, -1};
-    if (tid < kIHP && s_orig[tid] >= 0) {
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        sl3[t] = s_slot[tid * 4 + t];
-        if (sl3[t] >= 0) {
-          const int q = tid * 3 + t;
-          atomicAdd(&s_cnt[sl3[t]], 1);
-          atomicOr(&s_ref[sl3[t] * kQW + (q >> 5)], 1u << (q & 31));
-        }
-      }
-    }
-    __syncthreads();
-    if (tid < 64) {  // exclusive prefix of the kIHCap = 64 counts
-      const int c = s_cnt[tid];
-      int v = c;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(v, off, 64);
-        if (tid >= off) v += o;
-      }
-      s_loff[tid] = v - c;
-      if (tid == 63) s_loff[64] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
+      sl3[t] = s_slot[tid * 4 + t];
       if (sl3[t] >= 0) {
         const int q = tid * 3 + t;
-        const unsigned *row = s_ref + sl3[t] * kQW;
-        int r = __popc(row[q >> 5] & ((1u << (q & 31)) - 1u));
-        for (int w = 0; w < (q >> 5); ++w) r += __popc(row[w]);
-        s_lst[s_loff[sl3[t]] + r] = tid * 4 + t;
+        atomicAdd(&s_cnt[sl3[t]], 1);
+        atomicOr(&s_ref[sl3[t] * kQW + (q >> 5)], 1u << (q & 31));
       }
-    __syncthreads();
+    }
   }
+  __syncthreads();
+  if (tid < 64) {  // exclusive prefix of the kIHCap = 64 counts
+    const int c = s_cnt[tid];
+    int v = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(v, off, 64);
+      if (tid >= off) v += o;
+    }
+    s_loff[tid] = v - c;
+    if (tid == 63) s_loff[64] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+    if (sl3[t] >= 0) {
+      const int q = tid * 3 + t;
+      const unsigned *row = s_ref + sl3[t] * kQW;
+      int r = __popc(row[q >> 5] & ((1u << (q & 31)) - 1u));
+      for (int w = 0; w < (q >> 5); ++w) r += __popc(row[w]);
+      s_lst[s_loff[sl3[t]] + r] = tid * 4 + t;
+    }
   __syncthreads();
 }
 
@@ -1007,11 +923,13 @@ __global__ __launch_bounds__(kIHT) void walk_plan_kernel(const int32_t *__restri
                                                          int *__restrict__ plan) {
   __shared__ __attribute__((aligned(16))) float s_tab[kIHPlan];
   const int bi = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
-  // the table leaves parts unwritten (slot lists past their total, rows past the slot count, each point's 4th slot, the
-  // padding): zeroed, the plan is a function of its inputs alone and the walk's reads past a run's end (s_lst entries of
-  // a chunk's idle lanes -> s_w / s_inv) stay on entry 0.  (ih_build_table's first barrier orders these stores.)
+  // the table leaves parts unwritten (slot lists past their total, rows past the slot count, the padding): zeroed, the
+  // plan is a function of its inputs alone and the walk's reads past a run's end (s_lst entries of a chunk's idle
+  // lanes -> s_w / s_inv) stay on entry 0.  (build_slot_table's first barrier orders these stores.)
   for (int e = tid; e < kIHPlan; e += kIHT) reinterpret_cast<int *>(s_tab)[e] = 0;
-  ih_build_table<true>(s_tab, idx, dist, order, bi, blk, n, m);
+  const dh3d_walk::SlotTable tab = ih_table(s_tab);
+  dh3d_walk::build_slot_table<kIHCap, kIHT>(tab, idx, dist, nullptr, order, bi, blk, n, m, [](long long, int) { return 0.f; });
+  ih_build_lists(tab.slot, tab.row + kIHCap);
   int4 *dst = reinterpret_cast<int4 *>(plan) + (size_t)(bi * nblk + blk) * (kIHPlan / 4);
   for (int e = tid; e < kIHPlan / 4; e += kIHT) dst[e] = reinterpret_cast<const int4 *>(s_tab)[e];
 }
@@ -1026,12 +944,9 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
   extern __shared__ __attribute__((aligned(16))) float s_ih[];
   // the small tables FIRST: their addresses fit the 16-bit offset field of the ds instructions (behind 64 KB of rows every
   // table read cost a v_add), the rows behind them
-  int *s_slot = reinterpret_cast<int *>(s_ih);                    // [kIHP][4] slot (or -1 - coarse row)
-  float *s_w = reinterpret_cast<float *>(s_slot + kIHP * 4);      // [kIHP][4] interpolation weights
-  int *s_orig = reinterpret_cast<int *>(s_w + kIHP * 4);          // [kIHP] original index of the fine point (-1: none)
-  unsigned *s_bits = reinterpret_cast<unsigned *>(s_orig + kIHP); // [32] bitmap over the cloud's coarse rows
-  int *s_pre = reinterpret_cast<int *>(s_bits + 32);              // [33] popcount prefix
-  int *s_row = s_pre + 33;                                        // [kIHCap] slot -> coarse row
+  const dh3d_walk::SlotTable tab = ih_table(s_ih);
+  int *s_slot = tab.slot, *s_pre = tab.pre, *s_row = tab.row;
+  float *s_w = tab.w;
   int *s_loff = s_row + kIHCap;                                   // [kIHCap + 1] (planned walk only) offsets of the slots' reference lists
   int *s_lst = s_loff + kIHCap + 1;                               // [3 kIHP] entries point * 4 + t, slot-major
   float *s_z = s_ih + kIHPlan;                                    // [kIHP] logits, then s_inv [kIHP] and s_asum [64]
@@ -1046,7 +961,7 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
     for (int e = tid; e < kIHPlan / 4; e += kIHT) reinterpret_cast<int4 *>(s_ih)[e] = src[e];
     __syncthreads();
   } else {
-    ih_build_table<false>(s_ih, idx, dist, order, bi, blk, n, m);
+    dh3d_walk::build_slot_table<kIHCap, kIHT>(tab, idx, dist, nullptr, order, bi, blk, n, m, [](long long, int) { return 0.f; });
   }
   const int nd = min(s_pre[32], kIHCap);
   const bool overflow = s_pre[32] > kIHCap;  // block-uniform: some rows are not staged
@@ -1153,8 +1068,9 @@ __global__ __launch_bounds__(kIHT, 2 * kIHW / 4) void interp_head_lds_kernel(con
   }
   if (tid < kIHP) {
     const float bias = b_fc + (vt.b_dev ? vt.b_dev[0] : 0.f);
-    const float a = s_orig[tid] >= 0 ? 1.f / (1.f + expf(-(s_z[tid] + bias))) : 0.f;  // padding points weigh nothing
-    if (s_orig[tid] >= 0 && att) att[(size_t)bi * n + s_orig[tid]] = a;
+    const int orig = s_slot[tid * 4 + 3] - 1;
+    const float a = orig >= 0 ? 1.f / (1.f + expf(-(s_z[tid] + bias))) : 0.f;  // padding points weigh nothing
+    if (orig >= 0 && att) att[(size_t)bi * n + orig] = a;
     if (VLAD) s_z[tid] = a;
   }
   if (!VLAD) return;

@@ -31,9 +31,9 @@
 
 namespace {
 
-using dh3d_walk::idw3;
 using dh3d_walk::kP;
 using dh3d_walk::mix3;
+using dh3d_walk::row4;
 constexpr int kCap = 64;   // staged coarse rows per slice (a 128-point block touches 46 on average, 62 at most)
 constexpr int kPW = kP / 4;
 // MODE 2 keeps a chunk of dh rows next to the staged rows; 56 slots + 16 points x 272 floats leave room for two
@@ -41,12 +41,6 @@ constexpr int kPW = kP / 4;
 constexpr int kCap2 = 56;  // staged rows in MODE 2 (blocks touching more take the overflow path for the excess)
 constexpr int kCH = 16;    // points per dh chunk
 constexpr int kLDH = 272;  // row stride of the dh chunk (floats)
-
-template <bool OVF>
-__device__ __forceinline__ float4 row4(const float *s_rows, const float *gbase, int slot, int lane, int rs) {
-  if (OVF && slot < 0) return *reinterpret_cast<const float4 *>(gbase + (size_t)(-1 - slot) * rs + lane * 4);
-  return *reinterpret_cast<const float4 *>(s_rows + (size_t)slot * 256 + lane * 4);
-}
 
 // The parked rows live in ONE 64-float vector value (an SSA value: a float4 array of the same size was kept in scratch
 // -- stored right behind every load and reloaded -- whatever the control flow around it looked like).

@@ -1,6 +1,7 @@
-// The walk over the fine points that the training kernels of interp_train.hip and netvlad_train.hip share (gfx950).
+// The up-sampling arithmetic of every kernel that interpolates, and the walk over the fine points that the inference
+// walk of dense_x6.hip and the training kernels of interp_train.hip and netvlad_train.hip share (gfx950).
 //
-// A workgroup of 256 threads owns 128 consecutive points of one cloud in Morton order (records of dh3d_spatial_sort).
+// A workgroup owns 128 consecutive points of one cloud in Morton order (records of dh3d_spatial_sort).
 // Every point mixes three coarse rows (three_nn indices, inverse-distance weights, core/backbones.py:89-100); a block of
 // spatially coherent points touches few distinct coarse rows (46 on average at N/8 samples, 62 at most), so the block
 // builds a SLOT TABLE: a bitmap of the coarse rows it touches -> prefix sums -> slot = rank of the row among them.  Rows
@@ -14,22 +15,41 @@ namespace dh3d_walk {
 
 constexpr int kP = 128;  // fine points per workgroup
 
-// must round like three_interp_fwd_kernel<IDW> / interp_head_lds_kernel (no contraction)
-#pragma clang fp contract(off)
+// ---- the interpolation arithmetic: ONE definition for every up-sampling kernel of the library, whatever contraction
+// mode its object is built with.  Each helper scopes the contraction inside its own body; including this header leaves
+// the contraction mode of the including file as it was (the exact objects of the Makefile include it too).
+
+// inverse-distance weights of three_interpolate (core/backbones.py:92-95): d = max(dist, 1e-10), w = (1/d) / sum (1/d)
 __device__ __forceinline__ void idw3(float d1, float d2, float d3, float &w1, float &w2, float &w3) {
+#pragma clang fp contract(off)
   const float r1 = 1.0f / fmaxf(d1, 1e-10f), r2 = 1.0f / fmaxf(d2, 1e-10f), r3 = 1.0f / fmaxf(d3, 1e-10f);
   const float norm = (r1 + r2) + r3;
   w1 = r1 / norm; w2 = r2 / norm; w3 = r3 / norm;
 }
-__device__ __forceinline__ float4 mix3(const float4 a, const float4 b, const float4 c, float w1, float w2, float w3) {
-  float4 r;
-  r.x = (a.x * w1 + b.x * w2) + c.x * w3;
-  r.y = (a.y * w1 + b.y * w2) + c.y * w3;
-  r.z = (a.z * w1 + b.z * w2) + c.z * w3;
-  r.w = (a.w * w1 + b.w * w2) + c.w * w3;
-  return r;
+// the three-row mix in the reference's arithmetic: five roundings per channel, no fused multiply-add
+__device__ __forceinline__ float mix3(float a, float b, float c, float w1, float w2, float w3) {
+#pragma clang fp contract(off)
+  return (a * w1 + b * w2) + c * w3;
 }
-#pragma clang fp contract(fast)
+__device__ __forceinline__ float4 mix3(const float4 a, const float4 b, const float4 c, float w1, float w2, float w3) {
+  return make_float4(mix3(a.x, b.x, c.x, w1, w2, w3), mix3(a.y, b.y, c.y, w1, w2, w3),
+                     mix3(a.z, b.z, c.z, w1, w2, w3), mix3(a.w, b.w, c.w, w1, w2, w3));
+}
+// the same mix as an explicit fma chain (3 instructions per channel instead of 5): for the COMMUTED walks, whose
+// arithmetic is not the reference's association anyway (the interpolation there runs on rows a linear layer has
+// already been applied to)
+__device__ __forceinline__ float mix3_fma(float a, float b, float c, float w1, float w2, float w3) {
+  return fmaf(c, w3, fmaf(b, w2, a * w1));
+}
+
+// a staged row (slot >= 0) from LDS, or -- only in blocks that exceeded the slot capacity (OVF) -- row -1-slot from
+// global memory (row stride rs).  The common case has no branch at all: a taken scalar branch costs ~35 cycles and
+// there would be three per point and slice.
+template <bool OVF>
+__device__ __forceinline__ float4 row4(const float *s_rows, const float *gbase, int slot, int lane, int rs = 256) {
+  if (OVF && slot < 0) return *reinterpret_cast<const float4 *>(gbase + (size_t)(-1 - slot) * rs + lane * 4);
+  return *reinterpret_cast<const float4 *>(s_rows + (size_t)slot * 256 + lane * 4);
+}
 
 struct SlotTable {
   int *slot;       // [kP][4]: slots (or -1 - coarse row) of the three neighbours, .w = 1 + original index (0: none)
@@ -39,11 +59,12 @@ struct SlotTable {
   int *row;        // [CAP]: slot -> coarse row
 };
 
-// Builds the table for block `blk` of cloud `bi` (all 256 threads; contains barriers).  idx [B,n,3]; weights from
-// `weight` [B,n,3] if given, else inverse-distance weights of `dist` [B,n,3]; order [B,n] spatial_sort records or null
-// (index order); scalar(r, tid) -> the per-point scalar of the point with global row r (called by thread tid < kP for
-// live points only).  Returns the number of distinct rows (nd = min(that, CAP) are staged; more: overflow).
-template <int CAP, typename Scalar>
+// Builds the table for block `blk` of cloud `bi` (all NT threads of the workgroup; contains barriers).  idx [B,n,3];
+// weights from `weight` [B,n,3] if given, else inverse-distance weights of `dist` [B,n,3]; order [B,n] spatial_sort
+// records or null (index order); scalar(r, tid) -> the per-point scalar of the point with global row r (called by
+// thread tid < kP for live points only).  Returns the number of distinct rows (nd = min(that, CAP) are staged; more:
+// overflow).
+template <int CAP, int NT = 256, typename Scalar>
 __device__ __forceinline__ int build_slot_table(const SlotTable &T, const int32_t *__restrict__ idx,
                                                 const float *__restrict__ dist, const float *__restrict__ weight,
                                                 const float4 *__restrict__ order, int bi, int blk, int n, int m,
@@ -96,7 +117,7 @@ __device__ __forceinline__ int build_slot_table(const SlotTable &T, const int32_
     }
     *reinterpret_cast<int4 *>(T.slot + tid * 4) = make_int4(sl3[0], sl3[1], sl3[2], 1 + my_orig);
   }
-  for (int j = tid; j < m; j += 256) {
+  for (int j = tid; j < m; j += NT) {  // slot -> coarse row
     if ((T.bits[j >> 5] >> (j & 31)) & 1u) {
       const int slot = T.pre[j >> 5] + __popc(T.bits[j >> 5] & ((1u << (j & 31)) - 1u));
       if (slot < CAP) T.row[slot] = j;

@@ -9,6 +9,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "interp_walk.h"
 #include "wave_ops.h"
 
 #pragma clang fp contract(off)
@@ -477,12 +478,7 @@ __global__ __launch_bounds__(kBlock) void three_interp_fwd_kernel(
     const long long bi = row / n;
     const int i1 = idx[row * 3], i2 = idx[row * 3 + 1], i3 = idx[row * 3 + 2];
     float w1 = wd[row * 3], w2 = wd[row * 3 + 1], w3 = wd[row * 3 + 2];
-    if (IDW) {
-      const float r1 = 1.0f / fmaxf(w1, 1e-10f), r2 = 1.0f / fmaxf(w2, 1e-10f),
-                  r3 = 1.0f / fmaxf(w3, 1e-10f);
-      const float norm = (r1 + r2) + r3;
-      w1 = r1 / norm; w2 = r2 / norm; w3 = r3 / norm;
-    }
+    if (IDW) dh3d_walk::idw3(w1, w2, w3, w1, w2, w3);
     const float *p1 = points + (bi * m + i1) * c + l;
     const float *p2 = points + (bi * m + i2) * c + l;
     const float *p3 = points + (bi * m + i3) * c + l;
@@ -491,14 +487,9 @@ __global__ __launch_bounds__(kBlock) void three_interp_fwd_kernel(
       const float4 a = *reinterpret_cast<const float4 *>(p1);
       const float4 bq = *reinterpret_cast<const float4 *>(p2);
       const float4 cq = *reinterpret_cast<const float4 *>(p3);
-      float4 r;
-      r.x = (a.x * w1 + bq.x * w2) + cq.x * w3;
-      r.y = (a.y * w1 + bq.y * w2) + cq.y * w3;
-      r.z = (a.z * w1 + bq.z * w2) + cq.z * w3;
-      r.w = (a.w * w1 + bq.w * w2) + cq.w * w3;
-      *reinterpret_cast<float4 *>(o) = r;
+      *reinterpret_cast<float4 *>(o) = dh3d_walk::mix3(a, bq, cq, w1, w2, w3);
     } else {
-      o[0] = (p1[0] * w1 + p2[0] * w2) + p3[0] * w3;
+      o[0] = dh3d_walk::mix3(p1[0], p2[0], p3[0], w1, w2, w3);
     }
   }
 }
@@ -597,10 +588,14 @@ DH3D_API int dh3d_three_interpolate_idw_fwd(int b, int m, int c, int n, const fl
                                             const int32_t *idx, const float *dist, float *out,
                                             void *stream) {
   DH3D_REQUIRE(points && idx && dist && out && b > 0 && m > 0 && c > 0 && n > 0);
-  DH3D_SUPPORTED(c % 4 == 0);
   const long long rows = (long long)b * n;
-  hipLaunchKernelGGL((three_interp_fwd_kernel<true, 4>), dim3(flat_grid(rows * (c / 4))), dim3(kBlock), 0,
-                     (hipStream_t)stream, rows, n, m, c, points, idx, dist, out);
+  hipStream_t s = (hipStream_t)stream;
+  if (c % 4 == 0)
+    hipLaunchKernelGGL((three_interp_fwd_kernel<true, 4>), dim3(flat_grid(rows * (c / 4))), dim3(kBlock), 0, s,
+                       rows, n, m, c, points, idx, dist, out);
+  else
+    hipLaunchKernelGGL((three_interp_fwd_kernel<true, 1>), dim3(flat_grid(rows * c)), dim3(kBlock), 0, s,
+                       rows, n, m, c, points, idx, dist, out);
   return dh3d_launch_status();
 }
 

@@ -14,6 +14,7 @@
 // the saved pre-activation in place with its gradient.
 // Rows of padding clouds (sharded batches, dh3d_amd/dist.py) are excluded through a per-cloud mask.
 #include "common.h"
+#include "interp_walk.h"
 
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
@@ -395,10 +396,7 @@ __global__ __launch_bounds__(256) void idw_weights_kernel(const float *__restric
                                                          float *__restrict__ w) {
   const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
   if (r >= R) return;
-  const float r0 = 1.0f / fmaxf(dist[3 * r], 1e-10f), r1 = 1.0f / fmaxf(dist[3 * r + 1], 1e-10f),
-              r2 = 1.0f / fmaxf(dist[3 * r + 2], 1e-10f);
-  const float tot = (r0 + r1) + r2;
-  w[3 * r] = r0 / tot; w[3 * r + 1] = r1 / tot; w[3 * r + 2] = r2 / tot;
+  dh3d_walk::idw3(dist[3 * r], dist[3 * r + 1], dist[3 * r + 2], w[3 * r], w[3 * r + 1], w[3 * r + 2]);
 }
 
 // context gating (core/backbones.py:271-277): y = v * sigmoid(g); backward dv = dy * sig, dg = dy * v * sig * (1 - sig)

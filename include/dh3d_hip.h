@@ -515,7 +515,8 @@ int dh3d_se_res_pool_conv_pm_fwd(const float *x, const int32_t *nbr, int B, int 
 
 /* three_nn + inverse-distance weights + three_interpolate (core/backbones.py:90-96) fused:
  * weight = (1/max(d,1e-10)) / sum(1/max(d,1e-10)).  idx/dist from dh3d_three_nn.
- * points [b,m,c] -> out [b,n,c]; c % 4 == 0. */
+ * points [b,m,c] -> out [b,n,c] (16-byte accesses when c % 4 == 0, one channel per thread otherwise, like
+ * dh3d_three_interpolate_fwd). */
 int dh3d_three_interpolate_idw_fwd(int b, int m, int c, int n, const float *points,
                                    const int32_t *idx, const float *dist, float *out, void *stream);
 

@@ -338,6 +338,27 @@ def test_upsample_linear_x6_is_interpolate_then_linear(dev, oracle):
     assert torch.equal(one, two)
 
 
+@pytest.mark.parametrize("C", [8, 5])  # the float4 path and the scalar-channel path
+def test_idw_weights_then_interpolate_is_interpolate_idw(dev, C):
+    """One inverse-distance arithmetic across objects built with different contraction flags: the weights kernel (default
+    contraction) followed by three_interpolate == the fused three_interpolate_idw (exact object), bit for bit."""
+    from dh3d_amd import ops, pm
+    g = torch.Generator().manual_seed(29)
+    B, n, m = 2, 130, 40
+    dist = torch.rand(B, n, 3, generator=g) * 0.01
+    dist[0, 0] = torch.tensor([0.0, 2e-3, 5e-3])      # an exact 0 (a fine point on a sampled one)
+    dist[0, 1] = torch.tensor([3e-11, 4e-11, 1e-3])   # below the 1e-10 clamp
+    dist[1, 129] = torch.tensor([7e-4, 7e-4, 7e-4])   # three equal distances
+    dist[1, 2] = torch.tensor([0.0, 0.0, 0.0])
+    idx = torch.randint(0, m, (B, n, 3), generator=g, dtype=torch.int32)
+    points = torch.randn(B, m, C, generator=g)
+    dist, idx, points = dist.to(dev), idx.to(dev), points.to(dev)
+    two = ops.three_interpolate(points, idx, pm.idw_weights(dist))
+    one = pm.three_interpolate_idw(points, idx, dist)
+    assert torch.isfinite(one).all()
+    assert torch.equal(two, one)
+
+
 @pytest.mark.parametrize("C", [64, 128])
 def test_se_res_pm(dev, C):
     from dh3d_amd import pm
