@@ -10,9 +10,12 @@
 // computed in the accumulator layout (lane = output column, 16 rows per lane): 68 MB of traffic (x1, x2 in; rows out).
 //
 // Workgroup = 8 waves (two per SIMD) = 8 independent 32-row tiles; the packed weights (48 KB each, fragment order) pass
-// through LDS one after the other and are read back per K-step (no register double buffer: 128 accumulator registers
-// leave no room for one).  Per-row interpolation operands (three row offsets, three inverse-distance weights) are
-// computed once per row by lane = row and handed over through LDS.
+// through LDS one after the other (LDS-DMA, no registers) and are read back per K-step (no register double buffer: 128
+// accumulator registers leave no room for one).  Per-row interpolation operands (three row offsets, three
+// inverse-distance weights) are computed once per row by lane = row and read across lanes.  The up-sampled rows are the
+// INITIAL value of the lower block's accumulators: their gathers are issued first of all and return while the shortcut
+// weight and the A rows are on their way, so the epilogue behind the last product has no memory round trip before its
+// stores.
 #include "bf16x3.h"
 #include "interp_walk.h"
 #include "wave_ops.h"
@@ -22,10 +25,10 @@ namespace {
 constexpr int kTailWaves = 8;
 constexpr int kTailC = 64, kTailKB = kTailC / 16, kTailD = 128, kTailNCB = kTailD / 32;
 constexpr int kTailWFrag = kTailNCB * kTailKB * 3 * 64;  // uint4 per packed weight
-// ONE weight in LDS at a time (48 KB + 8 KB of row operands): a workgroup then fits on a CU beside a farthest-point-sampling
+// ONE weight in LDS at a time (48 KB): a workgroup then fits on a CU beside a farthest-point-sampling
 // workgroup of another step in flight (~100 KB of LDS, held for most of that step) -- with both weights resident (104 KB)
 // those CUs took none of this kernel's workgroups and the 256 of them ran as two waves on the rest
-constexpr size_t kTailLds = (size_t)kTailWFrag * 16 + (size_t)kTailWaves * 32 * 8 * 4;
+constexpr size_t kTailLds = (size_t)kTailWFrag * 16;
 
 struct TailArgs {
   const float *x1, *x2;            // [R, 64] stage-1 output, before_stage2 output
@@ -46,147 +49,158 @@ template <bool L2CAT>
 __global__ __launch_bounds__(kTailWaves * 64) void local_tail_fused_kernel(TailArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
   uint4 *s_w = reinterpret_cast<uint4 *>(s_raw);                              // [NCB][KB][3][64]: the shortcut weight, then the lower block
-  float *s_rw = reinterpret_cast<float *>(s_raw + (size_t)kTailWFrag * 16);   // [waves][32 rows][8]: o1 o2 o3 (int bits) w1 w2 w3 - -
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, lr = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int kPerThread = kTailWFrag / (kTailWaves * 64);
-  static_assert(kPerThread * kTailWaves * 64 == kTailWFrag, "weight copy");
-  uint4 wl[kPerThread];   // the lower block: requested now, parked in registers until the shortcut GEMM has left LDS
+  // a packed weight reaches LDS by LDS-DMA (no registers), half by half: half h = the fragments of K-steps 2h, 2h + 1 of
+  // every column block (384 uint4 per block); each wave moves three 1 KB pieces of a half
+  auto dma_half = [&](const uint4 *wp, int h) __attribute__((always_inline)) {
 #pragma unroll
-  for (int u = 0; u < kPerThread; ++u) {
-    s_w[tid + u * kTailWaves * 64] = a.wp_s[tid + u * kTailWaves * 64];
-    wl[u] = a.wp_l[tid + u * kTailWaves * 64];
-  }
+    for (int j = 0; j < 3; ++j) {
+      const int e0 = (wave * 3 + j) * 64, cb = e0 / 384, off = cb * 768 + h * 384 + (e0 - cb * 384);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(wp + off + lane),
+                                       (__attribute__((address_space(3))) void *)(s_w + off), 16, 0, 0);
+    }
+  };
+  auto dma_sync = [&]() __attribute__((always_inline)) {  // LDS-DMA counts on vmcnt
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  };
   // (XCD-aware, round 6: contiguous tile ranges per XCD -- round-robin, every L2 fetched every cloud's coarse rows: 176 MB of
   // fetches at 32 x 4096 where the operands are 80)
   const long long row0 = ((long long)dh3d_xcd_remap(blockIdx.x, gridDim.x) * kTailWaves + wave) * 32;
   const bool alive = row0 < a.R;   // wave-uniform; n % 32 == 0: a tile lies inside one cloud and is complete
   const long long rowc = alive ? row0 : 0;
   const long long cloud = rowc / a.n;
-  // ---- this lane's A rows (32 B pieces of row lr: the whole 256 B row over the four K-steps) and the row's
-  // interpolation operands
+  // ---- this lane's A rows (32 B pieces of row lr: the whole 256 B row over the four K-steps)
   const float4 *ap1 = reinterpret_cast<const float4 *>(a.x1 + (rowc + lr) * kTailC + 8 * half);
   const float4 *ap2 = reinterpret_cast<const float4 *>(a.x2 + (rowc + lr) * kTailC + 8 * half);
   float4 av[kTailKB][2];
-#pragma unroll
-  for (int ks = 0; ks < kTailKB; ++ks) { av[ks][0] = ap1[ks * 4]; av[ks][1] = ap1[ks * 4 + 1]; }
-  {
-    const long long g = (rowc + lr) * 3;
-    const int i1 = a.idx[g], i2 = a.idx[g + 1], i3 = a.idx[g + 2];
-    float w1, w2, w3;
-    dh3d_walk::idw3(a.dist[g], a.dist[g + 1], a.dist[g + 2], w1, w2, w3);
-    if (half == 0) {
-      float *q = s_rw + ((size_t)wave * 32 + lr) * 8;
-      *reinterpret_cast<float4 *>(q) = make_float4(__int_as_float(i1 * kTailD), __int_as_float(i2 * kTailD),
-                                                   __int_as_float(i3 * kTailD), w1);
-      *reinterpret_cast<float2 *>(q + 4) = make_float2(w2, w3);
-    }
-  }
-  __syncthreads();  // the shortcut weight (and this wave's row operands) are in LDS
-
   f32x16 acc_s[kTailNCB], acc_l[kTailNCB];
-  auto gemm = [&](f32x16 (&acc)[kTailNCB], const uint4 *sw) __attribute__((always_inline)) {
+  // the row's interpolation operands, by lane = row: requested first, the gathers below hang on them
+  const long long gi = (rowc + lr) * 3;
+  const int i1 = a.idx[gi], i2 = a.idx[gi + 1], i3 = a.idx[gi + 2];
+  const float d1 = a.dist[gi], d2 = a.dist[gi + 1], d3 = a.dist[gi + 2];
+  if (alive) {
 #pragma unroll
-    for (int cb = 0; cb < kTailNCB; ++cb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[cb][r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < kTailKB; ++ks) {
-      uint4 bq[kTailNCB][3];
-#pragma unroll
-      for (int cb = 0; cb < kTailNCB; ++cb)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) bq[cb][p] = sw[((size_t)(cb * kTailKB + ks) * 3 + p) * 64 + lane];
-      uint2 c1[2], c2[2], c3[2];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) split3x4(av[ks][j], c1[j], c2[j], c3[j]);
-      bf16x8 af[3];
-      af[0] = __builtin_bit_cast(bf16x8, make_uint4(c1[0].x, c1[0].y, c1[1].x, c1[1].y));
-      af[1] = __builtin_bit_cast(bf16x8, make_uint4(c2[0].x, c2[0].y, c2[1].x, c2[1].y));
-      af[2] = __builtin_bit_cast(bf16x8, make_uint4(c3[0].x, c3[0].y, c3[1].x, c3[1].y));
-#define DH3D_TAIL_PRODUCT(PA, PB)                                                                     \
-  _Pragma("unroll") for (int cb = 0; cb < kTailNCB; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16( \
-      af[PA], __builtin_bit_cast(bf16x8, bq[cb][PB]), acc[cb], 0, 0, 0);
-      DH3D_TAIL_PRODUCT(2, 0) DH3D_TAIL_PRODUCT(0, 2) DH3D_TAIL_PRODUCT(1, 1)
-      DH3D_TAIL_PRODUCT(1, 0) DH3D_TAIL_PRODUCT(0, 1) DH3D_TAIL_PRODUCT(0, 0)
-#undef DH3D_TAIL_PRODUCT
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  // ---- shortcut = relu(BN_s(x1 Ws + b_s)), in place  (waves past the last tile take part in the barriers only)
-  if (alive) gemm(acc_s, s_w);
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < kPerThread; ++u) s_w[tid + u * kTailWaves * 64] = wl[u];
-  __syncthreads();
-  if (!alive) return;
-#pragma unroll
-  for (int ks = 0; ks < kTailKB; ++ks) { av[ks][0] = ap2[ks * 4]; av[ks][1] = ap2[ks * 4 + 1]; }  // x2 rows: in flight under the epilogue
-#pragma unroll
-  for (int cb = 0; cb < kTailNCB; ++cb) {
-    const int col = cb * 32 + lr;
-    const float pb = a.ep_s.pre_bias ? a.ep_s.pre_bias[col] : 0.f, sc = a.ep_s.scale ? a.ep_s.scale[col] : 1.f;
-    const float sh = fmaf(pb, sc, a.ep_s.shift ? a.ep_s.shift[col] : 0.f);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc_s[cb][r] = fmaxf(fmaf(acc_s[cb][r], sc, sh), 0.f);
+    for (int ks = 0; ks < kTailKB; ++ks) { av[ks][0] = ap1[ks * 4]; av[ks][1] = ap1[ks * 4 + 1]; }
   }
-  // ---- lower block of the concat conv: x2 Wbot
-  gemm(acc_l, s_w);
-  // ---- up-sampling of the coarse rows + sum + BatchNorm / ReLU + shortcut, row normalisation, rows out -- in the
-  // accumulator layout: register r of lane (lr, half) = row (r & 3) + 8 (r >> 2) + 4 half, column 32 cb + lr
-  float pbc[kTailNCB], scc[kTailNCB], shc[kTailNCB];
+  dma_half(a.wp_s, 0);
+  dma_half(a.wp_s, 1);
+  __builtin_amdgcn_sched_barrier(0);   // (in this order: the A rows come from HBM and are not to queue behind the gathers)
+  if (alive) {
+    const int o1 = i1 * kTailD, o2 = i2 * kTailD, o3 = i3 * kTailD;
+    float w1, w2, w3;
+    dh3d_walk::idw3(d1, d2, d3, w1, w2, w3);
+    // ---- the up-sampled coarse rows SEED the lower block's accumulators (accumulator layout: register r of lane
+    // (lr, half) = row (r & 3) + 8 (r >> 2) + 4 half, column 32 cb + lr): the gathers need nothing a GEMM makes, so their
+    // round trips run while the weight and the A rows are still on their way, not behind the last product
+    const float *cwb = a.cw + cloud * (long long)a.m * kTailD + lr;
 #pragma unroll
-  for (int cb = 0; cb < kTailNCB; ++cb) {
-    const int col = cb * 32 + lr;
-    pbc[cb] = a.ep_c.pre_bias ? a.ep_c.pre_bias[col] : 0.f;
-    scc[cb] = a.ep_c.scale ? a.ep_c.scale[col] : 1.f;
-    shc[cb] = fmaf(pbc[cb], scc[cb], a.ep_c.shift ? a.ep_c.shift[col] : 0.f);
-  }
-  const float *cwb = a.cw + cloud * (long long)a.m * kTailD + lr;
-  constexpr int OW = L2CAT ? kTailD + 3 : kTailD;
-  float *orow = a.out + row0 * OW + (L2CAT ? 3 : 0) + lr;
-  const float *rw = s_rw + (size_t)wave * 32 * 8;
-#pragma unroll
-  for (int rg = 0; rg < 16; rg += 2) {   // two rows per lane in flight: 24 gathers
-    float g[2][3][kTailNCB], w[2][3];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int r = rg + u, row = (r & 3) + 8 * (r >> 2) + 4 * half;
-      const float4 q0 = *reinterpret_cast<const float4 *>(rw + row * 8);
-      const float2 q1 = *reinterpret_cast<const float2 *>(rw + row * 8 + 4);
-      const int o[3] = {__float_as_int(q0.x), __float_as_int(q0.y), __float_as_int(q0.z)};
-      w[u][0] = q0.w; w[u][1] = q1.x; w[u][2] = q1.y;
+    for (int r = 0; r < 16; ++r) {
+      const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+      // (operands of row `row` from the lane that holds them: a cross-lane read, not an LDS access -- one of those here
+      // would have to wait for the weight's LDS-DMA)
+      const int o[3] = {__shfl(o1, row, 64), __shfl(o2, row, 64), __shfl(o3, row, 64)};
+      const float v1 = __shfl(w1, row, 64), v2 = __shfl(w2, row, 64), v3 = __shfl(w3, row, 64);
+      float g3[3][kTailNCB];
 #pragma unroll
       for (int t = 0; t < 3; ++t)
 #pragma unroll
-        for (int cb = 0; cb < kTailNCB; ++cb) g[u][t][cb] = cwb[o[t] + cb * 32];
+        for (int cb = 0; cb < kTailNCB; ++cb) g3[t][cb] = cwb[o[t] + cb * 32];
+#pragma unroll
+      for (int cb = 0; cb < kTailNCB; ++cb)
+        acc_l[cb][r] = dh3d_walk::mix3_fma(g3[0][cb], g3[1][cb], g3[2][cb], v1, v2, v3);
     }
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int r = rg + u, row = (r & 3) + 8 * (r >> 2) + 4 * half;
-      float y[kTailNCB], ss = 0.f;
+    for (int cb = 0; cb < kTailNCB; ++cb)
 #pragma unroll
-      for (int cb = 0; cb < kTailNCB; ++cb) {
-        // (the same association as interp_combine_kernel: ((a w1 + b w2) + c w3) + partial, then BN with the bias folded)
-        float v = dh3d_walk::mix3_fma(g[u][0][cb], g[u][1][cb], g[u][2][cb], w[u][0], w[u][1], w[u][2]) + acc_l[cb][r];
-        v = fmaxf(fmaf(v, scc[cb], shc[cb]), 0.f) + acc_s[cb][r];
-        y[cb] = v;
-        ss = fmaf(v, v, ss);
-      }
-      float inv = 1.f;
-      if (L2CAT) {
-        ss = row16_sum_f32(ss);     // over the 32 lanes of this half (the row's 128 columns), in every lane
-        ss += __shfl_xor(ss, 16, 64);
-        inv = rsqrtf(fmaxf(ss, a.l2_eps));
-      }
+      for (int r = 0; r < 16; ++r) acc_s[cb][r] = 0.f;
+  }
+  dma_sync();  // the shortcut weight is in LDS
+
+  auto kstep = [&](f32x16 (&acc)[kTailNCB], int ks) __attribute__((always_inline)) {
+    uint4 bq[kTailNCB][3];
 #pragma unroll
-      for (int cb = 0; cb < kTailNCB; ++cb) orow[(size_t)row * OW + cb * 32] = L2CAT ? y[cb] * inv : y[cb];
+    for (int cb = 0; cb < kTailNCB; ++cb)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) bq[cb][p] = s_w[((size_t)(cb * kTailKB + ks) * 3 + p) * 64 + lane];
+    uint2 c1[2], c2[2], c3[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) split3x4(av[ks][j], c1[j], c2[j], c3[j]);
+    bf16x8 af[3];
+    af[0] = __builtin_bit_cast(bf16x8, make_uint4(c1[0].x, c1[0].y, c1[1].x, c1[1].y));
+    af[1] = __builtin_bit_cast(bf16x8, make_uint4(c2[0].x, c2[0].y, c2[1].x, c2[1].y));
+    af[2] = __builtin_bit_cast(bf16x8, make_uint4(c3[0].x, c3[0].y, c3[1].x, c3[1].y));
+#define DH3D_TAIL_PRODUCT(PA, PB)                                                                     \
+  _Pragma("unroll") for (int cb = 0; cb < kTailNCB; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16( \
+      af[PA], __builtin_bit_cast(bf16x8, bq[cb][PB]), acc[cb], 0, 0, 0);
+    DH3D_TAIL_PRODUCT(2, 0) DH3D_TAIL_PRODUCT(0, 2) DH3D_TAIL_PRODUCT(1, 1)
+    DH3D_TAIL_PRODUCT(1, 0) DH3D_TAIL_PRODUCT(0, 1) DH3D_TAIL_PRODUCT(0, 0)
+#undef DH3D_TAIL_PRODUCT
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // ---- shortcut = x1 Ws  (waves past the last tile move their share of the weights and take the barriers only)
+  if (alive) {
+#pragma unroll
+    for (int ks = 0; ks < kTailKB; ++ks) {
+      kstep(acc_s, ks);
+      av[ks][0] = ap2[ks * 4]; av[ks][1] = ap2[ks * 4 + 1];   // the x2 rows take the places of the x1 rows
     }
   }
-  // the xyz prefix of the 32 rows: 96 floats
-  if (L2CAT) for (int e = lane; e < 96; e += 64) {
-    const int p = e / 3, c = e - 3 * p;
-    a.out[(row0 + p) * (kTailD + 3) + c] = a.prefix[(row0 + p) * 3 + c];
+  __syncthreads();   // no wave reads the shortcut weight any more
+  dma_half(a.wp_l, 0);
+  dma_half(a.wp_l, 1);   // (an L2 hit: every workgroup reads the same 48 KB)
+  float scc[kTailNCB], shc[kTailNCB];
+  if (alive) {
+    // (in the shadow of the weight's way to LDS: the per-column operands of both epilogues and the xyz prefix)
+#pragma unroll
+    for (int cb = 0; cb < kTailNCB; ++cb) {
+      const int col = cb * 32 + lr;
+      const float pbc = a.ep_c.pre_bias ? a.ep_c.pre_bias[col] : 0.f;
+      scc[cb] = a.ep_c.scale ? a.ep_c.scale[col] : 1.f;
+      shc[cb] = fmaf(pbc, scc[cb], a.ep_c.shift ? a.ep_c.shift[col] : 0.f);
+    }
+    if (L2CAT) for (int e = lane; e < 96; e += 64) {   // the xyz prefix of the 32 rows: 96 floats
+      const int p = e / 3, c = e - 3 * p;
+      a.out[(row0 + p) * (kTailD + 3) + c] = a.prefix[(row0 + p) * 3 + c];
+    }
+    // relu(BN_s(. + b_s)), in place
+#pragma unroll
+    for (int cb = 0; cb < kTailNCB; ++cb) {
+      const int col = cb * 32 + lr;
+      const float pb = a.ep_s.pre_bias ? a.ep_s.pre_bias[col] : 0.f, sc = a.ep_s.scale ? a.ep_s.scale[col] : 1.f;
+      const float sh = fmaf(pb, sc, a.ep_s.shift ? a.ep_s.shift[col] : 0.f);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc_s[cb][r] = fmaxf(fmaf(acc_s[cb][r], sc, sh), 0.f);
+    }
+  }
+  dma_sync();
+  if (!alive) return;
+  // ---- lower block of the concat conv on top of the up-sampled rows: interp3(coarse Wtop) + x2 Wbot
+#pragma unroll
+  for (int ks = 0; ks < kTailKB; ++ks) kstep(acc_l, ks);
+  // ---- BatchNorm / ReLU + shortcut, row normalisation, rows out -- in the accumulator layout; no memory round trip
+  // in front of the first store
+  constexpr int OW = L2CAT ? kTailD + 3 : kTailD;
+  float *orow = a.out + row0 * OW + (L2CAT ? 3 : 0) + lr;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+    float y[kTailNCB], ss = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < kTailNCB; ++cb) {
+      const float v = fmaxf(fmaf(acc_l[cb][r], scc[cb], shc[cb]), 0.f) + acc_s[cb][r];
+      y[cb] = v;
+      ss = fmaf(v, v, ss);
+    }
+    float inv = 1.f;
+    if (L2CAT) {
+      ss = row16_sum_f32(ss);     // over the 32 lanes of this half (the row's 128 columns), in every lane
+      ss += __shfl_xor(ss, 16, 64);
+      inv = rsqrtf(fmaxf(ss, a.l2_eps));
+    }
+#pragma unroll
+    for (int cb = 0; cb < kTailNCB; ++cb) orow[(size_t)row * OW + cb * 32] = L2CAT ? y[cb] * inv : y[cb];
   }
 }
 
