@@ -18,17 +18,12 @@
 // Skew: a list of more than kChunk entries (a "hub") is summed in kChunk-entry chunks by separate lanes into partial
 // rows, which a second pass adds per target in chunk order (cdna_hip_programming.md, Appendix B "Scatter / gather"):
 // the main gather skips such targets, so a kNN neighbourhood (in-degree ~K) pays two empty launches for it.
-#include "internal.h"
+#include "flex_common.h"
 
 namespace {
 
-constexpr int kPts = 128;   // section A: points per block
-constexpr int kDT = 16;     // section A: output channels per thread
-constexpr int kMaxDp = 4;   // as flex_generic.hip
 constexpr int kChunk = 64;  // inverted-list entries one lane sums; longer lists are split
 constexpr int kScanThreads = 1024;
-
-#define AT3(p, b, c, n, C, N) (p)[((size_t)(b) * (C) + (c)) * (size_t)(N) + (n)]
 
 // ------------------------------------------------------------------ section A: reference formulation
 template <typename T>
@@ -370,43 +365,43 @@ __global__ __launch_bounds__(256) void csr_combine_kernel(const long long *__res
   }
 }
 
-inline int flat_grid256(long long work, int cap) {
-  long long g = (work + 255) / 256;
-  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// Workspace of one inverted-list sum over the first Ku ranks of R rows, rows of W floats (bytes; 0 = too large).
-inline size_t csr_bytes(size_t R, size_t Ku, size_t W) {
-  const size_t E = R * Ku, P = 2 * (E / kChunk) + 1;  // partial rows: a list of d > kChunk entries has < 2d / kChunk
-  return al256(4 * R) + 2 * al256(8 * (R + 1)) + 2 * al256(4 * E) + al256(4 * P * W);
-}
+// Workspace of one inverted-list sum over the first Ku ranks of R rows, rows of W floats.
+struct CsrWs {
+  int32_t *cnt, *ids, *payload;
+  long long *off, *part;
+  long long P;  // partial rows: a list of d > kChunk entries has < 2d / kChunk
+  float *partial;
+  CsrWs() = default;
+  CsrWs(Carve &c, size_t R, size_t Ku, size_t W) {
+    const size_t E = R * Ku;
+    P = (long long)(2 * (E / kChunk) + 1);
+    cnt = c.take<int32_t>(R, 256);
+    off = c.take<long long>(R + 1, 256);
+    part = c.take<long long>(R + 1, 256);
+    ids = c.take<int32_t>(E, 256);
+    payload = c.take<int32_t>(E, 256);
+    partial = c.take<float>((size_t)P * W, 256);
+  }
+};
 
 // out[t, :] (rows of 4*D when flex, else D) = the sum over t's inverted list (first Ku ranks of nbr) of feat rows, in
-// ascending edge order.  `w` holds csr_bytes(R, Ku, W) bytes.
+// ascending edge order.  `w`: CsrWs(R, Ku, FLEX ? 4 * D : D).
 template <bool FLEX>
 int csr_sum(const float *feat, const float *xyz, const int32_t *nbr, long long R, int N, int K, int Ku, int centre, int D,
-            char *w, float *out, hipStream_t s) {
+            const CsrWs &w, float *out, hipStream_t s) {
   const long long E = R * Ku;
-  int32_t *cnt = reinterpret_cast<int32_t *>(w); w += al256(4 * R);
-  long long *off = reinterpret_cast<long long *>(w); w += al256(8 * (R + 1));
-  long long *part = reinterpret_cast<long long *>(w); w += al256(8 * (R + 1));
-  int32_t *ids = reinterpret_cast<int32_t *>(w); w += al256(4 * E);
-  int32_t *payload = reinterpret_cast<int32_t *>(w); w += al256(4 * E);
-  float *partial = reinterpret_cast<float *>(w);
-  const long long P = 2 * (E / kChunk) + 1;
-  if (hipMemsetAsync(cnt, 0, sizeof(int32_t) * R, s) != hipSuccess) return DH3D_ERR_LAUNCH;
-  hipLaunchKernelGGL(csr_count_kernel, dim3(flat_grid256(E, 4096)), dim3(256), 0, s, nbr, R, N, K, Ku, cnt);
-  hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, cnt, R, off, part);
-  hipLaunchKernelGGL(csr_fill_kernel, dim3(flat_grid256(E, 4096)), dim3(256), 0, s, nbr, R, N, K, Ku, off, cnt, ids);
-  hipLaunchKernelGGL(csr_order_kernel, dim3(flat_grid256(E, 4096)), dim3(256), 0, s, nbr, R, N, K, Ku, centre, off, ids,
-                     payload);
-  hipLaunchKernelGGL(csr_gather_kernel<FLEX>, dim3(flat_grid256(R * (D / 4), 8192)), dim3(256), 0, s, feat, xyz, off,
-                     payload, R, N, D, out);
-  hipLaunchKernelGGL(csr_chunk_kernel<FLEX>, dim3(flat_grid256(P * (D / 4), 1024)), dim3(256), 0, s, feat, xyz, off, part,
-                     payload, R, N, D, partial);
-  hipLaunchKernelGGL(csr_combine_kernel<FLEX>, dim3(flat_grid256(P * (D / 4), 1024)), dim3(256), 0, s, part, R, D, partial,
-                     out);
+  if (hipMemsetAsync(w.cnt, 0, sizeof(int32_t) * R, s) != hipSuccess) return DH3D_ERR_LAUNCH;
+  hipLaunchKernelGGL(csr_count_kernel, dim3(flat_grid256(E, 4096)), dim3(256), 0, s, nbr, R, N, K, Ku, w.cnt);
+  hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, w.cnt, R, w.off, w.part);
+  hipLaunchKernelGGL(csr_fill_kernel, dim3(flat_grid256(E, 4096)), dim3(256), 0, s, nbr, R, N, K, Ku, w.off, w.cnt, w.ids);
+  hipLaunchKernelGGL(csr_order_kernel, dim3(flat_grid256(E, 4096)), dim3(256), 0, s, nbr, R, N, K, Ku, centre, w.off,
+                     w.ids, w.payload);
+  hipLaunchKernelGGL(csr_gather_kernel<FLEX>, dim3(flat_grid256(R * (D / 4), 8192)), dim3(256), 0, s, feat, xyz, w.off,
+                     w.payload, R, N, D, out);
+  hipLaunchKernelGGL(csr_chunk_kernel<FLEX>, dim3(flat_grid256(w.P * (D / 4), 1024)), dim3(256), 0, s, feat, xyz, w.off,
+                     w.part, w.payload, R, N, D, w.partial);
+  hipLaunchKernelGGL(csr_combine_kernel<FLEX>, dim3(flat_grid256(w.P * (D / 4), 1024)), dim3(256), 0, s, w.part, R, D,
+                     w.partial, out);
   return dh3d_launch_status();
 }
 
@@ -438,11 +433,53 @@ DH3D_FLEX_DECONV_API(_f64, double)
 #undef DH3D_FLEX_DECONV_API
 
 // ------------------------------------------------------------------ section A' entry points
+namespace {
+
+// Both layouts: R = B * N point-major rows, each segment rounded up to 256 bytes.
+struct DeconvFwdWs {
+  PointMajor in{};
+  float *Wcat, *out, *S;
+  CsrWs csr;
+  DeconvFwdWs(Carve &c, size_t R, int K, int Din, int Dout) {
+    in.f = c.take<float>(R * Din, 256);
+    in.nbr = c.take<int32_t>(R * K, 256);
+    in.xyz = c.take<float>(R * 3, 256);
+    Wcat = c.take<float>((size_t)4 * Din * Dout, 256);  // [bias; theta]: [4*Din, Dout]
+    out = c.take<float>(R * Dout, 256);
+    S = c.take<float>(R * 4 * Din, 256);
+    csr = CsrWs(c, R, K, 4 * (size_t)Din);
+  }
+};
+
+struct DeconvBwdWs {
+  PointMajor in{};
+  float *df, *Q, *Qc, *WT, *dW;
+  CsrWs csr;
+  DeconvBwdWs(Carve &c, size_t R, int K, int Din, int Dout) {
+    in.f = c.take<float>(R * Din, 256);
+    df = c.take<float>(R * Din, 256);
+    in.nbr = c.take<int32_t>(R * K, 256);
+    in.xyz = c.take<float>(R * 3, 256);
+    in.g = c.take<float>(R * Dout, 256);
+    Q = c.take<float>(R * 4 * Dout, 256);
+    Qc = c.take<float>(R * 4 * Dout, 256);
+    WT = c.take<float>((size_t)4 * Dout * Din, 256);  // [bias'; theta_d']: [4*Dout, Din]
+    dW = c.take<float>((size_t)4 * Dout * Din, 256);  // Q~^T f: [4*Dout, Din]
+    csr = CsrWs(c, R, 1, 4 * (size_t)Dout);
+  }
+};
+
+// [rows, cols] -> [cols, rows] of one plane (b) and of three (t): [bias; theta] <-> [bias'; theta_d']
+int transpose_planes(const float *b_in, const float *t_in, float *b_out, float *t_out, int rows, int cols, hipStream_t s) {
+  const int st = dh3d_internal_transpose32(b_in, b_out, 1, rows, cols, 0, 0, s);
+  return st != DH3D_OK ? st : dh3d_internal_transpose32(t_in, t_out, 3, rows, cols, 0, 0, s);
+}
+
+}  // namespace
+
 DH3D_API size_t dh3d_flex_deconv_fwd_workspace_bytes(int B, int N, int K, int Dp, int Din, int Dout) {
   if (!fast_shape(B, N, K, Dp, Din, Dout)) return 0;
-  const size_t R = (size_t)B * N;
-  return al256(4 * R * Din) + al256(4 * R * K) + al256(4 * R * 3) + al256((size_t)4 * 4 * Din * Dout) +
-         al256(4 * R * Dout) + al256(4 * R * 4 * Din) + csr_bytes(R, K, 4 * (size_t)Din);
+  return carve_bytes<DeconvFwdWs>((size_t)B * N, K, Din, Dout);
 }
 
 DH3D_API int dh3d_flex_deconv_fwd_ws(const float *features, const float *theta, const float *bias,
@@ -451,37 +488,24 @@ DH3D_API int dh3d_flex_deconv_fwd_ws(const float *features, const float *theta, 
                                      void *stream) {
   DH3D_REQUIRE(features && theta && bias && neighborhood && positions && output && workspace);
   DH3D_REQUIRE(B > 0 && N > 0 && K > 0 && Dp > 0 && Din > 0 && Dout > 0);
-  const size_t need = dh3d_flex_deconv_fwd_workspace_bytes(B, N, K, Dp, Din, Dout);
-  DH3D_SUPPORTED(need != 0);
-  DH3D_REQUIRE(workspace_bytes >= need);
-  hipStream_t s = (hipStream_t)stream;
+  DH3D_SUPPORTED(fast_shape(B, N, K, Dp, Din, Dout));
   const size_t R = (size_t)B * N;
-  char *w = static_cast<char *>(workspace);
-  float *f_pm = reinterpret_cast<float *>(w); w += al256(4 * R * Din);
-  int32_t *nbr_pm = reinterpret_cast<int32_t *>(w); w += al256(4 * R * K);
-  float *xyz_pm = reinterpret_cast<float *>(w); w += al256(4 * R * 3);
-  float *Wcat = reinterpret_cast<float *>(w); w += al256((size_t)4 * 4 * Din * Dout);  // [bias; theta]: [4*Din, Dout]
-  float *out_pm = reinterpret_cast<float *>(w); w += al256(4 * R * Dout);
-  float *S = reinterpret_cast<float *>(w); w += al256(4 * R * 4 * Din);
-  int st;
-  if ((st = dh3d_internal_transpose32(features, f_pm, B, Din, N, 0, 0, s)) != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(neighborhood, nbr_pm, B, K, N, 0, 0, s)) != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(positions, xyz_pm, B, 3, N, 0, 0, s)) != DH3D_OK) return st;
-  if (hipMemcpyAsync(Wcat, bias, sizeof(float) * Din * Dout, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(Wcat + (size_t)Din * Dout, theta, sizeof(float) * 3 * Din * Dout, hipMemcpyDeviceToDevice, s) !=
-          hipSuccess)
-    return DH3D_ERR_LAUNCH;
-  if ((st = csr_sum<true>(f_pm, xyz_pm, nbr_pm, (long long)R, N, K, K, 1, Din, w, S, s)) != DH3D_OK) return st;
-  st = dh3d_internal_gemm(false, S, 4 * Din, Wcat, Dout, out_pm, Dout, (int)R, Dout, 4 * Din, nullptr, 0, false, s);
+  Carve c(workspace);
+  const DeconvFwdWs w(c, R, K, Din, Dout);
+  DH3D_REQUIRE(workspace_bytes >= c.bytes());
+  hipStream_t s = (hipStream_t)stream;
+  int st = flex_to_point_major(w.in, features, neighborhood, positions, nullptr, B, N, K, Din, Dout, s);
   if (st != DH3D_OK) return st;
-  return dh3d_internal_transpose32(out_pm, output, B, N, Dout, 0, 0, s);
+  if ((st = flex_build_wcat(bias, theta, Din, Dout, w.Wcat, s)) != DH3D_OK) return st;
+  if ((st = csr_sum<true>(w.in.f, w.in.xyz, w.in.nbr, (long long)R, N, K, K, 1, Din, w.csr, w.S, s)) != DH3D_OK) return st;
+  st = dh3d_internal_gemm(false, w.S, 4 * Din, w.Wcat, Dout, w.out, Dout, (int)R, Dout, 4 * Din, nullptr, 0, false, s);
+  if (st != DH3D_OK) return st;
+  return dh3d_internal_transpose32(w.out, output, B, N, Dout, 0, 0, s);
 }
 
 DH3D_API size_t dh3d_flex_deconv_bwd_workspace_bytes(int B, int N, int K, int Dp, int Din, int Dout) {
   if (!fast_shape(B, N, K, Dp, Din, Dout)) return 0;
-  const size_t R = (size_t)B * N;
-  return al256(4 * R * Din) * 2 + al256(4 * R * K) + al256(4 * R * 3) + al256(4 * R * Dout) +
-         2 * al256(4 * R * 4 * Dout) + 2 * al256((size_t)4 * 4 * Dout * Din) + csr_bytes(R, 1, 4 * (size_t)Dout);
+  return carve_bytes<DeconvBwdWs>((size_t)B * N, K, Din, Dout);
 }
 
 DH3D_API int dh3d_flex_deconv_bwd_ws(const float *features, const float *theta, const float *bias,
@@ -491,39 +515,26 @@ DH3D_API int dh3d_flex_deconv_bwd_ws(const float *features, const float *theta, 
   DH3D_REQUIRE(features && theta && bias && neighborhood && positions && topdiff && grad_features && grad_theta &&
                grad_bias && workspace);
   DH3D_REQUIRE(B > 0 && N > 0 && K > 0 && Dp > 0 && Din > 0 && Dout > 0);
-  const size_t need = dh3d_flex_deconv_bwd_workspace_bytes(B, N, K, Dp, Din, Dout);
-  DH3D_SUPPORTED(need != 0);
-  DH3D_REQUIRE(workspace_bytes >= need);
-  hipStream_t s = (hipStream_t)stream;
+  DH3D_SUPPORTED(fast_shape(B, N, K, Dp, Din, Dout));
   const size_t R = (size_t)B * N;
   const int KQ = 4 * Dout;
-  char *w = static_cast<char *>(workspace);
-  float *f_pm = reinterpret_cast<float *>(w); w += al256(4 * R * Din);
-  float *df_pm = reinterpret_cast<float *>(w); w += al256(4 * R * Din);
-  int32_t *nbr_pm = reinterpret_cast<int32_t *>(w); w += al256(4 * R * K);
-  float *xyz_pm = reinterpret_cast<float *>(w); w += al256(4 * R * 3);
-  float *g_pm = reinterpret_cast<float *>(w); w += al256(4 * R * Dout);
-  float *Q = reinterpret_cast<float *>(w); w += al256(4 * R * KQ);
-  float *Qc = reinterpret_cast<float *>(w); w += al256(4 * R * KQ);
-  float *WT = reinterpret_cast<float *>(w); w += al256((size_t)4 * 4 * Dout * Din);  // [bias'; theta_d']: [4*Dout, Din]
-  float *dW = reinterpret_cast<float *>(w); w += al256((size_t)4 * 4 * Dout * Din);  // Q~^T f: [4*Dout, Din]
-  int st;
-  if ((st = dh3d_internal_transpose32(features, f_pm, B, Din, N, 0, 0, s)) != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(neighborhood, nbr_pm, B, K, N, 0, 0, s)) != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(positions, xyz_pm, B, 3, N, 0, 0, s)) != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(topdiff, g_pm, B, Dout, N, 0, 0, s)) != DH3D_OK) return st;
+  Carve c(workspace);
+  const DeconvBwdWs w(c, R, K, Din, Dout);
+  DH3D_REQUIRE(workspace_bytes >= c.bytes());
+  hipStream_t s = (hipStream_t)stream;
+  const size_t plane = (size_t)Dout * Din;
+  int st = flex_to_point_major(w.in, features, neighborhood, positions, topdiff, B, N, K, Din, Dout, s);
+  if (st != DH3D_OK) return st;
   // Q[n] = [sum_k g[m_k] | sum_k (p[m_k] - p[s_n])_d g[m_k]]: flex_conv's S of the upstream gradient, centred on rank 0
-  if ((st = dh3d_internal_flex_S(g_pm, xyz_pm, nbr_pm, (long long)R, N, K, Dout, 1, Q, s)) != DH3D_OK) return st;
+  if ((st = dh3d_internal_flex_S(w.in.g, w.in.xyz, w.in.nbr, (long long)R, N, K, Dout, 1, w.Q, s)) != DH3D_OK) return st;
   // Q~[c] = sum over the points n whose centre is c (the rank-0 inverted lists) of Q[n]
-  if ((st = csr_sum<false>(Q, nullptr, nbr_pm, (long long)R, N, K, 1, 0, KQ, w, Qc, s)) != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(bias, WT, 1, Din, Dout, 0, 0, s)) != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(theta, WT + (size_t)Dout * Din, 3, Din, Dout, 0, 0, s)) != DH3D_OK) return st;
+  if ((st = csr_sum<false>(w.Q, nullptr, w.in.nbr, (long long)R, N, K, 1, 0, KQ, w.csr, w.Qc, s)) != DH3D_OK) return st;
+  if ((st = transpose_planes(bias, theta, w.WT, w.WT + plane, Din, Dout, s)) != DH3D_OK) return st;
   // grad_f = Q~ @ [bias'; theta_d'] ;  [grad_bias'; grad_theta'] = Q~^T f  (split-K tn GEMM: f32 atomics)
-  st = dh3d_internal_gemm(false, Qc, KQ, WT, Din, df_pm, Din, (int)R, Din, KQ, nullptr, 0, false, s);
+  st = dh3d_internal_gemm(false, w.Qc, KQ, w.WT, Din, w.df, Din, (int)R, Din, KQ, nullptr, 0, false, s);
   if (st != DH3D_OK) return st;
-  st = dh3d_internal_gemm(true, Qc, KQ, f_pm, Din, dW, Din, KQ, Din, (int)R, nullptr, 0, false, s);
+  st = dh3d_internal_gemm(true, w.Qc, KQ, w.in.f, Din, w.dW, Din, KQ, Din, (int)R, nullptr, 0, false, s);
   if (st != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(dW, grad_bias, 1, Dout, Din, 0, 0, s)) != DH3D_OK) return st;
-  if ((st = dh3d_internal_transpose32(dW + (size_t)Dout * Din, grad_theta, 3, Dout, Din, 0, 0, s)) != DH3D_OK) return st;
-  return dh3d_internal_transpose32(df_pm, grad_features, B, N, Din, 0, 0, s);
+  if ((st = transpose_planes(w.dW, w.dW + plane, grad_bias, grad_theta, Dout, Din, s)) != DH3D_OK) return st;
+  return dh3d_internal_transpose32(w.df, grad_features, B, N, Din, 0, 0, s);
 }

@@ -10,15 +10,9 @@
 
 #include <limits>
 
-#include "common.h"
+#include "flex_common.h"
 
 namespace {
-
-constexpr int kPts = 128;  // points per block (one per lane)
-constexpr int kDT = 16;    // output channels held in registers per thread
-constexpr int kMaxDp = 4;
-
-#define AT3(p, b, c, n, C, N) (p)[((size_t)(b) * (C) + (c)) * (size_t)(N) + (n)]
 
 // ------------------------------------------------------------------ flex_conv forward
 template <typename T>

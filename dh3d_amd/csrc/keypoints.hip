@@ -13,6 +13,7 @@
 // Only comparisons, one f32 multiply and 1 - x: exact by construction (compiled without contraction, csrc/Makefile EXACT).
 #include "common.h"
 #include "wave_ops.h"
+#include "workspace.h"
 
 namespace {
 
@@ -233,15 +234,22 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restric
   for (int c = threadIdx.x & 63; c < C; c += 64) d[c] = id >= 0 ? s[c] : 0.f;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct NmsWs {
+  float *ap, *bmax;
+  unsigned long long *keys;
+  int nblk;
+  NmsWs(Carve &c, int B, int N) : nblk(dh3d_cdiv(N, kPtThreads)) {
+    ap = c.take<float>((size_t)B * N, 256);
+    bmax = c.take<float>((size_t)B * nblk, 256);
+    keys = c.take<unsigned long long>((size_t)B * N, 256);
+  }
+};
 
 }  // namespace
 
 DH3D_API size_t dh3d_keypoint_nms_workspace_bytes(int B, int N, int M) {
   if (B <= 0 || N <= 0 || M <= 0 || M > kMaxKeep) return 0;
-  const size_t nblk = (size_t)dh3d_cdiv(N, kPtThreads);
-  return align256((size_t)B * N * sizeof(float)) + align256((size_t)B * nblk * sizeof(float)) +
-         align256((size_t)B * N * sizeof(unsigned long long));
+  return carve_bytes<NmsWs>(B, N);
 }
 
 DH3D_API int dh3d_keypoint_nms(const float *score, long long score_stride, int invert, const int32_t *nn, const float *dist,
@@ -251,20 +259,15 @@ DH3D_API int dh3d_keypoint_nms(const float *score, long long score_stride, int i
   DH3D_REQUIRE(score && nn && dist && count && inds && workspace);
   DH3D_REQUIRE(B > 0 && N > 0 && K > 0 && M > 0 && score_stride >= 1);
   DH3D_SUPPORTED(M <= kMaxKeep && K <= kMaxK && B <= 65535);
-  const size_t need = dh3d_keypoint_nms_workspace_bytes(B, N, M);
-  DH3D_REQUIRE(workspace_bytes >= need);
-  const int nblk = dh3d_cdiv(N, kPtThreads);
-  char *ws = static_cast<char *>(workspace);
-  float *ap = reinterpret_cast<float *>(ws);
-  float *bmax = reinterpret_cast<float *>(ws + align256((size_t)B * N * sizeof(float)));
-  auto *keys = reinterpret_cast<unsigned long long *>(ws + align256((size_t)B * N * sizeof(float)) +
-                                                      align256((size_t)B * nblk * sizeof(float)));
+  Carve c(workspace);
+  const NmsWs w(c, B, N);
+  DH3D_REQUIRE(workspace_bytes >= c.bytes());
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(nms_mute_kernel, dim3(nblk, B), dim3(kPtThreads), 0, s, score, score_stride, invert, dist, K,
-                     num_valid, N, remove_noise, ap, bmax);
-  hipLaunchKernelGGL(nms_keys_kernel, dim3(nblk, B), dim3(kPtThreads), 0, s, ap, bmax, nn, dist, K, num_valid, N, radius,
-                     ratio, keys);
-  hipLaunchKernelGGL(nms_select_kernel, dim3(B), dim3(kSelThreads), 0, s, keys, N, M, count, inds);
+  hipLaunchKernelGGL(nms_mute_kernel, dim3(w.nblk, B), dim3(kPtThreads), 0, s, score, score_stride, invert, dist, K,
+                     num_valid, N, remove_noise, w.ap, w.bmax);
+  hipLaunchKernelGGL(nms_keys_kernel, dim3(w.nblk, B), dim3(kPtThreads), 0, s, w.ap, w.bmax, nn, dist, K, num_valid, N,
+                     radius, ratio, w.keys);
+  hipLaunchKernelGGL(nms_select_kernel, dim3(B), dim3(kSelThreads), 0, s, w.keys, N, M, count, inds);
   return dh3d_launch_status();
 }
 

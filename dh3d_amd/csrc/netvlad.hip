@@ -11,6 +11,7 @@
 //        16.8 MB weight streams from HBM exactly once across all CUs.
 //   K4 netvlad_gate              : reduce split-K partials, BN, context gating, final L2-normalise.
 #include "mfma_gemm.h"
+#include "workspace.h"
 
 namespace {
 
@@ -502,12 +503,71 @@ __global__ __launch_bounds__(1024) void netvlad_gate(const float *__restrict__ p
   out[(size_t)b * O + o] = v;
 }
 
+// The aggregation's workspace (unpadded) and its two launches; `tot` feeds netvlad_l2scale or netvlad_gate.
+struct AggregateWs {
+  float *part_vlad, *part_asum, *tot;
+  int ch;
+  AggregateWs(Carve &c, int B, int N) : ch(netvlad_chunks(B, N)) {
+    part_vlad = c.take<float>((size_t)B * ch * kCl * kD);
+    part_asum = c.take<float>((size_t)B * ch * kCl);
+    tot = c.take<float>((size_t)B * (kCl / kCG));
+  }
+};
+int launch_aggregate(const AggregateWs &w, const float *x, const float *att, const float *wc_packed,
+                     const float *bn_scale, const float *bn_shift, const float *W2, int B, int N, float *vlad,
+                     hipStream_t s) {
+  const size_t lds = sizeof(float) * (kTM * kLDX + kCl * kLDA + kCl);
+  auto kern = netvlad_assign_accumulate;
+  DH3D_ALLOW_BIG_LDS(kern);
+  hipLaunchKernelGGL(kern, dim3(w.ch, B), dim3(256), lds, s, x, att, wc_packed, bn_scale, bn_shift, N, w.ch,
+                     w.part_vlad, w.part_asum);
+  hipLaunchKernelGGL(netvlad_finalize, dim3(kCl / kCG, B), dim3(1024), 0, s, w.part_vlad, w.part_asum, W2, w.ch, vlad,
+                     w.tot);
+  return dh3d_launch_status();
+}
+
+// The head's workspace: two k-half partials [B, O] per slice of the split-K projection; then the gate.  tot (may be
+// null): see netvlad_gate.
+struct HeadWs {
+  float *part;
+  HeadWs(Carve &c, int B, int Kd, int O) : part(c.take<float>((size_t)2 * dh3d_cdiv(Kd, kKSlice) * B * O)) {}
+};
+int launch_head(float *part, const float *vlad, const float *Wh, const float *bn1_scale, const float *bn1_shift,
+                const float *Wg, const float *bn2_scale, const float *bn2_shift, int B, int Kd, int O, float l2_eps,
+                const float *tot, float *out, hipStream_t s) {
+  const int KS = dh3d_cdiv(Kd, kKSlice);
+  hipLaunchKernelGGL(netvlad_hidden_splitk, dim3(KS, dh3d_cdiv(B, 32), O / 64), dim3(256), 0, s, vlad, Wh, B, Kd, O,
+                     part);
+  hipLaunchKernelGGL(netvlad_gate, dim3(B), dim3(1024), 0, s, part, 2 * KS, B, O, bn1_scale, bn1_shift, Wg, bn2_scale,
+                     bn2_shift, l2_eps, tot, out);
+  return dh3d_launch_status();
+}
+
+struct TailWs {
+  float *part, *vlad, *tot;
+  TailWs(Carve &c, int B, int D, int Cl, int O) : part(HeadWs(c, B, D * Cl, O).part) {
+    c.pad(256);
+    vlad = c.take<float>((size_t)B * D * Cl);
+    tot = c.take<float>((size_t)B * (kCl / kCG));
+  }
+};
+
+struct FusedWs {
+  AggregateWs agg;
+  float *part, *vlad;
+  FusedWs(Carve &c, int B, int N, int D, int Cl, int O) : agg(c, B, N) {
+    c.pad(256);
+    part = HeadWs(c, B, D * Cl, O).part;
+    c.pad(256);
+    vlad = c.take<float>((size_t)B * D * Cl);
+  }
+};
+
 }  // namespace
 
 DH3D_API size_t dh3d_netvlad_workspace_bytes(int B, int N, int D, int Cl) {
   if (B <= 0 || N <= 0 || D != kD || Cl != kCl) return 0;
-  const int ch = netvlad_chunks(B, N);
-  return sizeof(float) * ((size_t)B * ch * kCl * kD + (size_t)B * ch * kCl + (size_t)B * (kCl / kCG));
+  return carve_bytes<AggregateWs>(B, N);
 }
 
 DH3D_API int dh3d_netvlad_aggregate_fwd(const float *x, const float *att, const float *wc_packed,
@@ -516,25 +576,19 @@ DH3D_API int dh3d_netvlad_aggregate_fwd(const float *x, const float *att, const 
                                         size_t workspace_bytes, float *vlad, void *stream) {
   DH3D_REQUIRE(x && att && wc_packed && bn_scale && bn_shift && W2 && workspace && vlad && B > 0 && N > 0);
   DH3D_SUPPORTED(D == kD && Cl == kCl && B <= 65535);
-  DH3D_REQUIRE(workspace_bytes >= dh3d_netvlad_workspace_bytes(B, N, D, Cl));
-  const int ch = netvlad_chunks(B, N);
-  float *part_vlad = static_cast<float *>(workspace);
-  float *part_asum = part_vlad + (size_t)B * ch * kCl * kD;
+  Carve c(workspace);
+  const AggregateWs w(c, B, N);
+  DH3D_REQUIRE(workspace_bytes >= c.bytes());
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = sizeof(float) * (kTM * kLDX + kCl * kLDA + kCl);
-  auto kern = netvlad_assign_accumulate;
-  DH3D_ALLOW_BIG_LDS(kern);
-  hipLaunchKernelGGL(kern, dim3(ch, B), dim3(256), lds, s, x, att, wc_packed, bn_scale, bn_shift, N, ch,
-                     part_vlad, part_asum);
-  float *tot = part_asum + (size_t)B * ch * kCl;
-  hipLaunchKernelGGL(netvlad_finalize, dim3(kCl / kCG, B), dim3(1024), 0, s, part_vlad, part_asum, W2, ch, vlad, tot);
-  hipLaunchKernelGGL(netvlad_l2scale, dim3(kCl / kCG, B), dim3(256), 0, s, tot, vlad);
+  const int st = launch_aggregate(w, x, att, wc_packed, bn_scale, bn_shift, W2, B, N, vlad, s);
+  if (st != DH3D_OK) return st;
+  hipLaunchKernelGGL(netvlad_l2scale, dim3(kCl / kCG, B), dim3(256), 0, s, w.tot, vlad);
   return dh3d_launch_status();
 }
 
 DH3D_API size_t dh3d_netvlad_head_workspace_bytes(int B, int Kd, int O) {
   if (B <= 0 || Kd <= 0 || O != 256) return 0;
-  return sizeof(float) * (size_t)2 * dh3d_cdiv(Kd, kKSlice) * B * O;  // two k-half partials per slice
+  return carve_bytes<HeadWs>(B, Kd, O);
 }
 
 DH3D_API int dh3d_netvlad_head_fwd(const float *vlad, const float *Wh, const float *bn1_scale,
@@ -545,15 +599,11 @@ DH3D_API int dh3d_netvlad_head_fwd(const float *vlad, const float *Wh, const flo
   DH3D_REQUIRE(!Wg || (bn2_scale && bn2_shift));  // Wg == NULL: no context gating (gating=False, backbones.py:276)
   DH3D_REQUIRE(B > 0 && Kd > 0);
   DH3D_SUPPORTED(O == 256 && B <= 65535);
-  DH3D_REQUIRE(workspace_bytes >= dh3d_netvlad_head_workspace_bytes(B, Kd, O));
-  const int KS = dh3d_cdiv(Kd, kKSlice);
-  float *part = static_cast<float *>(workspace);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(netvlad_hidden_splitk, dim3(KS, dh3d_cdiv(B, 32), O / 64), dim3(256), 0, s, vlad, Wh, B, Kd, O,
-                     part);
-  hipLaunchKernelGGL(netvlad_gate, dim3(B), dim3(1024), 0, s, part, 2 * KS, B, O, bn1_scale, bn1_shift, Wg,
-                     bn2_scale, bn2_shift, l2_eps, static_cast<const float *>(nullptr), out);
-  return dh3d_launch_status();
+  Carve c(workspace);
+  const HeadWs w(c, B, Kd, O);
+  DH3D_REQUIRE(workspace_bytes >= c.bytes());
+  return launch_head(w.part, vlad, Wh, bn1_scale, bn1_shift, Wg, bn2_scale, bn2_shift, B, Kd, O, l2_eps, nullptr, out,
+                     (hipStream_t)stream);
 }
 
 // The tail behind the commuted aggregation (dense_x6.hip, dh3d_global_walk_planned_fwd): apart [B, m, Cl] = A' (the walk's
@@ -561,9 +611,8 @@ DH3D_API int dh3d_netvlad_head_fwd(const float *vlad, const float *Wh, const flo
 // then asum * W2 subtracted, intra-normalised, flattened, projected, gated.  m <= 1024.  workspace:
 // dh3d_netvlad_tail_workspace_bytes.
 DH3D_API size_t dh3d_netvlad_tail_workspace_bytes(int B, int D, int Cl, int O) {
-  const size_t h = dh3d_netvlad_head_workspace_bytes(B, D * Cl, O);
-  if (!h || D != kD || Cl != kCl) return 0;
-  return ((h + 255) & ~(size_t)255) + sizeof(float) * ((size_t)B * D * Cl + (size_t)B * (kCl / kCG));
+  if (B <= 0 || O != 256 || D != kD || Cl != kCl) return 0;
+  return carve_bytes<TailWs>(B, D, Cl, O);
 }
 
 DH3D_API int dh3d_netvlad_tail_assign_fwd(const float *apart, const float *coarse, const float *asum, int m, const float *W2,
@@ -573,32 +622,24 @@ DH3D_API int dh3d_netvlad_tail_assign_fwd(const float *apart, const float *coars
   DH3D_REQUIRE(apart && coarse && asum && W2 && Wh && bn1_scale && bn1_shift && workspace && out && B > 0 && m > 0);
   DH3D_REQUIRE(!Wg || (bn2_scale && bn2_shift));
   DH3D_SUPPORTED(D == kD && Cl == kCl && O == 256 && B <= 65535 && m <= 1024);
-  DH3D_REQUIRE(workspace_bytes >= dh3d_netvlad_tail_workspace_bytes(B, D, Cl, O));
-  const size_t hb = (dh3d_netvlad_head_workspace_bytes(B, D * Cl, O) + 255) & ~(size_t)255;
-  char *w = static_cast<char *>(workspace);
-  float *part = reinterpret_cast<float *>(w);
-  float *vlad = reinterpret_cast<float *>(w + hb);
-  float *tot = vlad + (size_t)B * D * Cl;
+  Carve c(workspace);
+  const TailWs w(c, B, D, Cl, O);
+  DH3D_REQUIRE(workspace_bytes >= c.bytes());
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = sizeof(float) * ((size_t)m * 8 + 8 * 8 * kD);
   DH3D_ALLOW_BIG_LDS(netvlad_assign_finalize);
-  hipLaunchKernelGGL(netvlad_assign_finalize, dim3(8 * dh3d_cdiv(B, 8) * (kCl / kCG)), dim3(1024), lds, s, apart, coarse, asum, W2, m, B, vlad, tot);
-  const int Kd = D * Cl, KS = dh3d_cdiv(Kd, kKSlice);
-  hipLaunchKernelGGL(netvlad_hidden_splitk, dim3(KS, dh3d_cdiv(B, 32), O / 64), dim3(256), 0, s, vlad, Wh, B, Kd, O,
-                     part);
-  hipLaunchKernelGGL(netvlad_gate, dim3(B), dim3(1024), 0, s, part, 2 * KS, B, O, bn1_scale, bn1_shift, Wg, bn2_scale,
-                     bn2_shift, l2_eps, static_cast<const float *>(tot), out);
-  return dh3d_launch_status();
+  hipLaunchKernelGGL(netvlad_assign_finalize, dim3(8 * dh3d_cdiv(B, 8) * (kCl / kCG)), dim3(1024), lds, s, apart, coarse,
+                     asum, W2, m, B, w.vlad, w.tot);
+  return launch_head(w.part, w.vlad, Wh, bn1_scale, bn1_shift, Wg, bn2_scale, bn2_shift, B, D * Cl, O, l2_eps, w.tot, out,
+                     s);
 }
 
 // Aggregation + projection + gating in one call (the model path): same result as dh3d_netvlad_aggregate_fwd followed by
 // dh3d_netvlad_head_fwd up to the rounding of one multiplication per output -- the whole-vector L2 normalisation is not
 // a kernel of its own (a pass over [B, 16384] + a dependency gap), its factor multiplies the projected vector instead.
-// workspace: dh3d_netvlad_workspace_bytes + dh3d_netvlad_head_workspace_bytes + 4*B*D*Cl bytes.
 DH3D_API size_t dh3d_netvlad_fused_workspace_bytes(int B, int N, int D, int Cl, int O) {
-  const size_t a = dh3d_netvlad_workspace_bytes(B, N, D, Cl), h = dh3d_netvlad_head_workspace_bytes(B, D * Cl, O);
-  if (!a || !h) return 0;
-  return ((a + 255) & ~(size_t)255) + ((h + 255) & ~(size_t)255) + sizeof(float) * (size_t)B * D * Cl;
+  if (B <= 0 || N <= 0 || D != kD || Cl != kCl || O != 256) return 0;
+  return carve_bytes<FusedWs>(B, N, D, Cl, O);
 }
 
 DH3D_API int dh3d_netvlad_fused_fwd(const float *x, const float *att, const float *wc_packed, const float *bn_scale,
@@ -609,27 +650,12 @@ DH3D_API int dh3d_netvlad_fused_fwd(const float *x, const float *att, const floa
   DH3D_REQUIRE(x && att && wc_packed && bn_scale && bn_shift && W2 && Wh && bn1_scale && bn1_shift && workspace && out);
   DH3D_REQUIRE(B > 0 && N > 0 && (!Wg || (bn2_scale && bn2_shift)));
   DH3D_SUPPORTED(D == kD && Cl == kCl && O == 256 && B <= 65535);
-  DH3D_REQUIRE(workspace_bytes >= dh3d_netvlad_fused_workspace_bytes(B, N, D, Cl, O));
-  const size_t a = (dh3d_netvlad_workspace_bytes(B, N, D, Cl) + 255) & ~(size_t)255;
-  const size_t hb = (dh3d_netvlad_head_workspace_bytes(B, D * Cl, O) + 255) & ~(size_t)255;
-  char *w = static_cast<char *>(workspace);
-  float *vlad = reinterpret_cast<float *>(w + a + hb);
-  const int ch = netvlad_chunks(B, N);
-  float *part_vlad = reinterpret_cast<float *>(w);
-  float *part_asum = part_vlad + (size_t)B * ch * kCl * kD;
-  float *tot = part_asum + (size_t)B * ch * kCl;
+  Carve c(workspace);
+  const FusedWs w(c, B, N, D, Cl, O);
+  DH3D_REQUIRE(workspace_bytes >= c.bytes());
   hipStream_t s = (hipStream_t)stream;
-  const size_t lds = sizeof(float) * (kTM * kLDX + kCl * kLDA + kCl);
-  auto kern = netvlad_assign_accumulate;
-  DH3D_ALLOW_BIG_LDS(kern);
-  hipLaunchKernelGGL(kern, dim3(ch, B), dim3(256), lds, s, x, att, wc_packed, bn_scale, bn_shift, N, ch, part_vlad,
-                     part_asum);
-  hipLaunchKernelGGL(netvlad_finalize, dim3(kCl / kCG, B), dim3(1024), 0, s, part_vlad, part_asum, W2, ch, vlad, tot);
-  const int Kd = D * Cl, KS = dh3d_cdiv(Kd, kKSlice);
-  float *part = reinterpret_cast<float *>(w + a);
-  hipLaunchKernelGGL(netvlad_hidden_splitk, dim3(KS, dh3d_cdiv(B, 32), O / 64), dim3(256), 0, s, vlad, Wh, B, Kd, O,
-                     part);
-  hipLaunchKernelGGL(netvlad_gate, dim3(B), dim3(1024), 0, s, part, 2 * KS, B, O, bn1_scale, bn1_shift, Wg, bn2_scale,
-                     bn2_shift, l2_eps, static_cast<const float *>(tot), out);
-  return dh3d_launch_status();
+  const int st = launch_aggregate(w.agg, x, att, wc_packed, bn_scale, bn_shift, W2, B, N, w.vlad, s);
+  if (st != DH3D_OK) return st;
+  return launch_head(w.part, w.vlad, Wh, bn1_scale, bn1_shift, Wg, bn2_scale, bn2_shift, B, D * Cl, O, l2_eps, w.agg.tot,
+                     out, s);
 }

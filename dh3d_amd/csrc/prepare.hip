@@ -27,6 +27,7 @@
 // All three compactions: per-tile counts, a scan of the tile counts per cloud, in-tile ranks by a workgroup scan.
 // This file is built with -ffp-contract=off: the double expressions below are evaluated as written.
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -56,30 +57,20 @@ struct Ws {
   int N, H, T;
 };
 
-struct Layout {
-  size_t hkey, dkey, tpart, head, hrep, hcnt, slot, next, members, flag, big, tsum, toff, st, p1, p2, bytes;
-  int H, T;
-};
-
-Layout make_layout(int B, int N) {
-  Layout L;
-  L.H = 64;
-  while (L.H < 2 * N) L.H <<= 1;
-  L.T = dh3d_cdiv(N, kTile);
-  size_t o = 0;
-  auto take = [&](size_t count, size_t elem) {
-    const size_t at = o;
-    o += ((size_t)B * count * elem + 15) & ~(size_t)15;
-    return at;
-  };
-  L.hkey = take(L.H, 8), L.dkey = take(N, 8), L.tpart = take((size_t)L.T * 3, 8);
-  L.head = take(L.H, 4), L.hrep = take(L.H, 4), L.hcnt = take(L.H, 4);
-  L.slot = take(N, 4), L.next = take(N, 4), L.members = take(N, 4), L.flag = take(N, 4);
-  L.big = take((size_t)(N / kSmallVox + 1) * 3, 4);
-  L.tsum = take((size_t)L.T * 2, 4), L.toff = take((size_t)L.T * 2, 4), L.st = take(ST_INTS, 4);
-  L.p1 = take((size_t)N * 3, 4), L.p2 = take((size_t)N * 3, 4);
-  L.bytes = o;
-  return L;
+// The workspace of B clouds of N raw points, every segment rounded up to 16 bytes: fills every field of Ws.
+Ws make_layout(Carve &c, int B, int N) {
+  Ws w;
+  w.N = N, w.H = 64;
+  while (w.H < 2 * N) w.H <<= 1;
+  w.T = dh3d_cdiv(N, kTile);
+  const size_t b = (size_t)B, H = w.H, T = w.T, n = N;
+  w.hkey = c.take<u64>(b * H, 16), w.dkey = c.take<u64>(b * n, 16), w.tpart = c.take<double>(b * T * 3, 16);
+  w.head = c.take<int>(b * H, 16), w.hrep = c.take<int>(b * H, 16), w.hcnt = c.take<int>(b * H, 16);
+  w.slot = c.take<int>(b * n, 16), w.next = c.take<int>(b * n, 16), w.members = c.take<int>(b * n, 16);
+  w.flag = c.take<int>(b * n, 16), w.big = c.take<int>(b * (N / kSmallVox + 1) * 3, 16);
+  w.tsum = c.take<int>(b * T * 2, 16), w.toff = c.take<int>(b * T * 2, 16), w.st = c.take<int>(b * ST_INTS, 16);
+  w.p1 = c.take<float>(b * n * 3, 16), w.p2 = c.take<float>(b * n * 3, 16);
+  return w;
 }
 
 __device__ __forceinline__ unsigned ord_bits(float v) {
@@ -535,7 +526,9 @@ bool shape_served(int B, int Nraw, int targetnum) { return B <= 65535 && Nraw <=
 
 DH3D_API size_t dh3d_prepare_clouds_workspace(int B, int Nraw, int targetnum) {
   if (!shape_ok(B, Nraw, targetnum) || !shape_served(B, Nraw, targetnum)) return 0;
-  return make_layout(B, Nraw).bytes;
+  Carve c(nullptr);
+  make_layout(c, B, Nraw);
+  return c.bytes();
 }
 
 DH3D_API int dh3d_prepare_clouds(int B, int Nraw, int targetnum, const float *raw, const int32_t *num_raw, double voxel_size,
@@ -544,23 +537,12 @@ DH3D_API int dh3d_prepare_clouds(int B, int Nraw, int targetnum, const float *ra
   DH3D_REQUIRE(shape_ok(B, Nraw, targetnum) && raw && num_raw && points && num_valid && counts && centroid && workspace);
   DH3D_REQUIRE(voxel_size >= 0.0 && voxel_size < 1e300 && radius >= 0.0 && radius < 1e150 && nb_points >= 0);
   DH3D_SUPPORTED(shape_served(B, Nraw, targetnum));
-  const Layout L = make_layout(B, Nraw);
-  DH3D_REQUIRE(workspace_bytes >= L.bytes && ((uintptr_t)workspace & 15) == 0);
-  char *base = static_cast<char *>(workspace);
-  Ws w;
-  w.hkey = reinterpret_cast<u64 *>(base + L.hkey), w.dkey = reinterpret_cast<u64 *>(base + L.dkey);
-  w.tpart = reinterpret_cast<double *>(base + L.tpart);
-  w.head = reinterpret_cast<int *>(base + L.head), w.hrep = reinterpret_cast<int *>(base + L.hrep);
-  w.hcnt = reinterpret_cast<int *>(base + L.hcnt), w.slot = reinterpret_cast<int *>(base + L.slot);
-  w.next = reinterpret_cast<int *>(base + L.next), w.members = reinterpret_cast<int *>(base + L.members);
-  w.flag = reinterpret_cast<int *>(base + L.flag), w.big = reinterpret_cast<int *>(base + L.big);
-  w.tsum = reinterpret_cast<int *>(base + L.tsum), w.toff = reinterpret_cast<int *>(base + L.toff);
-  w.st = reinterpret_cast<int *>(base + L.st);
-  w.p1 = reinterpret_cast<float *>(base + L.p1), w.p2 = reinterpret_cast<float *>(base + L.p2);
-  w.N = Nraw, w.H = L.H, w.T = L.T;
+  Carve c(workspace);
+  const Ws w = make_layout(c, B, Nraw);
+  DH3D_REQUIRE(workspace_bytes >= c.bytes() && ((uintptr_t)workspace & 15) == 0);
 
   hipStream_t s = (hipStream_t)stream;
-  const dim3 blk(kThreads), per_slot(dh3d_cdiv(L.H, kThreads), B), per_point(dh3d_cdiv(Nraw, kThreads), B), per_tile(L.T, B);
+  const dim3 blk(kThreads), per_slot(dh3d_cdiv(w.H, kThreads), B), per_point(dh3d_cdiv(Nraw, kThreads), B), per_tile(w.T, B);
   hipLaunchKernelGGL(prep_init_kernel, per_slot, blk, 0, s, w, num_raw, 1);
   if (voxel_size > 0.0) {
     hipLaunchKernelGGL(prep_min_kernel, per_tile, blk, 0, s, w, raw, (int)ST_N0);
