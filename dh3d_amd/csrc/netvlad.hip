@@ -598,7 +598,8 @@ DH3D_API int dh3d_netvlad_head_fwd(const float *vlad, const float *Wh, const flo
   DH3D_REQUIRE(vlad && Wh && bn1_scale && bn1_shift && workspace && out);
   DH3D_REQUIRE(!Wg || (bn2_scale && bn2_shift));  // Wg == NULL: no context gating (gating=False, backbones.py:276)
   DH3D_REQUIRE(B > 0 && Kd > 0);
-  DH3D_SUPPORTED(O == 256 && B <= 65535);
+  // Kd % 8: netvlad_hidden_splitk walks k in blocks of eight (a remainder would be dropped) and stages float4s of a row
+  DH3D_SUPPORTED(O == 256 && B <= 65535 && Kd % 8 == 0);
   Carve c(workspace);
   const HeadWs w(c, B, Kd, O);
   DH3D_REQUIRE(workspace_bytes >= c.bytes());

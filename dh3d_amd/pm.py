@@ -941,6 +941,8 @@ def netvlad_head(vlad, Wh, bn1_scale, bn1_shift, Wg, bn2_scale, bn2_shift, l2_ep
     v = L.require_cuda_f32(vlad, "vlad", 2)
     B, Kd = v.shape
     O = Wh.shape[1]
+    if Kd % 8 != 0:
+        raise ValueError("netvlad_head: unsupported shape Kd=%d (vlad's width must be a multiple of 8)" % Kd)
     ws_bytes = L.lib().dh3d_netvlad_head_workspace_bytes(B, Kd, O)
     if ws_bytes == 0:
         raise ValueError("netvlad_head: unsupported output dim %d" % O)

@@ -624,7 +624,8 @@ int dh3d_netvlad_aggregate_fwd(const float *x, const float *att, const float *wc
 
 /* NetVLAD projection + context gating (core/backbones.py:262-320):
  *   h = bn1(vlad @ Wh);  out = h * sigmoid(bn2(h @ Wg));  optional final L2 normalise (model.py:205).
- * vlad [B,Kd], Wh [Kd,O], Wg [O,O] row-major; bn as (scale,shift) [O]. O = 256.
+ * vlad [B,Kd], Wh [Kd,O], Wg [O,O] row-major (NULL: no gating); bn as (scale,shift) [O]. O = 256, Kd % 8 == 0 (the
+ * split-K projection takes k in blocks of eight; anything else is DH3D_ERR_UNSUPPORTED).  l2_eps == 0: no final normalise.
  * workspace: dh3d_netvlad_head_workspace_bytes(B,Kd,O). */
 size_t dh3d_netvlad_head_workspace_bytes(int B, int Kd, int O);
 int dh3d_netvlad_head_fwd(const float *vlad, const float *Wh, const float *bn1_scale,

@@ -39,7 +39,7 @@ third-order product is 160 or more.
 Entry points of the three files this file does not reach: dh3d_pack_flex_weight (flex_conv's operand, with the flex
 tests), dh3d_interp_head_sorted_fwd_dev (the trainers' variant of the staged head: tests/test_commuted_walks_gpu.py),
 dh3d_walk_plan / dh3d_walk_plan_bytes / dh3d_global_walk_planned_fwd (the planned global walk) and, outside them, every
-netvlad_* entry point -- the NetVLAD side is a later pass.  dh3d_pack_weight and dh3d_pack_weight_x3 are reached
+netvlad_* entry point -- those are tests/test_netvlad_kernels_gpu.py's.  dh3d_pack_weight and dh3d_pack_weight_x3 are reached
 through every probe of (a): a wrong fragment order moves a column or a k.
 """
 import numpy as np
