@@ -758,30 +758,100 @@ __global__ __launch_bounds__(64 * S) void knn_split_kernel(const float4 *__restr
 // ------------------------------------------------------------------------------------------------
 // Small clouds (N <= 2048: the N/8 sampled sets of the model).  The lane-per-query kernels above leave most of the
 // chip idle there (B*N/64 waves, each a long dependent scan).  Here a WAVE owns a query: every lane holds
-// CPL = N/64 candidates in registers (loaded once, reused for 4 queries), computes their exact keys
-// (bits(sqrt d) << 32 | tb), and the K nearest come out of K rounds of "smallest key >= last + 1" -- a per-lane
-// scan plus a two-step unsigned wave minimum on the DPP crossbar.  Keys are unique (tb is), so the strict
-// threshold replaces any bookkeeping of what was taken.  Same keys, same order, same outputs as knn_kernel.
+// CPL = N/64 candidates in registers (loaded once, reused for Q queries) and evaluates their squared distances s.
+// The K nearest are the K smallest keys (bits(sqrt s) << 32 | tb); keys are unique (tb is).  Same keys, same order,
+// same outputs as knn_kernel.
+//
+// K <= 8 -- the screened path.  Only candidates that can reach the K-list get a square root and a key:
+//   U     = the largest of the eight minima of s over the lane groups 8g..8g+7 (all slots of a lane): eight disjoint
+//           groups each hold a candidate with s <= U, so at least 8 >= K candidates do and the K-th nearest has
+//           d_K <= sqrt(U) (sqrtf is correctly rounded, hence monotone).  A group without a valid candidate
+//           (N < 57 or so) makes U = +inf, which screens nothing out.
+//   keep  s <= U * 1.000001f.  The knn_insert_key margin: a relative 2^-20 in s is 2^-21 in d, more than 3 ulp, so
+//           any s above the inflated bound has sqrt(s) > sqrt(U) >= d_K strictly and loses to K candidates whatever
+//           its tb.  Two candidates with s1 < s2 but one rounded distance both stay, and tb orders them as the
+//           reference does.  U = 0 (8 copies of the query) keeps exactly the copies.
+//   Slots past N carry NaN coordinates: their s is a NaN, which no v_min picks and no `<=` admits, +inf bound or not.
+//   The survivors are compacted to one per lane through a 64-entry LDS strip per wave (position = v_mbcnt of the
+//   slot's ballot + a scalar running count), each lane takes ONE sqrtf and builds one key, and K rounds of the
+//   two-step unsigned wave minimum pick the list; the winner retires its key.
+//   Counted on uniform cubes (a numpy restatement, tests/test_knn_small_screen_gpu.py): 20-22 survivors per query on
+//   average at N = 512, 1024 and 2048, the most over the test clouds 64; a larger sample at N = 2048 has 0.3 % of the
+//   queries above 64.
+// Otherwise -- K > 8, more than 64 survivors (lattices, duplicate-heavy clouds), or fewer than K survivors in a cloud of
+// K or more (NaN distances) -- the wave takes knn_small_select_all for this query: every candidate's key, as before
+// the screen.  The choice is wave-uniform and made per query.
+
+// Every candidate's key; each lane caches its two smallest admissible keys (m1 < m2): a round is two wave minima and a
+// pop in the winning lane, the per-lane scan over all CPL keys is redone only when some lane has used up both.
+// s[] is overwritten with the distance bits.
+template <int CPL>
+__device__ __forceinline__ void knn_small_select_all(float (&s)[CPL], int N, int K, const KnnLadder &lad, int lane,
+                                                     unsigned &my_hi, unsigned &my_lo) {
+  // (the rank codes are rebuilt from an opaque copy of the lane id at every scan: as loop invariants of the query loop
+  // they would be hoisted into CPL registers held across the screened path too)
+  int ln = lane;
+  asm volatile("" : "+v"(ln));
+  unsigned kd[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) kd[c] = ln + 64 * c < N ? __float_as_uint(sqrtf(s[c])) : 0xFFFFFFFFu;
+  u64 need = 0;  // smallest key still admissible
+  u64 m1 = ~0ull, m2 = ~0ull;
+  bool more = false;  // this lane may hold admissible keys beyond m2
+  auto rescan = [&]() {
+    m1 = ~0ull; m2 = ~0ull;
+    int cnt = 0;
+    asm volatile("" : "+v"(ln));
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int j = ln + 64 * c;
+      const unsigned tb = j < N ? (unsigned)((j & lad.ctmask) * lad.cv + (j >> lad.log2ct)) : 0xFFFFFFFFu;
+      const u64 key = ((u64)kd[c] << 32) | tb;
+      const bool ok = key >= need && key != ~0ull;
+      const bool c1 = ok && key < m1, c2 = ok && key < m2;
+      m2 = c1 ? m1 : (c2 ? key : m2);
+      m1 = c1 ? key : m1;
+      cnt += ok ? 1 : 0;
+    }
+    more = cnt > 2;
+  };
+  rescan();
+  for (int r = 0; r < K; ++r) {
+    const unsigned hi = wave_min_u32((unsigned)(m1 >> 32));
+    const unsigned lo = wave_min_u32((unsigned)(m1 >> 32) == hi ? (unsigned)m1 : 0xFFFFFFFFu);
+    if (lane == r) { my_hi = hi; my_lo = lo; }
+    const u64 sel = ((u64)hi << 32) | lo;
+    if (sel == ~0ull) break;  // fewer than K points: the remaining slots keep the pad value
+    need = sel + 1;
+    const bool won = m1 == sel;
+    const bool dry = won && m2 == ~0ull && more;  // both cached keys used, more behind them
+    m1 = won ? m2 : m1;
+    m2 = won ? ~0ull : m2;
+    if (__ballot(dry) != 0ull) rescan();  // wave-uniform
+  }
+}
+
 template <int CPL, bool XYZ>
 __global__ __launch_bounds__(256) void knn_small_kernel(const float *__restrict__ pos, int N, int K, KnnLadder lad,
                                                        int32_t *__restrict__ nn, float *__restrict__ dist, int Q) {
   // Q: queries per wave (the candidates are loaded once per wave): 4, or 2 when that still leaves few waves per SIMD --
   // a query is K dependent rounds of two DPP reductions, the kernel is as long as one wave's queries
+  __shared__ uint2 s_strip[4][64];  // per wave: (bits(s), id) of the survivors, 2 KiB a workgroup
   const int b = blockIdx.y, lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q0 = (blockIdx.x * 4 + wave) * Q;
   if (q0 >= N) return;
   const float *base = pos + (size_t)b * N * 3;
   float cx[CPL], cy[CPL], cz[CPL];
-  unsigned tbk[CPL];
 #pragma unroll
   for (int c = 0; c < CPL; ++c) {
     const int j = lane + 64 * c, jj = j < N ? j : 0;
-    cx[c] = XYZ ? base[(size_t)jj * 3] : base[jj];
+    const float x = XYZ ? base[(size_t)jj * 3] : base[jj];
+    cx[c] = j < N ? x : __builtin_nanf("");  // (one NaN coordinate makes the slot's s a NaN)
     cy[c] = XYZ ? base[(size_t)jj * 3 + 1] : base[(size_t)N + jj];
     cz[c] = XYZ ? base[(size_t)jj * 3 + 2] : base[(size_t)2 * N + jj];
-    tbk[c] = j < N ? (unsigned)((j & lad.ctmask) * lad.cv + (j >> lad.log2ct)) : 0xFFFFFFFFu;
   }
+  uint2 *strip = s_strip[wave];
 #pragma unroll 1
   for (int qi = 0; qi < Q; ++qi) {
     const int q = q0 + qi;
@@ -789,48 +859,58 @@ __global__ __launch_bounds__(256) void knn_small_kernel(const float *__restrict_
     const float qx = XYZ ? base[(size_t)q * 3] : base[q];
     const float qy = XYZ ? base[(size_t)q * 3 + 1] : base[(size_t)N + q];
     const float qz = XYZ ? base[(size_t)q * 3 + 2] : base[(size_t)2 * N + q];
-    unsigned kd[CPL];
+    float s[CPL];
+    float smin = __builtin_inff();
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
       // same roundings as knn_offer / the reference: sqrt(fma(dz,dz,fma(dy,dy,dx*dx))), :102-107
       const float dx = qx - cx[c], dy = qy - cy[c], dz = qz - cz[c];
-      const float d = sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
-      kd[c] = tbk[c] != 0xFFFFFFFFu ? __float_as_uint(d) : 0xFFFFFFFFu;
+      s[c] = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+      smin = fminf(smin, s[c]);  // (minnum: the NaN of an invalid slot is dropped)
     }
-    // Every lane caches its two smallest admissible keys (m1 < m2): a round is then two wave minima and a pop in the
-    // winning lane; the per-lane scan over all CPL keys -- most of a round before -- is redone only when some lane has
-    // used up both (it won three of the rounds so far: rare, the K nearest spread over the 64 lanes).
-    u64 need = 0;  // smallest key still admissible
     unsigned my_hi = 0xFFFFFFFFu, my_lo = 0xFFFFFFFFu;  // lane r keeps result r
-    u64 m1 = ~0ull, m2 = ~0ull;
-    bool more = false;  // this lane may hold admissible keys beyond m2
-    auto rescan = [&]() {
-      m1 = ~0ull; m2 = ~0ull;
-      int cnt = 0;
+    bool screened = K <= 8;  // wave-uniform throughout
+    int cnt = 0;
+    if (screened) {
+      const float ub = __fmul_rn(wave_max_of_min8_f32(smin), 1.000001f);
+      // (an opaque copy of the lane id: the ids lane + 64 c are query-loop invariants, and hoisted they hold CPL registers)
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
 #pragma unroll
       for (int c = 0; c < CPL; ++c) {
-        const u64 key = ((u64)kd[c] << 32) | tbk[c];
-        const bool ok = key >= need && key != ~0ull;
-        const bool c1 = ok && key < m1, c2 = ok && key < m2;
-        m2 = c1 ? m1 : (c2 ? key : m2);
-        m1 = c1 ? key : m1;
-        cnt += ok ? 1 : 0;
+        const bool in = s[c] <= ub;
+        const u64 mk = __ballot(in);
+        const int at0 = cnt;
+        cnt += __popcll(mk);  // scalar; once past 64 it stays there and nothing more is written: the strip holds 64
+        if (in && cnt <= 64) {
+          const unsigned at = __builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+          (strip + at0)[at] = make_uint2(__float_as_uint(s[c]), (unsigned)(ln + 64 * c));
+        }
       }
-      more = cnt > 2;
-    };
-    rescan();
-    for (int r = 0; r < K; ++r) {
-      const unsigned hi = wave_min_u32((unsigned)(m1 >> 32));
-      const unsigned lo = wave_min_u32((unsigned)(m1 >> 32) == hi ? (unsigned)m1 : 0xFFFFFFFFu);
-      if (lane == r) { my_hi = hi; my_lo = lo; }
-      const u64 sel = ((u64)hi << 32) | lo;
-      if (sel == ~0ull) break;  // fewer than K points: the remaining slots keep the pad value
-      need = sel + 1;
-      const bool won = m1 == sel;
-      const bool dry = won && m2 == ~0ull && more;  // both cached keys used, more behind them
-      m1 = won ? m2 : m1;
-      m2 = won ? ~0ull : m2;
-      if (__ballot(dry) != 0ull) rescan();  // wave-uniform
+      screened = cnt <= 64 && (cnt >= K || cnt >= N);  // (only NaN distances can leave fewer than K of N >= K)
+    }
+    if (screened) {
+      // the strip is wave-private and LDS operations of a wave complete in order: the fences only pin the compiler
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const uint2 e = strip[lane];  // (lanes >= cnt read a stale entry and drop it)
+      const float d = sqrtf(__uint_as_float(e.x));
+      const int j = (int)e.y;
+      unsigned khi = lane < cnt ? __float_as_uint(d) : 0xFFFFFFFFu;
+      unsigned klo = lane < cnt ? (unsigned)((j & lad.ctmask) * lad.cv + (j >> lad.log2ct)) : 0xFFFFFFFFu;
+      for (int r = 0; r < K; ++r) {
+        const unsigned hi = wave_min_u32(khi);
+        const unsigned lo = wave_min_u32(khi == hi ? klo : 0xFFFFFFFFu);
+        if (lane == r) { my_hi = hi; my_lo = lo; }
+        if ((hi & lo) == 0xFFFFFFFFu) break;  // fewer than K points: the remaining slots keep the pad value
+        const bool won = khi == hi && klo == lo;
+        khi = won ? 0xFFFFFFFFu : khi;
+        klo = won ? 0xFFFFFFFFu : klo;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the next query's writes stay behind this read)
+    } else {
+      knn_small_select_all<CPL>(s, N, K, lad, lane, my_hi, my_lo);
     }
     if (lane < K) {
       const size_t o = ((size_t)b * N + q) * K + lane;

@@ -60,6 +60,19 @@ __device__ __forceinline__ float row16_min_f32(float v) {
   asm volatile(DH3D_DPP_ROW16("v_min_f32_dpp") "s_nop 1\n\t" : "+v"(v));
   return v;
 }
+// The largest of the eight 8-lane minima (lanes 8g .. 8g+7), wave-uniform: three min steps leave every lane of a half
+// row with its group's minimum, row_mirror pairs the two groups of a row, the row_bcast steps carry the maximum to
+// lane 63.  No input may be a NaN (v_min would drop it, v_max would not).
+__device__ __forceinline__ float wave_max_of_min8_f32(float v) {
+  asm volatile(
+      "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+      DH3D_DPP_ROWS("v_max_f32_dpp")
+      : "+v"(v));
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
 
 // Sums (not idempotent, but every step pairs DISJOINT partial groups, so nothing is counted twice):
 // after the four row steps every lane of a 16-lane row holds the row's sum; row_bcast:15 adds row 0's (2's) sum into
