@@ -71,6 +71,7 @@ _SIGNATURES = {
     "dh3d_flex_deconv_bwd_ws": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp,
                                 c_fp, c_fp, c_fp, c_size_t, c_fp],
     "dh3d_flex_conv_fwd_workspace_bytes": [c_int, c_int, c_int, c_int, c_int, c_int],
+    "dh3d_flex_conv_fwd_plan": [c_int, c_int, c_int, c_int, c_int, c_int],
     "dh3d_flex_conv_fwd_ws": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp,
                               c_size_t, c_fp],
     "dh3d_flex_conv_bwd_workspace_bytes": [c_int, c_int, c_int, c_int, c_int, c_int],

@@ -206,6 +206,12 @@ DH3D_API size_t dh3d_flex_conv_fwd_workspace_bytes(int B, int N, int K, int Dp, 
   return kind ? carve_bytes<ConvFwdWs>((size_t)B * N, K, Din, Dout, kind) : 0;
 }
 
+DH3D_API int dh3d_flex_conv_fwd_plan(int B, int N, int K, int Dp, int Din, int Dout) {
+  bool x6;
+  const int kind = fast_fwd_kind(B, N, K, Dp, Din, Dout, &x6);
+  return kind && x6 ? 3 : kind;
+}
+
 DH3D_API int dh3d_flex_conv_fwd_ws(const float *features, const float *theta, const float *bias,
                                    const int32_t *neighborhood, const float *positions, int B, int N, int K, int Dp,
                                    int Din, int Dout, float *output, void *workspace, size_t workspace_bytes,

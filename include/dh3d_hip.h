@@ -269,6 +269,12 @@ int dh3d_three_interpolate_bwd(int b, int n, int c, int m, const float *grad_out
  * The backward is  dWcat = S^T dOut,  dS = dOut Wcat^T  on the f32 MFMA pipe + an atomics scatter of dS over the
  * neighbour lists (the reference's feature gradient is atomics too, flex_conv_kernel_gpu.cu.cc:250-385). */
 size_t dh3d_flex_conv_fwd_workspace_bytes(int B, int N, int K, int Dp, int Din, int Dout);
+/* Which forward serves a shape in dh3d_flex_conv_fwd_ws: 3 the persistent bf16x6 kernel (Dp = 3, K = 8, Dout = 64, Din in
+ * {32, 64}), 1 the fused f32-MFMA kernel (the seven DH3D (Din, Dout) pairs, any K), 2 flex_S + GEMM (any other Din, Dout
+ * that are multiples of four), 0 not served: dh3d_flex_conv_fwd_workspace_bytes is 0 and the section-A entry runs (Dp != 3,
+ * N = 1, other channel counts, extents beyond the kernels' 32-bit indices).  Host only; looks at the shape alone, never
+ * at the data. */
+int dh3d_flex_conv_fwd_plan(int B, int N, int K, int Dp, int Din, int Dout);
 int dh3d_flex_conv_fwd_ws(const float *features, const float *theta, const float *bias,
                           const int32_t *neighborhood, const float *positions, int B, int N, int K, int Dp,
                           int Din, int Dout, float *output, void *workspace, size_t workspace_bytes, void *stream);

@@ -89,6 +89,42 @@ def test_knn_grid_plan_is_the_launchers_choice():
         assert codes == sorted(codes, reverse=True), N
 
 
+def test_flex_conv_fwd_plan_is_the_dispatchers_choice():
+    """dh3d_flex_conv_fwd_plan (host only): the forward dh3d_flex_conv_fwd_ws runs for a shape -- 3 the bf16x6 kernel, 1 the
+    fused f32-MFMA kernel, 2 flex_S + GEMM, 0 not served, which is exactly where the workspace query returns 0."""
+    from dh3d_amd import _lib
+    lib = _lib.lib()
+    header = open(os.path.join(ROOT, "include", "dh3d_hip.h")).read()
+    assert re.search(r"\bint\s+dh3d_flex_conv_fwd_plan\s*\(", header) and "dh3d_flex_conv_fwd_plan" in _lib.EXPORTED_SYMBOLS
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "dh3d_flex_conv_fwd_plan")
+    assert lib.dh3d_abi_version() == 4 == _lib.ABI_VERSION                                   # an addition only
+    said = header[header.index("size_t dh3d_flex_conv_fwd_workspace_bytes"):header.index("int dh3d_flex_conv_fwd_plan")]
+    assert "Host only; looks at the shape alone" in said
+    plan, ws = lib.dh3d_flex_conv_fwd_plan, lib.dh3d_flex_conv_fwd_workspace_bytes
+    pairs = [(32, 64), (32, 128), (64, 64), (64, 128), (64, 256), (128, 128), (128, 256)]
+    seen = set()
+    for B in (-1, 0, 1, 3):
+        for N in (0, 1, 2, 257):
+            for K in (0, 1, 5, 8, 12):
+                for Dp in (1, 2, 3, 4):
+                    for Din, Dout in pairs + [(4, 4), (36, 100), (48, 96), (64, 32), (128, 64), (3, 7), (33, 64), (32, 66)]:
+                        r = plan(B, N, K, Dp, Din, Dout)
+                        assert r in (0, 1, 2, 3) and (r == 0) == (ws(B, N, K, Dp, Din, Dout) == 0), (B, N, K, Dp, Din, Dout)
+                        if B <= 0 or N <= 1 or K <= 0 or Dp != 3 or Din % 4 or Dout % 4:
+                            assert r == 0, (B, N, K, Dp, Din, Dout)
+                        elif (Din, Dout) in pairs:
+                            assert r == (3 if K == 8 and Dout == 64 else 1), (K, Din, Dout)
+                        else:
+                            assert r == 2, (K, Din, Dout)
+                        seen.add(r)
+    assert seen == {0, 1, 2, 3}
+    assert [plan(2, 300, 8, 3, di, do) for di, do in pairs] == [3, 1, 3, 1, 1, 1, 1]          # the table's seven pairs
+    assert plan(2, 300, 8, 3, 32, 64) == 3 and plan(2, 300, 5, 3, 32, 64) == 1                # K != 8: x6 -> the f32 kernel
+    assert plan(2, 300, 12, 3, 64, 64) == 1 and plan(2, 300, 8, 3, 48, 96) == 2
+    assert plan(2, 300, 8, 2, 32, 64) == 0 and plan(4, 1, 1, 3, 32, 64) == 0                  # Dp = 2; N = 1
+    assert plan(1 << 14, 1 << 16, 8, 3, 64, 64) == 0 and plan(1 << 13, 1 << 14, 8, 3, 4, 4) == 0   # beyond 32-bit indices
+
+
 def test_library_was_built_from_this_tree():
     """The loaded library carries the hash of the sources it was compiled from (csrc/Makefile SRC_HASH -> dh3d_source_hash):
     a stale .so that travelled with the tree (built artefacts are git-ignored, not gpurun-ignored) fails here."""
