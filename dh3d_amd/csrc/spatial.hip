@@ -11,10 +11,12 @@
 // bits(original index)) and one box per group of 64.
 // The cell code (round 5) is a Morton code whose bits are dealt to the axes BY EXTENT: the top 12 bits (the grid of the
 // cell-list kNN) go one at a time to the axis whose cells are currently the widest (ties: z, y, x -- a cube gets 4 + 4 + 4
-// bits interleaved z y x z y x ..., exactly the plain Morton code of rounds 1-4), two more bits per axis follow.  A street
-// scene 36 x 36 x 8 m gets 5 + 5 + 2: 32 x 32 x 4 cells of 1.1 x 1.1 x 2 m instead of 16 x 16 x 16 cells of
-// 2.25 x 2.25 x 0.5 m -- with the ground plane in one or two layers either way, the 27 cells around a query then hold ~60
-// points instead of ~230.  The schedule (which axis every one of the 12 bits belongs to) travels in the cell table's header.
+// bits interleaved z y x z y x ..., exactly the plain Morton code of rounds 1-4), two more bits per axis follow.  A tie
+// is a width within 25 % of the widest so far, so equally wide axes do NOT end with equally many bits: a street scene
+// 36 x 36 x 8 m gets 4 + 5 + 3 (steps y x y x z y x z y x z y; tests/spatial_reference.py restates the rule and
+// tests/test_spatial_reference.py derives this list by hand): 16 x 32 x 8 cells of 2.25 x 1.125 x 1 m instead of
+// 16 x 16 x 16 cells of 2.25 x 2.25 x 0.5 m.  The schedule (which axis every one of the 12 bits belongs to) travels in
+// the cell table's header.
 // (The first version was a bitonic network: 91 barrier-separated stages, 70 us for 8 x 8192 -- on the critical
 //  path of both the kNN and the FPS.  The radix sort produces the identical order: stable by cell = (cell, index).)
 #include <math.h>

@@ -361,7 +361,9 @@ def test_fps_sorted_ordered_sampled_set(dev, oracle, case):
         cell_of_pos = np.searchsorted(ct[b, 1:4097], np.arange(N), side="right")     # cloud position -> cell
         assert np.array_equal(np.bincount(cell_of_pos[ppos], minlength=4096), np.diff(cs[b, :4097]))
         assert np.array_equal(cs[b, 4100:4106], ct[b, 4100:4106]) and cs[b, 4107] == ct[b, 4107]   # the cloud's grid
-        assert cs[b, 4106] in (0, 1)
+        # the crowded flag: spatial.hip's rule for a set of m points (fps.hip: occ_min) on the subset's own occupancy
+        occupied = int((np.diff(cs[b, :4097]) > 0).sum())
+        assert cs[b, 4106] == int(occupied < int(0.6 * 4096.0 * (1.0 - np.exp(-m / 4096.0)))), (b, cs[b, 4106], occupied)
     # consumers
     d3, i3 = pm.three_nn_sorted(srt, gbox, srt_s, gbox_s)
     ed, ei = oracle.three_nn(xyz, xs)
