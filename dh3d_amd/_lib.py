@@ -238,6 +238,9 @@ _SIGNATURES = {
     "dh3d_prepare_clouds_workspace": [c_int, c_int, c_int],
     "dh3d_prepare_clouds": [c_int, c_int, c_int, c_fp, c_fp, c_double, c_double, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
                             c_size_t, c_fp],
+    "dh3d_retrieve_plan": [c_int, c_int, c_int, c_int],
+    "dh3d_retrieve_ws_bytes": [c_int, c_int, c_int, c_int],
+    "dh3d_retrieve": [c_fp, c_ll, c_fp, c_fp, c_ll, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp],
 }
 _RESTYPES = {
     "dh3d_arch": ctypes.c_char_p,
@@ -256,6 +259,7 @@ _RESTYPES = {
     "dh3d_flex_deconv_bwd_workspace_bytes": c_size_t,
     "dh3d_keypoint_nms_workspace_bytes": c_size_t,
     "dh3d_prepare_clouds_workspace": c_size_t,
+    "dh3d_retrieve_ws_bytes": c_size_t,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

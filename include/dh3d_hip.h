@@ -973,6 +973,37 @@ int dh3d_prepare_clouds(int B, int Nraw, int targetnum, const float *raw, const 
                         double radius, int nb_points, int sortby_dis, float *points, int32_t *num_valid, int32_t *counts,
                         double *centroid, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Place retrieval (csrc/retrieval.hip) -- evaluation_retrieval.py:37-40, cKDTree(database).query(queries, k): the exact
+ * float64 top-k search of Q query descriptors in a map of R reference descriptors, without a [Q, R] matrix.
+ * INPUTS: ref holds R rows of D floats, row j at ref + j * ref_stride; qry holds Q rows likewise with qry_stride (strides in
+ *   elements, any value >= D: a column view such as rows[:, 3:131] of 132-column rows is read in place, as
+ *   dh3d_match_descriptors does).  ref_count: a device pointer to one int32, or NULL.  The live map is rows 0 .. r-1 with
+ *   r = clamp(*ref_count, 0, R); NULL means r = R.  Rows >= r are never read.  The host never learns r: a captured graph
+ *   keeps serving a map that grows inside its capacity R.
+ * DISTANCE: d2(q, j) = the sum over c ascending, starting from 0, of ((double)q_c - (double)r_jc)^2; every subtraction,
+ *   product and addition is rounded to float64 on its own (no fma contraction).
+ * ORDER: ascending by (d2, j): ties go to the lowest map id.
+ * OUTPUTS: idx [Q, k] and dist2 [Q, k] hold the first min(k, r) entries of that order per query; the remaining entries are
+ *   -1 and +inf.  Every element is written.
+ * INDEPENDENCE: a query's row does not depend on Q, on the other queries, on the capacity R beyond r, on the number of
+ *   slices S, on the workspace's content or on the run.
+ * NaN and infinite inputs are outside the contract.
+ * dh3d_retrieve_plan (host only; looks at the four numbers alone): the number S >= 1 of contiguous slices the map is cut into,
+ *   each scanned by its own workgroups (slice s = rows [s * L, (s + 1) * L) with L = 256 * ceil(ceil(R / 256) / S); none is
+ *   empty), or -1 for a shape the call refuses.  S = min(ceil(R / 256), max(1, 512 / ceil(Q / 16))), then lowered to
+ *   ceil(ceil(R / 256) / (L / 256)): a few queries against a large map still fill the machine, many queries do not split.
+ *   S > 1 adds one launch that merges the S partial lists of the workspace.
+ * dh3d_retrieve_ws_bytes (host only): bytes of the caller-owned workspace (16-byte aligned, no clearing needed); 0
+ *   exactly where the plan is -1.
+ * SIDE EFFECTS: caller's stream, no host sync, no allocation, no atomics on global memory; graph-capturable, one launch
+ *   after the other (no parallel branches).
+ * STATUS: D % 4 != 0, D > 256 or k > 64: DH3D_ERR_UNSUPPORTED (plan -1, workspace 0).  NULL ref, qry, idx or dist2,
+ *   Q / R / D / k <= 0, a stride below D, a NULL, misaligned or too small workspace: DH3D_ERR_INVALID_ARGUMENT. */
+int dh3d_retrieve_plan(int Q, int R, int D, int k);
+size_t dh3d_retrieve_ws_bytes(int Q, int R, int D, int k);
+int dh3d_retrieve(const float *ref, long long ref_stride, const int32_t *ref_count, const float *qry, long long qry_stride,
+                  int Q, int R, int D, int k, int32_t *idx, double *dist2, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
