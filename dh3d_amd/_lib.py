@@ -241,6 +241,12 @@ _SIGNATURES = {
     "dh3d_retrieve_plan": [c_int, c_int, c_int, c_int],
     "dh3d_retrieve_ws_bytes": [c_int, c_int, c_int, c_int],
     "dh3d_retrieve": [c_fp, c_ll, c_fp, c_fp, c_ll, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_size_t, c_fp],
+    "dh3d_resample_clouds_ws_bytes": [c_int, c_int, c_int],
+    "dh3d_resample_clouds": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp],
+    "dh3d_augment_clouds": [c_int, c_int, c_fp, ctypes.c_uint, c_double, c_double, c_double, c_double, c_double, c_double,
+                            c_double, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_pair_rotate": [c_int, c_int, c_fp, c_double, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_sample_pair_nodes": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
 }
 _RESTYPES = {
     "dh3d_arch": ctypes.c_char_p,
@@ -260,6 +266,7 @@ _RESTYPES = {
     "dh3d_keypoint_nms_workspace_bytes": c_size_t,
     "dh3d_prepare_clouds_workspace": c_size_t,
     "dh3d_retrieve_ws_bytes": c_size_t,
+    "dh3d_resample_clouds_ws_bytes": c_size_t,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

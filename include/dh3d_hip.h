@@ -1004,6 +1004,81 @@ size_t dh3d_retrieve_ws_bytes(int Q, int R, int D, int k);
 int dh3d_retrieve(const float *ref, long long ref_stride, const int32_t *ref_count, const float *qry, long long qry_stride,
                   int Q, int R, int D, int k, int32_t *idx, double *dist2, void *ws, size_t ws_bytes, void *stream);
 
+/* Training batches (csrc/pairs.hip) -- what core/datasets.py builds on the host, one cloud at a time, between the prepared
+ * clouds and the trainers: Local_train_dataset_selfpair.loadPair (:119-151) and Global_train_dataset_triplet.loadPC
+ * (:184-191) over core/utils.py get_fixednum_pcd(randsample = True), core/augment.py and FarthestSampler.sample.
+ * RANDOMNESS.  numpy's streams cannot be reproduced; every draw is a pure function of (seed, stream, b, j), with splitmix64
+ *   as written out at dh3d_ransac_rigid and uint64 wrap-around everywhere:
+ *     h(stream, b) = splitmix64(splitmix64(seed) ^ ((uint64(stream) << 32) | uint64(b)))
+ *     u(stream, b, j) = splitmix64(h(stream, b) + j)
+ *   b is the cloud's (for dh3d_pair_rotate / dh3d_sample_pair_nodes: the pair's) index in the call.  A uniform double in
+ *   [0, 1) is U = (u >> 11) * 2^-53; in (0, 1] it is (u >> 11) * 2^-53 + 2^-53.  An integer in [0, n) is u mod n.  A standard
+ *   normal for element e is z(stream, b, e) = sqrt(-2 ln U1) * cos(2 pi U2) in float64 (Box-Muller, cosine branch only) with
+ *   U1 in (0, 1] from u(stream, b, 2e) and U2 in [0, 1) from u(stream, b, 2e + 1).  A random choice of m from n without
+ *   replacement is the m indices i with the smallest keys (u(stream, b, i), i), emitted in ascending i (a stable compaction;
+ *   splitmix64 is a bijection, so the u alone never tie).  The streams:
+ *     1 resample keys   2 pad draws   3 Rotate1D angle   4 jitter   5 scale   6 RotateSmall angles   7 shift
+ *     8 pair rotation   9 subset keys   10 first pick
+ *   seed is a DEVICE pointer to one uint64, read by the kernels: a captured graph draws a fresh batch on every replay when
+ *   the caller changes that scalar between replays.
+ * Every entry point below: caller's stream, no allocation, no synchronisation, graph-capturable (launches one after the
+ *   other, no parallel branches); every output element is written; cloud b's result depends on (seed, b) and its own rows,
+ *   not on B, on the other clouds, on the workspace's content or on the run.  B, N, Nsrc, targetnum <= 0 or a NULL pointer:
+ *   DH3D_ERR_INVALID_ARGUMENT; B > 65535: DH3D_ERR_UNSUPPORTED.  NaN and infinite coordinates are outside the contract.
+ *
+ * dh3d_resample_clouds -- get_fixednum_pcd(randsample = True, sortby_dis = False) after its outlier removal (which
+ *   dh3d_prepare_clouds does; its sortby_dis crop followed by this call restates loadPC's sortby_dis = True draw).
+ *   points [B, Nsrc, 3], num_valid [B]: cloud b is rows 0 .. n-1, n = clamp(num_valid[b], 0, Nsrc); rows >= n are never read.
+ *   n >= targetnum: a random choice (stream 1) of targetnum from n.  0 < n < targetnum: the n rows, then row
+ *   u(2, b, j) mod n for j = 0 .. targetnum-n-1.  n == 0: rows of 100000.0.  out [B, targetnum, 3], num_orig [B] =
+ *   min(n, targetnum).  Nsrc <= 131072, targetnum <= 2^20 (else DH3D_ERR_UNSUPPORTED, workspace 0); a NULL, too small or not
+ *   16-byte aligned workspace: DH3D_ERR_INVALID_ARGUMENT.  The workspace needs no clearing. */
+size_t dh3d_resample_clouds_ws_bytes(int B, int Nsrc, int targetnum); /* bytes; 0 for a shape the call refuses.  Host only. */
+int dh3d_resample_clouds(int B, int Nsrc, int targetnum, const float *points, const int32_t *num_valid,
+                         const unsigned long long *seed, float *out, int32_t *num_orig, void *workspace, size_t workspace_bytes,
+                         void *stream);
+/* dh3d_augment_clouds -- core/augment.py.  aug_mask selects augmentations; they run in the fixed order of
+ *   get_augmentations_from_list (upright axis z), as one float64 chain on the exact float64 values of the float32 input, each
+ *   operation rounded to float64 on its own, the result rounded ONCE to float32 (the reference computes in float64 and casts
+ *   at the feed).  row * M below is ((x M[0][c] + y M[1][c]) + z M[2][c]) for c = 0, 1, 2; a 3 x 3 product A B has elements
+ *   (A[r][0] B[0][c] + A[r][1] B[1][c]) + A[r][2] B[2][c].
+ *     Rotate1D     angle = (U * 2) * pi, U = U(3, b, 0); M = [[c, s, 0], [-s, c, 0], [0, 0, 1]]; row = row * M
+ *     Jitter       coordinate c of point i: e = 3 i + c; v = clip(sigma * z(4, b, e), -clip, clip) + v
+ *     Scale        s = scale_low + (scale_high - scale_low) * U(5, b, 0); v = v * s
+ *     RotateSmall  a_e = clip(angle_sigma * z(6, b, e), -angle_clip, angle_clip), e = 0, 1, 2; Rx = [[1, 0, 0], [0, c0, -s0],
+ *                  [0, s0, c0]], Ry = [[c1, 0, s1], [0, 1, 0], [-s1, 0, c1]], Rz = [[c2, -s2, 0], [s2, c2, 0], [0, 0, 1]];
+ *                  M = Rz (Ry Rx); row = row * M
+ *     Shift        t_c = -shift_range + (shift_range - -shift_range) * U(7, b, c); v_c = v_c + t_c
+ *   The reference's defaults: sigma 0.05, clip 0.1, scale 0.8 .. 1.25, angle_sigma 0.06, angle_clip 0.18, shift_range 0.1.
+ *   Outputs: out [B, N, 3]; the cloud's parameters in float64 -- rot1d [B, 3, 3], scale [B], rot_small [B, 3, 3], shift
+ *   [B, 3] -- the identity, 1 and 0 for an augmentation that is off.  out may be points (in place).  A bit of aug_mask outside
+ *   DH3D_AUG_ALL, a negative or non-finite parameter, clip <= 0, scale_low <= 0 or > scale_high: DH3D_ERR_INVALID_ARGUMENT. */
+#define DH3D_AUG_ROTATE1D 1u
+#define DH3D_AUG_JITTER 2u
+#define DH3D_AUG_SCALE 4u
+#define DH3D_AUG_ROTATESMALL 8u
+#define DH3D_AUG_SHIFT 16u
+#define DH3D_AUG_ALL 31u
+int dh3d_augment_clouds(int B, int N, const float *points, unsigned aug_mask, double sigma, double clip, double scale_low,
+                        double scale_high, double angle_sigma, double angle_clip, double shift_range,
+                        const unsigned long long *seed, float *out, double *rot1d, double *scale, double *rot_small,
+                        double *shift, void *stream);
+/* dh3d_pair_rotate -- loadPair's rotation of the second cloud: angle = (2 U - 1) * rot_maxv, U = U(8, b, 0); Rot = [[c, s, 0],
+ *   [-s, c, 0], [0, 0, 1]] in float64; pc2_trans [B, N, 3] = float32(row * Rot) on the float64 values of pc2's rows; R [B, 3, 3]
+ *   = float32(Rot).  pc2_trans may be pc2.  rot_maxv negative or non-finite: DH3D_ERR_INVALID_ARGUMENT. */
+int dh3d_pair_rotate(int B, int N, const float *pc2, double rot_maxv, const unsigned long long *seed, float *pc2_trans, float *R,
+                     void *stream);
+/* dh3d_sample_pair_nodes -- the second half of loadPair for B pairs pc1, pc2 [B, N, 3].
+ *   subset = a random choice (stream 9) of N / 2 (rounded down) from N, in index order.  pick_0 = u(10, b, 0) mod (N / 2), a
+ *   POSITION in subset.  FarthestSampler.sample: dmin = d2(subset[pick_0], .); for t = 1 .. sample_nodes-1: pick_t = the
+ *   FIRST position holding the maximum of dmin; dmin = min(dmin, d2(subset[pick_t], .)).  d2 = (dx*dx + dy*dy) + dz*dz in
+ *   float64 on the float32 coordinates, no contraction (the rule of dh3d_prepare_clouds' radius test).
+ *   anc [B, sample_nodes] = the row in pc1 of subset[pick_t]; pos [B, sample_nodes] = the j with the smallest
+ *   d2(pc1[anc], pc2[j]), the lowest j on ties.  N <= 16384 and 1 <= sample_nodes <= N / 2, else DH3D_ERR_UNSUPPORTED.
+ *   (dh3d_farthest_point_sample* start at index 0 with a contracted float32 distance: another contract.)  No workspace. */
+int dh3d_sample_pair_nodes(int B, int N, int sample_nodes, const float *pc1, const float *pc2, const unsigned long long *seed,
+                           int32_t *anc, int32_t *pos, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
