@@ -176,6 +176,8 @@ struct FpsOrderedOut {
   int occ_min;         // fewer occupied cells than this: cells_s[4106] = 1 (spatial.hip's rule for a set of m points)
 };
 
+// Not keys.h's f32_order_bits: with this file's flags (csrc/Makefile EXTRA_fps) hipcc crashes selecting instructions for
+// that select form in fps_list_kernel<1,16,true>; this XOR form is the same map and stays local.
 __device__ __forceinline__ unsigned f32_ordered(float f) {  // monotonic float -> unsigned (for LDS atomicMin / atomicMax)
   const unsigned u = __float_as_uint(f);
   return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);

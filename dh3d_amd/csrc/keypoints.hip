@@ -6,12 +6,13 @@
 //                         2.0; one maximum of a' per 256-point block (wave DPP reduction + LDS);
 //   K2 nms_keys_kernel    every block reduces its cloud's block maxima -> thr = max * ratio; one thread per point walks its
 //                         K neighbours: a point is kept iff no neighbour inside the radius beats rank 0 and a' > thr.  The
-//                         point's key is (ordered_bits(a') << 32) | i, or 0 when it is not kept;
+//                         point's key is (f32_order_bits(a') << 32) | i, or 0 when it is not kept;
 //   K3 nms_select_kernel  one 1024-lane workgroup per cloud: compact the non-zero keys (in place), radix-select the M-th
 //                         largest (8 passes of 8 bits over the survivors), bitonic-sort the <= M winners in LDS (keys are
 //                         unique -- the index sits in the low bits -- so the order is total), write count and ids.
 // Only comparisons, one f32 multiply and 1 - x: exact by construction (compiled without contraction, csrc/Makefile EXACT).
 #include "common.h"
+#include "keys.h"
 #include "wave_ops.h"
 #include "workspace.h"
 
@@ -22,18 +23,6 @@ constexpr int kSelThreads = 1024;   // K3: one workgroup per cloud
 constexpr int kSelWaves = kSelThreads / 64;
 constexpr int kMaxKeep = 4096;      // M limit: the winners' sort buffer in LDS (32 KB)
 constexpr int kMaxK = 64;           // the kNN kernels' limit
-
-__device__ __forceinline__ int clamp_valid(const int32_t *num_valid, int b, int N) {
-  if (!num_valid) return N;
-  const int n = num_valid[b];
-  return n < 0 ? 0 : (n > N ? N : n);
-}
-
-// monotone map f32 -> u32 (total order of the finite floats; -0 is canonicalised before)
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // max over a 256-lane block; every lane must call it (DPP reads all 64 lanes)
 __device__ __forceinline__ float block256_max(float v, float *s_red) {
@@ -49,7 +38,7 @@ __global__ __launch_bounds__(kPtThreads) void nms_mute_kernel(const float *__res
                                                               float *__restrict__ ap, float *__restrict__ bmax) {
   __shared__ float s_red[kPtThreads / 64];
   const int b = blockIdx.y, i = blockIdx.x * kPtThreads + threadIdx.x;
-  const int nb = clamp_valid(num_valid, b, N);
+  const int nb = num_valid ? clamp_count(num_valid[b], N) : N;
   float m = -INFINITY;
   if (i < N) {
     const long long p = (long long)b * N + i;
@@ -70,7 +59,7 @@ __global__ __launch_bounds__(kPtThreads) void nms_keys_kernel(const float *__res
                                                               float ratio, unsigned long long *__restrict__ keys) {
   __shared__ float s_red[kPtThreads / 64];
   const int b = blockIdx.y, i = blockIdx.x * kPtThreads + threadIdx.x, nblk = gridDim.x;
-  const int nb = clamp_valid(num_valid, b, N);
+  const int nb = num_valid ? clamp_count(num_valid[b], N) : N;
   float m = -INFINITY;
   for (int j = threadIdx.x; j < nblk; j += kPtThreads) m = fmaxf(m, bmax[(long long)b * nblk + j]);
   const float thr = block256_max(m, s_red) * ratio;  // f32(max a') * f32(ratio)
@@ -91,14 +80,9 @@ __global__ __launch_bounds__(kPtThreads) void nms_keys_kernel(const float *__res
       const float s = (drow[r] > radius || j < 0 || j >= nb) ? 0.f : cloud[j];
       is_max = !(s > s0);
     }
-    if (is_max) key = ((unsigned long long)ordered_bits(a) << 32) | (unsigned)i;
+    if (is_max) key = ((unsigned long long)f32_order_bits(a) << 32) | (unsigned)i;  // (K1 wrote -0 as +0)
   }
   keys[p] = key;
-}
-
-__device__ __forceinline__ unsigned long long lanes_below() {
-  const unsigned lane = threadIdx.x & 63;
-  return lane ? (~0ull >> (64 - lane)) : 0ull;
 }
 
 __global__ __launch_bounds__(kSelThreads) void nms_select_kernel(unsigned long long *__restrict__ keys, int N, int M,

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "keys.h"
 #include "wave_ops.h"
 
 #pragma clang fp contract(off)
@@ -62,18 +63,6 @@ static KnnLadder knn_ladder(int N) {
   l.log2ct = 0;
   while ((1 << l.log2ct) < t) ++l.log2ct;
   return l;
-}
-
-// LDS image of 4 consecutive candidates c0..c3 (12 floats, three 16-byte reads):
-//   [x0 x1 y0 y1] [z0 z1 x2 x3] [y2 y3 z2 z3]   -> pairs feed v_pk_* directly
-__device__ __forceinline__ int cand_slot(int c, int comp) {
-  const int g = c >> 2, r = c & 3;
-  const int off = (r < 2) ? (2 * comp + r) : (4 + 2 * comp + r);  // comp 0:x 1:y 2:z
-  return g * 12 + off;
-}
-
-__device__ __forceinline__ float knn_bcast(float v, int lane) {  // lane is wave-uniform
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
 // the set bit of m (!= 0) nearest to position gl (0..63), wave-uniform: candidate groups are visited outwards from the
@@ -200,12 +189,12 @@ __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__re
     if (XYZ_LAYOUT) {
       for (int e = tid; e < len8 * 3; e += kQueriesPerBlock) {
         const int c = e / 3, comp = e - c * 3;
-        s_c[cand_slot(c, comp)] = c < len ? pc[(size_t)base * 3 + e] : INFINITY;
+        s_c[cand4_slot(c, comp)] = c < len ? pc[(size_t)base * 3 + e] : INFINITY;
       }
     } else {
       for (int e = tid; e < len8 * 3; e += kQueriesPerBlock) {
         const int comp = e / len8, c = e - comp * len8;
-        s_c[cand_slot(c, comp)] = c < len ? pc[(size_t)comp * N + base + c] : INFINITY;
+        s_c[cand4_slot(c, comp)] = c < len ? pc[(size_t)comp * N + base + c] : INFINITY;
       }
     }
     __syncthreads();
@@ -345,9 +334,9 @@ __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const flo
 
   // evaluate the 64 candidates of group gcc (records already in `cr`, one per lane)
   auto scan_group = [&](int gcc, const float4 cr) {
-    my_c[cand_slot(lane, 0)] = cr.x;
-    my_c[cand_slot(lane, 1)] = cr.y;
-    my_c[cand_slot(lane, 2)] = cr.z;
+    my_c[cand4_slot(lane, 0)] = cr.x;
+    my_c[cand4_slot(lane, 1)] = cr.y;
+    my_c[cand4_slot(lane, 2)] = cr.z;
     my_id[lane] = __float_as_int(cr.w);
     __builtin_amdgcn_wave_barrier();
     const int clen = min(64, N - gcc * 64);
@@ -421,14 +410,14 @@ __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const flo
           mask &= ~(1ull << l);
           nxt = load_group(c0 + l);
         }
-        const float bdl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bd), lcur));
+        const float bdl = wave_bcast_f32(bd, lcur);
         if (bdl <= wave_bound) {  // the bound may have tightened since the ballot
           // box against box says "some query of the wave MIGHT reach the group" with the union of the 64 queries and
           // the loosest of their bounds; the same test per query (point to box, own bound) is ~20 instructions
           // against the ~450 of scanning the group, and decides most of the overlapping (tier 0) groups of a query
           // group whose own box is large (Morton order jumps across the cloud inside it)
-          const float lx = knn_bcast(clo.x, lcur), ly = knn_bcast(clo.y, lcur), lz = knn_bcast(clo.z, lcur);
-          const float hx = knn_bcast(chi.x, lcur), hy = knn_bcast(chi.y, lcur), hz = knn_bcast(chi.z, lcur);
+          const float lx = wave_bcast_f32(clo.x, lcur), ly = wave_bcast_f32(clo.y, lcur), lz = wave_bcast_f32(clo.z, lcur);
+          const float hx = wave_bcast_f32(chi.x, lcur), hy = wave_bcast_f32(chi.y, lcur), hz = wave_bcast_f32(chi.z, lcur);
           const float px = fmaxf(fmaxf(lx - qr.x, qr.x - hx), 0.f);
           const float py = fmaxf(fmaxf(ly - qr.y, qr.y - hy), 0.f);
           const float pz = fmaxf(fmaxf(lz - qr.z, qr.z - hz), 0.f);
@@ -558,9 +547,9 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
   };
 
   auto scan_group = [&](int gcc, const float4 cr) {
-    my_c[cand_slot(lane, 0)] = cr.x;
-    my_c[cand_slot(lane, 1)] = cr.y;
-    my_c[cand_slot(lane, 2)] = cr.z;
+    my_c[cand4_slot(lane, 0)] = cr.x;
+    my_c[cand4_slot(lane, 1)] = cr.y;
+    my_c[cand4_slot(lane, 2)] = cr.z;
     my_id[lane] = __float_as_int(cr.w);
     __builtin_amdgcn_wave_barrier();
     const int clen = min(64, N - gcc * 64);
@@ -625,9 +614,9 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
     // the other groups with a list of its own and -- after the one barrier -- a bound all 64 candidates contributed
     // to.  (With the group scanned by its owner alone the other waves met their first group with no bound at all and
     // queued every candidate of it.)
-    my_c[cand_slot(lane, 0)] = qr.x;
-    my_c[cand_slot(lane, 1)] = qr.y;
-    my_c[cand_slot(lane, 2)] = qr.z;
+    my_c[cand4_slot(lane, 0)] = qr.x;
+    my_c[cand4_slot(lane, 1)] = qr.y;
+    my_c[cand4_slot(lane, 2)] = qr.z;
     my_id[lane] = __float_as_int(qr.w);
     __builtin_amdgcn_wave_barrier();
     const int clen = min(64, N - g * 64);
@@ -673,14 +662,14 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
           mask &= ~(1ull << l);
           nxt = load_group((ci * 64 + l) * S + wave);
         }
-        const float bdl = knn_bcast(bd, lcur);
+        const float bdl = wave_bcast_f32(bd, lcur);
         if (bdl <= wave_bound) {  // the bound may have tightened since the ballot
           // box against box says "some query of the wave MIGHT reach the group" with the union of the 64 queries and
           // the loosest of their bounds; the same test per query (point to box, own bound) is ~20 instructions
           // against the ~450 of scanning the group, and decides most of the overlapping (tier 0) groups of a query
           // group whose own box is large (Morton order jumps across the cloud inside it)
-          const float lx = knn_bcast(clo.x, lcur), ly = knn_bcast(clo.y, lcur), lz = knn_bcast(clo.z, lcur);
-          const float hx = knn_bcast(chi.x, lcur), hy = knn_bcast(chi.y, lcur), hz = knn_bcast(chi.z, lcur);
+          const float lx = wave_bcast_f32(clo.x, lcur), ly = wave_bcast_f32(clo.y, lcur), lz = wave_bcast_f32(clo.z, lcur);
+          const float hx = wave_bcast_f32(chi.x, lcur), hy = wave_bcast_f32(chi.y, lcur), hz = wave_bcast_f32(chi.z, lcur);
           const float px = fmaxf(fmaxf(lx - qr.x, qr.x - hx), 0.f);
           const float py = fmaxf(fmaxf(ly - qr.y, qr.y - hy), 0.f);
           const float pz = fmaxf(fmaxf(lz - qr.z, qr.z - hz), 0.f);

@@ -25,6 +25,8 @@
 // Rounding of the distance: every difference and every square rounded to f32 on its own, the squares added left to right
 // over c (this file is built with -ffp-contract=off).  NaN / infinite inputs are outside the contract.
 #include "common.h"
+#include "keys.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -38,46 +40,9 @@ constexpr int kFusedTile = 1024; // dataset points per LDS tile (12 KiB)
 constexpr int kRowMaxK = 1024;   // topk_row_kernel: k-list + walk arrays in LDS
 constexpr int kRowThreads = 256;
 
-// Float order as unsigned order; -0 and +0 are one value to the walk's strict <.
-__device__ __forceinline__ unsigned ord_bits(float v) {
-  if (v == 0.f) v = 0.f;
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ u64 umin64(u64 a, u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a < b ? b : a; }
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// ascending bitonic sort of one key per lane over the wave
-__device__ __forceinline__ u64 wave_sort64(u64 v, int lane) {
-#pragma unroll
-  for (int k2 = 2; k2 <= 64; k2 <<= 1) {
-#pragma unroll
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      const u64 o = __shfl_xor(v, j, 64);
-      const bool take_min = ((lane & k2) == 0) == ((lane & j) == 0);
-      v = take_min ? umin64(v, o) : umax64(v, o);
-    }
-  }
-  return v;
-}
-// a bitonic sequence over the wave -> ascending
-__device__ __forceinline__ u64 wave_merge64(u64 v, int lane) {
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const u64 o = __shfl_xor(v, j, 64);
-    v = (lane & j) == 0 ? umin64(v, o) : umax64(v, o);
-  }
-  return v;
-}
 __device__ __forceinline__ u64 wave_min64(u64 v) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = umin64(v, __shfl_xor(v, off, 64));
+  for (int off = 32; off > 0; off >>= 1) v = key_min(v, __shfl_xor(v, off, 64));
   return v;
 }
 
@@ -116,8 +81,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void knn3_fused_kernel(const floa
     wave_lds_sync();
     u64 bv = lane < cnt[q] ? s_buf[wave][q][lane] : kNoKey;
     wave_lds_sync();
-    bv = wave_sort64(bv, lane);
-    list[q] = wave_merge64(umin64(list[q], __shfl(bv, 63 - lane, 64)), lane);
+    list[q] = wave_fold(list[q], bv, lane);
     tau[q] = __shfl(list[q], kk - 1, 64);
     cnt[q] = 0;
   };
@@ -161,7 +125,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void knn3_fused_kernel(const floa
     if (j >= m) continue;                                      // (uniform)
     // the list by position: swap the halves of each key, sort, swap back
     u64 tl = lane < kk ? (list[q] << 32) | (list[q] >> 32) : kNoKey;
-    tl = wave_sort64(tl, lane);
+    tl = wave_sort(tl, lane);
     tl = (tl << 32) | (tl >> 32);
     u64 *w = s_buf[wave][q];                                   // (64 slots: walk positions k .. T-1 pass through LDS)
     wave_lds_sync();
@@ -178,7 +142,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) void knn3_fused_kernel(const floa
       // the first walk position t >= s with the smallest value: the minimum of (value bits, t)
       u64 c0 = lane >= s && lane < T ? (w0 & 0xFFFFFFFF00000000ull) | (unsigned)lane : kNoKey;
       const u64 c1 = 64 + lane < T ? (w1 & 0xFFFFFFFF00000000ull) | (unsigned)(64 + lane) : kNoKey;
-      const int t = (int)(unsigned)wave_min64(umin64(c0, c1));
+      const int t = (int)(unsigned)wave_min64(key_min(c0, c1));
       if (t != s) {                                            // (uniform) swap walk positions s (< 64) and t
         const u64 vs = __shfl(w0, s, 64);
         const u64 vt = t < 64 ? __shfl(w0, t, 64) : __shfl(w1, t - 64, 64);
@@ -262,7 +226,7 @@ __device__ __forceinline__ void topk_row(const SRC &src, int n, int k, int P, fl
       if (have + kRowThreads > P) compact(have);
       const int p = base + tid;
       if (p < n) {
-        const u64 key = ((u64)ord_bits(src.value(p)) << 32) | (unsigned)p;
+        const u64 key = ((u64)f32_order_bits_nz(src.value(p)) << 32) | (unsigned)p;
         if (key < tau) s_key[atomicAdd(&s_cnt, 1)] = key;
       }
       __syncthreads();
@@ -280,7 +244,7 @@ __device__ __forceinline__ void topk_row(const SRC &src, int n, int k, int P, fl
   // ---- stage 2: the walk on C, by the first wave; walk position t < k is row position t, k + i the i-th chosen
   for (int t = tid; t < T; t += kRowThreads) {
     if (t < k) {
-      s_wk[t] = ord_bits(src.value(t)), s_wi[t] = t;
+      s_wk[t] = f32_order_bits_nz(src.value(t)), s_wi[t] = t;
     } else {
       const u64 v = s_key[t - k];
       s_wk[t] = (unsigned)v, s_wi[t] = (int)(v >> 32);
@@ -290,7 +254,7 @@ __device__ __forceinline__ void topk_row(const SRC &src, int n, int k, int P, fl
   if (tid < 64) {
     for (int s = 0; s < k; ++s) {
       u64 best = kNoKey;
-      for (int t = s + tid; t < T; t += 64) best = umin64(best, ((u64)s_wk[t] << 32) | (unsigned)t);
+      for (int t = s + tid; t < T; t += 64) best = key_min(best, ((u64)s_wk[t] << 32) | (unsigned)t);
       const int t = (int)(unsigned)wave_min64(best);
       if (t != s && tid == 0) {
         const unsigned a = s_wk[s];
@@ -345,11 +309,11 @@ __global__ __launch_bounds__(kRowThreads) void walk_row_kernel(const float *__re
   __syncthreads();
   for (int s = 0; s < k; ++s) {
     u64 best = kNoKey;
-    for (int t = s + tid; t < n; t += kRowThreads) best = umin64(best, ((u64)ord_bits(o[t]) << 32) | (unsigned)t);
+    for (int t = s + tid; t < n; t += kRowThreads) best = key_min(best, ((u64)f32_order_bits_nz(o[t]) << 32) | (unsigned)t);
     best = wave_min64(best);
     if ((tid & 63) == 0) s_red[tid >> 6] = best;
     __syncthreads();
-    const int t = (int)(unsigned)umin64(umin64(s_red[0], s_red[1]), umin64(s_red[2], s_red[3]));
+    const int t = (int)(unsigned)key_min(key_min(s_red[0], s_red[1]), key_min(s_red[2], s_red[3]));
     if (t != s && tid == 0) {
       const float a = o[s];
       const int32_t ai = oi[s];

@@ -167,6 +167,8 @@ __global__ __launch_bounds__(256) void netvlad_assign_accumulate(
   if (tid < kCl) part_asum[((size_t)b * chunks + chunk) * kCl + tid] = s_asum[tid];
 }
 
+// Not common.h's block_sum_256: this one adds the wave partials as (s0 + s1) + (s2 + s3), that one left to right, and the
+// bits differ -- the two must not be merged.
 __device__ __forceinline__ float block_sum(float v, float *s_red) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

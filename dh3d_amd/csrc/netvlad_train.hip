@@ -62,10 +62,6 @@ struct NvArgs {
   float *scat;           // [B*m, 64]: A' (MODE 1), dcw (MODE 3); atomics
 };
 
-__device__ __forceinline__ float bcast(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256) void nv_walk_kernel(const NvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float s_mem[];
@@ -197,7 +193,7 @@ __global__ __launch_bounds__(256) void nv_walk_kernel(const NvArgs a) {
           u[h] = fmaf(wt[2], cv[2], fmaf(wt[1], cv[1], wt[0] * cv[0]));
         }
         const float t01 = pair_wave_sum_f32(part[0], part[1]);
-        const float tot[2] = {bcast(t01, 16), bcast(t01, 48)};
+        const float tot[2] = {wave_bcast_f32(t01, 16), wave_bcast_f32(t01, 48)};
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int o = orig_of(p + h);
@@ -234,7 +230,7 @@ __global__ __launch_bounds__(256) void nv_walk_kernel(const NvArgs a) {
         e2[h] = __expf(z - wave_max_f32(z));
       }
       const float hs = pair_wave_sum_f32(e2[0], e2[1]);
-      const float sum[2] = {bcast(hs, 16), bcast(hs, 48)};
+      const float sum[2] = {wave_bcast_f32(hs, 16), wave_bcast_f32(hs, 48)};
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int pt = wave * kPW + p + h;
@@ -311,11 +307,11 @@ __global__ __launch_bounds__(256) void nv_walk_kernel(const NvArgs a) {
           const int o = orig_of(p + h);
           if (o >= 0) {  // wave-uniform
             const int hl = h == 0 ? 16 : 48;
-            const float dzv = pv[p + h] * (dp[h] - bcast(rb, hl));
+            const float dzv = pv[p + h] * (dp[h] - wave_bcast_f32(rb, hl));
             a.dz[(rbase + o) * 64 + lane] = dzv;
             if (lane == 0) {
-              a.datt[rbase + o] = bcast(ra, hl);
-              a.t2[rbase + o] = bcast(rc, hl);
+              a.datt[rbase + o] = wave_bcast_f32(ra, hl);
+              a.t2[rbase + o] = wave_bcast_f32(rc, hl);
             }
             const float sh = (sv[p + h] - mean) * rstd;
             A1 += dzv;
@@ -354,7 +350,7 @@ __global__ __launch_bounds__(256) void nv_walk_kernel(const NvArgs a) {
         if (o >= 0 && lane == 0) {
           const float rv = s_f1[pt];
           // r^2 sum ds s + r^3 sum a e; 0 where the l2 clamp held the row (r constant: no gradient through it)
-          a.q[rbase + o] = rv >= kRinvClamped ? 0.f : rv * rv * (bcast(rg, h == 0 ? 16 : 48) + rv * s_f2[pt]);
+          a.q[rbase + o] = rv >= kRinvClamped ? 0.f : rv * rv * (wave_bcast_f32(rg, h == 0 ? 16 : 48) + rv * s_f2[pt]);
         }
         if (overflow) {
           const int4 si = *reinterpret_cast<const int4 *>(s_slot + pt * 4);

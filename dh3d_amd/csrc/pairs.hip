@@ -19,6 +19,7 @@
 //                           once for the 16; kept out of the FPS workgroup so that B pairs fill more than B compute units.
 // Compiled without contraction (csrc/Makefile EXACT): the picks and the neighbours depend on every rounding of d2.
 #include "common.h"
+#include "keys.h"
 #include "workspace.h"
 
 namespace {
@@ -41,12 +42,6 @@ enum Stream : unsigned {  // include/dh3d_hip.h lists these
   kFirst = 10
 };
 
-__device__ __forceinline__ u64 splitmix64(u64 z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __device__ __forceinline__ u64 stream_h(u64 seed, unsigned stream, unsigned b) {
   return splitmix64(splitmix64(seed) ^ (((u64)stream << 32) | (u64)b));
 }
@@ -57,10 +52,6 @@ __device__ __forceinline__ double normal(u64 h, u64 e) {  // Box-Muller, cosine 
   return sqrt(-2.0 * log(u1)) * cos(kTwoPi * u2);
 }
 __device__ __forceinline__ double clipd(double v, double c) { return fmin(fmax(v, -c), c); }
-__device__ __forceinline__ int live(const int32_t *num, int b, int cap) {
-  const int n = num[b];
-  return n < 0 ? 0 : (n > cap ? cap : n);
-}
 
 // The m-th smallest (1 <= m <= n) of the keys splitmix64(h + i), i < n, returned to every thread of a 1024-thread
 // workgroup.  splitmix64 is a bijection, so the keys are distinct: exactly m of them are <= the result, and the order by
@@ -115,7 +106,7 @@ __global__ __launch_bounds__(kBig) void resample_select_kernel(const int32_t *__
                                                                int32_t *__restrict__ base) {
   __shared__ unsigned s_hist[256], s_sel[2], s_cnt[kMaxSrc / kBig];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int n = live(num_valid, b, Nsrc), nch = (Nsrc + kBig - 1) / kBig;
+  const int n = clamp_count(num_valid[b], Nsrc), nch = (Nsrc + kBig - 1) / kBig;
   if (n < targetnum) {  // (workgroup-uniform) the write kernel reads neither; written so that the workspace is defined
     if (tid == 0) thr[b] = ~0ull;
     for (int c = tid; c < nch; c += kBig) base[(size_t)b * nch + c] = 0;
@@ -147,7 +138,7 @@ __global__ __launch_bounds__(kBig) void resample_write_kernel(const float *__res
                                                               float *__restrict__ out, int32_t *__restrict__ num_orig) {
   __shared__ unsigned s_w[kBig / 64];
   const int b = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = live(num_valid, b, Nsrc);
+  const int n = clamp_count(num_valid[b], Nsrc);
   const float *in = src + (size_t)b * Nsrc * 3;
   float *o = out + (size_t)b * targetnum * 3;
   if (c == 0 && tid == 0) num_orig[b] = n < targetnum ? n : targetnum;

@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "interp_walk.h"
+#include "keys.h"
 #include "wave_ops.h"
 
 #pragma clang fp contract(off)
@@ -65,12 +66,6 @@ __global__ __launch_bounds__(kBlock) void group_point_bwd_kernel(
 constexpr int kNNChunk = 1024;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// LDS image of 4 consecutive candidates (12 floats): [x0 x1 y0 y1] [z0 z1 x2 x3] [y2 y3 z2 z3]
-__device__ __forceinline__ int nn_slot(int c, int comp) {
-  const int g = c >> 2, r = c & 3;
-  return g * 12 + ((r < 2) ? (2 * comp + r) : (4 + 2 * comp + r));
-}
-
 // lane = query (64 per workgroup); the four waves split the candidates (32-candidate steps, interleaved) so a
 // query group keeps 4 waves per SIMD busy instead of one long scan, and their four 3-deep lists are merged
 // through LDS on (distance, index) -- the reference's strict '<' in index order = smallest index among equals.
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(kBlock) void three_nn_kernel(int n, int m, const fl
     __syncthreads();
     for (int e = threadIdx.x; e < len8 * 3; e += kBlock) {
       const int c = e / 3, comp = e - c * 3;
-      s_c[nn_slot(c, comp)] = c < len ? cand[(size_t)base * 3 + e] : INFINITY;  // padding: d = inf, never < best
+      s_c[cand4_slot(c, comp)] = c < len ? cand[(size_t)base * 3 + e] : INFINITY;  // padding: d = inf, never < best
     }
     __syncthreads();
     // 32 candidates per iteration with one wave-uniform test, so the LDS reads and packed ops pipeline
@@ -225,7 +220,7 @@ __global__ __launch_bounds__(kBlock) void three_nn_sorted_kernel(int n, int m, c
     for (int e = threadIdx.x; e < len32; e += kBlock) {
       float4 r = make_float4(INFINITY, INFINITY, INFINITY, __int_as_float(INT_MAX));  // padding: d = inf, never taken
       if (e < len) r = cand[base + e];
-      s_c[nn_slot(e, 0)] = r.x; s_c[nn_slot(e, 1)] = r.y; s_c[nn_slot(e, 2)] = r.z;
+      s_c[cand4_slot(e, 0)] = r.x; s_c[cand4_slot(e, 1)] = r.y; s_c[cand4_slot(e, 2)] = r.z;
       s_k[e] = __float_as_int(r.w);
     }
     __syncthreads();
@@ -331,7 +326,7 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel(int n, int m, c
   for (int e = threadIdx.x; e < len32; e += kBlock) {
     float4 r = make_float4(INFINITY, INFINITY, INFINITY, __int_as_float(INT_MAX));  // padding: d = inf, never taken
     if (e < m) r = cand[e];
-    s_c[nn_slot(e, 0)] = r.x; s_c[nn_slot(e, 1)] = r.y; s_c[nn_slot(e, 2)] = r.z;
+    s_c[cand4_slot(e, 0)] = r.x; s_c[cand4_slot(e, 1)] = r.y; s_c[cand4_slot(e, 2)] = r.z;
     s_k[e] = __float_as_int(r.w);
   }
   // boxes: the query group's, and (lane = candidate group) the candidates'

@@ -27,6 +27,7 @@
 // All three compactions: per-tile counts, a scan of the tile counts per cloud, in-tile ranks by a workgroup scan.
 // This file is built with -ffp-contract=off: the double expressions below are evaluated as written.
 #include "common.h"
+#include "keys.h"
 #include "workspace.h"
 
 namespace {
@@ -71,21 +72,6 @@ Ws make_layout(Carve &c, int B, int N) {
   w.tsum = c.take<int>(b * T * 2, 16), w.toff = c.take<int>(b * T * 2, 16), w.st = c.take<int>(b * ST_INTS, 16);
   w.p1 = c.take<float>(b * n * 3, 16), w.p2 = c.take<float>(b * n * 3, 16);
   return w;
-}
-
-__device__ __forceinline__ unsigned ord_bits(float v) {
-  if (v == 0.f) v = 0.f;
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord_value(unsigned o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-
-__device__ __forceinline__ u64 mix64(u64 z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 __device__ __forceinline__ double sqdist(double dx, double dy, double dz) { return (dx * dx + dy * dy) + dz * dz; }
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void prep_init_kernel(Ws w, const int32_t
     int *st = w.st + b * ST_INTS;
     if (stage == 1) {
       int v = 0;
-      if (s == ST_N0) v = min(max(num_raw[b], 0), w.N);
+      if (s == ST_N0) v = min(max(num_raw[b], 0), w.N);  // (not keys.h clamp_count: the select form compiles to other code here)
       if (s >= ST_LO && s < ST_LO + 3) v = -1;
       st[s] = v;
     } else if (s >= ST_LO && s < ST_LO + 3) {
@@ -159,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void prep_min_kernel(Ws w, const float *_
     const int i = i0 + e * kThreads;
     if (i < n) {
 #pragma unroll
-      for (int a = 0; a < 3; ++a) lo[a] = min(lo[a], ord_bits(p[(size_t)i * 3 + a]));
+      for (int a = 0; a < 3; ++a) lo[a] = min(lo[a], f32_order_bits_nz(p[(size_t)i * 3 + a]));
     }
   }
 #pragma unroll
@@ -175,7 +161,7 @@ __device__ __forceinline__ bool cell_of(const float *p, const int *st, double ha
   bool ok = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const double origin = (double)ord_value((unsigned)st[ST_LO + a]) - half;
+    const double origin = (double)f32_from_order_bits((unsigned)st[ST_LO + a]) - half;
     const double q = floor(((double)p[a] - origin) / edge);
     const bool in = q >= 0.0 && q < kCellLimit;   // (false for a NaN)
     c[a] = in ? (int)q : 0;

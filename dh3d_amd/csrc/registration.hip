@@ -14,6 +14,8 @@
 //                  with float64 block sums in a fixed order.
 // Compiled without contraction (csrc/Makefile EXACT): the ids and the inlier sets depend on every rounding.
 #include "common.h"
+#include "keys.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -24,11 +26,6 @@ constexpr int kMaxKp = 4096;       // keypoints per cloud (pm.KEYPOINT_MAX)
 constexpr int kRansacThreads = 256;
 constexpr int kRansacWaves = kRansacThreads / 64;
 
-__device__ __forceinline__ int clamp_count(const int32_t *count, int p, int M) {
-  const int n = count[p];
-  return n < 0 ? 0 : (n > M ? M : n);
-}
-
 __global__ __launch_bounds__(kMatchThreads) void match_kernel(const float *__restrict__ a, long long a_stride, int Ma,
                                                               const int32_t *__restrict__ a_count,
                                                               const float *__restrict__ b, long long b_stride, int Mb,
@@ -36,7 +33,7 @@ __global__ __launch_bounds__(kMatchThreads) void match_kernel(const float *__res
                                                               int32_t *__restrict__ match, float *__restrict__ dist) {
   __shared__ __align__(16) float s_b[kMatchTile * kMaxDim];
   const int p = blockIdx.y, i = blockIdx.x * kMatchThreads + threadIdx.x;
-  const int na = clamp_count(a_count, p, Ma), nb = clamp_count(b_count, p, Mb);
+  const int na = clamp_count(a_count[p], Ma), nb = clamp_count(b_count[p], Mb);
   const bool live = i < na;
   const float *arow = a + ((long long)p * Ma + (live ? i : 0)) * a_stride;
   const float *bp = b + (long long)p * Mb * b_stride;
@@ -84,13 +81,6 @@ __global__ __launch_bounds__(kMatchThreads) void match_kernel(const float *__res
 }
 
 // ---------------------------------------------------------------------------------------------------------- RANSAC
-
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // three distinct ids in [0, n), n >= 4, of trial k (include/dh3d_hip.h dh3d_ransac_rigid)
 __device__ __forceinline__ void sample3(unsigned long long seed_h, unsigned long long k, int n, int &i0, int &i1, int &i2) {
@@ -236,11 +226,6 @@ __device__ __forceinline__ bool is_inlier(const Corr &s, int j, const double *R,
   return sqrt(e0 * e0 + e1 * e1 + e2 * e2) < thr;
 }
 
-__device__ __forceinline__ unsigned long long lanes_below() {
-  const unsigned lane = threadIdx.x & 63;
-  return lane ? (~0ull >> (64 - lane)) : 0ull;
-}
-
 __global__ __launch_bounds__(kRansacThreads) void ransac_kernel(
     const float *__restrict__ axyz, long long a_stride, int Ma, const int32_t *__restrict__ a_count,
     const float *__restrict__ bxyz, long long b_stride, int Mb, const int32_t *__restrict__ match, double thr, double conf,
@@ -263,7 +248,7 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_kernel(
   s.id = reinterpret_cast<int *>(s.y2 + Ma);
 
   // (1) compact the valid correspondences (i < a_count, 0 <= match < Mb) in anchor order; clear the mask row
-  const int na = clamp_count(a_count, p, Ma);
+  const int na = clamp_count(a_count[p], Ma);
   int n = 0;
   for (int base = 0; base < Ma; base += kRansacThreads) {
     const int i = base + tid;

@@ -11,14 +11,16 @@
 //                          accumulator is the sum over c ascending.  After a tile's last chunk each distance is compared with
 //                          its query's threshold (the current k-th key); survivors are appended to the wave's 64-entry LDS
 //                          buffer of that query by ballot + prefix count, and a full buffer is folded into the sorted k-list
-//                          (one entry per lane) by a wave-wide bitonic sort + merge -- the scheme of knn3_fused_kernel
-//                          (knn_point.hip) on 96-bit keys.  Keys (d2 bits, id) are all distinct and a non-negative double
-//                          orders as its bit pattern, so a list is a function of the SET of rows scanned: it depends neither
-//                          on the order in which survivors arrive nor on S.
+//                          (one entry per lane) by a wave-wide bitonic sort + merge -- wave_fold (wave_ops.h), which
+//                          knn3_fused_kernel (knn_point.hip) runs on 64-bit keys, here on 96-bit ones.  Keys (d2 bits, id) are
+//                          all distinct and a non-negative double orders as its bit pattern, so a list is a function of the
+//                          SET of rows scanned: it depends neither on the order in which survivors arrive nor on S.
 //   retrieve_merge_kernel  S > 1 only: one wave per query merges the S partial lists [S, Q, k] of the workspace by the same key.
 // Bound: 3 float64 VALU operations (subtract, multiply, add -- no contraction) per (query, row, column) plus one conversion
 // per 4 of them; the map is read once per 16 queries.  Compiled without contraction (csrc/Makefile EXACT).
 #include "common.h"
+#include "keys.h"
+#include "wave_ops.h"
 #include "workspace.h"
 
 namespace {
@@ -44,50 +46,8 @@ struct Key {  // ascending by (d, id); d = the bits of a non-negative double
 constexpr u64 kNoDist = ~0ull;               // above the bits of +inf
 __device__ __forceinline__ Key no_key() { return Key{kNoDist, 0xFFFFFFFFu}; }
 __device__ __forceinline__ bool key_lt(const Key &a, const Key &b) { return a.d < b.d || (a.d == b.d && a.id < b.id); }
-__device__ __forceinline__ Key key_min(const Key &a, const Key &b) { return key_lt(b, a) ? b : a; }
-__device__ __forceinline__ Key key_max(const Key &a, const Key &b) { return key_lt(b, a) ? a : b; }
 __device__ __forceinline__ Key key_shfl_xor(const Key &v, int j) { return Key{__shfl_xor(v.d, j, 64), __shfl_xor(v.id, j, 64)}; }
 __device__ __forceinline__ Key key_shfl(const Key &v, int src) { return Key{__shfl(v.d, src, 64), __shfl(v.id, src, 64)}; }
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// ascending bitonic sort of one key per lane over the wave
-__device__ __forceinline__ Key wave_sort_key(Key v, int lane) {
-#pragma unroll
-  for (int k2 = 2; k2 <= 64; k2 <<= 1) {
-#pragma unroll
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      const Key o = key_shfl_xor(v, j);
-      const bool take_min = ((lane & k2) == 0) == ((lane & j) == 0);
-      v = take_min ? key_min(v, o) : key_max(v, o);
-    }
-  }
-  return v;
-}
-// a bitonic sequence over the wave -> ascending
-__device__ __forceinline__ Key wave_merge_key(Key v, int lane) {
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const Key o = key_shfl_xor(v, j);
-    v = (lane & j) == 0 ? key_min(v, o) : key_max(v, o);
-  }
-  return v;
-}
-// fold 64 keys (one per lane, any order) into the ascending list: sort them, reverse them against the list (the elementwise
-// minimum is a bitonic sequence holding the 64 smallest of both), merge
-__device__ __forceinline__ Key wave_fold_key(const Key &list, Key batch, int lane) {
-  batch = wave_sort_key(batch, lane);
-  return wave_merge_key(key_min(list, key_shfl(batch, 63 - lane)), lane);
-}
-
-__device__ __forceinline__ int live_rows(const int32_t *ref_count, int R) {
-  if (!ref_count) return R;
-  const int n = *ref_count;
-  return n < 0 ? 0 : (n > R ? R : n);
-}
 
 __device__ __forceinline__ void write_entry(const Key &e, long long o, int32_t *idx, double *dist2) {
   const bool some = e.d != kNoDist;
@@ -113,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void retrieve_scan_kernel(const float *__
   unsigned *s_bi = reinterpret_cast<unsigned *>(s_bd + kQb * 64);       // [16][64] survivors: ids
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q0 = blockIdx.x * kQb;
-  const int r = live_rows(ref_count, R);
+  const int r = ref_count ? clamp_count(*ref_count, R) : R;
   const long long begin = (long long)blockIdx.y * slice_rows;
   const long long end = begin + slice_rows < r ? begin + slice_rows : r;   // (begin >= end: an empty slice, nothing is read)
   const int ntiles = end > begin ? (int)((end - begin + kTile - 1) / kTile) : 0;
@@ -135,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void retrieve_scan_kernel(const float *__
     Key bv = no_key();
     if (lane < cnt[qi]) bv = Key{s_bd[slot], s_bi[slot]};
     wave_lds_sync();
-    list[qi] = wave_fold_key(list[qi], bv, lane);
+    list[qi] = wave_fold(list[qi], bv, lane);
     tau[qi] = key_shfl(list[qi], k - 1);
     cnt[qi] = 0;
   };
@@ -243,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void retrieve_merge_kernel(const u64 *__r
       bv = Key{part_d[o], part_id[o]};
     }
     if (!__ballot(key_lt(bv, tau))) continue;  // nothing here can enter the list
-    list = wave_fold_key(list, bv, lane);
+    list = wave_fold(list, bv, lane);
     tau = key_shfl(list, k - 1);
   }
   if (lane < k) write_entry(list, (long long)q * k + lane, idx, dist2);

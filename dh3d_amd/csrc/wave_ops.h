@@ -93,3 +93,70 @@ __device__ __forceinline__ float pair_wave_sum_f32(float a, float b) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
   return half32_sum_f32(__uint_as_float(r[0]) + __uint_as_float(r[1]));
 }
+
+// ---------------------------------------------------------------------------------------------- lanes, LDS, broadcast
+// The lanes of the wave below this one, as a ballot mask (kept in this form: the shift-and-decrement form compiles to
+// other code in the kernels that use it).
+__device__ __forceinline__ unsigned long long lanes_below() {
+  const unsigned lane = threadIdx.x & 63;
+  return lane ? (~0ull >> (64 - lane)) : 0ull;
+}
+
+// Orders the LDS traffic of ONE wave: what a lane wrote before is visible to every lane of the wave after.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// v of lane `lane` (wave-uniform) to every lane, through an SGPR.
+__device__ __forceinline__ float wave_bcast_f32(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+// ------------------------------------------------------------------------------------- sorted lists, one key per lane
+// wave_sort / wave_merge / wave_fold work on any key type K that supplies, next to its definition,
+//   bool key_lt(a, b)   a strict total order,     K key_shfl_xor(v, j)   v of lane ^ j,     K key_shfl(v, src)   v of lane src.
+// unsigned long long is a key as it is.  Its min / max are overloads, not the generic form below: `a < b ? a : b` and
+// `b < a ? b : a` are the same function and compile to different code.
+__device__ __forceinline__ bool key_lt(unsigned long long a, unsigned long long b) { return a < b; }
+__device__ __forceinline__ unsigned long long key_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+__device__ __forceinline__ unsigned long long key_max(unsigned long long a, unsigned long long b) { return a < b ? b : a; }
+__device__ __forceinline__ unsigned long long key_shfl_xor(unsigned long long v, int j) { return __shfl_xor(v, j, 64); }
+__device__ __forceinline__ unsigned long long key_shfl(unsigned long long v, int src) { return __shfl(v, src, 64); }
+
+template <typename K>
+__device__ __forceinline__ K key_min(const K &a, const K &b) { return key_lt(b, a) ? b : a; }
+template <typename K>
+__device__ __forceinline__ K key_max(const K &a, const K &b) { return key_lt(b, a) ? a : b; }
+
+// ascending bitonic sort of one key per lane over the wave
+template <typename K>
+__device__ __forceinline__ K wave_sort(K v, int lane) {
+#pragma unroll
+  for (int k2 = 2; k2 <= 64; k2 <<= 1) {
+#pragma unroll
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      const K o = key_shfl_xor(v, j);
+      const bool take_min = ((lane & k2) == 0) == ((lane & j) == 0);
+      v = take_min ? key_min(v, o) : key_max(v, o);
+    }
+  }
+  return v;
+}
+// a bitonic sequence over the wave -> ascending
+template <typename K>
+__device__ __forceinline__ K wave_merge(K v, int lane) {
+#pragma unroll
+  for (int j = 32; j > 0; j >>= 1) {
+    const K o = key_shfl_xor(v, j);
+    v = (lane & j) == 0 ? key_min(v, o) : key_max(v, o);
+  }
+  return v;
+}
+// fold 64 keys (one per lane, any order) into the ascending list: sort them, reverse them against the list (the elementwise
+// minimum is a bitonic sequence holding the 64 smallest of both), merge
+template <typename K>
+__device__ __forceinline__ K wave_fold(const K &list, K batch, int lane) {
+  batch = wave_sort(batch, lane);
+  return wave_merge(key_min(list, key_shfl(batch, 63 - lane)), lane);
+}

@@ -7,16 +7,9 @@ hypotheses came to a decision boundary (inlier threshold, eigen gap, integer N_k
 float64 rounding could break either way."""
 import numpy as np
 
+from pairs_reference import splitmix64  # the one numpy statement of include/dh3d_hip.h's generator
+
 EPS = 2.0 ** -52
-
-
-def splitmix64(z):
-    z = np.asarray(z, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = z + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
 
 
 def sample(seed, ks, n):
