@@ -1,0 +1,412 @@
+// Dense point-to-point ICP refinement of P registered cloud pairs for gfx950 (include/dh3d_hip.h dh3d_icp_refine states the
+// rule): from the pose of dh3d_ransac_rigid, T times { nearest anchor of every moved positive point within max_dist,
+// float64 estimateRigidTransform over those pairs }, then one last association that describes the returned pose.  Every
+// launch follows the previous one on the caller's stream -- init, pack, sort, T x (associate, fit), associate, stats --
+// no host sync, no allocation, no floating-point atomics: graph-capturable.
+//   icp_scan_kernel   association, any shape: lane = positive point, 256 per workgroup; the anchor cloud passes through
+//                     LDS in index order, 1024 points at a time, already widened to float64 (24 KiB; one conversion per
+//                     staged coordinate, not one per lane and candidate), and is read as broadcasts.  Bound by the float64
+//                     VALU: 3 subtractions, 3 products, 2 additions, a compare and two selects per (positive, anchor) --
+//                     Na * Nb * 11 float64 operations and nothing to hide them behind.  Walking in index order with a
+//                     strict < gives the lowest index at the smallest d2.
+//   icp_grid_kernel   association for Na <= 16384 on the anchor's cell table (dh3d_spatial_sort_cells, built once per call:
+//                     the anchor does not move).  Lane = positive point: every lane walks the cells that the box
+//                     y' +- max_dist meets and the sorted records of each -- about 90 candidates in 8 cells on a street
+//                     scene of 8192 points at 1 m, where the scan tests all Na.  Its float64 work is nothing; a step of
+//                     the walk is one dependent read (a cell's range or a 16-byte record) and the loop control around it,
+//                     and the lanes of a wave are at unrelated places of unrelated walks, so nearly every step of a wave
+//                     runs both sides: what bounds the kernel is instructions issued per step times the steps of the
+//                     slowest lane (8 waves per SIMD hide the reads).  Hence the cheap cell step: the cell's code comes
+//                     from three per-axis deposit tables in LDS (768 bytes, built once per workgroup) and the box is
+//                     walked with counters -- the first version divided t by the box's sides and deposited the twelve bits
+//                     in a loop for every cell, ~400 instructions that almost every step of a wave paid for some lane.
+//                     Candidates are compared by (d2, original index), so the order of the walk does not matter.  A box of
+//                     more than 512 cells takes the 64-point groups of the order whose box the ball meets instead: the
+//                     loop over the groups is wave-uniform, the records of a group are read as broadcasts.  The sort's
+//                     crowded flag (cells[4106]) is NOT a reason to leave the cells: for one radius-bound neighbour a
+//                     dense cell costs its points and no more, while 64 unrelated lanes meet nearly every group between
+//                     them (sending crowded clouds to the groups measured 2.47 ms for 64 x 8192 x 8192 on the demo
+//                     clouds, the scan 1.52).  The sort sees the rows below anchor_count only: icp_pack_kernel hands it
+//                     row r % na in place of every row r >= na (such rows are never candidates: their index says so), so
+//                     the grid of a cloud padded with rows of 100000.0 is the grid of its points, not of its padding.
+//   icp_fit_kernel    one 256-lane workgroup per pair: the pairs (anchor[nn[j]], positive[j]) with nn[j] >= 0, lane j % 256
+//                     over ascending j, float64 block sums in a fixed tree (count and centroids, then B over the centred
+//                     pairs), lane 0 solves (rigid_fit.h: the functions of ransac_kernel's refit).  n < 3 leaves the pose.
+//   icp_stats_kernel  num_corr, fitness, rmse (the sum in the fit's order) and the outputs of invalid pairs.
+// Compiled without contraction (csrc/Makefile EXACT): the ids depend on every rounding of d2.
+#include <math.h>
+
+#include "common.h"
+#include "keys.h"
+#include "rigid_fit.h"
+#include "wave_ops.h"
+#include "workspace.h"
+
+namespace {
+
+constexpr int kMaxPoints = 131072;  // Na, Nb
+constexpr int kMaxPairs = 65535;
+constexpr int kMaxIter = 256;
+constexpr int kGridMaxNa = 16384;   // dh3d_spatial_sort_cells
+constexpr int kCellInts = 4112;     // ints per cloud of the cell table (spatial.hip)
+constexpr int kGridMaxCells = 512;  // a box that meets more cells walks the 64-point groups
+constexpr int kThreads = 256;
+constexpr int kChunk = 1024;        // anchors staged per step of the scan
+
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// y' = R y + t in the form of registration.hip's is_inlier
+__device__ __forceinline__ void icp_move(const double *rt, float f0, float f1, float f2, double *m) {
+  const double y0 = f0, y1 = f1, y2 = f2;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) m[r] = ((rt[4 * r] * y0 + rt[4 * r + 1] * y1) + rt[4 * r + 2] * y2) + rt[4 * r + 3];
+}
+
+__device__ __forceinline__ double icp_d2(double x0, double x1, double x2, const double *m) {
+  const double dx = x0 - m[0], dy = x1 - m[1], dz = x2 - m[2];
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- init
+// the working pose (workspace) and valid: a pair is valid when valid0 is not 0 and Rt0 is finite
+__global__ __launch_bounds__(64) void icp_init_kernel(const double *__restrict__ Rt0, const int32_t *__restrict__ valid0, int P,
+                                                      double *__restrict__ pose, int32_t *__restrict__ valid) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= P) return;
+  double v[12];
+  bool ok = valid0 == nullptr || valid0[p] != 0;
+  for (int e = 0; e < 12; ++e) {
+    v[e] = Rt0[(long long)p * 12 + e];
+    ok = ok && isfinite(v[e]);
+  }
+  for (int e = 0; e < 12; ++e) pose[(long long)p * 12 + e] = ok ? v[e] : quiet_nan();
+  valid[p] = ok ? 1 : 0;
+}
+
+// anchor rows with an element stride -> [P, Na, 3] for the sort.  Row r >= na becomes a copy of row r % na: whatever lies
+// behind the count (prepare_clouds pads with 100000.0) stays out of the grid's extent, and the copies spread over the
+// cloud's cells instead of crowding one.  The copies keep their own index r >= na, which icp_take refuses.
+__global__ __launch_bounds__(kThreads) void icp_pack_kernel(const float *__restrict__ a, long long stride, int Na,
+                                                            const int32_t *__restrict__ a_count, float *__restrict__ out) {
+  const int p = blockIdx.y, r = blockIdx.x * kThreads + threadIdx.x;
+  if (r >= Na) return;
+  const int na = a_count ? clamp_count(a_count[p], Na) : Na;
+  const float *src = a + ((long long)p * Na + (r < na || na == 0 ? r : r % na)) * stride;
+  float *dst = out + ((long long)p * Na + r) * 3;
+  dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- scan
+__global__ __launch_bounds__(kThreads) void icp_scan_kernel(
+    const float *__restrict__ anchor, long long a_stride, int Na, const int32_t *__restrict__ a_count,
+    const float *__restrict__ positive, long long b_stride, int Nb, const int32_t *__restrict__ b_count,
+    const double *__restrict__ pose, const int32_t *__restrict__ valid, double r2, int32_t *__restrict__ nn) {
+  __shared__ __align__(16) double s_c[3 * kChunk];  // x[kChunk] | y[kChunk] | z[kChunk]
+  const int p = blockIdx.y, j = blockIdx.x * kThreads + threadIdx.x;
+  const int na = a_count ? clamp_count(a_count[p], Na) : Na, nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  int32_t *out = nn + (long long)p * Nb;
+  if ((int)blockIdx.x * kThreads >= nb || na == 0 || !valid[p]) {  // (workgroup-uniform)
+    if (j < Nb) out[j] = -1;
+    return;
+  }
+  const bool live = j < nb;
+  double m[3];
+  const float *yr = positive + ((long long)p * Nb + (live ? j : 0)) * b_stride;
+  icp_move(pose + (long long)p * 12, yr[0], yr[1], yr[2], m);
+  const float *pa = anchor + (long long)p * Na * a_stride;
+  double best = r2;  // strict: d2 == max_dist^2 is no neighbour
+  int best_i = -1;
+  for (int base = 0; base < na; base += kChunk) {
+    const int len = min(kChunk, na - base);
+    __syncthreads();  // the previous chunk has been read
+    for (int c = threadIdx.x; c < len; c += kThreads) {
+      const float *r = pa + (long long)(base + c) * a_stride;
+      s_c[c] = r[0]; s_c[kChunk + c] = r[1]; s_c[2 * kChunk + c] = r[2];
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int c = 0; c < len; ++c) {
+      const double d2 = icp_d2(s_c[c], s_c[kChunk + c], s_c[2 * kChunk + c], m);
+      if (d2 < best) {  // index order and a strict <: the lowest index keeps a tie
+        best = d2;
+        best_i = base + c;
+      }
+    }
+  }
+  if (j < Nb) out[j] = live ? best_i : -1;
+}
+
+// ---------------------------------------------------------------------------------------------------------- cell lists
+// The sort's cell arithmetic (spatial.hip) on one axis, as ball_query.hip's ball_cell: monotone in p, defined for +-inf.
+__device__ __forceinline__ int icp_cell(float p, float lo, float scl, int nb) {
+  const float t = fminf(fmaxf((p - lo) * scl, 0.f), 1.0e6f);
+  return min((4 << nb) - 1, (int)t) >> 2;
+}
+
+struct Best {
+  double d2;
+  int i;
+};
+// (d2, original index) ascending; the start value (max_dist^2, -1) refuses d2 == max_dist^2
+__device__ __forceinline__ void icp_take(Best &b, const float4 rec, const double *m, int na) {
+  const int k = __float_as_int(rec.w);  // (the plain original index: spatial.hip)
+  const double d2 = icp_d2(rec.x, rec.y, rec.z, m);
+  if (k < na && (d2 < b.d2 || (d2 == b.d2 && k < b.i))) {
+    b.d2 = d2;
+    b.i = k;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void icp_grid_kernel(
+    const float4 *__restrict__ sorted, const float *__restrict__ gbox, const int *__restrict__ cells, int Na,
+    const int32_t *__restrict__ a_count, const float *__restrict__ positive, long long b_stride, int Nb,
+    const int32_t *__restrict__ b_count, const double *__restrict__ pose, const int32_t *__restrict__ valid, double r2,
+    double max_dist, int32_t *__restrict__ nn) {
+  __shared__ unsigned s_dep[3][64];  // axis value -> its bits at their places in the cell's 12-bit code
+  const int p = blockIdx.y, j = blockIdx.x * kThreads + threadIdx.x;
+  const int na = a_count ? clamp_count(a_count[p], Na) : Na, nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  int32_t *out = nn + (long long)p * Nb;
+  if ((int)blockIdx.x * kThreads >= nb || na == 0 || !valid[p]) {  // (workgroup-uniform)
+    if (j < Nb) out[j] = -1;
+    return;
+  }
+  const bool live = j < nb;
+  const float *yr = positive + ((long long)p * Nb + (live ? j : 0)) * b_stride;
+  const float y0 = yr[0], y1 = yr[1], y2 = yr[2];
+  double m[3];
+  icp_move(pose + (long long)p * 12, y0, y1, y2, m);
+  const float4 *sc = sorted + (size_t)p * Na;
+  const int *ct = cells + (size_t)p * kCellInts;
+  const float *hd = reinterpret_cast<const float *>(ct) + 4100;
+  const unsigned sched = (unsigned)ct[4107];
+  int nbit[3] = {0, 0, 0};
+#pragma unroll
+  for (int s = 0; s < 12; ++s) {
+    const int a = (int)((sched >> (2 * s)) & 3u);
+    nbit[0] += (int)(a == 0); nbit[1] += (int)(a == 1); nbit[2] += (int)(a == 2);
+  }
+  if (threadIdx.x < 192) {  // the deposit tables: step s of the schedule puts the next lower bit of its axis at bit 11 - s
+    const int ax = threadIdx.x >> 6, v = threadIdx.x & 63;
+    unsigned code = 0;
+    int r = ax == 0 ? nbit[0] : ax == 1 ? nbit[1] : nbit[2];
+#pragma unroll
+    for (int s = 0; s < 12; ++s)
+      if ((int)((sched >> (2 * s)) & 3u) == ax) code |= ((unsigned)(v >> --r) & 1u) << (11 - s);
+    s_dep[ax][v] = code;
+  }
+  __syncthreads();
+  // The cells that the box y' +- max_dist meets.  An anchor x that the float64 test accepts has dx * dx <= d2 < max_dist^2
+  // up to three float64 roundings, so |x - y'| < max_dist (1 + 2^-50) on every axis.  The box edge y' -+ (max_dist + marg)
+  // is formed in float64 (2 roundings of 2^-53) and rounded to float32 (2^-24 relative to |y'| + max_dist + marg at most);
+  // marg = (max_dist + |y'|) * 1e-6 is 16 times that, so the float32 edge still lies outside x, which is a float32 itself.
+  // The cell function is the sort's own and monotone in its argument: cell(lower edge) <= cell(x) <= cell(upper edge).
+  int c0[3], cn[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double marg = (max_dist + fabs(m[a])) * 1e-6;
+    c0[a] = icp_cell((float)((m[a] - max_dist) - marg), hd[a], hd[3 + a], nbit[a]);
+    cn[a] = icp_cell((float)((m[a] + max_dist) + marg), hd[a], hd[3 + a], nbit[a]) - c0[a] + 1;
+  }
+  const int total = cn[0] * cn[1] * cn[2];
+  const bool by_cells = total <= kGridMaxCells;
+  Best b{r2, -1};
+  if (live && by_cells) {
+    // one step = one read: the next cell's range while the lane has none, else the next record
+    int pos = 0, end = 0, ox = 0, oy = 0, oz = 0;
+    while (pos < end || oz < cn[2]) {
+      if (pos < end) {
+        icp_take(b, sc[pos++], m, na);
+      } else {
+        const unsigned code = s_dep[0][c0[0] + ox] | s_dep[1][c0[1] + oy] | s_dep[2][c0[2] + oz];
+        if (++ox == cn[0]) {
+          ox = 0;
+          if (++oy == cn[1]) { oy = 0; ++oz; }
+        }
+        pos = max(ct[code], 0);
+        end = min(ct[code + 1], Na);
+      }
+    }
+  }
+  // wide box: every 64-point group of the order whose box the ball can reach.  The test is float64 on the
+  // exact box: an accepted anchor lies in its group's box, so the box distance is at most its d2 (up to the roundings that
+  // the 1e-9 margin covers).  Wave-uniform loop; a lane that walked its cells only skips the records.
+  if (__any(live && !by_cells)) {
+    const int NG = (Na + 63) / 64;
+    const float *gb = gbox + (size_t)p * NG * 8;
+    for (int g = 0; g < NG; ++g) {
+      const float4 lo = *reinterpret_cast<const float4 *>(gb + (size_t)g * 8);
+      const float4 hi = *reinterpret_cast<const float4 *>(gb + (size_t)g * 8 + 4);
+      const double dx = fmax(fmax((double)lo.x - m[0], m[0] - (double)hi.x), 0.0);
+      const double dy = fmax(fmax((double)lo.y - m[1], m[1] - (double)hi.y), 0.0);
+      const double dz = fmax(fmax((double)lo.z - m[2], m[2] - (double)hi.z), 0.0);
+      const bool meet = live && !by_cells && ((dx * dx + dy * dy) + dz * dz) * (1.0 - 1e-9) < r2;
+      if (!__any(meet)) continue;
+      const int len = min(64, Na - g * 64);
+      for (int e = 0; e < len; ++e) {
+        const float4 rec = sc[g * 64 + e];
+        if (meet) icp_take(b, rec, m, na);
+      }
+    }
+  }
+  if (j < Nb) out[j] = live ? b.i : -1;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- fit
+__global__ __launch_bounds__(kThreads) void icp_fit_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
+                                                           const float *__restrict__ positive, long long b_stride, int Nb,
+                                                           const int32_t *__restrict__ b_count,
+                                                           const int32_t *__restrict__ nn, double *__restrict__ pose) {
+  __shared__ double s_red[kThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  const float *pa = anchor + (long long)p * Na * a_stride, *pb = positive + (long long)p * Nb * b_stride;
+  const int32_t *row = nn + (long long)p * Nb;
+  // least-squares fit on the pairs: float64 sums, each lane over its slots in order, then a fixed tree
+  double cnt = 0.0, sx[3] = {0.0, 0.0, 0.0}, sy[3] = {0.0, 0.0, 0.0};
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    if (i >= 0) {
+      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
+      cnt += 1.0;
+      sx[0] += x[0]; sx[1] += x[1]; sx[2] += x[2];
+      sy[0] += y[0]; sy[1] += y[1]; sy[2] += y[2];
+    }
+  }
+  const int n = (int)block_sum_256<double>(cnt, s_red);
+  if (n < 3) return;  // the pose stays as it was (workgroup-uniform)
+  double xc[3], yc[3];
+  for (int r = 0; r < 3; ++r) {
+    xc[r] = block_sum_256<double>(sx[r], s_red) / (double)n;
+    yc[r] = block_sum_256<double>(sy[r], s_red) / (double)n;
+  }
+  double B[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    if (i >= 0) {
+      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
+      accumulate_b(B, x[0] - xc[0], x[1] - xc[1], x[2] - xc[2], y[0] - yc[0], y[1] - yc[1], y[2] - yc[2]);
+    }
+  }
+  for (int e = 0; e < 10; ++e) B[e] = block_sum_256<double>(B[e], s_red);
+  if (tid == 0) {
+    double Rf[9], tf[3];
+    rotation_from_b(B, Rf);
+    translation(Rf, xc, yc, tf);
+    double *rt = pose + (long long)p * 12;
+    for (int r = 0; r < 3; ++r) {
+      rt[4 * r] = Rf[3 * r];
+      rt[4 * r + 1] = Rf[3 * r + 1];
+      rt[4 * r + 2] = Rf[3 * r + 2];
+      rt[4 * r + 3] = tf[r];
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- stats
+__global__ __launch_bounds__(kThreads) void icp_stats_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
+                                                             const float *__restrict__ positive, long long b_stride, int Nb,
+                                                             const int32_t *__restrict__ b_count,
+                                                             const int32_t *__restrict__ nn, const double *__restrict__ pose,
+                                                             double *__restrict__ Rt, int32_t *__restrict__ num_corr,
+                                                             double *__restrict__ fitness, double *__restrict__ rmse) {
+  __shared__ double s_red[kThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  const float *pa = anchor + (long long)p * Na * a_stride, *pb = positive + (long long)p * Nb * b_stride;
+  const int32_t *row = nn + (long long)p * Nb;
+  const double *rt = pose + (long long)p * 12;
+  double cnt = 0.0, sum = 0.0;
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    if (i >= 0) {
+      const float *x = pa + (long long)i * a_stride;
+      const float *y = pb + (long long)j * b_stride;
+      double m[3];
+      icp_move(rt, y[0], y[1], y[2], m);
+      cnt += 1.0;
+      sum += icp_d2(x[0], x[1], x[2], m);
+    }
+  }
+  const int n = (int)block_sum_256<double>(cnt, s_red);
+  sum = block_sum_256<double>(sum, s_red);
+  if (tid < 12) Rt[(long long)p * 12 + tid] = rt[tid];  // (NaN where the pair is not valid: icp_init_kernel)
+  if (tid == 0) {
+    num_corr[p] = n;
+    fitness[p] = (double)n / (double)(nb > 1 ? nb : 1);
+    rmse[p] = n > 0 ? sqrt(sum / (double)n) : quiet_nan();
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------------- workspace
+struct IcpWs {
+  double *pose;    // [P, 12] the working pose
+  float4 *sorted;  // the anchor's spatial sort (Na <= 16384 only)
+  float *gbox;
+  int *cells;
+  float *packed;   // [P, Na, 3] what the sort reads: the anchor without its stride and without the rows behind its count
+  IcpWs(Carve &c, int P, int Na, int Nb) {
+    const bool grid = Na <= kGridMaxNa;
+    pose = c.take<double>((size_t)P * 12, 16);
+    sorted = c.take<float4>(grid ? (size_t)P * Na : 0, 16);
+    gbox = c.take<float>(grid ? (size_t)P * ((Na + 63) / 64) * 8 : 0, 16);
+    cells = c.take<int>(grid ? (size_t)P * kCellInts : 0, 16);
+    packed = c.take<float>(grid ? (size_t)P * Na * 3 : 0, 16);
+  }
+};
+
+bool icp_served(int P, int Na, int Nb) {
+  return P > 0 && Na > 0 && Nb > 0 && P <= kMaxPairs && Na <= kMaxPoints && Nb <= kMaxPoints;
+}
+
+}  // namespace
+
+DH3D_API int dh3d_icp_plan(int Na, int Nb) {
+  if (!icp_served(1, Na, Nb)) return -1;
+  return Na <= kGridMaxNa ? 2 : 1;
+}
+
+DH3D_API size_t dh3d_icp_refine_ws_bytes(int P, int Na, int Nb) {
+  return icp_served(P, Na, Nb) ? carve_bytes<IcpWs>(P, Na, Nb) : 0;
+}
+
+DH3D_API int dh3d_icp_refine(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *positive,
+                             long long positive_stride, const int32_t *positive_count, const double *Rt0,
+                             const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path,
+                             double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
+                             void *workspace, size_t workspace_bytes, void *stream) {
+  DH3D_REQUIRE(anchor && positive && Rt0 && Rt && nn && num_corr && fitness && rmse && valid);
+  DH3D_REQUIRE(P > 0 && Na > 0 && Nb > 0 && anchor_stride >= 3 && positive_stride >= 3);
+  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
+  DH3D_SUPPORTED(icp_served(P, Na, Nb) && iterations <= kMaxIter);
+  DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
+  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+               workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
+  Carve carve(workspace);
+  const IcpWs ws(carve, P, Na, Nb);
+  const bool grid = (path == 0 ? dh3d_icp_plan(Na, Nb) : path) == 2;
+  hipStream_t s = (hipStream_t)stream;
+  const double r2 = max_dist * max_dist;
+
+  hipLaunchKernelGGL(icp_init_kernel, dim3(dh3d_cdiv(P, 64)), dim3(64), 0, s, Rt0, valid0, P, ws.pose, valid);
+  if (grid) {
+    hipLaunchKernelGGL(icp_pack_kernel, dim3(dh3d_cdiv(Na, kThreads), P), dim3(kThreads), 0, s, anchor, anchor_stride, Na,
+                       anchor_count, ws.packed);
+    const int st = dh3d_spatial_sort_cells(ws.packed, P, Na, reinterpret_cast<float *>(ws.sorted), ws.gbox, ws.cells, stream);
+    if (st != DH3D_OK) return st;
+  }
+  const dim3 agrid(dh3d_cdiv(Nb, kThreads), P);
+  for (int it = 0; it <= iterations; ++it) {
+    if (grid)
+      hipLaunchKernelGGL(icp_grid_kernel, agrid, dim3(kThreads), 0, s, ws.sorted, ws.gbox, ws.cells, Na, anchor_count,
+                         positive, positive_stride, Nb, positive_count, ws.pose, valid, r2, max_dist, nn);
+    else
+      hipLaunchKernelGGL(icp_scan_kernel, agrid, dim3(kThreads), 0, s, anchor, anchor_stride, Na, anchor_count, positive,
+                         positive_stride, Nb, positive_count, ws.pose, valid, r2, nn);
+    if (it < iterations)
+      hipLaunchKernelGGL(icp_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, positive, positive_stride,
+                         Nb, positive_count, nn, ws.pose);
+  }
+  hipLaunchKernelGGL(icp_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, positive, positive_stride, Nb,
+                     positive_count, nn, ws.pose, Rt, num_corr, fitness, rmse);
+  return dh3d_launch_status();
+}

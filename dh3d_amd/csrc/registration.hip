@@ -15,6 +15,7 @@
 // Compiled without contraction (csrc/Makefile EXACT): the ids and the inlier sets depend on every rounding.
 #include "common.h"
 #include "keys.h"
+#include "rigid_fit.h"
 #include "wave_ops.h"
 
 namespace {
@@ -95,103 +96,10 @@ __device__ __forceinline__ void sample3(unsigned long long seed_h, unsigned long
   if (i2 >= hi) ++i2;
 }
 
-// B += A^T A for one centred pair (X anchor, Y positive): A = [0, (Y-X)^T; X-Y, crossTimesMatrix(Y+X)]
-// (estimateRigidTransform.m); B holds the upper triangle b00 b01 b02 b03 b11 b12 b13 b22 b23 b33
-__device__ __forceinline__ void accumulate_b(double *B, double x0, double x1, double x2, double y0, double y1, double y2) {
-  const double d0 = x0 - y0, d1 = x1 - y1, d2 = x2 - y2;
-  const double s0 = y0 + x0, s1 = y1 + x1, s2 = y2 + x2;
-  // columns of A
-  const double c0[4] = {0.0, d0, d1, d2};
-  const double c1[4] = {-d0, 0.0, s2, -s1};
-  const double c2[4] = {-d1, -s2, 0.0, s0};
-  const double c3[4] = {-d2, s1, -s0, 0.0};
-  const double *cols[4] = {c0, c1, c2, c3};
-  int e = 0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int c = r; c < 4; ++c) {
-      double v = 0.0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) v = v + cols[r][q] * cols[c][q];
-      B[e++] += v;
-    }
-  }
-}
-
-// R (row-major 3x3) from the unit eigenvector of B's smallest eigenvalue (cyclic Jacobi, float64), quat2rot.m
-__device__ void rotation_from_b(const double *Bu, double *R) {
-  double a[4][4], v[4][4];
-  int e = 0;
-  for (int r = 0; r < 4; ++r)
-    for (int c = r; c < 4; ++c) a[r][c] = a[c][r] = Bu[e++];
-  for (int r = 0; r < 4; ++r)
-    for (int c = 0; c < 4; ++c) v[r][c] = r == c ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 32; ++sweep) {  // (converges in 5-6 sweeps)
-    double off = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = r + 1; c < 4; ++c) off += a[r][c] * a[r][c];
-    if (!(off > 0.0)) break;  // (also stops on NaN)
-#pragma unroll
-    for (int pp = 0; pp < 3; ++pp) {
-#pragma unroll
-      for (int qq = pp + 1; qq < 4; ++qq) {
-        const double apq = a[pp][qq];
-        if (fabs(apq) <= 1e-18 * (fabs(a[pp][pp]) + fabs(a[qq][qq]))) {  // negligible: drop it
-          a[pp][qq] = a[qq][pp] = 0.0;
-          continue;
-        }
-        // the rotation that zeroes a[pp][qq], in the rounding-friendly form of Numerical Recipes' jacobi (tau = s / (1 + c))
-        const double theta = (a[qq][qq] - a[pp][pp]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
-        a[pp][pp] -= t * apq;
-        a[qq][qq] += t * apq;
-        a[pp][qq] = a[qq][pp] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (k != pp && k != qq) {
-            const double g = a[k][pp], h = a[k][qq];
-            a[k][pp] = a[pp][k] = g - s * (h + g * tau);
-            a[k][qq] = a[qq][k] = h + s * (g - h * tau);
-          }
-          const double g = v[k][pp], h = v[k][qq];
-          v[k][pp] = g - s * (h + g * tau);
-          v[k][qq] = h + s * (g - h * tau);
-        }
-      }
-    }
-  }
-  double lam = a[0][0], q0 = v[0][0], q1 = v[1][0], q2 = v[2][0], q3 = v[3][0];  // (the first smallest; no dynamic index)
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    if (a[k][k] < lam) {
-      lam = a[k][k];
-      q0 = v[0][k]; q1 = v[1][k]; q2 = v[2][k]; q3 = v[3][k];
-    }
-  }
-  R[0] = q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3;
-  R[1] = 2.0 * (q1 * q2 - q0 * q3);
-  R[2] = 2.0 * (q1 * q3 + q0 * q2);
-  R[3] = 2.0 * (q1 * q2 + q0 * q3);
-  R[4] = q0 * q0 - q1 * q1 + q2 * q2 - q3 * q3;
-  R[5] = 2.0 * (q2 * q3 - q0 * q1);
-  R[6] = 2.0 * (q1 * q3 - q0 * q2);
-  R[7] = 2.0 * (q2 * q3 + q0 * q1);
-  R[8] = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3;
-}
-
 struct Corr {  // the compacted correspondences in LDS (f32, exact in f64)
   float *x0, *x1, *x2, *y0, *y1, *y2;
   int *id;
 };
-
-// t = xc - R yc
-__device__ __forceinline__ void translation(const double *R, const double *xc, const double *yc, double *t) {
-  for (int r = 0; r < 3; ++r) t[r] = xc[r] - (R[3 * r] * yc[0] + R[3 * r + 1] * yc[1] + R[3 * r + 2] * yc[2]);
-}
 
 // the model of the sample (j0, j1, j2): centroid = (sum in sample order) / 3, B over the centred points in sample order
 __device__ void fit3(const Corr &s, int j0, int j1, int j2, double *R, double *t) {

@@ -11,6 +11,8 @@ sampler replaces randsample, whose stream cannot be reproduced).
     res = ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count)       # Rt, valid, inliers, ... (no host sync)
     res = register(anchor_rows, anchor_count, positive_rows, positive_count)  # rows as xyz_feat_att_nms / _nms_res.bin
     res = register_clouds(model, anchor_points, positive_points)              # forward (config.detection) + register
+    res = refine_icp(anchor_points, positive_points, res["Rt"], res["valid"])  # dense ICP: Rt, fitness, rmse, nn, ...
+    res = register_clouds(model, anchor_points, positive_points, refine=True)  # ... with the refined pose as Rt
     dt, ddeg = transform_errors(T_gt, res["Rt"], res["valid"])                # compareTransform, host float64
     summary = summarize_registration(dt, ddeg, res["inlier_ratio"], res["trials"])
 """
@@ -126,16 +128,107 @@ def register(anchor_rows, anchor_count, positive_rows, positive_count, desc_dim=
     return out
 
 
-def register_clouds(model, anchor_points, positive_points, num_valid=None, **kw):
+ICP_MAX_POINTS, ICP_MAX_ITERATIONS, ICP_GRID_MAX = 131072, 256, 16384  # csrc/icp.hip kMaxPoints, kMaxIter, kGridMaxNa
+_ICP_WS = {}  # (device, P, Na, Nb) -> the uint8 workspace of dh3d_icp_refine (its content carries nothing between calls)
+
+
+def icp_plan(Na, Nb):
+    """How refine_icp(path=0) associates a shape: "scan", "grid", or None for a shape the call refuses."""
+    return {1: "scan", 2: "grid"}.get(L.lib().dh3d_icp_plan(int(Na), int(Nb)))
+
+
+def refine_icp(anchor_points, positive_points, Rt, valid=None, anchor_count=None, positive_count=None, max_dist=1.0,
+               iterations=20, path=0):
+    """Dense point-to-point ICP of every pair from the pose Rt [P, 3, 4] float64 (anchor ~ R positive + t, ransac_rigid's
+    convention): `iterations` times { nearest anchor point of every moved positive point within max_dist, float64
+    least-squares fit over those pairs }, then one last association that describes the returned pose
+    (include/dh3d_hip.h dh3d_icp_refine states every rule).  anchor_points [P, Na, >=3] and positive_points [P, Nb, >=3]
+    float32 (the first three columns are read; column views are read in place); valid [P] bool / int32 or None (all);
+    counts [P] int32 or None (all rows; prepare_clouds' num_valid).  path: 0 the plan's choice, 1 scan, 2 cell lists
+    (Na <= 16384) -- the same result either way.  Returns a dict of device tensors: Rt [P, 3, 4] float64, valid [P] bool
+    (the input's, and False where Rt had a non-finite entry; such pairs come back with Rt NaN, nn -1, num_corr 0, fitness 0,
+    rmse NaN), nn [P, Nb] int32 (the anchor of every positive point under the returned pose, -1: none within max_dist),
+    num_corr [P] int32, fitness [P] float64 (num_corr / positive count) and rmse [P] float64 (over the pairs of nn; NaN
+    without any).  iterations = 0 evaluates the given pose.  No host sync: graph-capturable.  The workspace is kept per
+    (device, P, Na, Nb) and carries nothing between calls; calls of one shape share it, so they belong on one stream (or on
+    streams ordered against each other)."""
+    a = _rows(anchor_points, "anchor_points", 3)
+    b = _rows(positive_points, "positive_points", 3)
+    P, Na = a.shape[:2]
+    dev = a.device
+    if b.shape[0] != P or b.device != dev:
+        raise ValueError("positive_points must be [%d, Nb, >=3] on %s, got %s on %s" % (P, dev, tuple(b.shape), b.device))
+    Nb = b.shape[1]
+    if not isinstance(Rt, torch.Tensor) or Rt.dtype != torch.float64 or not Rt.is_cuda or tuple(Rt.shape) != (P, 3, 4) \
+            or Rt.device != dev:
+        raise ValueError("Rt must be a float64 [%d, 3, 4] tensor on %s" % (P, dev))
+    rt0 = Rt.contiguous()
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.int32) or not valid.is_cuda \
+                or tuple(valid.shape) != (P,) or valid.device != dev:
+            raise ValueError("valid must be a bool or int32 [%d] tensor on %s" % (P, dev))
+        valid = valid.to(torch.int32).contiguous()
+    ac = None if anchor_count is None else _count(anchor_count, "anchor_count", P, dev)
+    bc = None if positive_count is None else _count(positive_count, "positive_count", P, dev)
+    max_dist, iterations, path = float(max_dist), int(iterations), int(path)
+    if not 0.0 < max_dist < float("inf") or not 0 <= iterations <= ICP_MAX_ITERATIONS or path not in (0, 1, 2):
+        raise ValueError("need a positive finite max_dist, 0 <= iterations <= %d and path 0, 1 or 2, got %r, %r, %r"
+                         % (ICP_MAX_ITERATIONS, max_dist, iterations, path))
+    if Na > ICP_MAX_POINTS or Nb > ICP_MAX_POINTS or (path == 2 and Na > ICP_GRID_MAX):
+        raise ValueError("refine_icp: at most %d points per cloud (%d anchor points on path 2), got %d / %d"
+                         % (ICP_MAX_POINTS, ICP_GRID_MAX, Na, Nb))
+    lib = L.lib()
+    key = (dev, P, Na, Nb)
+    ws = _ICP_WS.get(key)
+    if ws is None:
+        nbytes = lib.dh3d_icp_refine_ws_bytes(P, Na, Nb)
+        if nbytes == 0:
+            raise ValueError("refine_icp: shape P = %d, Na = %d, Nb = %d is not served" % (P, Na, Nb))
+        ws = _ICP_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out_rt = torch.empty((P, 3, 4), dtype=torch.float64, device=dev)
+    nn = torch.empty((P, Nb), dtype=torch.int32, device=dev)
+    num_corr = torch.empty((P,), dtype=torch.int32, device=dev)
+    fitness = torch.empty((P,), dtype=torch.float64, device=dev)
+    rmse = torch.empty((P,), dtype=torch.float64, device=dev)
+    ok = torch.empty((P,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.dh3d_icp_refine(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(b), b.stride(1), L.ptr(bc), L.ptr(rt0), L.ptr(valid),
+                                    P, Na, Nb, max_dist, iterations, path, L.ptr(out_rt), L.ptr(nn), L.ptr(num_corr),
+                                    L.ptr(fitness), L.ptr(rmse), L.ptr(ok), L.ptr(ws), ws.numel(), L.stream_ptr()),
+                "refine_icp")
+    return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse)
+
+
+def _refine_kw(refine):
+    """refine: None / False (no refinement), True (refine_icp's defaults) or a dict of refine_icp keywords."""
+    if refine is None or refine is False:
+        return None
+    if refine is True:
+        return {}
+    if isinstance(refine, dict):
+        return dict(refine)
+    raise ValueError("refine must be None, True or a dict of refine_icp keywords, got %r" % (refine,))
+
+
+def register_clouds(model, anchor_points, positive_points, num_valid=None, refine=None, **kw):
     """Both batches of clouds [P, N, 3] through model.forward(fetch=("kp_count", "xyz_feat_att_nms")) (config.detection),
-    then register on the keypoints.  num_valid: None, one int32 [P] tensor for both batches, or a pair (anchor, positive)."""
+    then register on the keypoints.  num_valid: None, one int32 [P] tensor for both batches, or a pair (anchor, positive).
+    refine: None, True or a dict of refine_icp keywords -- the RANSAC pose is then refined by dense ICP of the full clouds
+    (num_valid as the counts): Rt is the refined pose and the result gains Rt_ransac (the keypoint fit), fitness, rmse,
+    num_corr_icp and nn; valid stays the RANSAC fit's."""
     if not getattr(model.config, "detection", False):
         raise ValueError("register_clouds needs a model with config.detection (the keypoint outputs)")
+    rkw = _refine_kw(refine)
     nv_a, nv_b = num_valid if isinstance(num_valid, (tuple, list)) else (num_valid, num_valid)
     fetch = ("kp_count", "xyz_feat_att_nms")
     oa = model.forward(anchor_points, fetch=fetch, num_valid=nv_a)
     ob = model.forward(positive_points, fetch=fetch, num_valid=nv_b)
-    return register(oa["xyz_feat_att_nms"], oa["kp_count"], ob["xyz_feat_att_nms"], ob["kp_count"], **kw)
+    out = register(oa["xyz_feat_att_nms"], oa["kp_count"], ob["xyz_feat_att_nms"], ob["kp_count"], **kw)
+    if rkw is not None:
+        icp = refine_icp(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv_a, positive_count=nv_b, **rkw)
+        out["Rt_ransac"], out["Rt"] = out["Rt"], icp["Rt"]
+        out["fitness"], out["rmse"], out["num_corr_icp"], out["nn"] = icp["fitness"], icp["rmse"], icp["num_corr"], icp["nn"]
+    return out
 
 
 def _host64(t):

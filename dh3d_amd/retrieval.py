@@ -13,6 +13,8 @@ grows inside its capacity.
     idx, dist = index.search(query_desc, 25)
     res = index.localize(query_desc, query_rows, query_count, k=5)  # place [Q], Rt [Q, 3, 4], num_inliers, rank, ...
     res = relocalize_clouds(global_model, local_model, index, points, k=5)
+    index = PlaceIndex(..., points=8192); index.add(..., cloud=points, cloud_count=num_valid)   # 12 * points bytes a place
+    res = relocalize_clouds(global_model, local_model, index, points, k=5, refine=True)  # + dense ICP: Rt, fitness, rmse
 """
 import torch
 
@@ -88,16 +90,18 @@ class PlaceIndex:
     """A fixed-capacity map of places on the device: desc [capacity, dim] float32 global descriptors, pos [capacity, 2]
     float64 (northing, easting), count int32 [1] (the fill level, on the device), and with keypoints = M > 0 the places'
     keypoint rows kp_rows [capacity, M, row_dim] float32 ([x, y, z, descriptor(, score)] as the model's xyz_feat_att_nms)
-    with kp_count [capacity] int32.  Buffers never move, so a graph captured around search / localize keeps serving the map
+    with kp_count [capacity] int32, and with points = N > 0 the places' clouds cloud [capacity, N, 3] float32 with
+    cloud_count [capacity] int32 -- what localize(refine=...) runs the dense ICP against; it costs 12 * points bytes a
+    place (96 KiB at 8192 points: 6 GiB for a map of 65536 places).  Buffers never move, so a graph captured around search / localize keeps serving the map
     while add() fills it."""
 
-    def __init__(self, dim=256, capacity=4096, device="cuda", keypoints=0, row_dim=132):
-        dim, capacity, keypoints, row_dim = int(dim), int(capacity), int(keypoints), int(row_dim)
-        if dim <= 0 or dim > DESC_MAX or dim % 4 or capacity <= 0 or keypoints < 0:
-            raise ValueError("need 0 < dim <= %d, a multiple of 4, capacity > 0 and keypoints >= 0" % DESC_MAX)
+    def __init__(self, dim=256, capacity=4096, device="cuda", keypoints=0, row_dim=132, points=0):
+        dim, capacity, keypoints, row_dim, points = int(dim), int(capacity), int(keypoints), int(row_dim), int(points)
+        if dim <= 0 or dim > DESC_MAX or dim % 4 or capacity <= 0 or keypoints < 0 or points < 0:
+            raise ValueError("need 0 < dim <= %d, a multiple of 4, capacity > 0, keypoints >= 0 and points >= 0" % DESC_MAX)
         if torch.device(device).type != "cuda":
             raise ValueError("PlaceIndex lives on the GPU (the HIP path has no CPU fallback), got %s" % (device,))
-        self.dim, self.capacity, self.keypoints, self.row_dim = dim, capacity, keypoints, row_dim
+        self.dim, self.capacity, self.keypoints, self.row_dim, self.points = dim, capacity, keypoints, row_dim, points
         self.desc = torch.zeros((capacity, dim), dtype=torch.float32, device=device)
         self.device = self.desc.device  # with its index ("cuda" -> cuda:0): what the tensors handed to search / localize carry
         self.pos = torch.zeros((capacity, 2), dtype=torch.float64, device=self.device)
@@ -106,14 +110,18 @@ class PlaceIndex:
         if keypoints:
             self.kp_rows = torch.zeros((capacity, keypoints, row_dim), dtype=torch.float32, device=self.device)
             self.kp_count = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
+        self.cloud = self.cloud_count = None
+        if points:
+            self.cloud = torch.zeros((capacity, points, 3), dtype=torch.float32, device=self.device)
+            self.cloud_count = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
         self._n = 0  # host mirror of count: add() needs no device -> host copy
 
     def __len__(self):
         return self._n
 
-    def add(self, desc, pos=None, kp_rows=None, kp_count=None):
+    def add(self, desc, pos=None, kp_rows=None, kp_count=None, cloud=None, cloud_count=None):
         """Append n places: desc [n, dim]; pos [n, 2] (None: zeros); with keypoints, kp_rows [n, M' <= M, row_dim] and
-        kp_count [n].  Returns the ids (a range).  Raises when the map is full; no device -> host sync."""
+        kp_count [n]; with points, cloud [n, N' <= N, 3] and cloud_count [n] (None: N' each).  Returns the ids (a range).  Raises when the map is full; no device -> host sync."""
         desc = torch.as_tensor(desc, dtype=torch.float32)
         if desc.dim() != 2 or desc.shape[1] != self.dim:
             raise ValueError("desc must be [n, %d], got %s" % (self.dim, tuple(desc.shape)))
@@ -131,6 +139,18 @@ class PlaceIndex:
                 raise ValueError("kp_rows must be [%d, <= %d, %d], got %s" % (n, self.keypoints, self.row_dim, tuple(kp_rows.shape)))
             if tuple(kp_count.shape) != (n,):
                 raise ValueError("kp_count must be [%d], got %s" % (n, tuple(kp_count.shape)))
+        if self.points and cloud is None:
+            raise ValueError("this PlaceIndex holds clouds: add() needs cloud")
+        if not self.points and (cloud is not None or cloud_count is not None):
+            raise ValueError("this PlaceIndex was built with points = 0")
+        if self.points:
+            cloud = torch.as_tensor(cloud, dtype=torch.float32)
+            if cloud.dim() != 3 or cloud.shape[0] != n or cloud.shape[1] > self.points or cloud.shape[2] != 3:
+                raise ValueError("cloud must be [%d, <= %d, 3], got %s" % (n, self.points, tuple(cloud.shape)))
+            if cloud_count is not None:
+                cloud_count = torch.as_tensor(cloud_count, dtype=torch.int32)
+                if tuple(cloud_count.shape) != (n,):
+                    raise ValueError("cloud_count must be [%d], got %s" % (n, tuple(cloud_count.shape)))
         if pos is not None:
             pos = torch.as_tensor(pos, dtype=torch.float64)
             if tuple(pos.shape) != (n, 2):
@@ -141,6 +161,14 @@ class PlaceIndex:
             self.kp_rows[o:o + n, :m].copy_(kp_rows)
             self.kp_rows[o:o + n, m:].zero_()
             self.kp_count[o:o + n].copy_(kp_count.clamp(0, m))
+        if self.points:
+            m = cloud.shape[1]
+            self.cloud[o:o + n, :m].copy_(cloud)
+            self.cloud[o:o + n, m:].zero_()
+            if cloud_count is None:
+                self.cloud_count[o:o + n].fill_(m)
+            else:
+                self.cloud_count[o:o + n].copy_(cloud_count.clamp(0, m))
         self.desc[o:o + n].copy_(desc)
         self._n = o + n
         self.count.fill_(self._n)  # after the rows: a search ordered after this add sees complete places
@@ -150,7 +178,8 @@ class PlaceIndex:
         """search_descriptors over the places added so far (the device count decides, not the host mirror)."""
         return search_descriptors(self.desc, qry, k, ref_count=self.count)
 
-    def localize(self, query_desc, query_rows, query_count, k=5, desc_dim=128, **ransac_kw):
+    def localize(self, query_desc, query_rows, query_count, k=5, desc_dim=128, refine=None, query_cloud=None,
+                 query_cloud_count=None, **ransac_kw):
         """Retrieve k candidate places per query, register the query's keypoints against every candidate's in ONE batch of
         Q * k pairs (registration.register: anchor = the place's keypoints, positive = the query's, so Rt maps query
         coordinates into the place's frame, place ~ R query + t) and keep, per query, the candidate with the most inliers;
@@ -158,10 +187,20 @@ class PlaceIndex:
         query_desc [Q, dim], query_rows [Q, Mq, row_dim], query_count [Q] int32.  Returns a dict of device tensors: place [Q]
         int32 (-1: no candidate is valid), rank [Q] int32 (the winner's retrieval rank, -1), Rt [Q, 3, 4] float64 (NaN where
         place is -1), num_inliers [Q] int32 (0 there), inlier_ratio [Q] float64, inliers [Q, M] bool (the winner's mask over
-        the place's keypoints), pos [Q, 2] float64 (the place's position, NaN there), idx / dist [Q, k] (the retrieval).  No
-        host sync."""
+        the place's keypoints), pos [Q, 2] float64 (the place's position, NaN there), idx / dist [Q, k] (the retrieval).
+        refine: None, True or a dict of registration.refine_icp keywords -- after the vote the winner's pose (and only the
+        winner's) is refined by dense ICP of query_cloud [Q, N, >=3] (query_cloud_count [Q] int32 or None) against the
+        winner's stored cloud, gathered by place id on the device; a query without a winner goes in as invalid.  Rt is then
+        the refined pose and the result gains Rt_ransac (the keypoint fit), fitness and rmse (the dense overlap: the check on
+        the retrieved place).  Needs an index built with points > 0 (else ValueError).  No host sync."""
         if not self.keypoints:
             raise ValueError("localize needs a PlaceIndex built with keypoints > 0")
+        rkw = registration._refine_kw(refine)
+        if rkw is not None:
+            if not self.points:
+                raise ValueError("localize(refine=...) needs a PlaceIndex built with points > 0 (the places' clouds)")
+            if query_cloud is None:
+                raise ValueError("localize(refine=...) needs query_cloud")
         k = int(k)
         idx, dist = self.search(query_desc, k)
         Q = idx.shape[0]
@@ -185,7 +224,7 @@ class PlaceIndex:
         pair = torch.arange(Q, device=self.device) * k + best
         nan = float("nan")
         place = torch.where(any_ok, idx.gather(1, best[:, None])[:, 0], torch.full_like(best, -1, dtype=torch.int32))
-        return dict(
+        out = dict(
             place=place, rank=torch.where(any_ok, best, torch.full_like(best, -1)).to(torch.int32),
             Rt=torch.where(any_ok[:, None, None], res["Rt"].index_select(0, pair), torch.full_like(res["Rt"][:1], nan)),
             num_inliers=torch.where(any_ok, res["num_inliers"].index_select(0, pair), torch.zeros_like(place)),
@@ -193,16 +232,29 @@ class PlaceIndex:
             inliers=res["inliers"].index_select(0, pair) & any_ok[:, None],
             pos=torch.where(any_ok[:, None], self.pos.index_select(0, place.clamp(min=0).long()), torch.full_like(self.pos[:1], nan)),
             idx=idx, dist=dist)
+        if rkw is not None:
+            safe_place = place.clamp(min=0).long()
+            icp = registration.refine_icp(self.cloud.index_select(0, safe_place), query_cloud, out["Rt"], any_ok,
+                                          anchor_count=self.cloud_count.index_select(0, safe_place),
+                                          positive_count=query_cloud_count, **rkw)
+            out["Rt_ransac"], out["Rt"] = out["Rt"], icp["Rt"]
+            out["fitness"], out["rmse"] = icp["fitness"], icp["rmse"]
+        return out
 
 
-def relocalize_clouds(global_model, local_model, index, points, k=5, num_valid=None, **kw):
+def relocalize_clouds(global_model, local_model, index, points, k=5, num_valid=None, refine=None, **kw):
     """Clouds [Q, N, 3] in, place ids and poses out: globaldesc from `global_model` (config.extract_global), kp_count /
     xyz_feat_att_nms from `local_model` (config.detection) -- two models, as the reference has two checkpoints -- then
-    index.localize.  num_valid: None or int32 [Q]."""
+    index.localize.  num_valid: None or int32 [Q].  refine: None, True or a dict of registration.refine_icp keywords -- the
+    winner's pose is refined by dense ICP of `points` against the place's stored cloud (PlaceIndex(points=...))."""
     if not getattr(global_model.config, "extract_global", False):
         raise ValueError("relocalize_clouds needs a global_model with config.extract_global (the globaldesc output)")
     if not getattr(local_model.config, "detection", False):
         raise ValueError("relocalize_clouds needs a local_model with config.detection (the keypoint outputs)")
+    if registration._refine_kw(refine) is not None and not index.points:
+        raise ValueError("relocalize_clouds(refine=...) needs a PlaceIndex built with points > 0 (the places' clouds)")
     g = global_model.forward(points, fetch=("globaldesc",), num_valid=num_valid)
     o = local_model.forward(points, fetch=("kp_count", "xyz_feat_att_nms"), num_valid=num_valid)
+    if refine is not None:
+        kw = dict(kw, refine=refine, query_cloud=points, query_cloud_count=num_valid)
     return index.localize(g["globaldesc"], o["xyz_feat_att_nms"], o["kp_count"], k=k, **kw)

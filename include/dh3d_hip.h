@@ -939,6 +939,44 @@ int dh3d_ransac_rigid(const float *anchor_xyz, long long anchor_stride, const fl
                       double confidence, int max_trials, unsigned long long seed, double *Rt, int32_t *valid,
                       uint8_t *inliers, int32_t *num_inliers, int32_t *trials, int32_t *num_corr, void *stream);
 
+/* Dense point-to-point ICP refinement of P registered cloud pairs (csrc/icp.hip): from a pose of dh3d_ransac_rigid to the
+ * least-squares pose over the clouds' nearest-neighbour pairs, with the dense overlap of the result.
+ * INPUTS: anchor point i of pair p at anchor + (p*Na + i) * anchor_stride (3 floats), positive point j at positive +
+ *   (p*Nb + j) * positive_stride (strides in elements, >= 3).  na = clamp(anchor_count[p], 0, Na), nb likewise; a NULL count
+ *   means Na / Nb.  Rt0 [P, 3, 4] float64 = [R | t], dh3d_ransac_rigid's convention: anchor ~ R * positive + t.  valid0 [P]
+ *   or NULL.  Everything below is float64 on the exact values of the float32 inputs, every operation rounded on its own.
+ * ASSOCIATION A(R, t): for every positive j < nb, y'_r = ((R_r0 * y_0 + R_r1 * y_1) + R_r2 * y_2) + t_r; for every anchor
+ *   i < na, d2(i, j) = (dx*dx + dy*dy) + dz*dz with dx = (double)x_i0 - y'_0 (dy, dz likewise); nn[j] = the i with the smallest
+ *   d2 among those with d2 < max_dist * max_dist (strict; the product in double), ties to the lowest i; nn[j] = -1 when there is
+ *   none or j >= nb.  The result does not depend on how the search is organised (scan or cell lists).
+ * FIT F(nn): the pairs (anchor[nn[j]], positive[j]) with nn[j] >= 0 in ascending j, n of them.  n >= 3: estimateRigidTransform
+ *   as dh3d_ransac_rigid's refit -- centroids, B over the centred pairs, the eigenvector of B's smallest eigenvalue (cyclic
+ *   Jacobi), R = quat2rot(q), t = x_centroid - R * y_centroid; sums: lane j % 256 over its j in ascending order, then a fixed
+ *   tree.  n < 3: the pose stays as it was.
+ * LOOP: pose = Rt0; `iterations` times { nn = A(pose); pose = F(nn) }; then nn = A(pose) once more, which describes the
+ *   returned pose.  No early exit: a pure function of the inputs.  iterations = 0 evaluates the given pose.
+ * OUTPUTS: Rt [P, 3, 4] float64; nn [P, Nb] the last association; num_corr [P] = #{j : nn[j] >= 0}; fitness [P] float64 =
+ *   num_corr / max(nb, 1); rmse [P] float64 = sqrt(sum of d2(nn[j], j) / num_corr) (the sum in the fit's order), NaN when
+ *   num_corr = 0; valid [P].  A pair whose valid0 is 0 or whose Rt0 has a non-finite entry: Rt NaN, nn -1, num_corr 0,
+ *   fitness 0, rmse NaN, valid 0; every other pair has valid 1.  Every element is written.  Rt may be Rt0.
+ * INDEPENDENCE: a pair's result does not depend on the batch, on the path, on the workspace's content or on the run.  NaN and
+ *   infinite coordinates are outside the contract.
+ * path: 0 = the plan's choice, 1 = scan (any shape), 2 = cell lists over dh3d_spatial_sort_cells(anchor) (Na <= 16384).
+ * dh3d_icp_plan (host only; the shape alone): 1 scan, 2 cell lists, -1 for a shape the call refuses.
+ * dh3d_icp_refine_ws_bytes (host only): bytes of the caller-owned workspace (16-byte aligned, no clearing needed); 0 exactly
+ *   where the plan is -1 or P is out of range.
+ * SIDE EFFECTS: caller's stream, one launch after the other (no parallel branches), no host sync, no allocation, no
+ *   floating-point atomics; graph-capturable.
+ * STATUS: NULL pointers (the counts and valid0 excepted), P / Na / Nb <= 0, a stride below 3, max_dist not positive and
+ *   finite, iterations < 0, a path other than 0 / 1 / 2, a NULL, misaligned or too small workspace:
+ *   DH3D_ERR_INVALID_ARGUMENT.  Na or Nb > 131072, P > 65535, iterations > 256, path 2 with Na > 16384: DH3D_ERR_UNSUPPORTED. */
+int dh3d_icp_plan(int Na, int Nb);
+size_t dh3d_icp_refine_ws_bytes(int P, int Na, int Nb);
+int dh3d_icp_refine(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *positive,
+                    long long positive_stride, const int32_t *positive_count, const double *Rt0, const int32_t *valid0, int P,
+                    int Na, int Nb, double max_dist, int iterations, int path, double *Rt, int32_t *nn, int32_t *num_corr,
+                    double *fitness, double *rmse, int32_t *valid, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Preparation of raw clouds (csrc/prepare.hip) -- get_fixednum_pcd(need_downsample = True, randsample = False)
  * (core/utils.py:87-110: open3d voxel_down_sample, remove_radius_outlier(nb_points, radius), crop to the points nearest the
  * centroid or pad), batched, for clouds of different sizes, with every size kept on the device.

@@ -1,0 +1,133 @@
+"""A numpy float64 restatement of include/dh3d_hip.h dh3d_icp_refine: brute-force nearest neighbours in chunks (the
+association), registration_reference.fit over the pairs in ascending positive index (the fit), the loop without an exit.
+The yardstick of dh3d_amd.registration.refine_icp.  numpy rounds every elementwise operation on its own, so the d2 below
+are the kernels' d2 bit for bit and so are the ids; the pose differs by the fit's summation order and eigen-solver only.
+Besides the state after every iteration it reports how close the run came to a decision that a last-bit rounding could turn:
+the smallest gap between the best d2 and a runner-up that is not bit-equal (bit-equal d2, as between duplicate anchor rows,
+is a genuine tie that the index rule decides), the smallest |d2 - max_dist^2|, and the smallest relative eigen gap."""
+import math
+import os
+
+import numpy as np
+
+import registration_reference as reg_ref
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def move(Rt, y):
+    """y' = ((R_r0 y_0 + R_r1 y_1) + R_r2 y_2) + t_r for float32 rows y [n, 3] -> float64 [n, 3]."""
+    y = np.asarray(y, np.float64)
+    return np.stack([((Rt[r, 0] * y[:, 0] + Rt[r, 1] * y[:, 1]) + Rt[r, 2] * y[:, 2]) + Rt[r, 3] for r in range(3)], axis=1)
+
+
+def associate(anchor, positive, Rt, max_dist, chunk=256):
+    """A(R, t) over anchor [na, 3] and positive [nb, 3]: (nn [nb] int32, d2 [nb] of the chosen pairs (inf without one),
+    gap, thr) with gap = the smallest difference between a positive's best d2 and the smallest d2 above it (inf without one)
+    and thr = the smallest |d2 - max_dist^2| over all pairs."""
+    x = np.asarray(anchor, np.float64)
+    m = move(Rt, positive)
+    nb, na = len(m), len(x)
+    r2 = float(max_dist) * float(max_dist)
+    nn, best = np.full(nb, -1, np.int32), np.full(nb, np.inf)
+    gap, thr = np.inf, np.inf
+    if na == 0:
+        return nn, best, gap, thr
+    for s in range(0, nb, chunk):
+        q = m[s:s + chunk]
+        dx, dy, dz = x[None, :, 0] - q[:, 0:1], x[None, :, 1] - q[:, 1:2], x[None, :, 2] - q[:, 2:3]
+        d2 = (dx * dx + dy * dy) + dz * dz
+        i = d2.argmin(axis=1)  # (the first smallest: ties to the lowest index)
+        b = d2[np.arange(len(q)), i]
+        ok = b < r2
+        nn[s:s + chunk] = np.where(ok, i, -1)
+        best[s:s + chunk] = np.where(ok, b, np.inf)
+        thr = min(thr, float(np.abs(d2 - r2).min()))
+        above = np.where(d2 > b[:, None], d2, np.inf).min(axis=1) - b
+        gap = min(gap, float(above.min()))
+    return nn, best, gap, thr
+
+
+def fit(anchor, positive, nn):
+    """F(nn): (Rt [3, 4], eigen gap) over the pairs in ascending positive index, or None when there are fewer than 3."""
+    j = np.nonzero(nn >= 0)[0]
+    if len(j) < 3:
+        return None
+    x = np.asarray(anchor, np.float64)[nn[j]]
+    y = np.asarray(positive, np.float64)[j]
+    R, t, g = reg_ref.fit(x[None], y[None])
+    return np.concatenate([R[0], t[0][:, None]], axis=1), float(g[0])
+
+
+def icp(anchor, positive, Rt0, max_dist=1.0, iterations=20, na=None, nb=None, valid0=True):
+    """dh3d_icp_refine on one pair: anchor [Na, 3], positive [Nb, 3] float32, Rt0 [3, 4].  Returns a dict: valid, states (a
+    list of iterations + 1 dicts Rt / nn [Nb] / num_corr / rmse / fitness: entry k is the result of the call with
+    iterations = k), and the margins gap / thr / eig over the whole run."""
+    anchor, positive = np.asarray(anchor, np.float32), np.asarray(positive, np.float32)
+    Na, Nb = len(anchor), len(positive)
+    na = Na if na is None else min(max(int(na), 0), Na)
+    nb = Nb if nb is None else min(max(int(nb), 0), Nb)
+    Rt = np.array(Rt0, np.float64)
+    out = dict(valid=bool(valid0) and bool(np.isfinite(Rt).all()), states=[], gap=np.inf, thr=np.inf, eig=np.inf)
+    if not out["valid"]:
+        dead = dict(Rt=np.full((3, 4), np.nan), nn=np.full(Nb, -1, np.int32), num_corr=0, rmse=np.nan, fitness=0.0)
+        out["states"] = [dead] * (iterations + 1)
+        return out
+    for k in range(iterations + 1):
+        nn = np.full(Nb, -1, np.int32)
+        nn[:nb], d2, gap, thr = associate(anchor[:na], positive[:nb], Rt, max_dist)
+        n = int((nn >= 0).sum())
+        out["gap"], out["thr"] = min(out["gap"], gap), min(out["thr"], thr)
+        out["states"].append(dict(Rt=Rt.copy(), nn=nn, num_corr=n, fitness=n / max(nb, 1),
+                                  rmse=math.sqrt(d2[np.isfinite(d2)].sum() / n) if n else np.nan))
+        if k < iterations:
+            f = fit(anchor, positive, nn)
+            if f is not None:
+                Rt, g = f
+                out["eig"] = min(out["eig"], g)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ fixtures
+
+def rotation(axis, angle):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + math.sin(angle) * K + (1.0 - math.cos(angle)) * (K @ K)
+
+
+def pose_errors(Rt, Rt_gt):
+    """(translation error in metres, rotation angle in degrees) between two [3, 4] poses."""
+    dR = Rt_gt[:, :3].T @ Rt[:, :3]
+    c = min(max((np.trace(dR) - 1.0) / 2.0, -1.0), 1.0)
+    return float(np.linalg.norm(Rt[:, 3] - Rt_gt[:, 3])), math.degrees(math.acos(c))
+
+
+def demo_pair(name, n, seed, noise=0.02, off_t=0.75, off_deg=3.2):
+    """Anchor and positive: disjoint random subsets of n points of the demo cloud `name`, the positive moved by a known
+    pose (anchor ~ R positive + t) with `noise` metres of Gaussian noise; and a start pose off_t metres / off_deg degrees
+    off the true one.  Returns (anchor [n, 3] f32, positive [n, 3] f32, Rt_gt [3, 4], Rt0 [3, 4])."""
+    cloud = np.load(os.path.join(HERE, "golden", "demo_clouds.npz"))[name].astype(np.float64)
+    rng = np.random.default_rng(seed)
+    perm = rng.permutation(len(cloud))
+    a, b = cloud[perm[:n]], cloud[perm[n:2 * n]]
+    R = rotation(rng.standard_normal(3), rng.uniform(0.2, 1.0))
+    t = rng.standard_normal(3) * 2.0
+    y = (b - t) @ R + rng.normal(0.0, noise, b.shape)  # = R^T (b - t)
+    d = rng.standard_normal(3)
+    R0 = rotation(rng.standard_normal(3), math.radians(off_deg)) @ R
+    t0 = t + d / np.linalg.norm(d) * off_t
+    return (a.astype(np.float32), y.astype(np.float32), np.concatenate([R, t[:, None]], axis=1),
+            np.concatenate([R0, t0[:, None]], axis=1))
+
+
+def clear_pair(name, n, max_dist, iterations, base=1):
+    """The first demo_pair (seeds base, base + 1, ... at most 50) whose run keeps a d2 gap above 1e-8 m^2, 1e-8 m^2 from
+    the threshold and an eigen gap above 1e-6: no id depends on a last-bit rounding.  Returns (pair, run, seed)."""
+    for s in range(base, base + 50):
+        pair = demo_pair(name, n, s)
+        run = icp(pair[0], pair[1], pair[3], max_dist=max_dist, iterations=iterations)
+        if run["gap"] > 1e-8 and run["thr"] > 1e-8 and run["eig"] > 1e-6:
+            return pair, run, s
+    raise AssertionError("no clear fixture for %s n=%d max_dist=%g" % (name, n, max_dist))
