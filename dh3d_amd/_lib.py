@@ -239,6 +239,10 @@ _SIGNATURES = {
     "dh3d_icp_refine_ws_bytes": [c_int, c_int, c_int],
     "dh3d_icp_refine": [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_double, c_int, c_int, c_fp,
                         c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp],
+    "dh3d_estimate_normals": [c_fp, c_ll, c_fp, c_fp, c_int, c_int, c_int, ctypes.POINTER(c_double), c_fp, c_fp, c_fp],
+    "dh3d_icp_refine_plane_ws_bytes": [c_int, c_int, c_int],
+    "dh3d_icp_refine_plane": [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_double, c_int,
+                              c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp],
     "dh3d_prepare_clouds_workspace": [c_int, c_int, c_int],
     "dh3d_prepare_clouds": [c_int, c_int, c_int, c_fp, c_fp, c_double, c_double, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
                             c_size_t, c_fp],
@@ -269,6 +273,7 @@ _RESTYPES = {
     "dh3d_flex_deconv_bwd_workspace_bytes": c_size_t,
     "dh3d_keypoint_nms_workspace_bytes": c_size_t,
     "dh3d_icp_refine_ws_bytes": c_size_t,
+    "dh3d_icp_refine_plane_ws_bytes": c_size_t,
     "dh3d_prepare_clouds_workspace": c_size_t,
     "dh3d_retrieve_ws_bytes": c_size_t,
     "dh3d_resample_clouds_ws_bytes": c_size_t,

@@ -33,6 +33,12 @@
 //                     over ascending j, float64 block sums in a fixed tree (count and centroids, then B over the centred
 //                     pairs), lane 0 solves (rigid_fit.h: the functions of ransac_kernel's refit).  n < 3 leaves the pose.
 //   icp_stats_kernel  num_corr, fitness, rmse (the sum in the fit's order) and the outputs of invalid pairs.
+// Point-to-plane (dh3d_icp_refine_plane): the same launches with another fit and two more outputs.
+//   icp_plane_fit_kernel    one 256-lane workgroup per pair: the pairs whose anchor has a non-zero normal, the centroid of
+//                           their moved positives, 21 + 6 float64 block sums (H = sum a a^T, g = sum a r), lane 0 solves the
+//                           6 x 6 system by Cholesky in registers and composes the step with the pose.  Fewer than 6 pairs or
+//                           a refused pivot leave the pose.  224 VGPRs, no scratch; one workgroup per pair as icp_fit_kernel.
+//   icp_plane_stats_kernel  num_plane and rmse_plane.
 // Compiled without contraction (csrc/Makefile EXACT): the ids depend on every rounding of d2.
 #include <math.h>
 
@@ -337,6 +343,184 @@ __global__ __launch_bounds__(kThreads) void icp_stats_kernel(const float *__rest
   }
 }
 
+// ----------------------------------------------------------------------------------------------------------- plane fit
+// the pairs of the point-to-plane fit: nn[j] >= 0 and an anchor normal with n . n > 0
+__device__ __forceinline__ bool icp_plane_pair(const float *nr, double *n) {
+  n[0] = nr[0]; n[1] = nr[1]; n[2] = nr[2];
+  return (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2] > 0.0;
+}
+
+// One 256-lane workgroup per pair (include/dh3d_hip.h dh3d_icp_refine_plane F_plane): the centroid c of the moved positives
+// of the pairs, then the 21 + 6 float64 sums of H = sum a a^T and g = sum a r over a = [(m - c) x n ; n], r = n . (x - m),
+// each lane over its j in ascending order and a fixed tree; lane 0 solves H s = g by Cholesky (registers: every index is a
+// constant after unrolling) and composes the step with the pose.  Fewer than 6 pairs or a refused pivot leave the pose.
+__global__ __launch_bounds__(kThreads) void icp_plane_fit_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
+                                                                 const float *__restrict__ normals, long long n_stride,
+                                                                 const float *__restrict__ positive, long long b_stride, int Nb,
+                                                                 const int32_t *__restrict__ b_count,
+                                                                 const int32_t *__restrict__ nn, double *__restrict__ pose) {
+  __shared__ double s_red[kThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  const float *pa = anchor + (long long)p * Na * a_stride, *pn = normals + (long long)p * Na * n_stride;
+  const float *pb = positive + (long long)p * Nb * b_stride;
+  const int32_t *row = nn + (long long)p * Nb;
+  double rt[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) rt[e] = pose[(long long)p * 12 + e];
+  double cnt = 0.0, sm[3] = {0.0, 0.0, 0.0};
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    double n[3], m[3];
+    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
+      const float *y = pb + (long long)j * b_stride;
+      icp_move(rt, y[0], y[1], y[2], m);
+      cnt += 1.0;
+      sm[0] += m[0]; sm[1] += m[1]; sm[2] += m[2];
+    }
+  }
+  const int npl = (int)block_sum_256<double>(cnt, s_red);
+  if (npl < 6) return;  // the pose stays as it was (workgroup-uniform)
+  double c[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) c[r] = block_sum_256<double>(sm[r], s_red) / (double)npl;
+  double H[21], g[6];  // H: the upper triangle, row by row
+#pragma unroll
+  for (int e = 0; e < 21; ++e) H[e] = 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) g[e] = 0.0;
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    double n[3], m[3];
+    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
+      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
+      icp_move(rt, y[0], y[1], y[2], m);
+      const double q0 = m[0] - c[0], q1 = m[1] - c[1], q2 = m[2] - c[2];
+      const double a[6] = {q1 * n[2] - q2 * n[1], q2 * n[0] - q0 * n[2], q0 * n[1] - q1 * n[0], n[0], n[1], n[2]};
+      const double dx = (double)x[0] - m[0], dy = (double)x[1] - m[1], dz = (double)x[2] - m[2];
+      const double res = (dx * n[0] + dy * n[1]) + dz * n[2];
+      int e = 0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) {
+#pragma unroll
+        for (int k = r; k < 6; ++k) H[e++] += a[r] * a[k];
+        g[r] += a[r] * res;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 21; ++e) H[e] = block_sum_256<double>(H[e], s_red);
+#pragma unroll
+  for (int e = 0; e < 6; ++e) g[e] = block_sum_256<double>(g[e], s_red);
+  if (tid != 0) return;
+  // Cholesky H = L L^T, row by row; L[k][j] lives at L[k * 6 + j]
+  double L[36], big = 0.0;
+  {
+    int e = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      big = fmax(big, H[e]);
+      e += 6 - r;
+    }
+  }
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+#pragma unroll
+    for (int j = 0; j <= k; ++j) {
+      double v = H[j * 6 - j * (j - 1) / 2 + (k - j)];  // H[j][k], j <= k
+#pragma unroll
+      for (int q = 0; q < j; ++q) v = v - L[k * 6 + q] * L[j * 6 + q];
+      if (j < k) {
+        L[k * 6 + j] = v / L[j * 6 + j];
+      } else {
+        ok = ok && isfinite(v) && v > 1e-12 * big;
+        L[k * 6 + k] = sqrt(v);
+      }
+    }
+  }
+  if (!ok) return;  // a rank-deficient or non-finite system: the pose stays as it was
+  double z[6], s[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    double v = g[k];
+#pragma unroll
+    for (int j = 0; j < k; ++j) v = v - L[k * 6 + j] * z[j];
+    z[k] = v / L[k * 6 + k];
+  }
+#pragma unroll
+  for (int k = 5; k >= 0; --k) {
+    double v = z[k];
+#pragma unroll
+    for (int j = k + 1; j < 6; ++j) v = v - L[j * 6 + k] * s[j];
+    s[k] = v / L[k * 6 + k];
+  }
+  // dR = I + (sin th / th) K + (2 sin^2(th / 2) / th^2) K^2, K = [w]x, K^2 = w w^T - (w . w) I
+  const double w0 = s[0], w1 = s[1], w2 = s[2];
+  const double tt = (w0 * w0 + w1 * w1) + w2 * w2, th = sqrt(tt);
+  double dR[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+  if (th > 0.0 && isfinite(th)) {
+    const double hs = sin(th / 2.0), A = sin(th) / th, B = (2.0 * (hs * hs)) / (th * th);
+    const double Km[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+    const double w[3] = {w0, w1, w2};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double k2 = r == k ? w[r] * w[k] - tt : w[r] * w[k];
+        dR[3 * r + k] = (dR[3 * r + k] + A * Km[3 * r + k]) + B * k2;
+      }
+  }
+  bool fin = true;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) fin = fin && isfinite(s[e]);
+  if (!fin) return;
+  const double u[3] = {rt[3] - c[0], rt[7] - c[1], rt[11] - c[2]};
+  double *out = pose + (long long)p * 12;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      out[4 * r + k] = (dR[3 * r] * rt[k] + dR[3 * r + 1] * rt[4 + k]) + dR[3 * r + 2] * rt[8 + k];
+    out[4 * r + 3] = (((dR[3 * r] * u[0] + dR[3 * r + 1] * u[1]) + dR[3 * r + 2] * u[2]) + c[r]) + s[3 + r];
+  }
+}
+
+// num_plane and rmse_plane of the last association under the returned pose (the sums in the fit's order)
+__global__ __launch_bounds__(kThreads) void icp_plane_stats_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
+                                                                   const float *__restrict__ normals, long long n_stride,
+                                                                   const float *__restrict__ positive, long long b_stride,
+                                                                   int Nb, const int32_t *__restrict__ b_count,
+                                                                   const int32_t *__restrict__ nn, const double *__restrict__ pose,
+                                                                   int32_t *__restrict__ num_plane, double *__restrict__ rmse_plane) {
+  __shared__ double s_red[kThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  const float *pa = anchor + (long long)p * Na * a_stride, *pn = normals + (long long)p * Na * n_stride;
+  const float *pb = positive + (long long)p * Nb * b_stride;
+  const int32_t *row = nn + (long long)p * Nb;
+  const double *rt = pose + (long long)p * 12;
+  double cnt = 0.0, sum = 0.0;
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    double n[3], m[3];
+    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
+      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
+      icp_move(rt, y[0], y[1], y[2], m);
+      const double dx = (double)x[0] - m[0], dy = (double)x[1] - m[1], dz = (double)x[2] - m[2];
+      const double res = (dx * n[0] + dy * n[1]) + dz * n[2];
+      cnt += 1.0;
+      sum += res * res;
+    }
+  }
+  const int npl = (int)block_sum_256<double>(cnt, s_red);
+  sum = block_sum_256<double>(sum, s_red);
+  if (tid == 0) {
+    num_plane[p] = npl;
+    rmse_plane[p] = npl > 0 ? sqrt(sum / (double)npl) : quiet_nan();
+  }
+}
+
 // ----------------------------------------------------------------------------------------------------------- workspace
 struct IcpWs {
   double *pose;    // [P, 12] the working pose
@@ -369,18 +553,12 @@ DH3D_API size_t dh3d_icp_refine_ws_bytes(int P, int Na, int Nb) {
   return icp_served(P, Na, Nb) ? carve_bytes<IcpWs>(P, Na, Nb) : 0;
 }
 
-DH3D_API int dh3d_icp_refine(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *positive,
-                             long long positive_stride, const int32_t *positive_count, const double *Rt0,
-                             const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path,
-                             double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
-                             void *workspace, size_t workspace_bytes, void *stream) {
-  DH3D_REQUIRE(anchor && positive && Rt0 && Rt && nn && num_corr && fitness && rmse && valid);
-  DH3D_REQUIRE(P > 0 && Na > 0 && Nb > 0 && anchor_stride >= 3 && positive_stride >= 3);
-  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
-  DH3D_SUPPORTED(icp_served(P, Na, Nb) && iterations <= kMaxIter);
-  DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
-  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-               workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
+// The launches of both entries: normals == nullptr is the point-to-point fit, else the point-to-plane fit and its two outputs.
+static int icp_run(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *normals,
+                   long long normals_stride, const float *positive, long long positive_stride, const int32_t *positive_count,
+                   const double *Rt0, const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path,
+                   double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
+                   int32_t *num_plane, double *rmse_plane, void *workspace, void *stream) {
   Carve carve(workspace);
   const IcpWs ws(carve, P, Na, Nb);
   const bool grid = (path == 0 ? dh3d_icp_plan(Na, Nb) : path) == 2;
@@ -402,11 +580,55 @@ DH3D_API int dh3d_icp_refine(const float *anchor, long long anchor_stride, const
     else
       hipLaunchKernelGGL(icp_scan_kernel, agrid, dim3(kThreads), 0, s, anchor, anchor_stride, Na, anchor_count, positive,
                          positive_stride, Nb, positive_count, ws.pose, valid, r2, nn);
-    if (it < iterations)
+    if (it < iterations && !normals)
       hipLaunchKernelGGL(icp_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, positive, positive_stride,
                          Nb, positive_count, nn, ws.pose);
+    else if (it < iterations)
+      hipLaunchKernelGGL(icp_plane_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals,
+                         normals_stride, positive, positive_stride, Nb, positive_count, nn, ws.pose);
   }
   hipLaunchKernelGGL(icp_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, positive, positive_stride, Nb,
                      positive_count, nn, ws.pose, Rt, num_corr, fitness, rmse);
+  if (normals)
+    hipLaunchKernelGGL(icp_plane_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals,
+                       normals_stride, positive, positive_stride, Nb, positive_count, nn, ws.pose, num_plane, rmse_plane);
   return dh3d_launch_status();
+}
+
+DH3D_API int dh3d_icp_refine(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *positive,
+                             long long positive_stride, const int32_t *positive_count, const double *Rt0,
+                             const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path,
+                             double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
+                             void *workspace, size_t workspace_bytes, void *stream) {
+  DH3D_REQUIRE(anchor && positive && Rt0 && Rt && nn && num_corr && fitness && rmse && valid);
+  DH3D_REQUIRE(P > 0 && Na > 0 && Nb > 0 && anchor_stride >= 3 && positive_stride >= 3);
+  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
+  DH3D_SUPPORTED(icp_served(P, Na, Nb) && iterations <= kMaxIter);
+  DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
+  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+               workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
+  return icp_run(anchor, anchor_stride, anchor_count, nullptr, 0, positive, positive_stride, positive_count, Rt0, valid0, P, Na,
+                 Nb, max_dist, iterations, path, Rt, nn, num_corr, fitness, rmse, valid, nullptr, nullptr, workspace, stream);
+}
+
+DH3D_API size_t dh3d_icp_refine_plane_ws_bytes(int P, int Na, int Nb) { return dh3d_icp_refine_ws_bytes(P, Na, Nb); }
+
+DH3D_API int dh3d_icp_refine_plane(const float *anchor, long long anchor_stride, const int32_t *anchor_count,
+                                   const float *anchor_normals, long long normals_stride, const float *positive,
+                                   long long positive_stride, const int32_t *positive_count, const double *Rt0,
+                                   const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path,
+                                   double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
+                                   int32_t *num_plane, double *rmse_plane, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
+  DH3D_REQUIRE(anchor && anchor_normals && positive && Rt0 && Rt && nn && num_corr && fitness && rmse && valid && num_plane &&
+               rmse_plane);
+  DH3D_REQUIRE(P > 0 && Na > 0 && Nb > 0 && anchor_stride >= 3 && normals_stride >= 3 && positive_stride >= 3);
+  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
+  DH3D_SUPPORTED(icp_served(P, Na, Nb) && iterations <= kMaxIter);
+  DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
+  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+               workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
+  return icp_run(anchor, anchor_stride, anchor_count, anchor_normals, normals_stride, positive, positive_stride, positive_count,
+                 Rt0, valid0, P, Na, Nb, max_dist, iterations, path, Rt, nn, num_corr, fitness, rmse, valid, num_plane,
+                 rmse_plane, workspace, stream);
 }

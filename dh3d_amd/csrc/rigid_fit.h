@@ -94,6 +94,66 @@ __device__ void rotation_from_b(const double *Bu, double *R) {
   R[8] = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3;
 }
 
+// The 3x3 twin of rotation_from_b's loop, for csrc/normals.hip: cyclic Jacobi on the symmetric C (upper triangle c00 c01 c02
+// c11 c12 c22), the same rotation formulas and the same drop rule.  lam = the diagonal after the sweeps, in its places; n = the
+// column of the accumulated rotations at the first smallest diagonal entry (unit up to the rotations' roundings); returns
+// that entry.  Registers only: every index is a constant after unrolling.
+__device__ __forceinline__ double smallest_eigenvector_3(const double *Cu, double *lam, double *n) {
+  double a[3][3], v[3][3];
+  int e = 0;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = r; c < 3; ++c) a[r][c] = a[c][r] = Cu[e++];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[r][c] = r == c ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 32; ++sweep) {  // (converges in 4-5 sweeps)
+    const double off = (a[0][1] * a[0][1] + a[0][2] * a[0][2]) + a[1][2] * a[1][2];
+    if (!(off > 0.0)) break;  // (also stops on NaN)
+#pragma unroll
+    for (int pp = 0; pp < 2; ++pp) {
+#pragma unroll
+      for (int qq = pp + 1; qq < 3; ++qq) {
+        const double apq = a[pp][qq];
+        if (fabs(apq) <= 1e-18 * (fabs(a[pp][pp]) + fabs(a[qq][qq]))) {  // negligible: drop it
+          a[pp][qq] = a[qq][pp] = 0.0;
+          continue;
+        }
+        const double theta = (a[qq][qq] - a[pp][pp]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+        a[pp][pp] -= t * apq;
+        a[qq][qq] += t * apq;
+        a[pp][qq] = a[qq][pp] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          if (k != pp && k != qq) {
+            const double g = a[k][pp], h = a[k][qq];
+            a[k][pp] = a[pp][k] = g - s * (h + g * tau);
+            a[k][qq] = a[qq][k] = h + s * (g - h * tau);
+          }
+          const double g = v[k][pp], h = v[k][qq];
+          v[k][pp] = g - s * (h + g * tau);
+          v[k][qq] = h + s * (g - h * tau);
+        }
+      }
+    }
+  }
+  lam[0] = a[0][0]; lam[1] = a[1][1]; lam[2] = a[2][2];
+  double low = a[0][0];
+  n[0] = v[0][0]; n[1] = v[1][0]; n[2] = v[2][0];
+#pragma unroll
+  for (int k = 1; k < 3; ++k) {
+    if (lam[k] < low) {
+      low = lam[k];
+      n[0] = v[0][k]; n[1] = v[1][k]; n[2] = v[2][k];
+    }
+  }
+  return low;
+}
+
 // t = xc - R yc
 __device__ __forceinline__ void translation(const double *R, const double *xc, const double *yc, double *t) {
   for (int r = 0; r < 3; ++r) t[r] = xc[r] - (R[3 * r] * yc[0] + R[3 * r + 1] * yc[1] + R[3 * r + 2] * yc[2]);

@@ -13,6 +13,9 @@ sampler replaces randsample, whose stream cannot be reproduced).
     res = register_clouds(model, anchor_points, positive_points)              # forward (config.detection) + register
     res = refine_icp(anchor_points, positive_points, res["Rt"], res["valid"])  # dense ICP: Rt, fitness, rmse, nn, ...
     res = register_clouds(model, anchor_points, positive_points, refine=True)  # ... with the refined pose as Rt
+    nrm = estimate_normals(anchor_points, k=16)                               # PCA normals, curvature, the ids used
+    res = refine_icp_plane(anchor_points, positive_points, res["Rt"], res["valid"])  # point-to-plane: + num_plane, rmse_plane
+    res = register_clouds(model, anchor_points, positive_points, refine={"method": "plane", "iterations": 5})
     dt, ddeg = transform_errors(T_gt, res["Rt"], res["valid"])                # compareTransform, host float64
     summary = summarize_registration(dt, ddeg, res["inlier_ratio"], res["trials"])
 """
@@ -152,6 +155,11 @@ def refine_icp(anchor_points, positive_points, Rt, valid=None, anchor_count=None
     without any).  iterations = 0 evaluates the given pose.  No host sync: graph-capturable.  The workspace is kept per
     (device, P, Na, Nb) and carries nothing between calls; calls of one shape share it, so they belong on one stream (or on
     streams ordered against each other)."""
+    return _icp_call(anchor_points, positive_points, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, None)
+
+
+def _icp_call(anchor_points, positive_points, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, normals):
+    """The checks, the workspace and the call of refine_icp (normals None: dh3d_icp_refine) and refine_icp_plane."""
     a = _rows(anchor_points, "anchor_points", 3)
     b = _rows(positive_points, "positive_points", 3)
     P, Na = a.shape[:2]
@@ -191,16 +199,104 @@ def refine_icp(anchor_points, positive_points, Rt, valid=None, anchor_count=None
     fitness = torch.empty((P,), dtype=torch.float64, device=dev)
     rmse = torch.empty((P,), dtype=torch.float64, device=dev)
     ok = torch.empty((P,), dtype=torch.int32, device=dev)
+    if normals is None:
+        with torch.cuda.device(dev):
+            L.check(lib.dh3d_icp_refine(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(b), b.stride(1), L.ptr(bc), L.ptr(rt0),
+                                        L.ptr(valid), P, Na, Nb, max_dist, iterations, path, L.ptr(out_rt), L.ptr(nn),
+                                        L.ptr(num_corr), L.ptr(fitness), L.ptr(rmse), L.ptr(ok), L.ptr(ws), ws.numel(),
+                                        L.stream_ptr()), "refine_icp")
+        return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse)
+    num_plane = torch.empty((P,), dtype=torch.int32, device=dev)
+    rmse_plane = torch.empty((P,), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        L.check(lib.dh3d_icp_refine(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(b), b.stride(1), L.ptr(bc), L.ptr(rt0), L.ptr(valid),
-                                    P, Na, Nb, max_dist, iterations, path, L.ptr(out_rt), L.ptr(nn), L.ptr(num_corr),
-                                    L.ptr(fitness), L.ptr(rmse), L.ptr(ok), L.ptr(ws), ws.numel(), L.stream_ptr()),
-                "refine_icp")
-    return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse)
+        L.check(lib.dh3d_icp_refine_plane(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(normals), normals.stride(1), L.ptr(b),
+                                          b.stride(1), L.ptr(bc), L.ptr(rt0), L.ptr(valid), P, Na, Nb, max_dist, iterations,
+                                          path, L.ptr(out_rt), L.ptr(nn), L.ptr(num_corr), L.ptr(fitness), L.ptr(rmse),
+                                          L.ptr(ok), L.ptr(num_plane), L.ptr(rmse_plane), L.ptr(ws), ws.numel(),
+                                          L.stream_ptr()), "refine_icp_plane")
+    return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse, num_plane=num_plane,
+                rmse_plane=rmse_plane)
+
+
+NORMALS_MAX_K = 64  # csrc/normals.hip kMaxK
+
+
+def _viewpoint(viewpoint):
+    v = [float(c) for c in viewpoint] if np.ndim(viewpoint) == 1 else []
+    if len(v) != 3 or not all(np.isfinite(v)):
+        raise ValueError("viewpoint must be three finite numbers, got %r" % (viewpoint,))
+    return (L.c_double * 3)(*v)
+
+
+def estimate_normals(points, num_valid=None, k=16, viewpoint=(0., 0., 0.), nbr=None):
+    """Surface normals by PCA of every point's k nearest neighbours, flipped towards `viewpoint` (the reference's
+    external/findPointNormals.m; include/dh3d_hip.h dh3d_estimate_normals states every rule).  points [P, N, >=3] float32
+    on the GPU (the first three columns are read; column views are read in place), num_valid [P] int32 or None (all rows).
+    nbr [P, N, K] int32, K <= 64: the neighbour ids of every point; None takes them from utils.batched_knn(points, k), whose
+    lists hold the point itself.  Ids outside 0 .. num_valid - 1 are skipped, so, as batched_nms says of its padding, rows
+    behind num_valid never enter a valid point's neighbourhood when the padding lies far away (prepare_clouds' rows of
+    100000.0) and the cloud has at least k points: that equals the normals of the cropped cloud.  Returns a dict of device
+    tensors: normals [P, N, 3] float32 (zero where fewer than 3 usable neighbours, coincident neighbours, or a row behind
+    num_valid), curvature [P, N] float32 (smallest eigenvalue / their sum) and nbr (the ids used).  No host sync:
+    graph-capturable."""
+    x = _rows(points, "points", 3)
+    P, N = x.shape[:2]
+    dev = x.device
+    cnt = None if num_valid is None else _count(num_valid, "num_valid", P, dev)
+    if nbr is None:
+        k = int(k)
+        if not 1 <= k <= NORMALS_MAX_K:
+            raise ValueError("estimate_normals: need 1 <= k <= %d, got %d" % (NORMALS_MAX_K, k))
+        from .utils import batched_knn
+        with torch.cuda.device(dev):
+            nbr = batched_knn(x[:, :, :3].contiguous(), k)[0]
+    nbr = L.require_cuda_i32(nbr, "nbr", 3)
+    if nbr.shape[0] != P or nbr.shape[1] != N or nbr.device != dev or not 1 <= nbr.shape[2] <= NORMALS_MAX_K:
+        raise ValueError("nbr must be int32 [%d, %d, 1..%d] on %s, got %s on %s"
+                         % (P, N, NORMALS_MAX_K, dev, tuple(nbr.shape), nbr.device))
+    if N > ICP_MAX_POINTS:
+        raise ValueError("estimate_normals: at most %d points per cloud, got %d" % (ICP_MAX_POINTS, N))
+    vp = _viewpoint(viewpoint)
+    normals = torch.empty((P, N, 3), dtype=torch.float32, device=dev)
+    curvature = torch.empty((P, N), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().dh3d_estimate_normals(L.ptr(x), x.stride(1), L.ptr(cnt), L.ptr(nbr), P, N, nbr.shape[2], vp,
+                                              L.ptr(normals), L.ptr(curvature), L.stream_ptr()), "estimate_normals")
+    return dict(normals=normals, curvature=curvature, nbr=nbr)
+
+
+def refine_icp_plane(anchor_points, positive_points, Rt, valid=None, anchor_count=None, positive_count=None, max_dist=1.0,
+                     iterations=20, path=0, anchor_normals=None, normals_k=16, viewpoint=(0., 0., 0.)):
+    """Dense point-to-plane ICP: refine_icp's inputs, association, loop and outputs with the fit that minimises the
+    residuals along the anchor's normals (a linearised 6 x 6 solve per iteration; include/dh3d_hip.h dh3d_icp_refine_plane
+    states every rule).  On street scenes it reaches in about 5 iterations what the point-to-point fit has not reached in
+    20, because walls and ground no longer hold the pose back along themselves.  anchor_normals [P, Na, >=3] float32 is read
+    in place (zero normals drop out of the fit); None computes it with estimate_normals(anchor_points, anchor_count,
+    normals_k, viewpoint).  The result is refine_icp's dict -- rmse stays the point-to-point one, so the two methods
+    compare -- plus num_plane [P] int32 (pairs with a normal in the last association) and rmse_plane [P] float64 (the rms
+    residual along the normals; NaN without pairs).  No host sync: graph-capturable; the workspace is refine_icp's."""
+    a = _rows(anchor_points, "anchor_points", 3)
+    if anchor_normals is None:
+        anchor_normals = estimate_normals(a, anchor_count, normals_k, viewpoint)["normals"]
+    nrm = _rows(anchor_normals, "anchor_normals", 3)
+    if tuple(nrm.shape[:2]) != tuple(a.shape[:2]) or nrm.device != a.device:
+        raise ValueError("anchor_normals must be [%d, %d, >=3] on %s, got %s on %s"
+                         % (a.shape[0], a.shape[1], a.device, tuple(nrm.shape), nrm.device))
+    return _icp_call(a, positive_points, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, nrm)
+
+
+def refine_pose(anchor_points, positive_points, Rt, valid=None, anchor_count=None, positive_count=None, method="point", **kw):
+    """The dense refinement behind register_clouds / PlaceIndex.localize(refine=...): method "point" is refine_icp (its
+    keywords max_dist, iterations, path), "plane" is refine_icp_plane (those plus anchor_normals, normals_k, viewpoint)."""
+    if method not in ("point", "plane"):
+        raise ValueError('method must be "point" or "plane", got %r' % (method,))
+    fn = refine_icp if method == "point" else refine_icp_plane
+    return fn(anchor_points, positive_points, Rt, valid, anchor_count=anchor_count, positive_count=positive_count, **kw)
 
 
 def _refine_kw(refine):
-    """refine: None / False (no refinement), True (refine_icp's defaults) or a dict of refine_icp keywords."""
+    """refine: None / False (no refinement), True (refine_icp's defaults) or a dict of refine_pose keywords: refine_icp's,
+    or method="plane" and refine_icp_plane's."""
     if refine is None or refine is False:
         return None
     if refine is True:
@@ -215,7 +311,8 @@ def register_clouds(model, anchor_points, positive_points, num_valid=None, refin
     then register on the keypoints.  num_valid: None, one int32 [P] tensor for both batches, or a pair (anchor, positive).
     refine: None, True or a dict of refine_icp keywords -- the RANSAC pose is then refined by dense ICP of the full clouds
     (num_valid as the counts): Rt is the refined pose and the result gains Rt_ransac (the keypoint fit), fitness, rmse,
-    num_corr_icp and nn; valid stays the RANSAC fit's."""
+    num_corr_icp and nn; valid stays the RANSAC fit's.  A dict with method="plane" (and refine_icp_plane's keywords) refines
+    point-to-plane instead and adds num_plane and rmse_plane."""
     if not getattr(model.config, "detection", False):
         raise ValueError("register_clouds needs a model with config.detection (the keypoint outputs)")
     rkw = _refine_kw(refine)
@@ -225,9 +322,11 @@ def register_clouds(model, anchor_points, positive_points, num_valid=None, refin
     ob = model.forward(positive_points, fetch=fetch, num_valid=nv_b)
     out = register(oa["xyz_feat_att_nms"], oa["kp_count"], ob["xyz_feat_att_nms"], ob["kp_count"], **kw)
     if rkw is not None:
-        icp = refine_icp(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv_a, positive_count=nv_b, **rkw)
+        icp = refine_pose(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv_a, positive_count=nv_b, **rkw)
         out["Rt_ransac"], out["Rt"] = out["Rt"], icp["Rt"]
         out["fitness"], out["rmse"], out["num_corr_icp"], out["nn"] = icp["fitness"], icp["rmse"], icp["num_corr"], icp["nn"]
+        if "rmse_plane" in icp:
+            out["num_plane"], out["rmse_plane"] = icp["num_plane"], icp["rmse_plane"]
     return out
 
 

@@ -192,7 +192,9 @@ class PlaceIndex:
         winner's) is refined by dense ICP of query_cloud [Q, N, >=3] (query_cloud_count [Q] int32 or None) against the
         winner's stored cloud, gathered by place id on the device; a query without a winner goes in as invalid.  Rt is then
         the refined pose and the result gains Rt_ransac (the keypoint fit), fitness and rmse (the dense overlap: the check on
-        the retrieved place).  Needs an index built with points > 0 (else ValueError).  No host sync."""
+        the retrieved place); a dict with method="plane" refines point-to-plane (registration.refine_icp_plane's keywords;
+        the winner's normals are computed per call) and adds rmse_plane.  Needs an index built with points > 0 (else
+        ValueError).  No host sync."""
         if not self.keypoints:
             raise ValueError("localize needs a PlaceIndex built with keypoints > 0")
         rkw = registration._refine_kw(refine)
@@ -234,19 +236,22 @@ class PlaceIndex:
             idx=idx, dist=dist)
         if rkw is not None:
             safe_place = place.clamp(min=0).long()
-            icp = registration.refine_icp(self.cloud.index_select(0, safe_place), query_cloud, out["Rt"], any_ok,
-                                          anchor_count=self.cloud_count.index_select(0, safe_place),
-                                          positive_count=query_cloud_count, **rkw)
+            icp = registration.refine_pose(self.cloud.index_select(0, safe_place), query_cloud, out["Rt"], any_ok,
+                                           anchor_count=self.cloud_count.index_select(0, safe_place),
+                                           positive_count=query_cloud_count, **rkw)
             out["Rt_ransac"], out["Rt"] = out["Rt"], icp["Rt"]
             out["fitness"], out["rmse"] = icp["fitness"], icp["rmse"]
+            if "rmse_plane" in icp:
+                out["rmse_plane"] = icp["rmse_plane"]
         return out
 
 
 def relocalize_clouds(global_model, local_model, index, points, k=5, num_valid=None, refine=None, **kw):
     """Clouds [Q, N, 3] in, place ids and poses out: globaldesc from `global_model` (config.extract_global), kp_count /
     xyz_feat_att_nms from `local_model` (config.detection) -- two models, as the reference has two checkpoints -- then
-    index.localize.  num_valid: None or int32 [Q].  refine: None, True or a dict of registration.refine_icp keywords -- the
-    winner's pose is refined by dense ICP of `points` against the place's stored cloud (PlaceIndex(points=...))."""
+    index.localize.  num_valid: None or int32 [Q].  refine: None, True or a dict of registration.refine_icp keywords (or
+    method="plane" and registration.refine_icp_plane's) -- the winner's pose is refined by dense ICP of `points` against the
+    place's stored cloud (PlaceIndex(points=...))."""
     if not getattr(global_model.config, "extract_global", False):
         raise ValueError("relocalize_clouds needs a global_model with config.extract_global (the globaldesc output)")
     if not getattr(local_model.config, "detection", False):

@@ -977,6 +977,66 @@ int dh3d_icp_refine(const float *anchor, long long anchor_stride, const int32_t 
                     int Na, int Nb, double max_dist, int iterations, int path, double *Rt, int32_t *nn, int32_t *num_corr,
                     double *fitness, double *rmse, int32_t *valid, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Surface normals from given neighbour lists (csrc/normals.hip) -- external/findPointNormals.m of the reference's
+ * evaluation: PCA of a point's k nearest neighbours, the eigenvector of the smallest eigenvalue flipped towards a view point.
+ * INPUTS: point i of cloud p at xyz + (p*N + i) * xyz_stride (3 floats; the stride in elements, >= 3).  n = clamp(count[p], 0,
+ *   N); a NULL count means N.  nbr [P, N, K] int32: the neighbour ids of every point, from the caller's exact kNN (the call
+ *   searches nothing).  viewpoint: three doubles in HOST memory, read before the call returns.
+ * RULE, float64 on the exact values of the float32 coordinates, every operation rounded on its own.  For every point i < n:
+ *   the usable neighbours are the entries of nbr[p, i, :] with 0 <= id < n, in list order, m of them; duplicates count as
+ *   given and i itself takes part only where the list holds it.  c = (sum of x) / m per axis; C_ab = (sum of (x_a - c_a) *
+ *   (x_b - c_b)) / m for ab = 00 01 02 11 12 22; every sum starts from 0 and runs in list order.  Cyclic Jacobi on C (the
+ *   rotations and the drop rule of dh3d_ransac_rigid's refit, on 3 x 3; csrc/rigid_fit.h) leaves the eigenvalues on the
+ *   diagonal, in their places d_0 d_1 d_2, and the accumulated rotations V.  l_0 = the first smallest d_k, e = column k of V
+ *   (unit up to the rotations' roundings; not normalised again).  sum = (d_0 + d_1) + d_2.
+ *   s = ((v_0 - x_i0) * e_0 + (v_1 - x_i1) * e_1) + (v_2 - x_i2) * e_2; the normal is -e when s < 0, else e.
+ * OUTPUTS: normals [P, N, 3] float32 (the float64 normal rounded once), curvature [P, N] float32 = l_0 / sum.  m < 3 or a sum
+ *   that is not > 0 (coincident neighbours): normal (0, 0, 0), curvature 0.  Rows i >= n: normal 0, curvature 0.  Every
+ *   element is written.  A point's result does not depend on the batch or on the run.  NaN and infinite coordinates are
+ *   outside the contract.
+ * SIDE EFFECTS: one launch on the caller's stream, no host sync, no allocation, no workspace, no atomics; graph-capturable
+ *   (the viewpoint is captured by value).
+ * STATUS: NULL pointers (count excepted), P / N / K <= 0, a stride below 3: DH3D_ERR_INVALID_ARGUMENT.  K > 64, N > 131072,
+ *   P > 65535: DH3D_ERR_UNSUPPORTED. */
+int dh3d_estimate_normals(const float *xyz, long long xyz_stride, const int32_t *count, const int32_t *nbr, int P, int N, int K,
+                          const double *viewpoint, float *normals, float *curvature, void *stream);
+
+/* Dense point-to-plane ICP refinement (csrc/icp.hip): dh3d_icp_refine with another fit.  The inputs, the ASSOCIATION A, the
+ * LOOP (pose = Rt0; `iterations` times { nn = A(pose); pose = F_plane(nn, pose) }; then nn = A(pose) once more), the paths,
+ * the plan, the limits and the independence guarantees are dh3d_icp_refine's, word for word.  In addition:
+ * INPUTS: the normal of anchor point i of pair p at anchor_normals + (p*Na + i) * normals_stride (3 floats, stride in elements,
+ *   >= 3), as dh3d_estimate_normals writes them; a zero normal takes its point out of the fit, not out of the association.
+ * FIT F_plane(nn, pose = [R | t]), float64 on the exact float32 values, every operation rounded on its own.  The pairs are
+ *   the j < nb in ascending order with i = nn[j] >= 0 and (n_0*n_0 + n_1*n_1) + n_2*n_2 > 0 for n = the normal of anchor i;
+ *   n_pl of them.  n_pl < 6: the pose stays as it was.  m_j = y'_j of the association under the pose; c = (sum of m_j) / n_pl.
+ *   Per pair q = m_j - c; a = (q_1*n_2 - q_2*n_1, q_2*n_0 - q_0*n_2, q_0*n_1 - q_1*n_0, n_0, n_1, n_2); d = (double)x_i - m_j
+ *   per axis; r = (d_0*n_0 + d_1*n_1) + d_2*n_2.  H_uv = sum of a_u * a_v (u <= v, 21 sums), g_u = sum of a_u * r (6 sums).
+ *   Every sum (n_pl's three for c included): lane j % 256 over its j in ascending order from 0, then a fixed tree.
+ *   H s = g by Cholesky, row by row: for k = 0..5, for j = 0..k: v = H_jk, then v = v - L_kq * L_jq for q = 0..j-1; j < k:
+ *   L_kj = v / L_jj; j = k: the pivot v, L_kk = sqrt(v).  A pivot that is not finite or is <= 1e-12 * max_u H_uu leaves the
+ *   pose as it was.  z_k = (g_k - L_k0 z_0 - ... - L_k,k-1 z_k-1) / L_kk for k = 0..5 and s_k = (z_k - L_k+1,k s_k+1 - ... -
+ *   L_5k s_5) / L_kk for k = 5..0, the subtractions one after the other in that order.  A non-finite s leaves the pose.
+ *   w = s[0:3], tt = (w_0*w_0 + w_1*w_1) + w_2*w_2, th = sqrt(tt).  th == 0: dR = I.  Else A = sin(th) / th, hs = sin(th / 2),
+ *   B = (2 * (hs * hs)) / (th * th), K = [[0, -w_2, w_1], [w_2, 0, -w_0], [-w_1, w_0, 0]], K2_uv = w_u * w_v (minus tt on the
+ *   diagonal), dR_uv = (I_uv + A * K_uv) + B * K2_uv.  The new pose: R_uv = (dR_u0 * R_0v + dR_u1 * R_1v) + dR_u2 * R_2v;
+ *   u = t - c; t_u = (((dR_u0 * u_0 + dR_u1 * u_1) + dR_u2 * u_2) + c_u) + s_3+u.
+ * OUTPUTS: Rt, nn, num_corr, fitness, rmse (point-to-point, over all pairs of nn: the two methods compare) and valid as
+ *   dh3d_icp_refine gives them; num_plane [P] int32 = n_pl of the last association; rmse_plane [P] float64 = sqrt(sum of
+ *   r * r / num_plane) under the returned pose (the sum in the fit's order), NaN when num_plane = 0.  A pair that is not valid
+ *   comes back as from dh3d_icp_refine, with num_plane 0 and rmse_plane NaN.  Every element is written.  Rt may be Rt0.
+ * dh3d_icp_refine_plane_ws_bytes (host only): the workspace, as dh3d_icp_refine_ws_bytes; the plan is dh3d_icp_plan.
+ * SIDE EFFECTS: caller's stream, one launch after the other (no parallel branches), no host sync, no allocation, no
+ *   floating-point atomics; graph-capturable.
+ * STATUS: dh3d_icp_refine's, with NULL anchor_normals / num_plane / rmse_plane or a normals_stride below 3 among the
+ *   DH3D_ERR_INVALID_ARGUMENT cases. */
+size_t dh3d_icp_refine_plane_ws_bytes(int P, int Na, int Nb);
+int dh3d_icp_refine_plane(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *anchor_normals,
+                          long long normals_stride, const float *positive, long long positive_stride,
+                          const int32_t *positive_count, const double *Rt0, const int32_t *valid0, int P, int Na, int Nb,
+                          double max_dist, int iterations, int path, double *Rt, int32_t *nn, int32_t *num_corr, double *fitness,
+                          double *rmse, int32_t *valid, int32_t *num_plane, double *rmse_plane, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* Preparation of raw clouds (csrc/prepare.hip) -- get_fixednum_pcd(need_downsample = True, randsample = False)
  * (core/utils.py:87-110: open3d voxel_down_sample, remove_radius_outlier(nb_points, radius), crop to the points nearest the
  * centroid or pad), batched, for clouds of different sizes, with every size kept on the device.

@@ -5,7 +5,11 @@ that produce the start pose) on `--reg-pairs` pairs.  Per iteration = (T iterati
 timed on one-anchor clouds, where the association costs nothing and every positive point is a pair; an association is the
 difference.  "padded": the demo pairs with 6144 valid rows of 8192 and rows of 100000.0 behind them in both clouds, as
 prepare_clouds pads.  Pose errors are registration.transform_errors' (compareTransform: |dt| in metres, the sum of the
-three |Euler angles| in degrees -- a start 2 degrees off about one axis reads as about 3).  Prints one JSON line.
+three |Euler angles| in degrees -- a start 2 degrees off about one axis reads as about 3).  "plane": on the demo pairs, the
+anchor normals at k = 16 (the kNN and the normals kernel timed apart), then point-to-plane ICP (registration.refine_icp_plane
+on given normals, cell lists) at 5, 10 and 20 iterations next to point-to-point at the same counts, each with its pose error
+against the truth; and both fits alone on eight-anchor clouds (the plane fit needs normals that span space).  Prints one JSON
+line.
 
     python tools/icp_bench.py [--pairs 64] [--points 8192] [--iterations 20] [--iters 5] [--reg-pairs 8]
 """
@@ -58,6 +62,38 @@ def timed(fn, iters):
     return t0.elapsed_time(t1) * 1000.0 / iters  # us per call
 
 
+def plane_rows(a, rng, demo_pairs, ypos, eye):
+    from dh3d_amd.utils import batched_knn
+    tA, tY, tT0, Tgt = demo_pairs
+    P, N, T = a.pairs, a.points, a.iterations
+    out = dict(k=16)
+    out["knn_us"] = timed(lambda: batched_knn(tA, 16), a.iters)
+    nbr = batched_knn(tA, 16)[0]
+    out["normals_us"] = timed(lambda: reg.estimate_normals(tA, nbr=nbr), a.iters)
+    nrm = reg.estimate_normals(tA, nbr=nbr)["normals"]
+    path = 2 if N <= reg.ICP_GRID_MAX else 1
+    for method, fn, kw in (("plane", reg.refine_icp_plane, dict(anchor_normals=nrm)), ("point", reg.refine_icp, {})):
+        for it in sorted({5, 10, T}):
+            us = timed(lambda: fn(tA, tY, tT0, iterations=it, path=path, **kw), a.iters)
+            r = fn(tA, tY, tT0, iterations=it, path=path, **kw)
+            dt, dd = reg.transform_errors(Tgt, r["Rt"], r["valid"])
+            row = dict(refine_us=us, end_dt=float(dt.mean()), end_dt_max=float(dt.max()), end_ddeg=float(dd.mean()),
+                       fitness=float(r["fitness"].mean()), rmse=float(r["rmse"].mean()))
+            if method == "plane":
+                row["rmse_plane"] = float(r["rmse_plane"].mean())
+            out["%s_%d" % (method, it)] = row
+    # both fits alone: eight anchors at the corners of a small cube with normals that span space; every positive pairs up
+    t = lambda v: torch.from_numpy(v).cuda()
+    corners = np.array([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], np.float32)
+    eight = t(np.tile(0.25 * corners, (P, 1, 1)))
+    n8 = t(np.tile(corners / np.float32(math.sqrt(3.0)), (P, 1, 1)))
+    for method, fn, kw in (("plane", reg.refine_icp_plane, dict(anchor_normals=n8)), ("point", reg.refine_icp, {})):
+        f0 = timed(lambda: fn(eight, ypos, eye, max_dist=10.0, iterations=0, path=1, **kw), a.iters)
+        fT = timed(lambda: fn(eight, ypos, eye, max_dist=10.0, iterations=T, path=1, **kw), a.iters)
+        out["%s_step8_us" % method] = (fT - f0) / T     # one 8-anchor scan + one fit
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=64)
@@ -106,6 +142,8 @@ def main():
         entry.update(start_dt=float(dt0.mean()), start_ddeg=float(dd0.mean()), end_dt=float(dt.mean()), end_ddeg=float(dd.mean()),
                      fitness=float(out["fitness"].mean()), rmse=float(out["rmse"].mean()))
         res[name] = entry
+        if name == "demo":
+            demo_pairs = (tA, tY, tT0, Tgt)
         if name == "demo" and a.reg_pairs > 0:
             from dh3d_amd import ConfigFactory
             from dh3d_amd.model import DH3D
@@ -115,6 +153,7 @@ def main():
                 res["register_clouds"] = dict(pairs=q, us=timed(lambda: reg.register_clouds(model, tA[:q], tY[:q]), a.iters))
                 res["register_clouds_refined"] = dict(pairs=q, us=timed(lambda: reg.register_clouds(model, tA[:q], tY[:q], refine=True),
                                                                         a.iters))
+    res["plane"] = plane_rows(a, rng, demo_pairs, ypos, eye)
     print(json.dumps(res))
 
 
