@@ -255,6 +255,11 @@ _SIGNATURES = {
                             c_double, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_pair_rotate": [c_int, c_int, c_fp, c_double, c_fp, c_fp, c_fp, c_fp],
     "dh3d_sample_pair_nodes": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_tuple_counts": [c_fp, c_fp, c_int, c_double, c_double, c_fp, c_fp, c_fp],
+    "dh3d_draw_queries_ws_bytes": [c_int, c_int],
+    "dh3d_draw_queries": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp],
+    "dh3d_sample_tuples": [c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int, c_double, c_double, c_fp, c_ll, c_int, c_int, c_double,
+                           c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
 }
 _RESTYPES = {
     "dh3d_arch": ctypes.c_char_p,
@@ -277,6 +282,7 @@ _RESTYPES = {
     "dh3d_prepare_clouds_workspace": c_size_t,
     "dh3d_retrieve_ws_bytes": c_size_t,
     "dh3d_resample_clouds_ws_bytes": c_size_t,
+    "dh3d_draw_queries_ws_bytes": c_size_t,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

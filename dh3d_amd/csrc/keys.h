@@ -25,6 +25,14 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
 }
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) { return mix64(z + 0x9E3779B97F4A7C15ull); }
 
+// The counter RNG of include/dh3d_hip.h "Training batches": h(stream, b), the draw u(stream, b, j) = splitmix64(h + j),
+// and a draw as a double in [0, 1) / (0, 1].
+__device__ __forceinline__ unsigned long long stream_h(unsigned long long seed, unsigned stream, unsigned b) {
+  return splitmix64(splitmix64(seed) ^ (((unsigned long long)stream << 32) | (unsigned long long)b));
+}
+__device__ __forceinline__ double unit_co(unsigned long long u) { return (double)(u >> 11) * 0x1p-53; }            // [0, 1)
+__device__ __forceinline__ double unit_oc(unsigned long long u) { return (double)(u >> 11) * 0x1p-53 + 0x1p-53; }  // (0, 1]
+
 // A per-cloud count read from the device, held to [0, cap].
 __device__ __forceinline__ int clamp_count(int n, int cap) { return n < 0 ? 0 : (n > cap ? cap : n); }
 

@@ -42,11 +42,7 @@ enum Stream : unsigned {  // include/dh3d_hip.h lists these
   kFirst = 10
 };
 
-__device__ __forceinline__ u64 stream_h(u64 seed, unsigned stream, unsigned b) {
-  return splitmix64(splitmix64(seed) ^ (((u64)stream << 32) | (u64)b));
-}
-__device__ __forceinline__ double unit_co(u64 u) { return (double)(u >> 11) * 0x1p-53; }            // [0, 1)
-__device__ __forceinline__ double unit_oc(u64 u) { return (double)(u >> 11) * 0x1p-53 + 0x1p-53; }  // (0, 1]
+// (stream_h, unit_co, unit_oc: keys.h)
 __device__ __forceinline__ double normal(u64 h, u64 e) {  // Box-Muller, cosine branch
   const double u1 = unit_oc(splitmix64(h + 2 * e)), u2 = unit_co(splitmix64(h + 2 * e + 1));
   return sqrt(-2.0 * log(u1)) * cos(kTwoPi * u2);

@@ -39,15 +39,9 @@ constexpr int kMaxDim = 256;
 constexpr int kMaxK = 64;                    // the k-list is one entry per lane
 constexpr int kTargetBlocks = 512;           // two workgroups (78 KB of LDS each) per CU on 256 CUs
 
-struct Key {  // ascending by (d, id); d = the bits of a non-negative double
-  u64 d;
-  unsigned id;
-};
-constexpr u64 kNoDist = ~0ull;               // above the bits of +inf
-__device__ __forceinline__ Key no_key() { return Key{kNoDist, 0xFFFFFFFFu}; }
-__device__ __forceinline__ bool key_lt(const Key &a, const Key &b) { return a.d < b.d || (a.d == b.d && a.id < b.id); }
-__device__ __forceinline__ Key key_shfl_xor(const Key &v, int j) { return Key{__shfl_xor(v.d, j, 64), __shfl_xor(v.id, j, 64)}; }
-__device__ __forceinline__ Key key_shfl(const Key &v, int src) { return Key{__shfl(v.d, src, 64), __shfl(v.id, src, 64)}; }
+typedef Key96 Key;  // (wave_ops.h) ascending by (d, id); d = the bits of a non-negative double
+constexpr u64 kNoDist = kNoKey96;
+__device__ __forceinline__ Key no_key() { return key96_none(); }
 
 __device__ __forceinline__ void write_entry(const Key &e, long long o, int32_t *idx, double *dist2) {
   const bool some = e.d != kNoDist;

@@ -124,6 +124,18 @@ __device__ __forceinline__ unsigned long long key_max(unsigned long long a, unsi
 __device__ __forceinline__ unsigned long long key_shfl_xor(unsigned long long v, int j) { return __shfl_xor(v, j, 64); }
 __device__ __forceinline__ unsigned long long key_shfl(unsigned long long v, int src) { return __shfl(v, src, 64); }
 
+// A 96-bit key, ascending by (d, id): d = the bits of a non-negative double (retrieval.hip) or a 64-bit random key
+// (tuples.hip), id = the row it belongs to.
+struct Key96 {
+  unsigned long long d;
+  unsigned id;
+};
+constexpr unsigned long long kNoKey96 = ~0ull;  // above the bits of +inf
+__device__ __forceinline__ Key96 key96_none() { return Key96{kNoKey96, 0xFFFFFFFFu}; }
+__device__ __forceinline__ bool key_lt(const Key96 &a, const Key96 &b) { return a.d < b.d || (a.d == b.d && a.id < b.id); }
+__device__ __forceinline__ Key96 key_shfl_xor(const Key96 &v, int j) { return Key96{__shfl_xor(v.d, j, 64), __shfl_xor(v.id, j, 64)}; }
+__device__ __forceinline__ Key96 key_shfl(const Key96 &v, int src) { return Key96{__shfl(v.d, src, 64), __shfl(v.id, src, 64)}; }
+
 template <typename K>
 __device__ __forceinline__ K key_min(const K &a, const K &b) { return key_lt(b, a) ? b : a; }
 template <typename K>

@@ -1177,6 +1177,70 @@ int dh3d_pair_rotate(int B, int N, const float *pc2, double rot_maxv, const unsi
 int dh3d_sample_pair_nodes(int B, int N, int sample_nodes, const float *pc1, const float *pc2, const unsigned long long *seed,
                            int32_t *anc, int32_t *pos, void *stream);
 
+/* Training tuples (csrc/tuples.hip) -- which places form a quadruplet: Global_train_dataset_triplet.__iter__
+ * (core/datasets.py:202-233), there Python set differences over the whole training set, here decided on the device from
+ * the positions (and, for hard negatives, the descriptors) of a map of places; the ids feed "Training batches".
+ * MAP.  pos holds M rows of two float64 (16-byte aligned).  count: a device pointer to one int32, or NULL.  The live map is
+ *   places 0 .. n-1 with n = clamp(*count, 0, M); NULL means n = M.  Rows at or beyond n are never read (positions and
+ *   descriptors alike).  The host never learns n.
+ * DISTANCE.  Planar: d2(i, j) = (dx*dx) + (dy*dy) with dx = pos[j][0] - pos[i][0], dy = pos[j][1] - pos[i][1]; every
+ *   operation is rounded to float64 on its own (no fma contraction).  rp2 = pos_radius * pos_radius and rn2 = neg_radius *
+ *   neg_radius are rounded likewise, on the host side of the entry point.
+ * SETS of a query place q -- the positives / nonnegtives convention of the tuple pickles the reference's loader reads; the
+ *   query is its own non-negative:
+ *     POS(q) = { j < n, j != q, d2(q, j) <= rp2 }          NEG(q) = { j < n, d2(q, j) > rn2 }
+ *   The reference's radii: pos_radius = 10.0, neg_radius = 50.0.  A non-finite or non-positive radius, or neg_radius <
+ *   pos_radius: DH3D_ERR_INVALID_ARGUMENT.
+ * RANDOMNESS.  The scheme of "Training batches": u(stream, b, j) and U = (u >> 11) * 2^-53, with b = the query's slot in
+ *   the call (dh3d_draw_queries: b = 0) and j = the place id.  The streams:
+ *     11 positive keys   12 negative keys   13 pool membership   14 other-negative keys   15 query keys
+ *   "The k smallest of a set by a stream" are the k members with the smallest keys (u(stream, b, j), j), emitted in
+ *   ASCENDING KEY order: a uniform random k-subset in uniform random order.  (dh3d_resample_clouds emits its choice in index
+ *   order: another rule.)  seed is a DEVICE pointer to one uint64, as there.
+ * Every entry point below: caller's stream, no allocation, no synchronisation, graph-capturable (launches one after the
+ *   other, no parallel branches); every output element is written; slot b's result depends on (seed, b, queries[b]) and the
+ *   live map, not on Q, on the other slots, on the capacity M beyond n, on the workspace's content or on the run.
+ * LIMITS.  M <= 2^20, Q <= 65535, 1 <= num_pos <= 64, 1 <= num_neg <= 64, 0 <= num_hard <= num_neg, D <= 256 and a multiple
+ *   of 4; a shape beyond them: DH3D_ERR_UNSUPPORTED.  A NULL pointer (count, other_idx and desc excepted), M, Q, num_pos,
+ *   num_neg or (with desc) D <= 0, num_hard < 0, a misaligned pos: DH3D_ERR_INVALID_ARGUMENT.  NaN and infinite values in
+ *   the live map are outside the contract.
+ *
+ * dh3d_tuple_counts -- n_pos [M] = |POS(i)|, n_neg [M] = |NEG(i)| for i < n, 0 for i >= n.  O(n^2): once per map, or
+ *   whenever the map grows. */
+int dh3d_tuple_counts(const double *pos, const int32_t *count, int M, double pos_radius, double neg_radius, int32_t *n_pos,
+                      int32_t *n_neg, void *stream);
+/* dh3d_draw_queries -- the reference's shuffle plus its `continue` on too few positives: queries [Q] = the Q smallest by
+ *   stream 15 of { i < n : n_pos[i] >= num_pos and n_neg[i] >= num_neg }.  Fewer than Q such places: the remaining entries
+ *   are -1 and ok[0] = 0; otherwise ok[0] = 1.  The workspace (dh3d_draw_queries_ws_bytes: 0 for a shape the call refuses;
+ *   16-byte aligned, no clearing needed; NULL, too small or misaligned: DH3D_ERR_INVALID_ARGUMENT) holds the chosen keys. */
+size_t dh3d_draw_queries_ws_bytes(int M, int Q);
+int dh3d_draw_queries(const int32_t *n_pos, const int32_t *n_neg, const int32_t *count, int M, int Q, int num_pos, int num_neg,
+                      const unsigned long long *seed, int32_t *queries, int32_t *ok, void *workspace, size_t workspace_bytes,
+                      void *stream);
+/* dh3d_sample_tuples -- queries [Q] (device) -> pos_idx [Q, num_pos], neg_idx [Q, num_neg], other_idx [Q] (NULL: that stage
+ *   is skipped), valid [Q].  Slot b with q = queries[b]:
+ *   q < 0 or q >= n: everything is -1, valid = 0.
+ *   POSITIVES  the num_pos smallest of POS(q) by stream 11; |POS(q)| < num_pos: the row is all -1.
+ *   HARD NEGATIVES  only with num_hard > 0 and desc != NULL: desc holds M rows of D floats, row j at desc + j * desc_stride
+ *     (elements; desc_stride >= D and a multiple of 4, desc 16-byte aligned, 0 <= pool_fraction <= 1, else
+ *     DH3D_ERR_INVALID_ARGUMENT).  POOL = { j in NEG(q) : U(13, b, j) < pool_fraction } (1.0: all of NEG(q), 0.0: none).
+ *     D2(q, j) = the sum over c ascending, starting from 0, of ((double)desc[q][c] - (double)desc[j][c])^2, every operation
+ *     rounded on its own -- dh3d_retrieve's rule.  The hard negatives are the h' = min(num_hard, |POOL|) smallest of POOL
+ *     by (bits of D2, j), ascending.  Without them h' = 0.
+ *   RANDOM NEGATIVES  the num_neg - h' smallest of NEG(q) minus the hard ones, by stream 12.
+ *   The negative row is [hard | random]; |NEG(q)| < num_neg: the row is all -1.
+ *   OTHER NEGATIVE  -1 when the negative row is unfilled.  Otherwise, with BAR = { j < n : d2(q, j) <= rp2, or
+ *     d2(g, j) <= rp2 for some g in the negative row }, other_idx[b] = the smallest of { j < n } \ BAR by stream 14, or -1
+ *     if there is none.  DEVIATION from the reference: BAR holds the query and the chosen negatives themselves (their
+ *     d2 = 0); the reference's set difference (datasets.py:224-232) subtracts only their neighbours and leaves them
+ *     eligible, which can hand the loss the query as its own "other negative".
+ *   valid [b] = 1 only if the positive row, the negative row and (when asked for) the other negative are all filled.
+ *   No workspace. */
+int dh3d_sample_tuples(const double *pos, const int32_t *count, int M, const int32_t *queries, int Q, int num_pos, int num_neg,
+                       double pos_radius, double neg_radius, const float *desc, long long desc_stride, int D, int num_hard,
+                       double pool_fraction, const unsigned long long *seed, int32_t *pos_idx, int32_t *neg_idx,
+                       int32_t *other_idx, int32_t *valid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
