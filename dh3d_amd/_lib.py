@@ -260,6 +260,8 @@ _SIGNATURES = {
     "dh3d_draw_queries": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp],
     "dh3d_sample_tuples": [c_fp, c_fp, c_int, c_fp, c_int, c_int, c_int, c_double, c_double, c_fp, c_ll, c_int, c_int, c_double,
                            c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_prob_sample": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_prob_sample_seeded": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
 }
 _RESTYPES = {
     "dh3d_arch": ctypes.c_char_p,

@@ -2,7 +2,7 @@
 
 Mirrors user_ops/__init__.py (knn_bruteforce :50, flex_convolution :63-89, flex_convolution_transpose,
 flex_pooling :115-135, convolution_pointset :205-225) and tf_ops/{sampling,grouping,interpolation}/tf_*.py
-(farthest_point_sample tf_sampling.py:63-71, gather_point tf_sampling.py:38-61, query_ball_point / query_ball_point2
+(prob_sample tf_sampling.py:15-26, farthest_point_sample tf_sampling.py:63-71, gather_point tf_sampling.py:38-61, query_ball_point / query_ball_point2
 tf_grouping.py:9-36, select_top_k / knn_point tf_grouping.py:37-47,63-88, group_point tf_grouping.py:48-56,
 three_nn / three_interpolate
 tf_interpolate.py:8-34), with torch.autograd.Function standing in for the RegisterGradient hooks
@@ -17,7 +17,7 @@ from . import _lib as L
 __all__ = [
     "knn_bruteforce", "flex_convolution", "flex_convolution_transpose", "flex_pooling", "convolution_pointset",
     "farthest_point_sample", "group_point", "three_nn", "three_interpolate", "query_ball_point", "query_ball_point2",
-    "knn_point", "select_top_k", "gather_point",
+    "knn_point", "select_top_k", "gather_point", "prob_sample",
 ]
 
 
@@ -318,6 +318,15 @@ def gather_point(inp, idx):
         raise ValueError("GatherPoint expects (batch_size,num_result) idx shape")  # tf_sampling.cpp:135
     ix = L.require_cuda_i32(idx, "idx", 2)
     return _GroupPoint.apply(inp, ix.unsqueeze(2)).squeeze(2)
+
+
+def prob_sample(inp, inpr):
+    """inp [b,n] float32 weights, inpr [b,m] float32 draws in [0, 1) -> [b,m] int32 (tf_sampling.py:15-26): id j of row b is
+    drawn with probability proportional to inp[b], by the reference's own cumulative sums and halving walk, bit for bit
+    (include/dh3d_hip.h "Weighted sampling").  Not differentiable.  utils.sample_by_weight draws inpr on the device."""
+    from . import pm
+    with torch.no_grad():  # ops.NoGradient('ProbSample') (tf_sampling.py:26)
+        return pm.prob_sample(inp, inpr)[0]
 
 
 def three_nn(xyz1, xyz2):

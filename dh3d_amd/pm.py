@@ -225,6 +225,63 @@ def knn_point(k, xyz1, xyz2):
     return val, idx
 
 
+PROB_SAMPLE_MAX_N, PROB_SAMPLE_MAX_M = 1 << 20, 1 << 20  # csrc/prob_sample.hip kMaxN, kMaxM
+
+
+def _prob_rows(inp, what):
+    """The checks ProbSample's weights go through, the operator's own refusal first (tf_sampling.cpp:76)."""
+    if isinstance(inp, torch.Tensor) and inp.dim() != 2:
+        raise ValueError("ProbSample expects (batch_size,num_choices) inp shape")
+    p = L.require_cuda_f32(inp, "inp", 2)
+    if p.shape[0] < 1 or p.shape[1] < 1:
+        raise ValueError("%s: empty inp %s" % (what, tuple(p.shape)))
+    if p.shape[1] > PROB_SAMPLE_MAX_N:
+        raise ValueError("%s: num_choices = %d is beyond the kernels (%d)" % (what, p.shape[1], PROB_SAMPLE_MAX_N))
+    return p
+
+
+def prob_sample(inp, inpr):
+    """inp [b,n] float32 weights, inpr [b,m] float32 draws -> (ids [b,m] int32, cum [b,n] float32 the reference's cumulative
+    sums, its `temp`): include/dh3d_hip.h dh3d_prob_sample."""
+    if isinstance(inp, torch.Tensor) and inp.dim() != 2:
+        raise ValueError("ProbSample expects (batch_size,num_choices) inp shape")  # tf_sampling.cpp:76
+    if isinstance(inp, torch.Tensor) and isinstance(inpr, torch.Tensor) and (inpr.dim() != 2 or inpr.shape[0] != inp.shape[0]):
+        raise ValueError("ProbSample expects (batch_size,num_points) inpr shape")  # tf_sampling.cpp:79
+    p = _prob_rows(inp, "prob_sample")
+    r = L.require_cuda_f32(inpr, "inpr", 2)
+    if p.device != r.device:
+        raise ValueError("prob_sample: inp and inpr live on different devices")
+    (b, n), m = p.shape, r.shape[1]
+    if m < 1 or m > PROB_SAMPLE_MAX_M:
+        raise ValueError("prob_sample: num_points = %d is outside 1 .. %d" % (m, PROB_SAMPLE_MAX_M))
+    cum = torch.empty((b, n), dtype=torch.float32, device=p.device)
+    ids = torch.empty((b, m), dtype=torch.int32, device=p.device)
+    with torch.cuda.device(p.device):
+        L.check(L.lib().dh3d_prob_sample(b, n, m, L.ptr(p), L.ptr(r), L.ptr(cum), L.ptr(ids), L.stream_ptr()), "prob_sample")
+    return ids, cum
+
+
+def prob_sample_seeded(inp, m, count, seed):
+    """inp [b,n] float32 weights, count [b] int32 or None, seed a 1-element int64 GPU tensor -> (ids [b,m] int32, cum [b,n]):
+    include/dh3d_hip.h dh3d_prob_sample_seeded.  cum holds the sums of a row's first count[b] entries only."""
+    p = _prob_rows(inp, "prob_sample_seeded")
+    m = int(m)
+    if m < 1 or m > PROB_SAMPLE_MAX_M:
+        raise ValueError("prob_sample_seeded: m = %d is outside 1 .. %d" % (m, PROB_SAMPLE_MAX_M))
+    b, n = p.shape
+    c = None
+    if count is not None:
+        c = L.require_cuda_i32(count, "count", 1)
+        if c.shape[0] != b:
+            raise ValueError("prob_sample_seeded expects (batch_size) count = (%d,), got %s" % (b, tuple(c.shape)))
+    cum = torch.empty((b, n), dtype=torch.float32, device=p.device)
+    ids = torch.empty((b, m), dtype=torch.int32, device=p.device)
+    with torch.cuda.device(p.device):
+        L.check(L.lib().dh3d_prob_sample_seeded(b, n, m, L.ptr(p), L.ptr(c), L.ptr(seed), L.ptr(cum), L.ptr(ids),
+                                                L.stream_ptr()), "prob_sample_seeded")
+    return ids, cum
+
+
 PREPARE_MAX_N, PREPARE_MAX_TARGET = 131072, 1 << 20  # csrc/prepare.hip kMaxN, kMaxTarget
 
 

@@ -1,10 +1,10 @@
 """Host-side helpers either side of the hot path: keypoint NMS on the device, raw .bin clouds and
-descriptors, fixed-size clouds.  Mirrors core/utils.py:15-43 (single_nms), :87-110 (get_fixednum_pcd),
+descriptors, fixed-size clouds, weighted random choice.  Mirrors core/utils.py:15-43 (single_nms), :87-110 (get_fixednum_pcd),
 :139-153 (load_descriptor_bin / load_single_pcfile / write_to_bin)."""
 import numpy as np
 import torch
 
-from . import pm
+from . import pairs, pm
 
 
 def single_nms(xyz, attention, nms_radius, min_response_ratio, max_keypoints, remove_noise=True, knn=50):
@@ -72,6 +72,28 @@ def batched_nms(xyz, scores, nms_radius, min_response_ratio, max_keypoints, remo
     nn, dist = batched_knn(x, knn)
     return pm.keypoint_nms(scores, nn, dist, nms_radius, min_response_ratio, max_keypoints, remove_noise=remove_noise,
                            num_valid=num_valid, invert=invert)
+
+
+def sample_by_weight(weights, m, count=None, seed=0):
+    """m ids a row drawn WITH replacement, id i of row b with probability weights[b, i] / sum(weights[b]), on the device, no
+    host sync -- graph-capturable (HIP: dh3d_prob_sample_seeded; the reference's ProbSample with the draws made on the device).
+
+    weights [B,n] float32 on the GPU, non-negative and finite.  count [B] int32 (optional): row b is its first count[b]
+    entries, held to 0 .. n; the entries behind them are never read.  Returns ids [B,m] int32; a row without entries or with
+    a total that is not > 0 is all -1.  An id of weight 0 is never drawn as long as the sums before it are exact.
+
+    seed is an int or a 1-element int64 tensor on the GPU, as pairs.py takes it: the kernels read the tensor, so a captured
+    graph draws afresh on every replay once the caller changes it.  The ids feed ops.gather_point / ops.group_point, e.g.
+    keypoints in proportion to the detector's attention:
+        ids = sample_by_weight(attention, 256, count=num_valid, seed=seed)
+        xyz = ops.gather_point(points, ids)"""
+    if isinstance(weights, torch.Tensor) and weights.dim() != 2:
+        raise ValueError("sample_by_weight expects (batch_size,num_choices) weights, got %s" % (tuple(weights.shape),))
+    if isinstance(weights, torch.Tensor) and not weights.is_cuda:
+        raise ValueError("weights must live on the GPU (the HIP path has no CPU fallback)")
+    sd = pairs.seed_tensor(seed, weights.device if isinstance(weights, torch.Tensor) else None)
+    with torch.no_grad():
+        return pm.prob_sample_seeded(weights, m, count, sd)[0]
 
 
 def load_descriptor_bin(filename, dim=131, dtype=np.float32):

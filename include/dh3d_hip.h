@@ -1117,6 +1117,7 @@ int dh3d_retrieve(const float *ref, long long ref_stride, const int32_t *ref_cou
  *   splitmix64 is a bijection, so the u alone never tie).  The streams:
  *     1 resample keys   2 pad draws   3 Rotate1D angle   4 jitter   5 scale   6 RotateSmall angles   7 shift
  *     8 pair rotation   9 subset keys   10 first pick
+ *   ("Training tuples" below takes 11 .. 15, "Weighted sampling" 16.)
  *   seed is a DEVICE pointer to one uint64, read by the kernels: a captured graph draws a fresh batch on every replay when
  *   the caller changes that scalar between replays.
  * Every entry point below: caller's stream, no allocation, no synchronisation, graph-capturable (launches one after the
@@ -1240,6 +1241,41 @@ int dh3d_sample_tuples(const double *pos, const int32_t *count, int M, const int
                        double pos_radius, double neg_radius, const float *desc, long long desc_stride, int D, int num_hard,
                        double pool_fraction, const unsigned long long *seed, int32_t *pos_idx, int32_t *neg_idx,
                        int32_t *other_idx, int32_t *valid, void *stream);
+
+/* Weighted sampling (csrc/prob_sample.hip) -- ProbSample of tf_ops/sampling (tf_sampling.py:15-26, tf_sampling.cpp:65-92,
+ * tf_sampling_g.cu:7-104) and its seeded form: m indices a row, WITH replacement, with probability proportional to a row of
+ * n non-negative weights.  The op has no CPU twin upstream; the contract is the arithmetic of its two kernels.  All values
+ * are float32 and every operation is rounded on its own (no fma contraction).
+ * CUMULATIVE SUMS of a row w[0 .. n-1] (cumsumKernel, tf_sampling_g.cu:7-88).  Chunks of 8192 entries, the last may be
+ *   shorter; the running sum R and its compensation C start at 0.  A chunk of L entries has G = ceil(L / 4) quads.
+ *     full quad (a, b, c, d):  l0 = a, l1 = b + a, t = d + c, l2 = c + l1, l3 = t + l1, s[g] = l3
+ *     partial last quad (1 .. 3 entries):  v = 0, then v += x in order; l_i = the running v, s[g] = the last v
+ *     tree over s[0 .. G-1], in place:
+ *       up-sweep    for u = 0, 1, .. while 2^(u+1) <= G, for k < floor(G / 2^(u+1)):  s[(2k+2) 2^u - 1] += s[(2k+1) 2^u - 1]
+ *       down-sweep  from the last such u down to 0, for k < floor((G - 2^u) / 2^(u+1)):  s[(2k+3) 2^u - 1] += s[(2k+2) 2^u - 1]
+ *     quads g >= 1:  l_i += s[g-1];   cum = l_i + R;   then t = s[G-1] + C, R' = R + t, C = t - (R' - R), R = R'
+ *   The result is within 16 * 2^-24 relative of the exact sums, differs from a sequential float32 prefix sum in most entries
+ *   and is NOT monotone: it can step down by an ulp between two quads.
+ * SEARCH of one draw r_in (binarysearchKernel, :90-104).  P = the smallest power of two >= n, q = r_in * cum[n-1] (one
+ *   multiply), r = n-1; for k = P, P/2, .. 1: if r >= k and cum[r-k] >= q then r -= k; the id is r.  The walk never assumes
+ *   order, so on a non-monotone row it is not a lower bound of a sorted search; on a monotone row it is the first index with
+ *   cum >= q, held to n-1.  A draw of 0 gives id 0 whatever its weight (the reference's behaviour).
+ * Both entry points: caller's stream, no allocation, no synchronisation, graph-capturable (two launches, one after the other);
+ *   every element of out is written; row b's result does not depend on the batch size, on the other rows or on temp's prior
+ *   content.  b, n or m <= 0 or a NULL pointer (count excepted): DH3D_ERR_INVALID_ARGUMENT; b > 65535, n > 2^20 or m > 2^20:
+ *   DH3D_ERR_UNSUPPORTED.  Negative, NaN and infinite weights are outside the contract.
+ *
+ * dh3d_prob_sample -- probsampleLauncher's arguments: inp_p [b, n] weights, inp_r [b, m] draws (the op feeds uniform values
+ *   in [0, 1)), temp [b, n] the reference's scratch, which HOLDS THE CUMULATIVE SUMS on return, out [b, m].
+ * dh3d_prob_sample_seeded -- the draws are made on the device by the scheme of "Training batches", stream 16:
+ *     r_in(b, j) = (float)((u(16, b, j) >> 40) + 1) * 2^-24       exact in float32, in (0, 1]: q > 0
+ *   count: NULL, or a device pointer [b]: row b is its entries 0 .. n_b-1 with n_b = clamp(count[b], 0, n) (NULL: n_b = n);
+ *   entries at or beyond n_b are never read, and temp holds the sums of the first n_b entries only.  n_b == 0, or a total
+ *   cum[n_b-1] that is not > 0: every id of the row is -1.  Otherwise no id has weight 0 as long as the sums before it are
+ *   exact (q > 0 and the walk stops at the first cum >= q).  seed is a DEVICE pointer to one uint64, as there. */
+int dh3d_prob_sample(int b, int n, int m, const float *inp_p, const float *inp_r, float *temp, int32_t *out, void *stream);
+int dh3d_prob_sample_seeded(int b, int n, int m, const float *inp_p, const int32_t *count, const unsigned long long *seed,
+                            float *temp, int32_t *out, void *stream);
 
 #ifdef __cplusplus
 }
