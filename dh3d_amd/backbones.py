@@ -346,7 +346,7 @@ def compute_level(xyz, dilate, knn, ordered=None, fps_contract=None, cells=None)
     0.2 vs 0.28 ms at 4096 -> 512; no gain at 2048 and below).
     fps_contract: None = default kernels; 0 / 1 forces the any-N kernel with that distance rounding
     (ops.farthest_point_sample).
-    The level records the kernels it took in lv["_path"] = {"fps", "knn", "nn3" (finish_level)}."""
+    The level records the kernels it took in lv["_path"] = {"fps", "knn", "nn3", "nn3_cells" (finish_level)}."""
     B, N, _ = xyz.shape
     npoint = N // dilate
     ordered_s, cells_s = None, None
@@ -401,6 +401,8 @@ def compute_level(xyz, dilate, knn, ordered=None, fps_contract=None, cells=None)
         lv["_ordered"] = ordered            # Morton records + boxes of the full cloud: the pruned three_nn uses them
         if ordered_s is not None:
             lv["_ordered_s"] = ordered_s
+            if cells_s is not None:
+                lv["_cells_s"] = cells_s    # the sampled set's cell table (the cloud's grid, or the set's own): three_nn
     return lv
 
 
@@ -418,14 +420,19 @@ def finish_level(xyz, lv, same_stream=False):
             # rest of the scan is the bare distance test (bit-identical outputs, csrc/pointnet2.hip
             # three_nn_sorted_kernel); the sampled set is sorted here unless the level's kNN already did
             srt_s, gbox_s = lv["_ordered_s"] if "_ordered_s" in lv else pm.spatial_sort(xyz_s)
-            d3, i3 = pm.three_nn_sorted(lv["_ordered"][0], lv["_ordered"][1], srt_s, gbox_s)
+            # with the sampled set's cell table (the FPS kernel's, or the grid kNN's sort) a query group stages and scans
+            # only the samples of the cells it can reach (csrc/pointnet2.hip three_nn_pruned_kernel_cells)
+            cells_s = lv.get("_cells_s")
+            d3, i3 = pm.three_nn_sorted(lv["_ordered"][0], lv["_ordered"][1], srt_s, gbox_s, cells2=cells_s)
             lv.setdefault("_path", {})["nn3"] = "sorted"
+            lv["_path"]["nn3_cells"] = cells_s is not None and 128 <= xyz_s.shape[1] <= 1024 and N <= 16384
         else:
             d3 = torch.empty((B, N, 3), dtype=torch.float32, device=xyz.device)
             i3 = torch.empty((B, N, 3), dtype=torch.int32, device=xyz.device)
             L.check(L.lib().dh3d_three_nn(B, N, xyz_s.shape[1], L.ptr(xyz), L.ptr(xyz_s), L.ptr(d3), L.ptr(i3),
                                           L.stream_ptr()), "three_nn")
             lv.setdefault("_path", {})["nn3"] = "plain"
+            lv["_path"]["nn3_cells"] = False
         lv["nn3_dist"], lv["nn3_idx"] = d3, i3
         if lv.get("_want_walk_plan") and "_ordered" in lv and xyz_s.shape[1] <= 1024:
             # the global tail's walk over the fine points (pm.global_tail): its per-block slot tables depend on three_nn's

@@ -2,7 +2,11 @@
 //   group_point(+grad)        replaces tf_ops/grouping/tf_grouping_g.cu:94-132 (one CUDA block per
 //                             cloud, serial over channels) with a flat, channel-coalesced gather.
 //   three_nn                  replaces the host loop tf_ops/interpolation/tf_interpolate.cpp:60-103
-//                             (the reference has no GPU kernel: every call crossed PCIe twice).
+//                             (the reference has no GPU kernel: every call crossed PCIe twice).  Four kernels, one
+//                             result: plain (any order), both sets in Morton order (every candidate visited), the
+//                             same pruned by the candidates' 64-sample group boxes, and -- dh3d_three_nn_cells, what
+//                             the model's levels take -- the candidates of a query group read off the sampled set's
+//                             cell table (three_nn_pruned_kernel_cells).
 //   three_interpolate(+grad)  replaces tf_interpolate.cpp:107-153.
 //   three_interpolate_idw     fuses the weight computation of core/backbones.py:92-95.
 // Arithmetic that decides integer outputs (three_nn) is written with explicit, unfused roundings.
@@ -292,6 +296,59 @@ __global__ __launch_bounds__(kBlock) void three_nn_sorted_kernel(int n, int m, c
   }
 }
 
+// U 8-candidate sub-steps of the LDS image (cand4_slot coordinates in s_c, original indices in s_k) from candidate k on
+// (k % 8 == 0) against the lane's query: packed f32 with the reference's unfused roundings; a sub-step reaches the 3-deep
+// list -- 64-bit keys (bits(d) << 32 | index), see three_nn_sorted_kernel -- only when one of its distances passes some
+// lane's screen kb.  All U sub-steps' LDS reads are issued before the first is used.
+template <int U>
+__device__ __forceinline__ void nn3_scan(const float *s_c, const int *s_k, int k, bool valid, f32x2 qx, f32x2 qy, f32x2 qz,
+                                         unsigned long long &k1, unsigned long long &k2, unsigned long long &k3,
+                                         float &kb) {
+  f32x2 d[U][4];
+  float mn[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float *g0 = s_c + ((k >> 2) + 2 * u) * 12;
+    const f32x4 a0 = *reinterpret_cast<const f32x4 *>(g0), a1 = *reinterpret_cast<const f32x4 *>(g0 + 4),
+                a2 = *reinterpret_cast<const f32x4 *>(g0 + 8), b0 = *reinterpret_cast<const f32x4 *>(g0 + 12),
+                b1 = *reinterpret_cast<const f32x4 *>(g0 + 16), b2 = *reinterpret_cast<const f32x4 *>(g0 + 20);
+    {
+      const f32x2 dx = f32x2{a0[0], a0[1]} - qx, dy = f32x2{a0[2], a0[3]} - qy, dz = f32x2{a1[0], a1[1]} - qz;
+      d[u][0] = (dx * dx + dy * dy) + dz * dz;
+    }
+    {
+      const f32x2 dx = f32x2{a1[2], a1[3]} - qx, dy = f32x2{a2[0], a2[1]} - qy, dz = f32x2{a2[2], a2[3]} - qz;
+      d[u][1] = (dx * dx + dy * dy) + dz * dz;
+    }
+    {
+      const f32x2 dx = f32x2{b0[0], b0[1]} - qx, dy = f32x2{b0[2], b0[3]} - qy, dz = f32x2{b1[0], b1[1]} - qz;
+      d[u][2] = (dx * dx + dy * dy) + dz * dz;
+    }
+    {
+      const f32x2 dx = f32x2{b1[2], b1[3]} - qx, dy = f32x2{b2[0], b2[1]} - qy, dz = f32x2{b2[2], b2[3]} - qz;
+      d[u][3] = (dx * dx + dy * dy) + dz * dz;
+    }
+    mn[u] = fminf(fminf(fminf(d[u][0][0], d[u][0][1]), fminf(d[u][1][0], d[u][1][1])),
+                  fminf(fminf(d[u][2][0], d[u][2][1]), fminf(d[u][3][0], d[u][3][1])));
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    // '<=': an equal distance with a smaller index must still be seen
+    if (__any(valid && mn[u] <= kb)) {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        const unsigned long long x = ((unsigned long long)__float_as_uint(d[u][t >> 1][t & 1]) << 32) |
+                                     (unsigned)s_k[k + 8 * u + t];
+        const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
+        k3 = l2 ? k2 : (l3 ? x : k3);
+        k2 = l1 ? k1 : (l2 ? x : k2);
+        k1 = l1 ? x : k1;
+      }
+      kb = fminf(kb, __uint_as_float((unsigned)(k3 >> 32)));
+    }
+  }
+}
+
 // The same search with the candidates pruned by their group boxes (m <= kNNChunk: the whole sampled set in LDS -- every
 // DH3D level).  three_nn_sorted_kernel evaluates every candidate for every query: 2.5 k VALU instructions per wave, the
 // kernel is VALU-issue bound (profiles/r03_d_pmc_three_nn.txt: 37 us for 8 x 8192 against 8 x 1024).  Here
@@ -347,50 +404,7 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel(int n, int m, c
   __syncthreads();
 
   auto scan_step = [&](int step) __attribute__((always_inline)) {
-    const int k = step << 5;
-    f32x2 d[4][4];
-    float mn[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float *g0 = s_c + ((k >> 2) + 2 * u) * 12;
-      const f32x4 a0 = *reinterpret_cast<const f32x4 *>(g0), a1 = *reinterpret_cast<const f32x4 *>(g0 + 4),
-                  a2 = *reinterpret_cast<const f32x4 *>(g0 + 8), b0 = *reinterpret_cast<const f32x4 *>(g0 + 12),
-                  b1 = *reinterpret_cast<const f32x4 *>(g0 + 16), b2 = *reinterpret_cast<const f32x4 *>(g0 + 20);
-      {
-        const f32x2 dx = f32x2{a0[0], a0[1]} - qx, dy = f32x2{a0[2], a0[3]} - qy, dz = f32x2{a1[0], a1[1]} - qz;
-        d[u][0] = (dx * dx + dy * dy) + dz * dz;
-      }
-      {
-        const f32x2 dx = f32x2{a1[2], a1[3]} - qx, dy = f32x2{a2[0], a2[1]} - qy, dz = f32x2{a2[2], a2[3]} - qz;
-        d[u][1] = (dx * dx + dy * dy) + dz * dz;
-      }
-      {
-        const f32x2 dx = f32x2{b0[0], b0[1]} - qx, dy = f32x2{b0[2], b0[3]} - qy, dz = f32x2{b1[0], b1[1]} - qz;
-        d[u][2] = (dx * dx + dy * dy) + dz * dz;
-      }
-      {
-        const f32x2 dx = f32x2{b1[2], b1[3]} - qx, dy = f32x2{b2[0], b2[1]} - qy, dz = f32x2{b2[2], b2[3]} - qz;
-        d[u][3] = (dx * dx + dy * dy) + dz * dz;
-      }
-      mn[u] = fminf(fminf(fminf(d[u][0][0], d[u][0][1]), fminf(d[u][1][0], d[u][1][1])),
-                    fminf(fminf(d[u][2][0], d[u][2][1]), fminf(d[u][3][0], d[u][3][1])));
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      // '<=': an equal distance with a smaller index must still be seen
-      if (__any(valid && mn[u] <= kb)) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          const unsigned long long x = ((unsigned long long)__float_as_uint(d[u][t >> 1][t & 1]) << 32) |
-                                       (unsigned)s_k[k + 8 * u + t];
-          const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
-          k3 = l2 ? k2 : (l3 ? x : k3);
-          k2 = l1 ? k1 : (l2 ? x : k2);
-          k1 = l1 ? x : k1;
-        }
-        kb = fminf(kb, __uint_as_float((unsigned)(k3 >> 32)));
-      }
-    }
+    nn3_scan<4>(s_c, s_k, step << 5, valid, qx, qy, qz, k1, k2, k3, kb);  // a 32-candidate step
   };
 
   // A. one step per wave around the rank-proportional start
@@ -455,6 +469,249 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel(int n, int m, c
     dist[o] = __uint_as_float((unsigned)(k1 >> 32)); dist[o + 1] = __uint_as_float((unsigned)(k2 >> 32));
     dist[o + 2] = __uint_as_float((unsigned)(k3 >> 32));
     idx[o] = (int)(unsigned)k1; idx[o + 1] = (int)(unsigned)k2; idx[o + 2] = (int)(unsigned)k3;
+  }
+}
+
+// The pruned search with the candidates chosen through the sampled set's CELL TABLE (cells2 of dh3d_three_nn_cells: the
+// table dh3d_fps_sorted_ordered writes on the cloud's grid, or dh3d_spatial_sort_cells of the sampled set on its own).
+// The boxes above prune by 64-sample Morton groups, 16 boxes of ~0.4 of the cloud each: a query group stages all m
+// records and scans about half of them.  Here the workgroup stages only the samples of the cells it can reach:
+//   1. the grid is coarsened by dropping the schedule's last D steps (nn3_cell_drop), so a coarse cell is ONE range
+//      ct[c << D] .. ct[(c + 1) << D] of the order; round 1 takes the coarse cells of the query group's box +- 1 (a lane
+//      per cell: it requests the cell's first kNNDirect records at once and a prefix sum over the cells places them in
+//      the cand4_slot image; the rest of a fuller cell follows by a search over the prefix; +inf pads the list to the
+//      8-candidate sub-step), the sub-steps are dealt to the four waves one by one and merged;
+//   2. every query has a third distance r now.  If the coarse cells of its [q - r, q + r] lie inside round 1's for every
+//      query, the lists are final; otherwise the samples of the ADDITIONAL cells of the union are appended and scanned
+//      (an unbounded r -- fewer than three candidates so far -- takes every cell: the whole set, what the boxes cost at
+//      worst).  (Per query, not the group's box widened by its largest r: the query with the largest r is seldom the one
+//      next to the edge of round 1's cells.)
+// Exactness.  nn3_cell is the sort's own expression (spatial.hip: (int)((x - lo) * scale), clamped, fine coordinate >> 2)
+// on the table's own origin and scales, and every step of it -- the subtraction, the product with a positive scale, the
+// truncation, the clamps, the shifts -- is monotone in x IN FLOAT ARITHMETIC: a sample with s.x >= t lies in a cell
+// >= nn3_cell(t), whatever was rounded.  A sample that belongs to a query's list has d <= the query's third distance <=
+// r^2, so |s.x - q.x| <= r (1 + 4 * 2^-24) on every axis: s.x >= q.x - r' for the inflated r' = r (1 + 1e-5), and the
+// margin subtracted on top covers the two roundings of (q.x - r') - margin.  The samples are inside the grid they were
+// binned on, so the clamps only ever act on the query side (a table of the sampled set's own grid: queries outside it reach
+// its border cells).  Lists only improve in round 2, so round 1's r stays valid.
+// The schedule steps dropped: a coarse cell should hold about two samples (512 coarse cells from 768 samples on: 2 x 2 x 2
+// cells of a cube's grid; 256 below), so that a query group looks up a few dozen ranges and a third distance seldom
+// exceeds the one coarse cell of margin.  (8 x 8192 vs 1024 / 32 x 4096 vs 512, uniform: D = 3 everywhere 16.5 / 28.2 us,
+// D = 4 everywhere 17.3 / 26.7 us, this rule 16.3 / 27.0 us -- profiles/three_nn_cells.txt.)
+constexpr int nn3_cell_drop(int m) { return m < 768 ? 4 : 3; }
+constexpr int kNNCoarse = 4096 >> 3;                // coarse cells of the grid at most
+constexpr int kNNDirect = 8;                        // records a cell's own lane copies (Poisson(2): 2e-4 hold more)
+constexpr int kNNCellCap = kNNChunk + 16;           // both rounds are padded to the sub-step: at most m + 14 slots
+
+__device__ __forceinline__ int nn3_cell(float p, float lo, float scl, int nb) {
+  // (the float clamp changes nothing inside the grid and keeps the conversion defined for a far or infinite p)
+  const float t = fminf(fmaxf((p - lo) * scl, 0.f), 1.0e6f);
+  return min((4 << nb) - 1, (int)t) >> 2;
+}
+
+__device__ __forceinline__ void nn3_insert(unsigned long long x, unsigned long long &k1, unsigned long long &k2,
+                                           unsigned long long &k3) {
+  const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
+  k3 = l2 ? k2 : (l3 ? x : k3);
+  k2 = l1 ? k1 : (l2 ? x : k2);
+  k1 = l1 ? x : k1;
+}
+
+template <int D>  // the schedule steps dropped: 2^D table cells are one coarse cell
+__global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel_cells(int n, int m, const float4 *__restrict__ qs,
+                                                                      const float *__restrict__ qbox,
+                                                                      const float4 *__restrict__ cs,
+                                                                      const int *__restrict__ cells,
+                                                                      float *__restrict__ dist, int32_t *__restrict__ idx) {
+  __shared__ __attribute__((aligned(16))) float s_c[kNNCellCap * 3];
+  __shared__ int s_k[kNNCellCap];
+  __shared__ int s_ro[kNNCoarse], s_rb[kNNCoarse];  // per cell of the box: records up to and with it | first record - its slot
+  __shared__ int s_wt[2][4];                        // the waves' record counts of one 256-cell pass (two passes alternate)
+  __shared__ float s_b[64];                         // round 1's third distance per query
+  __shared__ int s_box2[7];                         // round 2's coarse box (lo, hi) and whether there is a round 2
+  __shared__ unsigned long long s_mk[3][3][64];     // partial lists of waves 1..3
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bx = (int)((blockIdx.x + 37u * (unsigned)b) % gridDim.x);  // (rotated by the cloud: three_nn_pruned_kernel)
+  const int j = bx * 64 + lane;
+  const bool valid = j < n;
+  const float4 q = qs[(size_t)b * n + (valid ? j : bx * 64)];
+  const float4 *cand = cs + (size_t)b * m;
+  const f32x2 qx = {q.x, q.x}, qy = {q.y, q.y}, qz = {q.z, q.z};
+
+  // ---- the grid (the table's header) and the query group's box on it
+  const int *ct = cells + (size_t)b * DH3D_CELL_INTS;
+  const float *hd = reinterpret_cast<const float *>(ct) + 4100;
+  const unsigned sched = (unsigned)ct[4107];
+  int nb[3] = {0, 0, 0}, nc[3] = {0, 0, 0};  // grid bits per axis: all 12 steps | the coarse grid's 12 - D
+#pragma unroll
+  for (int s = 0; s < 12; ++s) {
+    const int a = (int)((sched >> (2 * s)) & 3u);
+    nb[0] += (int)(a == 0); nb[1] += (int)(a == 1); nb[2] += (int)(a == 2);
+    if (s < 12 - D) { nc[0] += (int)(a == 0); nc[1] += (int)(a == 1); nc[2] += (int)(a == 2); }
+  }
+  const float *qb = qbox + ((size_t)b * ((n + 63) / 64) + bx) * 8;
+  const float ql[3] = {qb[0], qb[1], qb[2]}, qh[3] = {qb[4], qb[5], qb[6]};
+  int lo1[3], hi1[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int sh = nb[a] - nc[a];
+    lo1[a] = max((nn3_cell(ql[a], hd[a], hd[3 + a], nb[a]) >> sh) - 1, 0);
+    hi1[a] = min((nn3_cell(qh[a], hd[a], hd[3 + a], nb[a]) >> sh) + 1, (1 << nc[a]) - 1);
+  }
+
+  // The samples of the coarse cells [lo, hi] (outer: without round 1's) appended to the LDS image from slot `at` on, padded
+  // to the sub-step.  Returns the slots taken.  (t < 512 and c <= 64: the float quotient is off by < 1e-4, (t + 0.5) / c is
+  // never within 0.5 / 64 of an integer.)
+  auto put = [&](int e, float4 rec) __attribute__((always_inline)) {
+    s_c[cand4_slot(e, 0)] = rec.x; s_c[cand4_slot(e, 1)] = rec.y; s_c[cand4_slot(e, 2)] = rec.z;
+    s_k[e] = __float_as_int(rec.w);
+  };
+  auto small_div = [](int t, int c) { return (int)(((float)t + 0.5f) * (1.0f / (float)c)); };
+  auto stage = [&](const int (&lo)[3], const int (&hi)[3], bool outer, int at) __attribute__((always_inline)) {
+    const int c0 = hi[0] - lo[0] + 1, c1 = hi[1] - lo[1] + 1, total = c0 * c1 * (hi[2] - lo[2] + 1);
+    int run = 0;
+    bool big = false;  // a cell with more than kNNDirect samples
+    for (int t0 = 0, pass = 0; t0 < total; t0 += kBlock, pass ^= 1) {
+      const int t = t0 + (int)threadIdx.x;
+      int beg = 0, len = 0;
+      if (t < total) {
+        const int tq = small_div(t, c0), iz = lo[2] + small_div(tq, c1);
+        const int ix = lo[0] + t - tq * c0, iy = lo[1] + tq - (iz - lo[2]) * c1;
+        const bool inner = ix >= lo1[0] && ix <= hi1[0] && iy >= lo1[1] && iy <= hi1[1] && iz >= lo1[2] && iz <= hi1[2];
+        if (!(outer && inner)) {
+          unsigned code = 0;
+          int r0 = nc[0], r1 = nc[1], r2 = nc[2];
+#pragma unroll
+          for (int s = 0; s < 12 - D; ++s) {  // (the schedule is uniform: scalar branches)
+            const int a = (int)((sched >> (2 * s)) & 3u);
+            unsigned bit;
+            if (a == 0) bit = (unsigned)(ix >> --r0) & 1u;
+            else if (a == 1) bit = (unsigned)(iy >> --r1) & 1u;
+            else bit = (unsigned)(iz >> --r2) & 1u;
+            code |= bit << (11 - D - s);
+          }
+          beg = min(max(ct[code << D], 0), m);
+          len = min(max(ct[(code + 1) << D], beg), m) - beg;
+        }
+      }
+      // a cell's first kNNDirect records are its own lane's, requested now: their way runs under the prefix sum
+      float4 rec[kNNDirect];
+#pragma unroll
+      for (int i = 0; i < kNNDirect; ++i)
+        if (i < len) rec[i] = cand[beg + i];
+      int inc = len;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += up;
+      }
+      if (lane == 63) s_wt[pass][wave] = inc;
+      big |= __syncthreads_or(len > kNNDirect) != 0;
+      int base = run;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const int v = s_wt[pass][w];
+        base += w < wave ? v : 0;
+        run += v;
+      }
+      const int first = base + inc - len;
+#pragma unroll
+      for (int i = 0; i < kNNDirect; ++i)
+        if (i < len && at + first + i < kNNCellCap) put(at + first + i, rec[i]);
+      if (t < total) { s_ro[t] = first + len; s_rb[t] = beg - first; }
+    }
+    // (A table of this set never fills more than kNNCellCap slots; the cap keeps any other table inside the image.)
+    const int cnt = min(run, kNNCellCap - at), pad = min((cnt + 7) & ~7, kNNCellCap - at);
+    if ((int)threadIdx.x < pad - cnt)  // padding: d = inf, never taken
+      put(at + cnt + (int)threadIdx.x, make_float4(INFINITY, INFINITY, INFINITY, __int_as_float(INT_MAX)));
+    if (big) {  // (workgroup-uniform) fuller cells: a lane per record, the first cell whose inclusive count exceeds its rank
+      __syncthreads();
+      int top = 1;
+      while (2 * top <= total) top *= 2;
+      for (int r = threadIdx.x; r < cnt; r += kBlock) {
+        int o = 0;
+        for (int step = top; step > 0; step >>= 1)
+          if (o + step <= total && s_ro[o + step - 1] <= r) o += step;
+        if (r - (o > 0 ? s_ro[o - 1] : 0) >= kNNDirect) put(at + r, cand[s_rb[o] + r]);
+      }
+    }
+    __syncthreads();
+    return pad;
+  };
+
+  const unsigned long long kInf = (unsigned long long)__float_as_uint(INFINITY) << 32;
+  unsigned long long k1 = kInf, k2 = kInf, k3 = kInf;
+  float kb = INFINITY;  // the screen: the lane's third distance so far
+  auto merge_into_wave0 = [&]() __attribute__((always_inline)) {  // (behind a barrier that follows the other waves' stores)
+#pragma unroll
+    for (int w = 0; w < 3; ++w)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) nn3_insert(s_mk[w][t][lane], k1, k2, k3);
+  };
+  auto write_out = [&]() __attribute__((always_inline)) {
+    const size_t o = ((size_t)b * n + __float_as_int(q.w)) * 3;
+    dist[o] = __uint_as_float((unsigned)(k1 >> 32)); dist[o + 1] = __uint_as_float((unsigned)(k2 >> 32));
+    dist[o + 2] = __uint_as_float((unsigned)(k3 >> 32));
+    idx[o] = (int)(unsigned)k1; idx[o + 1] = (int)(unsigned)k2; idx[o + 2] = (int)(unsigned)k3;
+  };
+
+  // ---- round 1.  (The sub-steps are dealt from a wave that turns with the query group: the waves of the workgroups of a CU
+  // that share a SIMD do not all get the odd sub-step.)
+  const int w0 = (wave - bx) & 3;
+  const int pad1 = stage(lo1, hi1, false, 0);
+  for (int k = 8 * w0; k < pad1; k += 32) nn3_scan<1>(s_c, s_k, k, valid, qx, qy, qz, k1, k2, k3, kb);
+  if (wave > 0) { s_mk[wave - 1][0][lane] = k1; s_mk[wave - 1][1][lane] = k2; s_mk[wave - 1][2][lane] = k3; }
+  __syncthreads();
+  if (wave == 0) {
+    merge_into_wave0();
+    const float d3 = __uint_as_float((unsigned)(k3 >> 32));
+    s_b[lane] = d3;
+    // ---- the cells the lists can still reach: every query's own box [q - r, q + r], r = its third distance
+    const float r = sqrtf(d3) * 1.00001f;
+    const float qc[3] = {q.x, q.y, q.z};
+    int lo2[3], hi2[3];
+    bool out = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int sh = nb[a] - nc[a];
+      // (1e-18: a difference whose square underflows counts as distance zero)
+      const float marg = r * 1e-5f + fabsf(qc[a]) * 1e-6f + 1e-18f;
+      lo2[a] = valid ? nn3_cell((qc[a] - r) - marg, hd[a], hd[3 + a], nb[a]) >> sh : lo1[a];
+      hi2[a] = valid ? nn3_cell((qc[a] + r) + marg, hd[a], hd[3 + a], nb[a]) >> sh : hi1[a];
+      out = out || lo2[a] < lo1[a] || hi2[a] > hi1[a];
+    }
+    const bool more = __any(out);
+    if (more) {  // (wave-uniform) round 2's box: the union of the queries' and round 1's
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        lo2[a] = wave_min_i32(min(lo2[a], lo1[a]));
+        hi2[a] = -wave_min_i32(-max(hi2[a], hi1[a]));
+      }
+    }
+    if (lane == 0) {
+      s_box2[0] = lo2[0]; s_box2[1] = lo2[1]; s_box2[2] = lo2[2];
+      s_box2[3] = hi2[0]; s_box2[4] = hi2[1]; s_box2[5] = hi2[2];
+      s_box2[6] = (int)more;
+    }
+  }
+  __syncthreads();
+  if (!s_box2[6]) {  // (workgroup-uniform)
+    if (wave == 0 && valid) write_out();
+    return;
+  }
+
+  // ---- round 2: the additional cells.  Wave 0 keeps the merged lists, the others start empty behind the same screen.
+  const int lo2[3] = {s_box2[0], s_box2[1], s_box2[2]}, hi2[3] = {s_box2[3], s_box2[4], s_box2[5]};
+  const int pad2 = stage(lo2, hi2, true, pad1);
+  if (wave > 0) k1 = k2 = k3 = kInf;
+  kb = s_b[lane];
+  for (int k = pad1 + 8 * w0; k < pad1 + pad2; k += 32) nn3_scan<1>(s_c, s_k, k, valid, qx, qy, qz, k1, k2, k3, kb);
+  if (wave > 0) { s_mk[wave - 1][0][lane] = k1; s_mk[wave - 1][1][lane] = k2; s_mk[wave - 1][2][lane] = k3; }
+  __syncthreads();
+  if (wave == 0 && valid) {
+    merge_into_wave0();
+    write_out();
   }
 }
 
@@ -562,6 +819,24 @@ DH3D_API int dh3d_three_nn_sorted(int b, int n, int m, const float *sorted1, con
   hipLaunchKernelGGL(three_nn_sorted_kernel, dim3(dh3d_cdiv(n, 64), b), dim3(kBlock), 0, (hipStream_t)stream, n, m,
                      reinterpret_cast<const float4 *>(sorted1), reinterpret_cast<const float4 *>(sorted2), dist, idx);
   return dh3d_launch_status();
+}
+
+DH3D_API int dh3d_three_nn_cells(int b, int n, int m, const float *sorted1, const float *gbox1, const float *sorted2,
+                                 const float *gbox2, const int32_t *cells2, float *dist, int32_t *idx, void *stream) {
+  DH3D_REQUIRE(sorted1 && sorted2 && dist && idx && b > 0 && n > 0 && m > 0);
+  DH3D_SUPPORTED(b <= 65535);
+  if (cells2 && gbox1 && m <= kNNChunk && m >= 128 && n <= 16384) {  // candidates through the sampled set's cell table
+    const dim3 grid(dh3d_cdiv(n, 64), b);
+    const float4 *s1 = reinterpret_cast<const float4 *>(sorted1), *s2 = reinterpret_cast<const float4 *>(sorted2);
+    if (nn3_cell_drop(m) == 4)
+      hipLaunchKernelGGL(three_nn_pruned_kernel_cells<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, n, m, s1, gbox1, s2,
+                         cells2, dist, idx);
+    else
+      hipLaunchKernelGGL(three_nn_pruned_kernel_cells<3>, grid, dim3(kBlock), 0, (hipStream_t)stream, n, m, s1, gbox1, s2,
+                         cells2, dist, idx);
+    return dh3d_launch_status();
+  }
+  return dh3d_three_nn_sorted(b, n, m, sorted1, gbox1, sorted2, gbox2, dist, idx, stream);
 }
 
 DH3D_API int dh3d_three_interpolate_fwd(int b, int m, int c, int n, const float *points,

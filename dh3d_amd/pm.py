@@ -424,13 +424,22 @@ def fps_sorted_ordered(srt, gbox, npoint, cells=None):
     return out, xyz_s, srt_s, gbox_s, cells_s
 
 
-def three_nn_sorted(srt1, gbox1, srt2, gbox2):
+def three_nn_sorted(srt1, gbox1, srt2, gbox2, cells2=None):
     """three_nn from spatial_sort() outputs of the query cloud and of the candidate set: same (dist [B,n,3] squared,
-    idx [B,n,3]) as ops.three_nn, original indexing on both sides."""
+    idx [B,n,3]) as ops.three_nn, original indexing on both sides.  cells2: the candidate set's cell table [B,CELL_INTS]
+    (fps_sorted_ordered's cells_s, or spatial_sort_cells of the set) -- a query group then visits only the samples of the
+    cells it can reach (128 <= m <= 1024; other sizes ignore the table)."""
     B, n, _ = srt1.shape
     m = srt2.shape[1]
     d3 = torch.empty((B, n, 3), dtype=torch.float32, device=srt1.device)
     i3 = torch.empty((B, n, 3), dtype=torch.int32, device=srt1.device)
+    if cells2 is not None:
+        c2 = L.require_cuda_i32(cells2, "cells2", 2)
+        if tuple(c2.shape) != (B, CELL_INTS):
+            raise ValueError("three_nn_sorted: cells2 is not the cell table of a batch of %d sets" % B)
+        L.check(L.lib().dh3d_three_nn_cells(B, n, m, L.ptr(srt1), L.ptr(gbox1), L.ptr(srt2), L.ptr(gbox2), L.ptr(c2),
+                                            L.ptr(d3), L.ptr(i3), L.stream_ptr()), "three_nn_cells")
+        return d3, i3
     L.check(L.lib().dh3d_three_nn_sorted(B, n, m, L.ptr(srt1), L.ptr(gbox1), L.ptr(srt2), L.ptr(gbox2), L.ptr(d3),
                                          L.ptr(i3), L.stream_ptr()), "three_nn_sorted")
     return d3, i3

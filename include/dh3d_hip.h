@@ -383,11 +383,23 @@ int dh3d_knn_grid_plan(int B, int N, int K);
 
 /* ThreeNN on ordered clouds: identical dist / idx to dh3d_three_nn (original indexing on both sides) from the
  * dh3d_spatial_sort outputs of the query cloud (sorted1 [b,n,4], gbox1) and of the candidate set (sorted2 [b,m,4],
- * gbox2; the boxes are not needed by the current kernel and may be NULL).  Every candidate is still visited; the
- * ordering makes the 3-deep insertion rare (a wave's queries are a compact region and its scan starts at the matching
- * place of the candidates' order). */
+ * gbox2).  With 128 <= m <= 1024 and both boxes given, the candidates' 64-sample groups are pruned by their boxes (a query
+ * group stages all m records and scans about half of them: 22.2 us at 8 x 8192 vs 1024, 29.5 at 32 x 4096 vs 512, uniform
+ * clouds, the kernel alone); otherwise -- the boxes may be NULL -- every candidate is visited, and the ordering makes the
+ * 3-deep insertion rare (a wave's queries are a compact region and its scan starts at the matching place of the
+ * candidates' order). */
 int dh3d_three_nn_sorted(int b, int n, int m, const float *sorted1, const float *gbox1, const float *sorted2,
                          const float *gbox2, float *dist, int32_t *idx, void *stream);
+/* The same with the candidates chosen through the candidate set's CELL TABLE cells2 [b, DH3D_CELL_INTS]: the table
+ * dh3d_fps_sorted_ordered writes for the sampled set on the cloud's grid, or dh3d_spatial_sort_cells of the candidate set
+ * itself (queries outside that grid reach its border cells).  A 64-query group stages and scans only the samples of the
+ * cells it can reach: the coarse cells (2^3 table cells each, 2^4 below 768 samples) of its box +- 1, widened once to the
+ * cells its queries' third distances span -- about 130 records instead of m: 16.3 / 27.0 us at the two shapes above
+ * (15.2 / 22.7 on street-scene-like clouds, where the boxes take 25.1 / 26.0; profiles/three_nn_cells.txt).  Identical
+ * dist / idx to dh3d_three_nn bit for bit.  Serves 128 <= m <= 1024, n <= 16384 with gbox1 given; outside that range, or
+ * with cells2 == NULL, it is dh3d_three_nn_sorted.  No workspace, no allocation: capture-safe. */
+int dh3d_three_nn_cells(int b, int n, int m, const float *sorted1, const float *gbox1, const float *sorted2,
+                        const float *gbox2, const int32_t *cells2, float *dist, int32_t *idx, void *stream);
 
 /* FarthestPointSample on an ordered cloud: identical outputs to dh3d_farthest_point_sample (original
  * indices); per round only the 64-point groups the new sample can affect are re-evaluated.  N <= 12288, and the

@@ -1,5 +1,5 @@
-"""Dev: long randomised comparison of the ordered three_nn (three_nn_pruned_kernel for 128 <= m <= 1024 samples: candidate
-groups pruned by their boxes; three_nn_sorted_kernel otherwise) with the plain op -- indices AND squared distances bit for
+"""Dev: long randomised comparison of the ordered three_nn (128 <= m <= 1024 samples: candidate groups pruned by their boxes,
+and the candidates read off the set's cell table; three_nn_sorted_kernel otherwise) with the plain op -- indices AND squared distances bit for
 bit (uniform, blobs, planes, lines, lattices with exact ties, duplicated / coincident points; samples = a random subset,
 an FPS subset or unrelated points).   python tools/three_nn_fuzz.py [cases] [seed]"""
 import os, sys
@@ -47,11 +47,12 @@ for it in range(cases):
         s2 = torch.gather(t0, 1, ops.farthest_point_sample(m, t0).long()[:, :, None].expand(-1, -1, 3)).cpu().numpy()
     t, s2 = torch.from_numpy(x).to(dev), torch.from_numpy(np.ascontiguousarray(s2)).to(dev)
     srt, gbox = pm.spatial_sort(t)
-    srt2, gbox2 = pm.spatial_sort(s2)
-    d, i = pm.three_nn_sorted(srt, gbox, srt2, gbox2)
+    srt2, gbox2, cells2 = pm.spatial_sort_cells(s2)
     d0, i0 = ops.three_nn(t, s2)
-    ok = bool(torch.equal(i, i0)) and bool(torch.equal(d.view(torch.int32), d0.view(torch.int32)))
+    ok = True
+    for d, i in (pm.three_nn_sorted(srt, gbox, srt2, gbox2), pm.three_nn_sorted(srt, gbox, srt2, gbox2, cells2=cells2)):
+        ok = ok and bool(torch.equal(i, i0)) and bool(torch.equal(d.view(torch.int32), d0.view(torch.int32)))
     if not ok:
         bad += 1
-        print("MISMATCH", it, B, N, m, kind, how, int((i != i0).sum()), flush=True)
+        print("MISMATCH", it, B, N, m, kind, how, flush=True)
 print("cases %d mismatches %d" % (cases, bad))
