@@ -16,13 +16,12 @@
 #include <float.h>
 #include <math.h>
 
+#include "cell_grid.h"
 #include "common.h"
 #include "wave_ops.h"
 
 namespace {
 
-constexpr int kCellInts = 4112;  // ints per cloud of the cell table (spatial.hip)
-constexpr int kCellFlag = 4106;  // 1 = the sort found the cloud crowded: not one for cell lists
 constexpr int kChunk = 1024;     // candidates staged per step of the scan (12 KiB of LDS)
 
 // Everything at or below this squared distance goes to the exact test: d < r needs s < r^2 (1 + 2^-22) at most, and s = 0
@@ -111,13 +110,6 @@ __global__ __launch_bounds__(64) void ball_scan_kernel(const float *__restrict__
 constexpr int kGridWaves = 4;       // queries per workgroup
 constexpr int kGridMaxCells = 512;  // a ball whose box meets more cells restarts over the 64-point group boxes
 
-// The sort's cell arithmetic (spatial.hip) on one axis; the float clamp changes nothing inside the grid and keeps the
-// conversion defined for +-inf / NaN.  Monotone in p: a point of [plo, phi] lies in a cell of [cell(plo), cell(phi)].
-__device__ __forceinline__ int ball_cell(float p, float lo, float scl, int nb) {
-  const float t = fminf(fmaxf((p - lo) * scl, 0.f), 1.0e6f);
-  return min((4 << nb) - 1, (int)t) >> 2;
-}
-
 __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
     const float4 *__restrict__ sorted, const float *__restrict__ gbox, const int *__restrict__ cells,
     const float *__restrict__ xyz2, const float *__restrict__ radii, int per_query, int n, int m, int nsample, int wpl,
@@ -133,7 +125,6 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
   __builtin_amdgcn_wave_barrier();
 
   const float4 *sc = sorted + (size_t)b * n;
-  const int *ct = cells + (size_t)b * kCellInts;
   const size_t qrow = (size_t)b * m + j;
   const float q[3] = {xyz2[qrow * 3], xyz2[qrow * 3 + 1], xyz2[qrow * 3 + 2]};
   const float r = radii[per_query ? qrow : 0];
@@ -148,22 +139,25 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
   };
 
   if (r > 0.f) {  // (a radius <= 0 or NaN has no hits)
-    const float *hd = reinterpret_cast<const float *>(ct) + 4100;
-    const unsigned sched = (unsigned)ct[4107];
-    int nb[3] = {0, 0, 0};
+    // This kernel counts the schedule's bits again itself, cell_grid.h's sched_bits restated as a loop: with the shared
+    // population counts the compiler builds another cell loop below, and a ball whose box meets ~500 cells took 39.4 us
+    // against 35.6 (profiles/cell_grid_header.txt).
+    CellGrid g = cell_grid(cells, b);
+    const int *ct = g.ct;
+    g.nb[0] = g.nb[1] = g.nb[2] = 0;
 #pragma unroll
-    for (int s = 0; s < 12; ++s) {
-      const int a = (int)((sched >> (2 * s)) & 3u);
-      nb[0] += (int)(a == 0); nb[1] += (int)(a == 1); nb[2] += (int)(a == 2);
+    for (int s = 0; s < kGridSteps; ++s) {
+      const int a = sched_axis(g.sched, s);
+      g.nb[0] += (int)(a == 0); g.nb[1] += (int)(a == 1); g.nb[2] += (int)(a == 2);
     }
     // the cells the ball's axis-aligned box meets.  A hit has |q - p| < r (1 + 5 * 2^-24) on every axis; the margin also
-    // covers the two roundings of q -+ r -+ margin, and the cell function is monotone (ball_cell)
+    // covers the two roundings of q -+ r -+ margin, and the cell function is monotone (cell_grid.h grid_cell)
     int c0[3], cn[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const float marg = r * 1e-5f + fabsf(q[a]) * 1e-6f;
-      c0[a] = ball_cell((q[a] - r) - marg, hd[a], hd[3 + a], nb[a]);
-      cn[a] = ball_cell((q[a] + r) + marg, hd[a], hd[3 + a], nb[a]) - c0[a] + 1;
+      c0[a] = grid_cell(g, a, (q[a] - r) - marg);
+      cn[a] = grid_cell(g, a, (q[a] + r) + marg) - c0[a] + 1;
     }
     const int total = cn[0] * cn[1] * cn[2];
     if (!ct[kCellFlag] && total <= kGridMaxCells) {
@@ -173,17 +167,7 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
         int beg = 0, len = 0;
         if (t < total) {
           const int ix = c0[0] + t % cn[0], iy = c0[1] + (t / cn[0]) % cn[1], iz = c0[2] + t / (cn[0] * cn[1]);
-          unsigned code = 0;
-          int r0 = nb[0], r1 = nb[1], r2 = nb[2];
-#pragma unroll
-          for (int s = 0; s < 12; ++s) {  // (the schedule is uniform: scalar branches)
-            const int a = (int)((sched >> (2 * s)) & 3u);
-            unsigned bit;
-            if (a == 0) bit = (unsigned)(ix >> --r0) & 1u;
-            else if (a == 1) bit = (unsigned)(iy >> --r1) & 1u;
-            else bit = (unsigned)(iz >> --r2) & 1u;
-            code |= bit << (11 - s);
-          }
+          const unsigned code = cell_code(g.sched, g.nb, ix, iy, iz);
           beg = max(ct[code], 0);
           len = max(min(ct[code + 1], n) - beg, 0);
         }

@@ -19,6 +19,7 @@
 //          ties (:158-161).  Encoded here as key(k) = ((k & 511) << 16) | (k >> 9), smaller wins.
 #include <limits.h>
 
+#include "cell_grid.h"
 #include "common.h"
 #include "wave_ops.h"
 
@@ -173,7 +174,7 @@ struct FpsOrderedOut {
   float *gbox_s;       // [B, ceil(m / 64), 8]
   const int *cells;    // [B, DH3D_CELL_INTS] of the cloud, or NULL
   int *cells_s;        // [B, DH3D_CELL_INTS] of the sampled set (iff cells)
-  int occ_min;         // fewer occupied cells than this: cells_s[4106] = 1 (spatial.hip's rule for a set of m points)
+  int occ_min;         // fewer occupied cells than this: cells_s[kCellFlag] = 1 (spatial.hip's rule for a set of m points)
 };
 
 // Not keys.h's f32_order_bits: with this file's flags (csrc/Makefile EXTRA_fps) hipcc crashes selecting instructions for
@@ -508,22 +509,22 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
       }
       __syncthreads();
       if (oo.cells) {  // the subset's cell table on the cloud's grid: cell c opens at the number of picks in front of it
-        const int *ct = oo.cells + (size_t)b * DH3D_CELL_INTS;
-        int *cs = oo.cells_s + (size_t)b * DH3D_CELL_INTS;
+        const int *ct = oo.cells + (size_t)b * kCellInts;
+        int *cs = oo.cells_s + (size_t)b * kCellInts;
         int occ = 0;
-        for (int c = tid; c <= 4096; c += T) {
+        for (int c = tid; c <= kGridCells; c += T) {
           const unsigned v = s_cnt[min(max(ct[c], 0), N)];
           cs[c] = (int)v;
-          if (c < 4096) occ += (int)(s_cnt[min(max(ct[c + 1], 0), N)] > v);
+          if (c < kGridCells) occ += (int)(s_cnt[min(max(ct[c + 1], 0), N)] > v);
         }
-        for (int c = 4097 + tid; c < DH3D_CELL_INTS; c += T)
-          if (c != 4106) cs[c] = ct[c];  // origin, scales, bit schedule: the cloud's grid
+        for (int c = kCellCopy + tid; c < kCellInts; c += T)
+          if (c != kCellFlag) cs[c] = ct[c];  // origin, scales, bit schedule: the cloud's grid
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) occ += __shfl_xor(occ, off, 64);
         if (lane == 0) atomicAdd(&s_wsum[WAVES], (unsigned)occ);
       }
       __syncthreads();  // every prefix value has been read: the counters now hand out the slots
-      if (oo.cells && tid == 0) oo.cells_s[(size_t)b * DH3D_CELL_INTS + 4106] = (int)s_wsum[WAVES] < oo.occ_min ? 1 : 0;
+      if (oo.cells && tid == 0) oo.cells_s[(size_t)b * kCellInts + kCellFlag] = (int)s_wsum[WAVES] < oo.occ_min ? 1 : 0;
       float4 *so = oo.sorted_s + (size_t)b * m;
       for (int r = tid; r < m; r += T) {
         const int k = s_out[r];
@@ -734,6 +735,6 @@ DH3D_API int dh3d_fps_sorted_ordered(const float *sorted, const float *gbox, con
   oo.gbox_s = gbox_s;
   oo.cells = cells;
   oo.cells_s = cells_s;
-  oo.occ_min = (int)(0.6 * 4096.0 * (1.0 - exp(-(double)m / 4096.0)));  // spatial.hip sort_launch's rule for m points
+  oo.occ_min = (int)(0.6 * kGridCells * (1.0 - exp(-(double)m / kGridCells)));  // spatial.hip sort_launch's rule for m points
   return fps_sorted_dispatch(sorted, gbox, B, N, m, out, xyz_out, nullptr, stream, oo);
 }

@@ -23,7 +23,7 @@
 //                     Candidates are compared by (d2, original index), so the order of the walk does not matter.  A box of
 //                     more than 512 cells takes the 64-point groups of the order whose box the ball meets instead: the
 //                     loop over the groups is wave-uniform, the records of a group are read as broadcasts.  The sort's
-//                     crowded flag (cells[4106]) is NOT a reason to leave the cells: for one radius-bound neighbour a
+//                     crowded flag (cells[kCellFlag]) is NOT a reason to leave the cells: for one radius-bound neighbour a
 //                     dense cell costs its points and no more, while 64 unrelated lanes meet nearly every group between
 //                     them (sending crowded clouds to the groups measured 2.47 ms for 64 x 8192 x 8192 on the demo
 //                     clouds, the scan 1.52).  The sort sees the rows below anchor_count only: icp_pack_kernel hands it
@@ -42,6 +42,7 @@
 // Compiled without contraction (csrc/Makefile EXACT): the ids depend on every rounding of d2.
 #include <math.h>
 
+#include "cell_grid.h"
 #include "common.h"
 #include "keys.h"
 #include "rigid_fit.h"
@@ -54,7 +55,6 @@ constexpr int kMaxPoints = 131072;  // Na, Nb
 constexpr int kMaxPairs = 65535;
 constexpr int kMaxIter = 256;
 constexpr int kGridMaxNa = 16384;   // dh3d_spatial_sort_cells
-constexpr int kCellInts = 4112;     // ints per cloud of the cell table (spatial.hip)
 constexpr int kGridMaxCells = 512;  // a box that meets more cells walks the 64-point groups
 constexpr int kThreads = 256;
 constexpr int kChunk = 1024;        // anchors staged per step of the scan
@@ -143,12 +143,6 @@ __global__ __launch_bounds__(kThreads) void icp_scan_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------- cell lists
-// The sort's cell arithmetic (spatial.hip) on one axis, as ball_query.hip's ball_cell: monotone in p, defined for +-inf.
-__device__ __forceinline__ int icp_cell(float p, float lo, float scl, int nb) {
-  const float t = fminf(fmaxf((p - lo) * scl, 0.f), 1.0e6f);
-  return min((4 << nb) - 1, (int)t) >> 2;
-}
-
 struct Best {
   double d2;
   int i;
@@ -182,36 +176,26 @@ __global__ __launch_bounds__(kThreads) void icp_grid_kernel(
   double m[3];
   icp_move(pose + (long long)p * 12, y0, y1, y2, m);
   const float4 *sc = sorted + (size_t)p * Na;
-  const int *ct = cells + (size_t)p * kCellInts;
-  const float *hd = reinterpret_cast<const float *>(ct) + 4100;
-  const unsigned sched = (unsigned)ct[4107];
-  int nbit[3] = {0, 0, 0};
-#pragma unroll
-  for (int s = 0; s < 12; ++s) {
-    const int a = (int)((sched >> (2 * s)) & 3u);
-    nbit[0] += (int)(a == 0); nbit[1] += (int)(a == 1); nbit[2] += (int)(a == 2);
-  }
-  if (threadIdx.x < 192) {  // the deposit tables: step s of the schedule puts the next lower bit of its axis at bit 11 - s
-    const int ax = threadIdx.x >> 6, v = threadIdx.x & 63;
-    unsigned code = 0;
-    int r = ax == 0 ? nbit[0] : ax == 1 ? nbit[1] : nbit[2];
-#pragma unroll
-    for (int s = 0; s < 12; ++s)
-      if ((int)((sched >> (2 * s)) & 3u) == ax) code |= ((unsigned)(v >> --r) & 1u) << (11 - s);
-    s_dep[ax][v] = code;
+  const CellGrid g = cell_grid(cells, p);
+  const int *ct = g.ct;
+  if (threadIdx.x < 192) {  // the deposit tables
+    const int ax = threadIdx.x >> 6;
+    s_dep[ax][threadIdx.x & 63] =
+        cell_deposit(g.sched, ax, threadIdx.x & 63, kGridSteps, ax == 0 ? g.nb[0] : ax == 1 ? g.nb[1] : g.nb[2], kGridSteps - 1);
   }
   __syncthreads();
   // The cells that the box y' +- max_dist meets.  An anchor x that the float64 test accepts has dx * dx <= d2 < max_dist^2
   // up to three float64 roundings, so |x - y'| < max_dist (1 + 2^-50) on every axis.  The box edge y' -+ (max_dist + marg)
   // is formed in float64 (2 roundings of 2^-53) and rounded to float32 (2^-24 relative to |y'| + max_dist + marg at most);
   // marg = (max_dist + |y'|) * 1e-6 is 16 times that, so the float32 edge still lies outside x, which is a float32 itself.
-  // The cell function is the sort's own and monotone in its argument: cell(lower edge) <= cell(x) <= cell(upper edge).
+  // The cell function is the sort's own and monotone in its argument (cell_grid.h grid_cell): cell(lower edge) <= cell(x)
+  // <= cell(upper edge).
   int c0[3], cn[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const double marg = (max_dist + fabs(m[a])) * 1e-6;
-    c0[a] = icp_cell((float)((m[a] - max_dist) - marg), hd[a], hd[3 + a], nbit[a]);
-    cn[a] = icp_cell((float)((m[a] + max_dist) + marg), hd[a], hd[3 + a], nbit[a]) - c0[a] + 1;
+    c0[a] = grid_cell(g, a, (float)((m[a] - max_dist) - marg));
+    cn[a] = grid_cell(g, a, (float)((m[a] + max_dist) + marg)) - c0[a] + 1;
   }
   const int total = cn[0] * cn[1] * cn[2];
   const bool by_cells = total <= kGridMaxCells;

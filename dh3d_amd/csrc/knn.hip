@@ -24,6 +24,7 @@
 
 #include <type_traits>
 
+#include "cell_grid.h"
 #include "common.h"
 #include "keys.h"
 #include "wave_ops.h"
@@ -277,8 +278,6 @@ __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__re
 // exactly the same screen / queue / 64-bit-key insertion as knn_kernel, so ids and distances are
 // bit-identical to it (tests).  Waves are independent: no block-level barrier.
 constexpr int kSortedWaves = 4;
-constexpr int kCellInts = 4112;  // ints per cloud of the cell table (spatial.hip)
-constexpr int kCellFlag = 4106;  // ... [kCellFlag]: 1 = not a cloud for cell lists (dense cells), the pruned scan takes it
 
 template <int KMAX>
 __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const float4 *__restrict__ sorted,
@@ -1148,31 +1147,27 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   const int qi = (int)((blockIdx.x + 37u * (unsigned)b) % gridDim.x) * QB + threadIdx.x / L;
   const bool valid = qi < N;
   const float4 *sc = sorted + (size_t)b * N;
-  const int *ct = cells + (size_t)b * kCellInts;
-  const float *hd = reinterpret_cast<const float *>(ct) + 4100;
-  const float lo[3] = {hd[0], hd[1], hd[2]}, scl[3] = {hd[3], hd[4], hd[5]};
+  const CellGrid g = cell_grid(cells, b);
+  const int *ct = g.ct;
+  // (copies: indexed by a per-thread axis below, which on the struct's members would put them in scratch memory)
+  const float lo[3] = {g.lo[0], g.lo[1], g.lo[2]}, scl[3] = {g.scl[0], g.scl[1], g.scl[2]};
+  const int nb[3] = {g.nb[0], g.nb[1], g.nb[2]};
   const float4 qr = sc[valid ? qi : N - 1];
   const float q[3] = {qr.x, qr.y, qr.z};
   // The grid: the sort dealt the cell code's 12 bits to the axes by extent (spatial.hip: `sched`, step 0 = the top bit;
   // a cube: z y x z y x ... = 16 x 16 x 16).  D = low bits of the code left out: a coarser grid whose cells are still
   // contiguous ranges of the order -- 2^D consecutive cells of the table.
-  const unsigned sched = (unsigned)ct[4107];
-  int nb[3] = {0, 0, 0}, drop[3] = {0, 0, 0};
+  int nc[3], drop[3];  // bits per axis of the coarser grid | of the D steps left out
+  sched_bits(g.sched, nc, kGridSteps - D);
 #pragma unroll
-  for (int s = 0; s < 12; ++s) {
-    const int a = (int)((sched >> (2 * s)) & 3u);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      nb[c] += (int)(a == c);
-      drop[c] += (int)(a == c && s >= 12 - D);
-    }
-  }
+  for (int a = 0; a < 3; ++a) drop[a] = nb[a] - nc[a];
   const int span = 1 << D;
   int cq[3], gmax[3];
   float w[3], eps[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    cq[a] = min((4 << nb[a]) - 1, max(0, (int)((q[a] - lo[a]) * scl[a]))) >> (2 + drop[a]);  // the sort's cell arithmetic
+    // (= grid_cell(g, a, q[a]) >> drop[a]: q is a point of the cloud, so the product is finite and below the float clamp)
+    cq[a] = min((4 << nb[a]) - 1, max(0, (int)((q[a] - lo[a]) * scl[a]))) >> (2 + drop[a]);
     gmax[a] = ((1 << nb[a]) >> drop[a]) - 1;
     w[a] = (float)(4 << drop[a]) / scl[a];  // cell width
     eps[a] = 2.5e-6f * ((float)(4 << nb[a]) / scl[a]);  // a point may sit outside its cell's nominal interval by a few ulps of the extent
@@ -1181,18 +1176,11 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   // workgroup, in LDS: 64 entries per axis)
   unsigned (*s_ctab)[64] = reinterpret_cast<unsigned (*)[64]>(s_raw);   // [3][64]
   if (threadIdx.x < 192) {
-    const int a = threadIdx.x >> 6, v = threadIdx.x & 63;
-    unsigned code = 0;
-    int rem = nb[a] - drop[a];
-    for (int s = 0; s < 12 - D; ++s)
-      if ((int)((sched >> (2 * s)) & 3u) == a && rem > 0) {
-        --rem;
-        code |= (unsigned)((v >> rem) & 1) << (11 - s);
-      }
-    s_ctab[a][v] = code;
+    const int a = threadIdx.x >> 6;
+    s_ctab[a][threadIdx.x & 63] = cell_deposit(g.sched, a, threadIdx.x & 63, kGridSteps - D, nc[a], kGridSteps - 1);
   }
   __syncthreads();
-  auto cell_code = [&](int ax, int ay, int az) { return s_ctab[0][ax & 63] | s_ctab[1][ay & 63] | s_ctab[2][az & 63]; };
+  auto tab_code = [&](int ax, int ay, int az) { return s_ctab[0][ax & 63] | s_ctab[1][ay & 63] | s_ctab[2][az & 63]; };
   KnnState<8> st;
 #pragma unroll
   for (int i = 0; i < 8; ++i) st.keys[i] = ~0ull;
@@ -1291,7 +1279,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     const int ay = cq[1] + dy - 2, az = cq[2] + dz - 2;
     if ((unsigned)ay > (unsigned)gmax[1] || (unsigned)az > (unsigned)gmax[2]) return;
     const float d2yz = axis_d2(1, dy - 2) + axis_d2(2, dz - 2);
-    const unsigned bityz = cell_code(0, ay, az);
+    const unsigned bityz = tab_code(0, ay, az);
     int beg[5], end[5];
 #pragma unroll
     for (int t = 0; t < 5; ++t)

@@ -12,6 +12,7 @@
 // Arithmetic that decides integer outputs (three_nn) is written with explicit, unfused roundings.
 #include <limits.h>
 
+#include "cell_grid.h"
 #include "common.h"
 #include "interp_walk.h"
 #include "keys.h"
@@ -191,6 +192,35 @@ __global__ __launch_bounds__(kBlock) void three_nn_kernel(int n, int m, const fl
 // candidates and the rest of the scan is the bare distance test.  Every candidate is still visited -- no pruning
 // structure, nothing to get wrong -- and equal distances resolve to the smallest candidate index explicitly, so ids
 // and distances are bit-identical to three_nn_kernel whatever the visiting order (tf_interpolate.cpp:66-96).
+// The 3-deep list as 64-bit keys (bits(d) << 32 | index), ascending: one insertion is three compares + selects, no branch.
+__device__ __forceinline__ void nn3_insert(unsigned long long x, unsigned long long &k1, unsigned long long &k2,
+                                           unsigned long long &k3) {
+  const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
+  k3 = l2 ? k2 : (l3 ? x : k3);
+  k2 = l1 ? k1 : (l2 ? x : k2);
+  k1 = l1 ? x : k1;
+}
+// The lists of waves 1..3 merged into wave 0's through s_mk (a workgroup barrier inside: every wave calls).
+__device__ __forceinline__ void nn3_merge_waves(unsigned long long (*s_mk)[3][64], int wave, int lane, unsigned long long &k1,
+                                                unsigned long long &k2, unsigned long long &k3) {
+  if (wave > 0) { s_mk[wave - 1][0][lane] = k1; s_mk[wave - 1][1][lane] = k2; s_mk[wave - 1][2][lane] = k3; }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int w = 0; w < 3; ++w)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) nn3_insert(s_mk[w][t][lane], k1, k2, k3);
+  }
+}
+// a query's three distances and ids, row = its place in the original order
+__device__ __forceinline__ void nn3_write(float *dist, int32_t *idx, size_t row, unsigned long long k1, unsigned long long k2,
+                                          unsigned long long k3) {
+  const size_t o = row * 3;
+  dist[o] = __uint_as_float((unsigned)(k1 >> 32)); dist[o + 1] = __uint_as_float((unsigned)(k2 >> 32));
+  dist[o + 2] = __uint_as_float((unsigned)(k3 >> 32));
+  idx[o] = (int)(unsigned)k1; idx[o + 1] = (int)(unsigned)k2; idx[o + 2] = (int)(unsigned)k3;
+}
+
 __global__ __launch_bounds__(kBlock) void three_nn_sorted_kernel(int n, int m, const float4 *__restrict__ qs,
                                                                 const float4 *__restrict__ cs,
                                                                 float *__restrict__ dist, int32_t *__restrict__ idx) {
@@ -264,36 +294,15 @@ __global__ __launch_bounds__(kBlock) void three_nn_sorted_kernel(int n, int m, c
         if (__any(valid && mn[u] <= __uint_as_float((unsigned)(k3 >> 32)))) {
 #pragma unroll
           for (int t = 0; t < 8; ++t) {
-            const unsigned long long x = ((unsigned long long)__float_as_uint(d[u][t >> 1][t & 1]) << 32) |
-                                         (unsigned)s_k[k + 8 * u + t];
-            const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
-            k3 = l2 ? k2 : (l3 ? x : k3);
-            k2 = l1 ? k1 : (l2 ? x : k2);
-            k1 = l1 ? x : k1;
+            nn3_insert(((unsigned long long)__float_as_uint(d[u][t >> 1][t & 1]) << 32) | (unsigned)s_k[k + 8 * u + t], k1, k2, k3);
           }
         }
       }
     }
   }
   __shared__ unsigned long long s_mk[3][3][64];  // partial lists of waves 1..3
-  if (wave > 0) { s_mk[wave - 1][0][lane] = k1; s_mk[wave - 1][1][lane] = k2; s_mk[wave - 1][2][lane] = k3; }
-  __syncthreads();
-  if (wave == 0 && valid) {
-#pragma unroll
-    for (int w = 0; w < 3; ++w)
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        const unsigned long long x = s_mk[w][t][lane];
-        const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
-        k3 = l2 ? k2 : (l3 ? x : k3);
-        k2 = l1 ? k1 : (l2 ? x : k2);
-        k1 = l1 ? x : k1;
-      }
-    const size_t o = ((size_t)b * n + __float_as_int(q.w)) * 3;
-    dist[o] = __uint_as_float((unsigned)(k1 >> 32)); dist[o + 1] = __uint_as_float((unsigned)(k2 >> 32));
-    dist[o + 2] = __uint_as_float((unsigned)(k3 >> 32));
-    idx[o] = (int)(unsigned)k1; idx[o + 1] = (int)(unsigned)k2; idx[o + 2] = (int)(unsigned)k3;
-  }
+  nn3_merge_waves(s_mk, wave, lane, k1, k2, k3);
+  if (wave == 0 && valid) nn3_write(dist, idx, (size_t)b * n + __float_as_int(q.w), k1, k2, k3);
 }
 
 // U 8-candidate sub-steps of the LDS image (cand4_slot coordinates in s_c, original indices in s_k) from candidate k on
@@ -337,12 +346,7 @@ __device__ __forceinline__ void nn3_scan(const float *s_c, const int *s_k, int k
     if (__any(valid && mn[u] <= kb)) {
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
-        const unsigned long long x = ((unsigned long long)__float_as_uint(d[u][t >> 1][t & 1]) << 32) |
-                                     (unsigned)s_k[k + 8 * u + t];
-        const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
-        k3 = l2 ? k2 : (l3 ? x : k3);
-        k2 = l1 ? k1 : (l2 ? x : k2);
-        k1 = l1 ? x : k1;
+        nn3_insert(((unsigned long long)__float_as_uint(d[u][t >> 1][t & 1]) << 32) | (unsigned)s_k[k + 8 * u + t], k1, k2, k3);
       }
       kb = fminf(kb, __uint_as_float((unsigned)(k3 >> 32)));
     }
@@ -452,24 +456,8 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel(int n, int m, c
     }
   }
 
-  if (wave > 0) { s_mk[wave - 1][0][lane] = k1; s_mk[wave - 1][1][lane] = k2; s_mk[wave - 1][2][lane] = k3; }
-  __syncthreads();
-  if (wave == 0 && valid) {
-#pragma unroll
-    for (int w = 0; w < 3; ++w)
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        const unsigned long long x = s_mk[w][t][lane];
-        const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
-        k3 = l2 ? k2 : (l3 ? x : k3);
-        k2 = l1 ? k1 : (l2 ? x : k2);
-        k1 = l1 ? x : k1;
-      }
-    const size_t o = ((size_t)b * n + __float_as_int(q.w)) * 3;
-    dist[o] = __uint_as_float((unsigned)(k1 >> 32)); dist[o + 1] = __uint_as_float((unsigned)(k2 >> 32));
-    dist[o + 2] = __uint_as_float((unsigned)(k3 >> 32));
-    idx[o] = (int)(unsigned)k1; idx[o + 1] = (int)(unsigned)k2; idx[o + 2] = (int)(unsigned)k3;
-  }
+  nn3_merge_waves(s_mk, wave, lane, k1, k2, k3);
+  if (wave == 0 && valid) nn3_write(dist, idx, (size_t)b * n + __float_as_int(q.w), k1, k2, k3);
 }
 
 // The pruned search with the candidates chosen through the sampled set's CELL TABLE (cells2 of dh3d_three_nn_cells: the
@@ -486,36 +474,21 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel(int n, int m, c
 //      (an unbounded r -- fewer than three candidates so far -- takes every cell: the whole set, what the boxes cost at
 //      worst).  (Per query, not the group's box widened by its largest r: the query with the largest r is seldom the one
 //      next to the edge of round 1's cells.)
-// Exactness.  nn3_cell is the sort's own expression (spatial.hip: (int)((x - lo) * scale), clamped, fine coordinate >> 2)
-// on the table's own origin and scales, and every step of it -- the subtraction, the product with a positive scale, the
-// truncation, the clamps, the shifts -- is monotone in x IN FLOAT ARITHMETIC: a sample with s.x >= t lies in a cell
-// >= nn3_cell(t), whatever was rounded.  A sample that belongs to a query's list has d <= the query's third distance <=
-// r^2, so |s.x - q.x| <= r (1 + 4 * 2^-24) on every axis: s.x >= q.x - r' for the inflated r' = r (1 + 1e-5), and the
-// margin subtracted on top covers the two roundings of (q.x - r') - margin.  The samples are inside the grid they were
-// binned on, so the clamps only ever act on the query side (a table of the sampled set's own grid: queries outside it reach
-// its border cells).  Lists only improve in round 2, so round 1's r stays valid.
+// Exactness.  grid_cell (cell_grid.h) is the sort's own expression on the table's own origin and scales, and monotone in x
+// IN FLOAT ARITHMETIC: a sample with s.x >= t lies in a cell >= grid_cell(t), whatever was rounded.  A sample that belongs
+// to a query's list has d <= the query's third distance <= r^2, so |s.x - q.x| <= r (1 + 4 * 2^-24) on every axis:
+// s.x >= q.x - r' for the inflated r' = r (1 + 1e-5), and the margin subtracted on top covers the two roundings of
+// (q.x - r') - margin.  The samples are inside the grid they were binned on, so the clamps only ever act on the query side
+// (a table of the sampled set's own grid: queries outside it reach its border cells).  Lists only improve in round 2, so
+// round 1's r stays valid.
 // The schedule steps dropped: a coarse cell should hold about two samples (512 coarse cells from 768 samples on: 2 x 2 x 2
 // cells of a cube's grid; 256 below), so that a query group looks up a few dozen ranges and a third distance seldom
 // exceeds the one coarse cell of margin.  (8 x 8192 vs 1024 / 32 x 4096 vs 512, uniform: D = 3 everywhere 16.5 / 28.2 us,
 // D = 4 everywhere 17.3 / 26.7 us, this rule 16.3 / 27.0 us -- profiles/three_nn_cells.txt.)
 constexpr int nn3_cell_drop(int m) { return m < 768 ? 4 : 3; }
-constexpr int kNNCoarse = 4096 >> 3;                // coarse cells of the grid at most
+constexpr int kNNCoarse = kGridCells >> 3;                // coarse cells of the grid at most
 constexpr int kNNDirect = 8;                        // records a cell's own lane copies (Poisson(2): 2e-4 hold more)
 constexpr int kNNCellCap = kNNChunk + 16;           // both rounds are padded to the sub-step: at most m + 14 slots
-
-__device__ __forceinline__ int nn3_cell(float p, float lo, float scl, int nb) {
-  // (the float clamp changes nothing inside the grid and keeps the conversion defined for a far or infinite p)
-  const float t = fminf(fmaxf((p - lo) * scl, 0.f), 1.0e6f);
-  return min((4 << nb) - 1, (int)t) >> 2;
-}
-
-__device__ __forceinline__ void nn3_insert(unsigned long long x, unsigned long long &k1, unsigned long long &k2,
-                                           unsigned long long &k3) {
-  const bool l1 = x < k1, l2 = x < k2, l3 = x < k3;
-  k3 = l2 ? k2 : (l3 ? x : k3);
-  k2 = l1 ? k1 : (l2 ? x : k2);
-  k1 = l1 ? x : k1;
-}
 
 template <int D>  // the schedule steps dropped: 2^D table cells are one coarse cell
 __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel_cells(int n, int m, const float4 *__restrict__ qs,
@@ -540,24 +513,18 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel_cells(int n, in
   const f32x2 qx = {q.x, q.x}, qy = {q.y, q.y}, qz = {q.z, q.z};
 
   // ---- the grid (the table's header) and the query group's box on it
-  const int *ct = cells + (size_t)b * DH3D_CELL_INTS;
-  const float *hd = reinterpret_cast<const float *>(ct) + 4100;
-  const unsigned sched = (unsigned)ct[4107];
-  int nb[3] = {0, 0, 0}, nc[3] = {0, 0, 0};  // grid bits per axis: all 12 steps | the coarse grid's 12 - D
-#pragma unroll
-  for (int s = 0; s < 12; ++s) {
-    const int a = (int)((sched >> (2 * s)) & 3u);
-    nb[0] += (int)(a == 0); nb[1] += (int)(a == 1); nb[2] += (int)(a == 2);
-    if (s < 12 - D) { nc[0] += (int)(a == 0); nc[1] += (int)(a == 1); nc[2] += (int)(a == 2); }
-  }
+  const CellGrid g = cell_grid(cells, b);
+  const int *ct = g.ct;
+  int nc[3];  // the coarse grid's bits per axis
+  sched_bits(g.sched, nc, kGridSteps - D);
   const float *qb = qbox + ((size_t)b * ((n + 63) / 64) + bx) * 8;
   const float ql[3] = {qb[0], qb[1], qb[2]}, qh[3] = {qb[4], qb[5], qb[6]};
   int lo1[3], hi1[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const int sh = nb[a] - nc[a];
-    lo1[a] = max((nn3_cell(ql[a], hd[a], hd[3 + a], nb[a]) >> sh) - 1, 0);
-    hi1[a] = min((nn3_cell(qh[a], hd[a], hd[3 + a], nb[a]) >> sh) + 1, (1 << nc[a]) - 1);
+    const int sh = g.nb[a] - nc[a];
+    lo1[a] = max((grid_cell(g, a, ql[a]) >> sh) - 1, 0);
+    hi1[a] = min((grid_cell(g, a, qh[a]) >> sh) + 1, (1 << nc[a]) - 1);
   }
 
   // The samples of the coarse cells [lo, hi] (outer: without round 1's) appended to the LDS image from slot `at` on, padded
@@ -580,17 +547,7 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel_cells(int n, in
         const int ix = lo[0] + t - tq * c0, iy = lo[1] + tq - (iz - lo[2]) * c1;
         const bool inner = ix >= lo1[0] && ix <= hi1[0] && iy >= lo1[1] && iy <= hi1[1] && iz >= lo1[2] && iz <= hi1[2];
         if (!(outer && inner)) {
-          unsigned code = 0;
-          int r0 = nc[0], r1 = nc[1], r2 = nc[2];
-#pragma unroll
-          for (int s = 0; s < 12 - D; ++s) {  // (the schedule is uniform: scalar branches)
-            const int a = (int)((sched >> (2 * s)) & 3u);
-            unsigned bit;
-            if (a == 0) bit = (unsigned)(ix >> --r0) & 1u;
-            else if (a == 1) bit = (unsigned)(iy >> --r1) & 1u;
-            else bit = (unsigned)(iz >> --r2) & 1u;
-            code |= bit << (11 - D - s);
-          }
+          const unsigned code = cell_code<D>(g.sched, nc, ix, iy, iz);
           beg = min(max(ct[code << D], 0), m);
           len = min(max(ct[(code + 1) << D], beg), m) - beg;
         }
@@ -643,28 +600,15 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel_cells(int n, in
   const unsigned long long kInf = (unsigned long long)__float_as_uint(INFINITY) << 32;
   unsigned long long k1 = kInf, k2 = kInf, k3 = kInf;
   float kb = INFINITY;  // the screen: the lane's third distance so far
-  auto merge_into_wave0 = [&]() __attribute__((always_inline)) {  // (behind a barrier that follows the other waves' stores)
-#pragma unroll
-    for (int w = 0; w < 3; ++w)
-#pragma unroll
-      for (int t = 0; t < 3; ++t) nn3_insert(s_mk[w][t][lane], k1, k2, k3);
-  };
-  auto write_out = [&]() __attribute__((always_inline)) {
-    const size_t o = ((size_t)b * n + __float_as_int(q.w)) * 3;
-    dist[o] = __uint_as_float((unsigned)(k1 >> 32)); dist[o + 1] = __uint_as_float((unsigned)(k2 >> 32));
-    dist[o + 2] = __uint_as_float((unsigned)(k3 >> 32));
-    idx[o] = (int)(unsigned)k1; idx[o + 1] = (int)(unsigned)k2; idx[o + 2] = (int)(unsigned)k3;
-  };
+  const size_t row = (size_t)b * n + __float_as_int(q.w);
 
   // ---- round 1.  (The sub-steps are dealt from a wave that turns with the query group: the waves of the workgroups of a CU
   // that share a SIMD do not all get the odd sub-step.)
   const int w0 = (wave - bx) & 3;
   const int pad1 = stage(lo1, hi1, false, 0);
   for (int k = 8 * w0; k < pad1; k += 32) nn3_scan<1>(s_c, s_k, k, valid, qx, qy, qz, k1, k2, k3, kb);
-  if (wave > 0) { s_mk[wave - 1][0][lane] = k1; s_mk[wave - 1][1][lane] = k2; s_mk[wave - 1][2][lane] = k3; }
-  __syncthreads();
+  nn3_merge_waves(s_mk, wave, lane, k1, k2, k3);
   if (wave == 0) {
-    merge_into_wave0();
     const float d3 = __uint_as_float((unsigned)(k3 >> 32));
     s_b[lane] = d3;
     // ---- the cells the lists can still reach: every query's own box [q - r, q + r], r = its third distance
@@ -674,11 +618,11 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel_cells(int n, in
     bool out = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const int sh = nb[a] - nc[a];
+      const int sh = g.nb[a] - nc[a];
       // (1e-18: a difference whose square underflows counts as distance zero)
       const float marg = r * 1e-5f + fabsf(qc[a]) * 1e-6f + 1e-18f;
-      lo2[a] = valid ? nn3_cell((qc[a] - r) - marg, hd[a], hd[3 + a], nb[a]) >> sh : lo1[a];
-      hi2[a] = valid ? nn3_cell((qc[a] + r) + marg, hd[a], hd[3 + a], nb[a]) >> sh : hi1[a];
+      lo2[a] = valid ? grid_cell(g, a, (qc[a] - r) - marg) >> sh : lo1[a];
+      hi2[a] = valid ? grid_cell(g, a, (qc[a] + r) + marg) >> sh : hi1[a];
       out = out || lo2[a] < lo1[a] || hi2[a] > hi1[a];
     }
     const bool more = __any(out);
@@ -697,7 +641,7 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel_cells(int n, in
   }
   __syncthreads();
   if (!s_box2[6]) {  // (workgroup-uniform)
-    if (wave == 0 && valid) write_out();
+    if (wave == 0 && valid) nn3_write(dist, idx, row, k1, k2, k3);
     return;
   }
 
@@ -707,12 +651,8 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel_cells(int n, in
   if (wave > 0) k1 = k2 = k3 = kInf;
   kb = s_b[lane];
   for (int k = pad1 + 8 * w0; k < pad1 + pad2; k += 32) nn3_scan<1>(s_c, s_k, k, valid, qx, qy, qz, k1, k2, k3, kb);
-  if (wave > 0) { s_mk[wave - 1][0][lane] = k1; s_mk[wave - 1][1][lane] = k2; s_mk[wave - 1][2][lane] = k3; }
-  __syncthreads();
-  if (wave == 0 && valid) {
-    merge_into_wave0();
-    write_out();
-  }
+  nn3_merge_waves(s_mk, wave, lane, k1, k2, k3);
+  if (wave == 0 && valid) nn3_write(dist, idx, row, k1, k2, k3);
 }
 
 // ------------------------------------------------------------------ three_interpolate

@@ -21,6 +21,7 @@
 //  path of both the kNN and the FPS.  The radix sort produces the identical order: stable by cell = (cell, index).)
 #include <math.h>
 
+#include "cell_grid.h"
 #include "common.h"
 #include "wave_ops.h"
 
@@ -28,7 +29,6 @@ namespace {
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = 16;
-constexpr int kCellInts = 4112;  // ints per cloud of the cell table (dh3d_spatial_sort_cells)
 
 __device__ __forceinline__ unsigned spread6(unsigned v) {  // 6 bits -> every third bit
   v &= 63u;
@@ -38,10 +38,6 @@ __device__ __forceinline__ unsigned spread6(unsigned v) {  // 6 bits -> every th
   return v;
 }
 constexpr unsigned kSchedCube = 0x186186u;  // z y x z y x ... : 2 1 0 repeated, step 0 in the low bits
-
-// Axis of step s of the 18-step bit schedule (step 0 = the code's most significant bit): the 12 grid steps from `sched`
-// (2 bits each), then z y x z y x.
-__device__ __forceinline__ int sched_axis(unsigned sched, int s) { return s < 12 ? (int)((sched >> (2 * s)) & 3u) : 2 - (s - 12) % 3; }
 
 // The 12 grid bits dealt by extent: every step goes to the axis whose cells are the widest so far (at most 6 per axis;
 // ties -- cell widths within 25 % of each other -- go to the highest axis first, so a (near-)cube gets z y x z y x ...).  nb[a] = grid bits of axis a.
@@ -65,11 +61,11 @@ __device__ __forceinline__ unsigned deal_grid_bits(const float ext[3], int nb[3]
   return sched;
 }
 
-// cells (may be NULL): per cloud kCellInts ints -- [0, 4096]: first sorted position of every grid cell in the order of
-// the cells' 12-bit codes (the top 12 bits of the sort key; an empty cell's entry = the next cell's), [4096] = N;
-// [4100..4105] as floats: the grid's origin (x, y, z) and the quantisation scale 2^(nb + 2) / extent per axis (a cell = 4
-// quantisation steps); [4107]: the bit schedule (12 x 2 bits, step 0 = the code's top bit) -- the grid the cell-list kNN
-// (knn.hip: knn_grid_kernel) searches.
+// cells (may be NULL): per cloud kCellInts ints, the slots of cell_grid.h -- [0, 4096]: first sorted position of every grid
+// cell in the order of the cells' 12-bit codes (the top 12 bits of the sort key; an empty cell's entry = the next cell's),
+// [4096] = N; [4100..4105] as floats: the grid's origin (x, y, z) and the quantisation scale 2^(nb + 2) / extent per axis (a
+// cell = 4 quantisation steps); [4107]: the bit schedule (12 x 2 bits, step 0 = the code's top bit).  The key computation
+// below is the expression cell_grid.h's grid_cell restates for the table's readers.
 template <int PPT>
 __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__restrict__ xyz, int N,
                                                                int npad, float4 *__restrict__ sorted,
@@ -122,25 +118,19 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
 #pragma unroll
   for (int a = 0; a < 3; ++a) scale[a] = (float)(4 << nb[a]) / fmaxf(ext[a], 1e-30f);  // nb + 2 bits per axis
   if (cells && tid == 0) {  // the grid's header, now: origin, scales and schedule need not stay in registers until the end
-    float *hd = reinterpret_cast<float *>(cells + (size_t)b * kCellInts) + 4100;
+    int *ct = cells + (size_t)b * kCellInts;
+    float *hd = reinterpret_cast<float *>(ct) + kCellHead;
     hd[0] = lo[0]; hd[1] = lo[1]; hd[2] = lo[2];
     hd[3] = scale[0]; hd[4] = scale[1]; hd[5] = scale[2];
-    reinterpret_cast<int *>(hd)[7] = (int)sched;
+    ct[kCellSched] = (int)sched;
   }
   // (near-)cubic clouds get the plain Morton code of rounds 1-4 from three bit-spreads; any other schedule goes through
   // per-axis deposit tables in LDS (a table build, a barrier and three look-ups per point: ~2.5 us at 8 x 8192)
   const bool cube = sched == kSchedCube;  // workgroup-uniform
   if (!cube) {
     if (tid < 768) {  // the three axes' deposit tables
-      const int a = tid >> 8, v = tid & 255;
-      unsigned code = 0;
-      int rem = nb[a] + 2;
-      for (int st = 0; st < 18; ++st)
-        if (sched_axis(sched, st) == a && rem > 0) {
-          --rem;
-          code |= (unsigned)((v >> rem) & 1) << (17 - st);
-        }
-      s_tab[tid] = code;
+      const int a = tid >> 8;
+      s_tab[tid] = cell_deposit(sched, a, tid & 255, 18, nb[a] + 2, 17);
     }
     __syncthreads();
   }
@@ -275,10 +265,10 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
         const int cur = (int)(s_keys[i] >> 20), prev = i > 0 ? (int)(s_keys[i - 1] >> 20) : -1;
         for (int c = prev + 1; c <= cur; ++c) ct[c] = i;
         if (i == N - 1)
-          for (int c = cur + 1; c <= 4096; ++c) ct[c] = N;
+          for (int c = cur + 1; c <= kGridCells; ++c) ct[c] = N;
       }
     }
-    // [4106]: is this cloud one for cell lists?  Not when its points crowd into far fewer cells than a uniform cloud of the
+    // [kCellFlag]: is this cloud one for cell lists?  Not when its points crowd into far fewer cells than a uniform cloud of the
     // same size would occupy (street scenes: ground plane + walls in a bounding box a tenth as high as wide; clusters) --
     // dh3d_knn_grid then runs the pruned scan of the Morton order for this cloud (tools/knn_scene_bench.py, 8 x 8192: cell
     // lists 30 us on a uniform cloud, 66 on a uniform 60 x 60 x 8 slab, 410 on a scene where the scan takes 190; occupied
@@ -296,7 +286,7 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
     __syncthreads();
     if (lane == 0) atomicAdd(&s_occupied, occupied);
     __syncthreads();
-    if (tid == 0) ct[4106] = s_occupied < occ_min ? 1 : 0;   // (the grid's header was written at the top)
+    if (tid == 0) ct[kCellFlag] = s_occupied < occ_min ? 1 : 0;   // (the grid's header was written at the top)
   }
 }
 
@@ -307,8 +297,8 @@ int sort_launch(const float *xyz, int B, int N, float4 *sorted, float *gbox, int
   if (npad < 64 * kWaves) npad = 64 * kWaves;  // one 64-key step per wave at least
   const size_t lds = sizeof(unsigned) * (2 * (size_t)npad + kWaves * 64 + 3 * 256) + sizeof(float) * 6 * kWaves;
   DH3D_ALLOW_BIG_LDS((spatial_sort_kernel<PPT>));
-  // fewer occupied cells than 0.6 x what a uniform cloud of N points leaves non-empty: not a cloud for cell lists (cells[4106])
-  const int occ_min = (int)(0.6 * 4096.0 * (1.0 - exp(-(double)N / 4096.0)));
+  // fewer occupied cells than 0.6 x what a uniform cloud of N points leaves non-empty: not a cloud for cell lists (cells[kCellFlag])
+  const int occ_min = (int)(0.6 * kGridCells * (1.0 - exp(-(double)N / kGridCells)));
   hipLaunchKernelGGL((spatial_sort_kernel<PPT>), dim3(B), dim3(kThreads), lds, s, xyz, N, npad, sorted, gbox, cells,
                      occ_min);
   return dh3d_launch_status();

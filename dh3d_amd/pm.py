@@ -31,7 +31,9 @@ def spatial_sort(xyz):
     return srt, gbox
 
 
-CELL_INTS = 4112  # include/dh3d_hip.h DH3D_CELL_INTS
+CELL_INTS = 4112   # include/dh3d_hip.h DH3D_CELL_INTS
+CELL_FLAG = 4106   # csrc/cell_grid.h kCellFlag: 1 = a crowded cloud, knn_grid serves it with the pruned scan
+CELL_SCHED = 4107  # csrc/cell_grid.h kCellSched: the grid's bit schedule (0x186186 = a cube's z y x z y x ...)
 
 
 def spatial_sort_cells(xyz):

@@ -357,7 +357,8 @@ int dh3d_knn_sorted(const float *sorted, const float *gbox, int B, int N, int K,
  *                 code from that axis' most significant cell-coordinate bit downwards.  0x186186 = z y x z y x ... (cube).
  * To decode cell code c into per-axis cell coordinates: walk s = 0..11, append bit (c >> (11 - s)) & 1 to the coordinate of
  * axis (sched >> 2s) & 3.  A table written by an ABI <= 3 sort (no schedule, scale 64 / extent) must not be handed to an
- * ABI 4 dh3d_knn_grid. */
+ * ABI 4 dh3d_knn_grid.  (The device-side definitions -- slots, header decode, cell map, cell code -- live in
+ * csrc/cell_grid.h.) */
 #define DH3D_CELL_INTS 4112
 int dh3d_spatial_sort_cells(const float *xyz, int B, int N, float *sorted, float *gbox, int32_t *cells, void *stream);
 

@@ -129,6 +129,40 @@ def test_kernels_equal_restatement_on_fresh_clouds(dev, case):
         _check("%s %s" % (case, kname), outs[kname], ref_idx, ref_cnt)
     if "grid" in outs:
         assert torch.equal(outs["grid"][0], outs["scan"][0]) and torch.equal(outs["grid"][1], outs["scan"][1])
+    if kind == "oxford_extent" and "grid" in outs:
+        # the table of a slab is no cube's and not crowded.  (These cases do not reach the cell walk with anything to find:
+        # one query with an empty ball, and a ball over the whole cloud -- test_cell_walk_on_a_grid_that_is_no_cube does.)
+        from dh3d_amd import pm
+        sort = pm.spatial_sort_cells(t1)
+        assert bool((sort[2][:, 4107] != 0x186186).all()) and bool((sort[2][:, 4106] == 0).all())
+        _check("%s grid, this table" % (case,), pm.ball_query_grid(radius, k, t1, t2, sort=sort), ref_idx, ref_cnt)
+
+
+def test_cell_walk_on_a_grid_that_is_no_cube(dev):
+    """The cell walk (flag 0, a box of at most 512 cells) on a 60 x 60 x 8 m slab: its schedule deals 5 + 5 + 2 bits, where a
+    cube's 4 + 4 + 4 hides a wrong axis, bit position or slot in the decode.  A ball of 1.5 m meets at most 3 x 3 x 3 of the
+    1.875 x 1.875 x 2 m cells.  Half the queries are points of the cloud (each finds itself at least), half lie uniformly
+    inside the slab: at 2048 / 28800 points per m^3 a 14.1 m^3 ball holds one point on average, so a walk that reads the
+    wrong cells loses hits that the restatement and the scan kernel have."""
+    from dh3d_amd import pm
+    b, n, m, k, r = 2, 2048, 64, 16, 1.5
+    rng = np.random.default_rng(6082)
+    x1 = np.ascontiguousarray(_knn_clouds("oxford_extent", b, n, rng), np.float32)
+    x2 = np.stack([x1[i, rng.permutation(n)[:m]] for i in range(b)])
+    x2[:, m // 2:] = _knn_clouds("oxford_extent", b, m - m // 2, rng)
+    x2 = np.ascontiguousarray(x2, np.float32)
+    ref_idx, ref_cnt = R.query_ball_point(r, k, x1, x2)
+    assert (ref_cnt[:, :m // 2] > 0).all() and (ref_cnt > 0).mean() > 0.7 and (ref_cnt > 1).mean() > 0.3
+    assert ref_cnt.max() < k                                  # no ball is cut short: every hit of every cell is in the row
+    t1, t2 = _t(x1, dev), _t(x2, dev)
+    sort = pm.spatial_sort_cells(t1)
+    assert bool((sort[2][:, 4107] != 0x186186).all()) and bool((sort[2][:, 4106] == 0).all())
+    scan = pm.ball_query_scan(r, k, t1, t2)
+    _check("slab scan", scan, ref_idx, ref_cnt)
+    for name, grid in (("slab grid, this table", pm.ball_query_grid(r, k, t1, t2, sort=sort)),
+                       ("slab grid", pm.ball_query_grid(r, k, t1, t2))):
+        _check(name, grid, ref_idx, ref_cnt)
+        assert torch.equal(grid[0], scan[0]) and torch.equal(grid[1], scan[1])
 
 
 def test_batch_of_eight_extents_crowded_and_coincident(dev):

@@ -192,6 +192,31 @@ def test_scan_and_grid_agree_where_the_cell_walk_gives_way(dev):
         _assert_same(reg.refine_icp(wide_a[:, :, :3], wide_y[:, :, :3], t(Rt0[None]), iterations=3, path=path), exp, path)
 
 
+@pytest.mark.parametrize("max_dist", [1.0, 4.0, 12.0])
+def test_scan_and_grid_agree_on_a_grid_that_is_no_cube(dev, max_dist):
+    """The cell walk on a table whose schedule is not a cube's 4 + 4 + 4 (which would hide a wrong axis or bit position in
+    the header's decode or the cell's code): a uniform 60 x 60 x 8 slab deals 5 + 5 + 2 bits, 32 x 32 x 4 cells of
+    1.875 x 1.875 x 2 m.  The box of +-1 m meets at most 27 of them and that of +-4 m at most 6 x 6 x 4 = 144, so both walk
+    the cells; at +-12 m most boxes meet more than 512 and take the 64-point groups (_box_cells counts them)."""
+    from dh3d_amd import pm, registration as reg
+    rng = np.random.default_rng(355)
+    P, Na, Nb = 2, 2048, 1000
+    A = (rng.random((P, Na, 3)) * (60, 60, 8) - (30, 30, 4)).astype(np.float32)
+    c, s = math.cos(math.radians(3.0)), math.sin(math.radians(3.0))
+    rot = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])
+    Y = (A[:, :Nb].astype(np.float64) @ rot.T + 0.3).astype(np.float32)     # the anchor's own points, turned and shifted
+    most = max(_box_cells(A[0], Y[0, j].astype(np.float64), max_dist) for j in range(0, Nb, 50))
+    assert (most > 512) == (max_dist == 12.0) and most > 8, most
+    t = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+    cells = pm.spatial_sort_cells(t(A))[2]                                  # (the table the cell lists build: no counts)
+    assert bool((cells[:, 4107] != 0x186186).all()) and bool((cells[:, 4106] == 0).all())
+    Rt0 = t(np.stack([EYE] * P))
+    scan = reg.refine_icp(t(A), t(Y), Rt0, max_dist=max_dist, iterations=2, path=1)
+    grid = reg.refine_icp(t(A), t(Y), Rt0, max_dist=max_dist, iterations=2, path=2)
+    _assert_same(grid, scan, max_dist)
+    assert int(scan["num_corr"].min()) > 300, scan["num_corr"]
+
+
 def test_the_limit_of_the_cell_lists(dev):
     from dh3d_amd import registration as reg
     demo = np.load(os.path.join(HERE, "golden", "demo_clouds.npz"))
