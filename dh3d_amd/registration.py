@@ -16,6 +16,8 @@ sampler replaces randsample, whose stream cannot be reproduced).
     nrm = estimate_normals(anchor_points, k=16)                               # PCA normals, curvature, the ids used
     res = refine_icp_plane(anchor_points, positive_points, res["Rt"], res["valid"])  # point-to-plane: + num_plane, rmse_plane
     res = register_clouds(model, anchor_points, positive_points, refine={"method": "plane", "iterations": 5})
+    f = compute_fpfh(anchor_points, k=32)                                     # fpfh [P, N, 36], counts, normals, nbr
+    res = register_fpfh(anchor_points, positive_points, refine=True)          # no model: normals -> FPFH -> match -> RANSAC -> ICP
     dt, ddeg = transform_errors(T_gt, res["Rt"], res["valid"])                # compareTransform, host float64
     summary = summarize_registration(dt, ddeg, res["inlier_ratio"], res["trials"])
 """
@@ -283,6 +285,140 @@ def refine_icp_plane(anchor_points, positive_points, Rt, valid=None, anchor_coun
         raise ValueError("anchor_normals must be [%d, %d, >=3] on %s, got %s on %s"
                          % (a.shape[0], a.shape[1], a.device, tuple(nrm.shape), nrm.device))
     return _icp_call(a, positive_points, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, nrm)
+
+
+FPFH_MAX_K, FPFH_COLS = 64, 36  # csrc/fpfh.hip kMaxK, kRow: 33 bins and three zero columns
+
+
+def _max_dist(max_dist, what):
+    d = 0.0 if max_dist is None else float(max_dist)
+    if max_dist is not None and not 0.0 < d < float("inf"):
+        raise ValueError("%s: max_dist must be None or positive and finite, got %r" % (what, max_dist))
+    return d
+
+
+def compute_fpfh(points, normals=None, num_valid=None, k=32, max_dist=None, nbr=None, ids=None, normals_k=16,
+                 viewpoint=(0., 0., 0.)):
+    """FPFH descriptors (Fast Point Feature Histograms, Rusu et al. 2009) from normals and neighbour lists: per point three
+    11-bin histograms of the angles between its normal, its neighbours' normals and the lines to them (stage 1, the SPFH
+    counts), then the 1 / d^2 weighted sum of the neighbours' histograms (stage 2); include/dh3d_hip.h dh3d_spfh_counts /
+    dh3d_fpfh state every rule.  points [P, N, >=3] float32 on the GPU (the first three columns are read; column views are
+    read in place), num_valid [P] int32 or None (all rows).  normals [P, N, >=3] float32, read in place and used as given
+    (zero normals take their pairs out of the histograms); None computes them with estimate_normals(points, num_valid,
+    normals_k, viewpoint).  nbr [P, N, K] int32, K <= 64: the neighbour ids of every point; None takes them from
+    utils.batched_knn(points, k), whose lists hold the point itself (it never pairs with itself) -- with padding far away
+    and at least k valid points no padded row enters a valid point's list, as estimate_normals says.  max_dist: None, or the
+    radius beyond which a listed neighbour is left out.  ids [P, M] int32 or None: the points to describe (keypoints); an id
+    outside 0 .. num_valid - 1 gives a zero row.  Returns a dict of device tensors: fpfh [P, M or N, 36] float32 (33 bins,
+    a block of 11 sums to 200 when the point and one of its near neighbours have usable pairs, to 100 when only one of the
+    two has, else to 0; columns 33-35 are zero so that match_descriptors reads the rows in place),
+    counts [P, N, 36] uint8 (the SPFH counts of every point, byte 33 the number of pairs), normals and nbr as used.  No host
+    sync: graph-capturable."""
+    x = _rows(points, "points", 3)
+    P, N = x.shape[:2]
+    dev = x.device
+    cnt = None if num_valid is None else _count(num_valid, "num_valid", P, dev)
+    r = _max_dist(max_dist, "compute_fpfh")
+    if N > ICP_MAX_POINTS:
+        raise ValueError("compute_fpfh: at most %d points per cloud, got %d" % (ICP_MAX_POINTS, N))
+    if nbr is None:
+        k = int(k)
+        if not 1 <= k <= FPFH_MAX_K:
+            raise ValueError("compute_fpfh: need 1 <= k <= %d, got %d" % (FPFH_MAX_K, k))
+        from .utils import batched_knn
+        with torch.cuda.device(dev):
+            nbr = batched_knn(x[:, :, :3].contiguous(), k)[0]
+    nbr = L.require_cuda_i32(nbr, "nbr", 3)
+    if nbr.shape[0] != P or nbr.shape[1] != N or nbr.device != dev or not 1 <= nbr.shape[2] <= FPFH_MAX_K:
+        raise ValueError("nbr must be int32 [%d, %d, 1..%d] on %s, got %s on %s"
+                         % (P, N, FPFH_MAX_K, dev, tuple(nbr.shape), nbr.device))
+    if normals is None:
+        normals = estimate_normals(x, cnt, normals_k, viewpoint)["normals"]
+    nrm = _rows(normals, "normals", 3)
+    if tuple(nrm.shape[:2]) != (P, N) or nrm.device != dev:
+        raise ValueError("normals must be [%d, %d, >=3] on %s, got %s on %s" % (P, N, dev, tuple(nrm.shape), nrm.device))
+    M = N
+    if ids is not None:
+        ids = L.require_cuda_i32(ids, "ids", 2)
+        if ids.shape[0] != P or ids.shape[1] < 1 or ids.shape[1] > ICP_MAX_POINTS or ids.device != dev:
+            raise ValueError("ids must be int32 [%d, 1..%d] on %s, got %s on %s"
+                             % (P, ICP_MAX_POINTS, dev, tuple(ids.shape), ids.device))
+        M = ids.shape[1]
+    K = nbr.shape[2]
+    counts = torch.empty((P, N, FPFH_COLS), dtype=torch.uint8, device=dev)
+    fpfh = torch.empty((P, M, FPFH_COLS), dtype=torch.float32, device=dev)
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        L.check(lib.dh3d_spfh_counts(L.ptr(x), x.stride(1), L.ptr(nrm), nrm.stride(1), L.ptr(cnt), L.ptr(nbr), P, N, K, r,
+                                     L.ptr(counts), L.stream_ptr()), "compute_fpfh (counts)")
+        L.check(lib.dh3d_fpfh(L.ptr(x), x.stride(1), L.ptr(cnt), L.ptr(nbr), L.ptr(counts), L.ptr(ids), P, N, K, M, r,
+                              L.ptr(fpfh), L.stream_ptr()), "compute_fpfh")
+    return dict(fpfh=fpfh, counts=counts, normals=nrm, nbr=nbr)
+
+
+def _fpfh_keypoints(x, cnt, keypoints, keypoint_ids, name):
+    """The keypoints of register_fpfh on one batch of clouds: (ids [P, M] int32 or None for all points, count [P] int32)."""
+    P, N = x.shape[:2]
+    dev = x.device
+    full = torch.full((P,), N, dtype=torch.int32, device=dev) if cnt is None else cnt.clamp(0, N)
+    if keypoint_ids is not None:
+        ids = L.require_cuda_i32(keypoint_ids, name + " keypoint_ids", 2)
+        if ids.shape[0] != P or ids.device != dev:
+            raise ValueError("%s keypoint_ids must be int32 [%d, M] on %s, got %s" % (name, P, dev, tuple(ids.shape)))
+        _check_m(ids.shape[1], name + " keypoint_ids")
+        return ids, (ids >= 0).sum(dim=1).to(torch.int32)       # (-1 padding at the tail, as batched_nms / FPS give it)
+    if keypoints is None and N <= KEYPOINT_MAX:
+        return None, full
+    M = KEYPOINT_MAX if keypoints is None else int(keypoints)
+    if M < 1:
+        raise ValueError("keypoints must be at least 1, got %r" % (keypoints,))
+    _check_m(M, name + " keypoints")
+    r = torch.arange(M, dtype=torch.int64, device=dev)
+    ids = ((r[None, :] * full[:, None].to(torch.int64)) // M).to(torch.int32)    # ids[p, r] = (r * n_p) // M, on the device
+    return ids, torch.where(full > 0, torch.full_like(full, M), torch.zeros_like(full))
+
+
+def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None, keypoint_ids=None, k=32, max_dist=None,
+                  refine=None, **ransac_kw):
+    """Registration of cloud pairs from geometry alone, no model and no weights: compute_fpfh on both batches (normals by
+    estimate_normals at k = 16, the k nearest neighbours of utils.batched_knn, max_dist as compute_fpfh's), match_descriptors
+    on the 36-column rows of the keypoints, ransac_rigid (its keywords threshold, confidence, max_trials, seed), and
+    refine_pose exactly as register_clouds wires it.  anchor_points [P, Na, >=3] and positive_points [P, Nb, >=3] float32 on
+    the GPU.  num_valid: None, one int32 [P] tensor for both batches, or a pair (anchor, positive).  The keypoints of a cloud:
+    every point when it has at most 4096 rows and nothing is asked; otherwise `keypoints` = M (default 4096) of them spread
+    over the valid rows, ids[p, r] = (r * n_p) // M, computed on the device; or the caller's keypoint_ids -- one int32 [P, M]
+    tensor or a pair (anchor, positive), e.g. farthest-point picks, -1 padded at the tail.  keypoints may be a pair too.
+    refine: None, True or a dict of refine_pose keywords, on the full clouds.  Returns register_clouds' keys: ransac_rigid's
+    dict plus match / dist (indices into the keypoint lists), and with refine Rt_ransac, fitness, rmse, num_corr_icp, nn (and
+    num_plane, rmse_plane); plus anchor_ids / positive_ids (the keypoint ids, None: all points).  No host sync."""
+    rkw = _refine_kw(refine)
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    nv, kp, kid = pair(num_valid), pair(keypoints), pair(keypoint_ids)
+    rows, cnts, idl = [], [], []
+    for s, (pts, name) in enumerate(((anchor_points, "anchor"), (positive_points, "positive"))):
+        x = _rows(pts, name + "_points", 3)
+        c = None if nv[s] is None else _count(nv[s], "num_valid", x.shape[0], x.device)
+        ids, kc = _fpfh_keypoints(x, c, kp[s], kid[s], name)
+        desc = compute_fpfh(x, None, c, k=k, max_dist=max_dist, ids=ids)["fpfh"]
+        if ids is None:
+            xyz = x
+        else:
+            from .pm import gather_rows
+            xyz = gather_rows(x[:, :, :3], ids, kc)
+        rows.append((xyz, desc))
+        cnts.append(kc)
+        idl.append(ids)
+    match, dist = match_descriptors(rows[0][1], cnts[0], rows[1][1], cnts[1])
+    out = ransac_rigid(rows[0][0], rows[1][0], match, cnts[0], **ransac_kw)
+    out["match"], out["dist"] = match, dist
+    out["anchor_ids"], out["positive_ids"] = idl
+    if rkw is not None:
+        icp = refine_pose(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv[0], positive_count=nv[1], **rkw)
+        out["Rt_ransac"], out["Rt"] = out["Rt"], icp["Rt"]
+        out["fitness"], out["rmse"], out["num_corr_icp"], out["nn"] = icp["fitness"], icp["rmse"], icp["num_corr"], icp["nn"]
+        if "rmse_plane" in icp:
+            out["num_plane"], out["rmse_plane"] = icp["num_plane"], icp["rmse_plane"]
+    return out
 
 
 def refine_pose(anchor_points, positive_points, Rt, valid=None, anchor_count=None, positive_count=None, method="point", **kw):

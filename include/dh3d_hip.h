@@ -1050,6 +1050,47 @@ int dh3d_icp_refine_plane(const float *anchor, long long anchor_stride, const in
                           double *rmse, int32_t *valid, int32_t *num_plane, double *rmse_plane, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* FPFH descriptors from given normals and neighbour lists (csrc/fpfh.hip) -- Fast Point Feature Histograms (Rusu, Blodow,
+ * Beetz, ICRA 2009): per point three 11-bin histograms of the angular features of its point pairs (the SPFH), then the
+ * 1 / d^2 weighted sum of its neighbours' SPFHs.  The reference tree holds no FPFH: the rule below is this project's own; it
+ * follows the published definition and the usual conventions (3 x 11 bins, weights 1 / d^2, blocks scaled to 100), and DESIGN.md
+ * lists every point where it had to choose (INFERRED).
+ * INPUTS: point i of cloud p at xyz + (p*N + i) * xyz_stride and its normal at normals + (p*N + i) * normals_stride (3 floats
+ *   each; the strides in elements, >= 3); normals are used as given, never normalised again.  n = clamp(count[p], 0, N); a
+ *   NULL count means N.  nbr [P, N, K] int32, 1 <= K <= 64: the neighbour ids of every point, from the caller's exact kNN (the
+ *   calls search nothing).  max_dist: <= 0 (or NaN) means no radius, else r2 = max_dist * max_dist.
+ * ARITHMETIC: float64 on the exact values of the float32 inputs, every operation rounded on its own.
+ *   dot(a, b) = (a_0*b_0 + a_1*b_1) + a_2*b_2; cross(a, b) = (a_1*b_2 - a_2*b_1, a_2*b_0 - a_0*b_2, a_0*b_1 - a_1*b_0);
+ *   sqrt is IEEE; atan2 is the device library's.
+ * PAIRS: for point i < n and k ascending, j = nbr[p, i, k]: d = x_j - x_i per axis, d2 = dot(d, d).  The pair is NEAR iff
+ *   0 <= j < n, j != i, d2 > 0 and (no radius or d2 <= r2).  A repeated id counts as often as it occurs.  A near pair is USABLE
+ *   iff dot(n_i, n_i) > 0, dot(n_j, n_j) > 0 and vn > 0 below.
+ * STAGE 1, dh3d_spfh_counts.  Per usable pair: len = sqrt(d2), a1 = dot(n_i, d) / len, a2 = dot(n_j, d) / len.  If |a1| < |a2|
+ *   then (n1, n2, d, f3) = (n_j, n_i, -d, -a2), else (n1, n2, d, f3) = (n_i, n_j, d, a1).  v = cross(d, n1), vn = sqrt(dot(v,
+ *   v)), v = v / vn per axis, w = cross(n1, v); f2 = dot(v, n2), f1 = atan2(dot(w, n2), dot(n1, n2)).  Bin coordinates s1 =
+ *   (f1 + pi) * (11 / (2 pi)), s2 = (f2 + 1) * 5.5, s3 = (f3 + 1) * 5.5 (pi the double nearest pi, 11 / (2 pi) = 11.0 /
+ *   (2.0 * pi) rounded as written); bin = min(max(floor(s), 0), 10).
+ *   OUTPUT counts [P, N, 36] uint8 (4-byte aligned): bytes 0-10 the f1 histogram, 11-21 f2, 22-32 f3, byte 33 m_i = the
+ *   number of usable pairs, bytes 34-35 zero.  Rows i >= n are all zero.  Every byte is written.  counts is an ordinary
+ *   output of the caller's, not scratch memory: dh3d_fpfh reads it.
+ * STAGE 2, dh3d_fpfh.  Output row r < M of cloud p describes point i = ids[p, r] (ids [P, M] int32), or i = r when ids is NULL
+ *   (then M must equal N); an i outside 0 .. n-1 gives a zero row.  SPFH(i)[c] = counts[i][c] * (100.0 / m_i) for c < 33, zero
+ *   when m_i = 0.  acc[c] starts from 0 and runs over the NEAR pairs of i in list order (usable or not; the lists, count and
+ *   max_dist must be stage 1's): acc[c] = acc[c] + (1.0 / d2) * SPFH(j)[c].  Per block t = 0, 1, 2 of 11 bins: S_t = the sum
+ *   of acc[11 t .. 11 t + 10] in ascending order from 0; scale_t = S_t > 0 ? 100.0 / S_t : 0.
+ *   OUTPUT fpfh [P, M, 36] float32: fpfh[c] = (float)(acc[c] * scale_t + SPFH(i)[c]) for c < 33; columns 33-35 are zero, so
+ *   dh3d_match_descriptors (D a multiple of 4) reads the rows in place.  Up to rounding a block sums to 200 when m_i > 0 and a near neighbour has m_j > 0, to 100
+ *   when only one of the two holds (a point without near pairs gets its own SPFH), else to 0.  Every element is written.
+ * A point's result does not depend on the batch or on the run.  NaN and infinite inputs are outside the contract.
+ * SIDE EFFECTS: one launch each on the caller's stream, no host sync, no allocation, no scratch buffer, no atomics on global
+ *   memory; graph-capturable.
+ * STATUS: NULL pointers (count and ids excepted), a counts pointer that is not 4-byte aligned, P / N / M <= 0, K < 1 or K > 64,
+ *   a stride below 3, ids NULL with M != N: DH3D_ERR_INVALID_ARGUMENT.  N or M > 131072, P > 65535: DH3D_ERR_UNSUPPORTED. */
+int dh3d_spfh_counts(const float *xyz, long long xyz_stride, const float *normals, long long normals_stride, const int32_t *count,
+                     const int32_t *nbr, int P, int N, int K, double max_dist, uint8_t *counts, void *stream);
+int dh3d_fpfh(const float *xyz, long long xyz_stride, const int32_t *count, const int32_t *nbr, const uint8_t *counts,
+              const int32_t *ids, int P, int N, int K, int M, double max_dist, float *fpfh, void *stream);
+
 /* Preparation of raw clouds (csrc/prepare.hip) -- get_fixednum_pcd(need_downsample = True, randsample = False)
  * (core/utils.py:87-110: open3d voxel_down_sample, remove_radius_outlier(nb_points, radius), crop to the points nearest the
  * centroid or pad), batched, for clouds of different sizes, with every size kept on the device.
