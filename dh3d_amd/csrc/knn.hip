@@ -1062,6 +1062,15 @@ DH3D_API int dh3d_knn_sorted(const float *sorted, const float *gbox, int B, int 
 // Same distances (reference rounding order, IEEE sqrt) and the same 64-bit (distance, CUB rank) order as every other
 // kernel of this file: ids and distance bits are identical.
 constexpr int kGridCap = 256;    // pooled candidates per query and pass (knn_grid_kernel)
+// A query's row of the pool in LDS, in 16-bit entries: kGridCap and one dword more.  At 128 dwords the rows of the eight
+// queries that share a 32-lane half start on one bank, and every drain access (slot i of each) is an 8-way conflict; at 129
+// consecutive queries sit on consecutive banks.
+constexpr int kGridRow = kGridCap + 2;
+// Pass 0's screened drain takes pools up to this size: the query's 512-byte row then holds 80 record indices (bytes 0..159,
+// replaced by the 16-bit ids as they are read) and behind them the 80 squared distances (bytes 160..479).  A multiple of
+// 4 x 4 lanes: a padded trip stays inside the row.  (Pools of a uniform 8192-point cube: 48 on average, 77 at most.)
+constexpr int kGridScreenCap = 80;
+static_assert(kGridScreenCap % 16 == 0 && kGridScreenCap * 6 <= kGridCap * 2, "the screened drain's row");
 
 __device__ __forceinline__ unsigned knn_spread4(unsigned v) {  // 4 bits -> every third bit (the sort's spread6 >> 6)
   return (v & 1u) | ((v & 2u) << 2) | ((v & 4u) << 4) | ((v & 8u) << 6);
@@ -1081,6 +1090,10 @@ __device__ __forceinline__ u64 knn_dpp_u64(u64 v) {
   return ((u64)(unsigned)hi << 32) | (unsigned)lo;
 }
 template <int CTRL>
+__device__ __forceinline__ int knn_dpp_i32(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+}
+template <int CTRL>
 __device__ __forceinline__ void knn_merge_step(KnnState<8> &st) {
   u64 c[8];
 #pragma unroll
@@ -1094,16 +1107,33 @@ __device__ __forceinline__ void knn_merge_step(KnnState<8> &st) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) st.keys[i] = c[i];
 }
-template <int L>
-__device__ __forceinline__ void knn_merge_sublanes(KnnState<8> &st) {
-  if (L >= 2) knn_merge_step<0xB1>(st);   // quad_perm [1,0,3,2]
-  if (L >= 4) knn_merge_step<0x4E>(st);   // quad_perm [2,3,0,1]
-  if (L >= 8) knn_merge_step<0x141>(st);  // row_half_mirror
+__device__ __forceinline__ void knn_bound_of_list(KnnState<8> &st) {
   const unsigned hb = (unsigned)(st.keys[7] >> 32);
   if (hb <= 0x7f800000u) {
     const float dk = __uint_as_float(hb);
     st.bound = __fmul_rn(__fmul_rn(dk, dk), 1.000001f);
   }
+}
+template <int L>
+__device__ __forceinline__ void knn_merge_sublanes(KnnState<8> &st) {
+  if (L >= 2) knn_merge_step<0xB1>(st);   // quad_perm [1,0,3,2]
+  if (L >= 4) knn_merge_step<0x4E>(st);   // quad_perm [2,3,0,1]
+  if (L >= 8) knn_merge_step<0x141>(st);  // row_half_mirror
+  knn_bound_of_list(st);
+}
+// The merge of a query whose lanes 1..L-1 started a pass with empty lists (keep_one_copy) and took nothing in it: lane 0's
+// list IS the merged one (its own insertions included), so the others copy it -- 16 permutes instead of two exchange
+// steps.  The same lists and the same bound as knn_merge_sublanes.  The choice is the wave's: one lane that took an entry
+// sends all of it through the merge.
+template <int L>
+__device__ __forceinline__ void knn_merge_after_sparse_pass(KnnState<8> &st, int sub) {
+  if (L != 4 || __any(sub != 0 && st.keys[0] != ~0ull)) {
+    knn_merge_sublanes<L>(st);
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) st.keys[i] = knn_dpp_u64<0x00>(st.keys[i]);  // quad_perm [0,0,0,0]
+  knn_bound_of_list(st);
 }
 
 // L = lanes per query (2, 4 or 8): fewer lanes = longer private candidate streams, but an insertion round serves 64 / L
@@ -1117,7 +1147,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
                                                       int32_t *__restrict__ nn, float *__restrict__ dist) {
   constexpr int QB = 256 / L;  // queries per workgroup
   static_assert(SF == 0 || (L == 4 && SF <= 4), "the merged scan: 64 queries per workgroup, at most four waves");
-  constexpr int kGridLds = 3 * 64 * 4 + QB * kGridCap * 2 + QB * 4;
+  constexpr int kGridLds = 3 * 64 * 4 + QB * kGridRow * 2 + QB * 4;
   constexpr int kSplitLds = SF == 2 ? 2 * knn_split_lds_bytes<2>() : SF > 0 ? knn_split_lds_bytes<(SF > 0 ? SF : 1)>() : 0;
   __shared__ __attribute__((aligned(16))) unsigned char s_raw[kGridLds > kSplitLds ? kGridLds : kSplitLds];
   const int b = blockIdx.y, lane = threadIdx.x & 63, sub = lane & (L - 1);
@@ -1232,8 +1262,8 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
       for (int i = 0; i < 8; ++i) st.keys[i] = ~0ull;
     }
   };
-  unsigned short (*s_list)[kGridCap] = reinterpret_cast<unsigned short (*)[kGridCap]>(s_raw + 3 * 64 * 4);   // [QB][kGridCap]
-  int *s_cnt = reinterpret_cast<int *>(s_raw + 3 * 64 * 4 + QB * kGridCap * 2);                                // [QB]
+  unsigned short (*s_list)[kGridRow] = reinterpret_cast<unsigned short (*)[kGridRow]>(s_raw + 3 * 64 * 4);   // [QB][kGridRow]
+  int *s_cnt = reinterpret_cast<int *>(s_raw + 3 * 64 * 4 + QB * kGridRow * 2);                                // [QB]
   const int qs = threadIdx.x / L;
   auto direct = [&](int j) {
     const float4 r = sc[j];
@@ -1248,10 +1278,111 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     for (int k = 0; k < fit; ++k) s_list[qs][off + k] = (unsigned short)(beg + k);
     for (int k = max(fit, 0); k < len; ++k) direct(beg + k);
   };
-  auto drain = [&]() {
+  auto lds_order = [&]() {  // (a row is wave-private and a wave's LDS operations complete in order: this pins the compiler)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const int total = min(s_cnt[qs], kGridCap);
+  };
+  // Pass 0's pool is ~48 candidates of which 8 are wanted, the list is empty and the bound infinite: offered one by one,
+  // every slot pays the square root, the rank code and the insertion (some lane of the wave always inserts).  So the pool
+  // is SCREENED first, on squared distances alone (the rule written out above knn_small_kernel):
+  //   sweep 1  every lane walks its share (records L apart, four loads in flight), keeps its two smallest s, m1 <= m2
+  //            (v_min semantics: a NaN never enters them), and leaves (s, 16-bit id) in the row -- the id over the record
+  //            index it has just read, s behind the indices;
+  //   U        = the largest m2 of the query's L lanes (two quad permutes): every lane saw two candidates, so at least
+  //            2 L >= 8 >= K candidates have s <= U and the K-th distance is at most sqrt(U).  thr = U * (1 + 2^-20):
+  //            anything above it has a strictly larger rounded distance than K others, whatever its rank code; equal
+  //            rounded distances from different s both stay and the rank orders them; U = 0 keeps exactly the copies.
+  //            A lane with fewer than two finite s (NaN coordinates) makes U = thr = +inf: everything is ranked, as before;
+  //   sweep 2  the survivors (s <= thr) are compacted IN PLACE, sixteen slots of the row per trip: a lane's place is the
+  //            query's count so far + a prefix over the quad (DPP, no atomic), which never passes the slots already read;
+  //   ranking  the query's lanes take the compacted survivors L apart -- ~13 of 48, ~3.6 insertion rounds per lane
+  //            instead of ~12.5 -- through the one knn_offer below.
+  // The choice is the WAVE's (16 queries), so that no wave runs both drains: it screens when every pool of its queries fits
+  // the row (T <= kGridScreenCap: nothing went down direct() then) and some pool is past two trips of the old drain
+  // (T > 32: below that the two sweeps cost what the insertions they save do).  A pool below 2 L in such a wave has a lane
+  // with fewer than two candidates: U = +inf, everything is ranked.  Any other wave -- a dense cell, an overflow, a coarse
+  // grid with short pools -- drains as before, below.  Returns the number of candidates the old drain has left to do.
+  auto drain_screened = [&]() __attribute__((always_inline)) {
+    const int T = s_cnt[qs];
+    if constexpr (L != 4) return min(T, kGridCap);
+    const bool screen = !__any(T > kGridScreenCap) && __any(T > 32);
+    const int ns = screen ? T : 0;
+    unsigned short *row = s_list[qs];
+    float *s2v = reinterpret_cast<float *>(row + kGridScreenCap);
+    float m1 = INFINITY, m2 = INFINITY;
+#pragma unroll 1
+    for (int k0 = 0; k0 < ns; k0 += 4 * L) {
+      float4 r[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) r[u] = sc[row[min(k0 + sub + u * L, ns - 1)]];
+      lds_order();  // (a padded slot reads the last index: before its owner replaces it)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = k0 + sub + u * L;
+        const float dx = r[u].x - q[0], dy = r[u].y - q[1], dz = r[u].z - q[2];
+        const float s = i < ns ? fmaf(dz, dz, fmaf(dy, dy, dx * dx)) : __builtin_nanf("");  // the reference's rounding order
+        m2 = s < m1 ? m1 : fminf(m2, s);
+        m1 = fminf(m1, s);
+        s2v[i] = s;
+        row[i] = (unsigned short)__float_as_int(r[u].w);  // (ids are below 16384)
+      }
+    }
+    float U = m2;
+    U = fmaxf(U, __int_as_float(knn_dpp_i32<0xB1>(__float_as_int(U))));  // quad_perm [1,0,3,2]
+    U = fmaxf(U, __int_as_float(knn_dpp_i32<0x4E>(__float_as_int(U))));  // quad_perm [2,3,0,1]
+    const float thr = __fmul_rn(U, 1.000001f);
+    lds_order();
+    int c = 0;  // survivors of the query so far
+#pragma unroll 1
+    for (int k0 = 0; k0 < ns; k0 += 4 * L) {
+      float s[4];
+      unsigned short id[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        s[u] = s2v[k0 + sub + u * L];
+        id[u] = row[k0 + sub + u * L];
+      }
+      lds_order();  // (all sixteen slots are read before one of them is written)
+      int n = 0, at[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        at[u] = n;
+        n += s[u] <= thr ? 1 : 0;  // (the NaN of a padded slot stays out)
+      }
+      // inclusive prefix over the quad (the permutes are taken by all four lanes, then selected: not under a branch)
+      const int n1 = knn_dpp_i32<0x90>(n);  // quad_perm [0,0,1,2]
+      int p = n + (sub >= 1 ? n1 : 0);
+      const int p2 = knn_dpp_i32<0x40>(p);  // quad_perm [0,0,0,1]
+      p += sub >= 2 ? p2 : 0;
+      const int first = c + p - n;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (s[u] <= thr) {
+          s2v[first + at[u]] = s[u];
+          row[first + at[u]] = id[u];
+        }
+      c += knn_dpp_i32<0xFF>(p);  // quad_perm [3,3,3,3]
+      lds_order();
+    }
+    // one entry ahead of the insertion; lanes past the end drop out (an entry read past c is stale and never offered)
+    float s_n = s2v[sub];
+    int id_n = row[sub];
+#pragma unroll 1
+    for (int j = sub; j < c; j += L) {
+      const float s = s_n;
+      const int id = id_n;
+      const int jn = min(j + L, kGridScreenCap - 1);
+      s_n = s2v[jn];
+      id_n = row[jn];
+      knn_offer<8, false>(st, s, id, lad);
+    }
+    return screen ? 0 : min(T, kGridCap);
+  };
+  auto drain = [&](auto screen) __attribute__((always_inline)) {
+    lds_order();
+    int total;
+    if constexpr (decltype(screen)::value) total = drain_screened();
+    else total = min(s_cnt[qs], kGridCap);
 #pragma unroll 1
     for (int base = sub; base < total; base += 4 * L) {
       float4 r[4];
@@ -1269,8 +1400,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
         knn_offer<8, false>(st, ok[u] ? s2 : __builtin_nanf(""), __float_as_int(r[u].w), lad);
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    lds_order();
   };
   // One column (dy, dz: offsets + 2) of the 5 x 5 x 5 block, the cells at the x offsets of TMASK: ranges of all of them in
   // flight together (no load under the per-cell branches), then the box tests and the pooling.
@@ -1330,9 +1460,24 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   // as the second's 98, and the two together two thirds of the kernel.
   // pass 0: shells 0-1 = the nine inner columns at dx in -1..1
   begin_pass();
+  if constexpr (L == 4) {
+    // nine columns over four lanes are 4 + 4 + 1: a third trip through the whole column body for one lane in four.  The
+    // ninth column (dy = dz = +1) goes cell by cell to lanes 0..2 instead; its ranges are asked for here, ahead of the two
+    // trips, and pooled behind them
+    const int ay = cq[1] + 1, az = cq[2] + 1;
+    const bool mine = sub < 3 && (unsigned)ay <= (unsigned)gmax[1] && (unsigned)az <= (unsigned)gmax[2];
+    const bool okc = sub == 0 ? okx[1] : sub == 1 ? okx[2] : okx[3];
+    const float d2c = (sub == 0 ? d2x[1] : sub == 1 ? d2x[2] : d2x[3]) + axis_d2(1, 1) + axis_d2(2, 1);
+    const unsigned code = tab_code(0, ay, az) | (sub == 0 ? bitx[1] : sub == 1 ? bitx[2] : bitx[3]);
+    const int beg9 = ct[mine ? code : 0], end9 = ct[mine ? code + span : 0];
 #pragma unroll 1
-  for (int ci = sub; ci < 9; ci += L) column(std::integral_constant<int, 0b01110>{}, 1 + ci % 3, 1 + ci / 3);
-  drain();
+    for (int ci = sub; ci < 8; ci += L) column(std::integral_constant<int, 0b01110>{}, 1 + ci % 3, 1 + ci / 3);
+    if (mine && okc && !(d2c * 0.99999f > st.bound)) enqueue(beg9, end9);
+  } else {
+#pragma unroll 1
+    for (int ci = sub; ci < 9; ci += L) column(std::integral_constant<int, 0b01110>{}, 1 + ci % 3, 1 + ci / 3);
+  }
+  drain(std::true_type{});
   knn_merge_sublanes<L>(st);
   // pass 1: every other cell the ball of the merged bound meets.  The K nearest neighbours all lie within the K-th distance
   // seen so far, so the cells to look at are a BOX with its own radius per axis -- two cells each way in a uniform cloud
@@ -1367,8 +1512,8 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     if (abs(dy) <= 1 && abs(dz) <= 1) column(std::integral_constant<int, 0b10001>{}, dy + 2, dz + 2);  // (dx in -1..1: pass 0)
     else column(std::integral_constant<int, 0b11111>{}, dy + 2, dz + 2);
   }
-  drain();
-  knn_merge_sublanes<L>(st);
+  drain(std::false_type{});
+  knn_merge_after_sparse_pass<L>(st, sub);  // (0.03 insertions per query in this pass on a uniform cloud)
   // What is left -- sparse corners, outliers, clusters that put everything into a few cells -- restarts against the bound
   // it has, over the 64-point groups of the Morton order whose box the search ball meets (the sort's group boxes): exact
   // (the list is emptied first, every point within the bound is offered again, nothing twice) and bounded: N / 64 box
