@@ -265,6 +265,8 @@ _SIGNATURES = {
                            c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_prob_sample": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_prob_sample_seeded": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_scan_context": [c_fp, c_ll, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_float, c_fp, c_fp, c_fp],
+    "dh3d_scan_context_distance": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp],
 }
 _RESTYPES = {
     "dh3d_arch": ctypes.c_char_p,

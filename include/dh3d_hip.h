@@ -1331,6 +1331,60 @@ int dh3d_prob_sample(int b, int n, int m, const float *inp_p, const float *inp_r
 int dh3d_prob_sample_seeded(int b, int n, int m, const float *inp_p, const int32_t *count, const unsigned long long *seed,
                             float *temp, int32_t *out, void *stream);
 
+/* Scan Context (csrc/scan_context.hip) -- Kim & Kim, "Scan Context: Egocentric Spatial Descriptor for Place Recognition
+ * within 3D Point Cloud Map", IROS 2018: a rings x sectors polar height image per cloud, a rotation-invariant ring key to
+ * short-list map places with (the exact top-k search of "Place retrieval" above takes it: Nr is a multiple of 4), and a
+ * column-shifted cosine distance whose best shift is the yaw between two clouds.  The reference tree holds no Scan Context:
+ * the rules below are this project's own statement of it, written so that the image is bit-defined.  No trained weights.
+ *
+ * THE IMAGE.  xyz holds P clouds of N rows, row i of cloud p at xyz + (p * N + i) * xyz_stride (stride in elements, >= 3: the
+ *   first three columns of wider rows are read in place).  count: NULL, or [P] int32 -- cloud p is its rows 0 .. n_p-1 with
+ *   n_p = clamp(count[p], 0, N) (NULL: N); rows at or beyond n_p are never read.  center: NULL (the origin), or [P, 2] float32
+ *   (cx, cy).  z_offset: the sensor's height above the ground, added so that heights are positive.
+ *   TABLES, made by the caller ONCE in float64 and read as they are -- no trigonometry and no division runs on the device, so
+ *   the kernel and any restatement that reads the same tables see identical bits:
+ *     sector_dir [Ns/2 - 1, 2] = (cos, sin)(2 pi k / Ns) for k = 1 .. Ns/2 - 1       ring_edge2 [Nr + 1] = (i * max_radius / Nr)^2
+ *   PER POINT (x, y, z):  dx = x - cx, dy = y - cy, h = z + z_offset, each rounded once in float32;  X, Y = dx, dy as float64;
+ *     r2 = X * X + Y * Y (two products, one addition).  The point COUNTS iff dx, dy and h are finite, r2 < ring_edge2[Nr] and
+ *     h > 0 strictly (-0.0 does not count: the bit pattern of every counted height orders as an unsigned integer).
+ *     RING    = the number of i in 1 .. Nr-1 with r2 >= ring_edge2[i].
+ *     HALF    H = 0 if Y > 0, or if Y == 0 and X > 0; otherwise H = 1 and (X, Y) is negated.  (The origin is H = 1.)
+ *     SECTOR  = H * Ns/2 + the number of k in 1 .. Ns/2-1 with c_k * Y - s_k * X >= 0: two products and a subtraction, each
+ *               rounded on its own (no fma contraction).  The count is what is defined, not the search that finds it.
+ *   OUTPUT desc [P, Nr, Ns] float32: a bin holds the maximum h of its counted points; an empty bin holds 0.  A maximum does
+ *     not depend on order, so desc is bit-defined.  A point reflected through the centre lands exactly Ns/2 sectors on.
+ *   OUTPUT ring_key [P, Nr] float32: the ring's mean, s = 0.0; for j ascending: s += (double)desc[p, r, j]; then
+ *     ring_key[p, r] = (float)(s / (double)Ns).  It does not change when the columns are rolled, up to the sum's rounding.
+ *   Every element of both outputs is written; a cloud's image does not depend on P or on the other clouds.
+ *
+ * THE DISTANCE.  qry [Q, Nr, Ns] and map [R, Nr, Ns] float32 images, contiguous.  map_count: NULL, or a device pointer to
+ *   one int32: the live map is rows 0 .. r-1 with r = clamp(*map_count, 0, R) (NULL: R); the host never learns r.
+ *   cand [Q, C] int32: the map ids to compare with each query (the id output of the top-k search, -1 past the map's end).
+ *   All arithmetic is float64.  For an image D and a column j, w_j = the sum over the rings of D[i, j]^2; the column is EMPTY
+ *   iff w_j == 0.  For a shift n in 0 .. Ns-1 take the j for which query column j and candidate column (j + n) % Ns are both
+ *   non-empty, m_n of them:
+ *     d_n = 1 - (1 / m_n) * sum over those j of dot(q_j, c_(j+n)) / sqrt(wq_j * wc_(j+n));      m_n == 0: d_n = 1.0 exactly
+ *   dist = the minimum of d_n and shift = the smallest n that attains it.  If the map cloud is the query cloud turned by
+ *   Rz(theta), shift = theta / (2 pi / Ns): place ~ Rz(2 pi shift / Ns) query.  The order of the sums inside a shift, and
+ *   whether a column is divided by its norm before or after the dot product, are FREE: dist is defined to rounding (a few
+ *   1e-16 per term, at most Ns unit-size terms), not to the bit; two images of zeros give exactly (1.0, 0).
+ *   A candidate id below 0, or at or above r, gives dist = +inf and shift = -1, and nothing of the map is read for it.
+ *   OUTPUTS dist [Q, C] float64, shift [Q, C] int32, and order [Q, C] int32: the slots 0 .. C-1 of query q sorted ascending
+ *   by (the dist this call wrote, the id in cand, the slot) -- a permutation.  Every element is written.  A query's row does
+ *   not depend on Q, on the other queries or on the run.
+ *
+ * BOTH: caller's stream, caller-owned outputs, no allocation, no synchronisation, no scratch memory of any kind;
+ *   graph-capturable (the image: three launches, one after the other, the first clears desc; the distance: one launch).
+ * STATUS, before anything is enqueued.  DH3D_ERR_INVALID_ARGUMENT: a NULL pointer (count, center and map_count excepted),
+ *   xyz_stride < 3, P, N, Q, R or C <= 0, C > 64, Nr outside 4 .. 32 or not a multiple of 4, Ns outside 8 .. 128 or not a
+ *   multiple of 4.  DH3D_ERR_UNSUPPORTED: N > 2^20, P > 65535, Q > 2^20, R > 2^24.
+ * NaN and infinite image values are outside the distance's contract (in a cloud they are simply not counted). */
+int dh3d_scan_context(const float *xyz, long long xyz_stride, const int32_t *count, const float *center,
+                      const double *sector_dir, const double *ring_edge2, int P, int N, int Nr, int Ns, float z_offset,
+                      float *desc, float *ring_key, void *stream);
+int dh3d_scan_context_distance(const float *qry, const float *map, const int32_t *map_count, const int32_t *cand, int Q, int R,
+                               int C, int Nr, int Ns, double *dist, int32_t *shift, int32_t *order, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
