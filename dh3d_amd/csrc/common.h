@@ -58,6 +58,15 @@ __device__ __forceinline__ T block_sum_256(T v, T *s_red) {
   return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
+// Folded training-mode BatchNorm coefficients: y = x * scale + shift with scale = gamma * rstd and shift = beta - mean *
+// scale in ONE rounding (explicit fmaf: contraction cannot differ between translation units).  Every pass of a site --
+// the finalize that stores (scale, shift) and the backward sums that only get (mean, rstd, gamma, beta) -- folds through
+// this, so all of them decide the ReLU gate fmaf(x, scale, shift) > 0 on the same bits.
+__device__ __forceinline__ void dh3d_bn_fold(float mean, float rstd, float gamma, float beta, float &scale, float &shift) {
+  scale = gamma * rstd;
+  shift = fmaf(-mean, scale, beta);
+}
+
 // Epilogue y = act(scale*(x+pre_bias)+shift), by value for kernels.
 struct EpilogueArgs {
   const float *pre_bias;

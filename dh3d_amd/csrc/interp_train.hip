@@ -136,6 +136,11 @@ __global__ __launch_bounds__(256) void interp_bn_kernel(const InterpBnArgs a) {
       q2 = *reinterpret_cast<const float4 *>(a.v2 + c); q3 = *reinterpret_cast<const float4 *>(a.v3 + c);
       wf = *reinterpret_cast<const float4 *>(a.wfc + c);
     }
+    float4 fsc = {}, fsh = {};  // MODE 1: the forward's folded (scale, shift) from (mean, rstd, gamma, beta)
+    if (MODE == 1) {
+      dh3d_bn_fold(q0.x, q1.x, q2.x, q3.x, fsc.x, fsh.x); dh3d_bn_fold(q0.y, q1.y, q2.y, q3.y, fsc.y, fsh.y);
+      dh3d_bn_fold(q0.z, q1.z, q2.z, q3.z, fsc.z, fsh.z); dh3d_bn_fold(q0.w, q1.w, q2.w, q3.w, fsc.w, fsh.w);
+    }
     __syncthreads();
 
     if (MODE == 0 || MODE == 1) {
@@ -157,12 +162,13 @@ __global__ __launch_bounds__(256) void interp_bn_kernel(const InterpBnArgs a) {
             A2.x = fmaf(h.x, h.x, A2.x); A2.y = fmaf(h.y, h.y, A2.y); A2.z = fmaf(h.z, h.z, A2.z); A2.w = fmaf(h.w, h.w, A2.w);
             (void)f;
           } else {
-            // xhat = (h - mean) rstd; y = xhat gamma + beta; dz = dlogit w_fc [y > 0]   (dlogit = 0 on padding points)
+            // xhat = (h - mean) rstd; y = h scale + shift (the apply walk's expression: one gate for both);
+            // dz = dlogit w_fc [y > 0]   (dlogit = 0 on padding points)
             const float dl = sw.w;
 #define DH3D_IB_SUMS(X)                                                                         \
   {                                                                                             \
     const float xh = (h.X - q0.X) * q1.X;                                                       \
-    const float y = fmaf(xh, q2.X, q3.X);                                                       \
+    const float y = fmaf(h.X, fsc.X, fsh.X);                                                    \
     const float dz = y > 0.f ? dl * wf.X : 0.f;                                                 \
     A1.X += dz; A2.X = fmaf(dz, xh, A2.X); A3.X = fmaf(dl, fmaxf(y, 0.f), A3.X);               \
   }

@@ -90,7 +90,8 @@ __global__ __launch_bounds__(256) void row_logit_kernel(const float *__restrict_
 }
 
 // backward sums.  dy == nullptr: dy[n,c] = rowscale[n] * colvec[c] (attention head) and S3[c] += rowscale[n] * y[n,c].
-// xhat = (x - mean) * rstd;  y = xhat * gamma + beta;  dz = relu ? dy * [y > 0] : dy
+// xhat = (x - mean) * rstd (for S2);  y = x * scale + shift with the forward's folded coefficients (dh3d_bn_fold: the same
+// bits as bn_finalize stored, so the gate is the forward's);  dz = relu ? dy * [y > 0] : dy
 __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float *__restrict__ x, const float *__restrict__ dy,
                                                          const float *__restrict__ rowscale,
                                                          const float *__restrict__ colvec, long long R, int C,
@@ -105,11 +106,14 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float *__restric
   const long long r0 = (long long)blockIdx.y * rows_per, r1 = min(R, r0 + rows_per);
   float a = 0.f, b = 0.f, d = 0.f;
   if (c < C) {
-    const float mu = mean[c], rs = rstd[c], g = gamma[c], be = beta[c], cvv = colvec ? colvec[c] : 0.f;
+    const float mu = mean[c], rs = rstd[c], cvv = colvec ? colvec[c] : 0.f;
+    float sc, sh;
+    dh3d_bn_fold(mu, rs, gamma[c], beta[c], sc, sh);
     for (long long r = r0 + q; r < r1; r += 4) {
       if (!row_live(mask, r, rows_per_cloud)) continue;
-      const float xh = (x[r * C + c] - mu) * rs;
-      const float y = fmaf(xh, g, be);
+      const float xv = x[r * C + c];
+      const float xh = (xv - mu) * rs;
+      const float y = fmaf(xv, sc, sh);
       float dz = dy ? dy[r * C + c] : rowscale[r] * cvv;
       if (relu && !(y > 0.f)) dz = 0.f;
       a += dz; b = fmaf(dz, xh, b);
@@ -216,7 +220,8 @@ __global__ __launch_bounds__(256) void bn_small_kernel(const float *__restrict__
     double var = Bq / n - m * m;
     var = var > 0.0 ? var : 0.0;
     rs = (float)(1.0 / sqrt(var + (double)eps));
-    sc = gamma[c] * rs; mu = (float)m; sh = beta[c] - mu * sc;
+    mu = (float)m;
+    dh3d_bn_fold(mu, rs, gamma[c], beta[c], sc, sh);
     if (q == 0) {
       stats[c] = mu; stats[C + c] = rs; stats[2 * C + c] = sc; stats[3 * C + c] = sh;
       if (s_n > 0) {
@@ -267,8 +272,9 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double *__restri
   double var = s2 / n - mu * mu;
   var = var > 0.0 ? var : 0.0;
   const float rs = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * rs;
-  mean[c] = (float)mu; rstd[c] = rs; scale[c] = sc; shift[c] = beta[c] - (float)mu * sc;
+  float sc, sh;
+  dh3d_bn_fold((float)mu, rs, gamma[c], beta[c], sc, sh);
+  mean[c] = (float)mu; rstd[c] = rs; scale[c] = sc; shift[c] = sh;
   if (cnt[0] > 0.0) {
     run_mean[c] = momentum * run_mean[c] + (1.f - momentum) * (float)mu;
     const double uv = unbiased && n > 1.0 ? var * (n / (n - 1.0)) : var;

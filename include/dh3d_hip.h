@@ -691,7 +691,9 @@ int dh3d_colsum_f32(const float *x, long long R, int C, int accumulate, float *o
  *   scale_shift_act: y = act(x*scale[c] + shift[c])   (relu = 0/1; y may alias x)
  *   row_logit_sigmoid: att[r] = sigmoid(sum_c relu(h*scale+shift)[r,c] w[c] + b)    (attention head, backbones.py:170-173)
  *   bn_colstats    : sum / sumsq [C] f64 += column sums of x over the live rows (zeroed by the CALLER)
- *   bn_bwd_sums    : (S1, S2, S3 zeroed by the CALLER) S1 = sum dz, S2 = sum dz*xhat with xhat = (x-mean)*rstd, dz = dy masked by relu(xhat*gamma+beta) > 0;
+ *   bn_bwd_sums    : (S1, S2, S3 zeroed by the CALLER) S1 = sum dz, S2 = sum dz*xhat with xhat = (x-mean)*rstd, dz = dy masked by
+ *                    x*scale+shift > 0 -- the forward's own float32 expression, (scale, shift) folded from (mean, rstd, gamma, beta) exactly
+ *                    as bn_finalize folds them, so forward, sums and apply agree on every gate bit for bit;
  *                    dy == NULL: dy[r,c] = rowscale[r]*colvec[c] (rank one) and S3[c] = sum_r rowscale[r]*y[r,c]
  *   bn_finalize    : (sum, sumsq, count) -> mean, rstd, scale = gamma*rstd, shift = beta - mean*scale; running buffers
  *                    <- momentum*old + (1-momentum)*batch statistic (untouched when count == 0)
@@ -771,7 +773,7 @@ int dh3d_context_gate_bwd(const float *v, const float *g, const float *dy, long 
  *              sums over B -> dh3d_bn_finalize
  *   forward  : dh3d_interp_head_sorted_fwd with the folded batch statistics as its epilogue
  *   bwd_sums : per-cloud partials part [3][B][Hd] f64 (zeroed by the CALLER) of S1, S2, S3 of dh3d_bn_bwd_sums for dy = dlogit x w_fc (dlogit [B*n]
- *              by original point index)
+ *              by original point index); the gate is bwd_apply's h*scale+shift > 0 on the same folded coefficients
  *   bwd_apply: dG [Hd/256][B*m][256] = interp^T(scale dz - k2 - k3 h) (zeroed by the CALLER, f32 atomics), from which
  *              dW = coarse^T dG and dcoarse = dG W^T are GEMMs on B*m rows.  Hd <= 1024, m <= 1024. */
 int dh3d_interp_bn_colstats(const float *G, int Hd, int row_major, const int32_t *idx, const float *dist,
