@@ -244,6 +244,9 @@ _SIGNATURES = {
     "dh3d_icp_refine_plane_ws_bytes": [c_int, c_int, c_int],
     "dh3d_icp_refine_plane": [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_double, c_int,
                               c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp],
+    "dh3d_icp_refine_gicp_ws_bytes": [c_int, c_int, c_int],
+    "dh3d_icp_refine_gicp": [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_double,
+                             c_int, c_int, c_double, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_size_t, c_fp],
     "dh3d_spfh_counts": [c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_int, c_int, c_int, c_double, c_fp, c_fp],
     "dh3d_fpfh": [c_fp, c_ll, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_double, c_fp, c_fp],
     "dh3d_prepare_clouds_workspace": [c_int, c_int, c_int],
@@ -286,6 +289,7 @@ _RESTYPES = {
     "dh3d_keypoint_nms_workspace_bytes": c_size_t,
     "dh3d_icp_refine_ws_bytes": c_size_t,
     "dh3d_icp_refine_plane_ws_bytes": c_size_t,
+    "dh3d_icp_refine_gicp_ws_bytes": c_size_t,
     "dh3d_prepare_clouds_workspace": c_size_t,
     "dh3d_retrieve_ws_bytes": c_size_t,
     "dh3d_resample_clouds_ws_bytes": c_size_t,

@@ -39,6 +39,13 @@
 //                           6 x 6 system by Cholesky in registers and composes the step with the pose.  Fewer than 6 pairs or
 //                           a refused pivot leave the pose.  224 VGPRs, no scratch; one workgroup per pair as icp_fit_kernel.
 //   icp_plane_stats_kernel  num_plane and rmse_plane.
+// Generalized / plane-to-plane (dh3d_icp_refine_gicp): the same launches with a third fit and its two outputs.
+//   icp_gicp_fit_kernel     one 256-lane workgroup per pair: every pair of nn, weighted by M = (C_A + C_B)^-1 of the two
+//                           normals' covariances (closed-form 3 x 3 inverse per pair), 21 + 6 float64 sums of H = sum J^T M J
+//                           and g = sum J^T M d reduced in ONE LDS pass (block_sums_256: the tree of block_sum_256 for all 27
+//                           behind two barriers, where the plane kernel pays 27 pairs), then icp_solve_compose, the plane
+//                           fit's Cholesky and composition.  138 VGPRs, no scratch, 864 bytes of LDS.
+//   icp_gicp_stats_kernel   num_planar and rmse_gicp.  60 VGPRs, no scratch.
 // Compiled without contraction (csrc/Makefile EXACT): the ids depend on every rounding of d2.
 #include <math.h>
 
@@ -334,69 +341,11 @@ __device__ __forceinline__ bool icp_plane_pair(const float *nr, double *n) {
   return (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2] > 0.0;
 }
 
-// One 256-lane workgroup per pair (include/dh3d_hip.h dh3d_icp_refine_plane F_plane): the centroid c of the moved positives
-// of the pairs, then the 21 + 6 float64 sums of H = sum a a^T and g = sum a r over a = [(m - c) x n ; n], r = n . (x - m),
-// each lane over its j in ascending order and a fixed tree; lane 0 solves H s = g by Cholesky (registers: every index is a
-// constant after unrolling) and composes the step with the pose.  Fewer than 6 pairs or a refused pivot leave the pose.
-__global__ __launch_bounds__(kThreads) void icp_plane_fit_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
-                                                                 const float *__restrict__ normals, long long n_stride,
-                                                                 const float *__restrict__ positive, long long b_stride, int Nb,
-                                                                 const int32_t *__restrict__ b_count,
-                                                                 const int32_t *__restrict__ nn, double *__restrict__ pose) {
-  __shared__ double s_red[kThreads / 64];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
-  const float *pa = anchor + (long long)p * Na * a_stride, *pn = normals + (long long)p * Na * n_stride;
-  const float *pb = positive + (long long)p * Nb * b_stride;
-  const int32_t *row = nn + (long long)p * Nb;
-  double rt[12];
-#pragma unroll
-  for (int e = 0; e < 12; ++e) rt[e] = pose[(long long)p * 12 + e];
-  double cnt = 0.0, sm[3] = {0.0, 0.0, 0.0};
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    double n[3], m[3];
-    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
-      const float *y = pb + (long long)j * b_stride;
-      icp_move(rt, y[0], y[1], y[2], m);
-      cnt += 1.0;
-      sm[0] += m[0]; sm[1] += m[1]; sm[2] += m[2];
-    }
-  }
-  const int npl = (int)block_sum_256<double>(cnt, s_red);
-  if (npl < 6) return;  // the pose stays as it was (workgroup-uniform)
-  double c[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) c[r] = block_sum_256<double>(sm[r], s_red) / (double)npl;
-  double H[21], g[6];  // H: the upper triangle, row by row
-#pragma unroll
-  for (int e = 0; e < 21; ++e) H[e] = 0.0;
-#pragma unroll
-  for (int e = 0; e < 6; ++e) g[e] = 0.0;
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    double n[3], m[3];
-    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
-      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
-      icp_move(rt, y[0], y[1], y[2], m);
-      const double q0 = m[0] - c[0], q1 = m[1] - c[1], q2 = m[2] - c[2];
-      const double a[6] = {q1 * n[2] - q2 * n[1], q2 * n[0] - q0 * n[2], q0 * n[1] - q1 * n[0], n[0], n[1], n[2]};
-      const double dx = (double)x[0] - m[0], dy = (double)x[1] - m[1], dz = (double)x[2] - m[2];
-      const double res = (dx * n[0] + dy * n[1]) + dz * n[2];
-      int e = 0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-#pragma unroll
-        for (int k = r; k < 6; ++k) H[e++] += a[r] * a[k];
-        g[r] += a[r] * res;
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 21; ++e) H[e] = block_sum_256<double>(H[e], s_red);
-#pragma unroll
-  for (int e = 0; e < 6; ++e) g[e] = block_sum_256<double>(g[e], s_red);
-  if (tid != 0) return;
+// The end of F_plane and F_gicp, one lane: H s = g by Cholesky (H: the upper triangle, row by row; registers: every index is
+// a constant after unrolling), then the step composed with the pose rt about the centroid c.  A refused pivot or a
+// non-finite s leaves `out` as it was.
+__device__ __forceinline__ void icp_solve_compose(const double *H, const double *g, const double *rt, const double *c,
+                                                  double *out) {
   // Cholesky H = L L^T, row by row; L[k][j] lives at L[k * 6 + j]
   double L[36], big = 0.0;
   {
@@ -460,7 +409,6 @@ __global__ __launch_bounds__(kThreads) void icp_plane_fit_kernel(const float *__
   for (int e = 0; e < 6; ++e) fin = fin && isfinite(s[e]);
   if (!fin) return;
   const double u[3] = {rt[3] - c[0], rt[7] - c[1], rt[11] - c[2]};
-  double *out = pose + (long long)p * 12;
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
 #pragma unroll
@@ -468,6 +416,71 @@ __global__ __launch_bounds__(kThreads) void icp_plane_fit_kernel(const float *__
       out[4 * r + k] = (dR[3 * r] * rt[k] + dR[3 * r + 1] * rt[4 + k]) + dR[3 * r + 2] * rt[8 + k];
     out[4 * r + 3] = (((dR[3 * r] * u[0] + dR[3 * r + 1] * u[1]) + dR[3 * r + 2] * u[2]) + c[r]) + s[3 + r];
   }
+}
+
+// One 256-lane workgroup per pair (include/dh3d_hip.h dh3d_icp_refine_plane F_plane): the centroid c of the moved positives
+// of the pairs, then the 21 + 6 float64 sums of H = sum a a^T and g = sum a r over a = [(m - c) x n ; n], r = n . (x - m),
+// each lane over its j in ascending order and a fixed tree; lane 0 solves H s = g by Cholesky (registers: every index is a
+// constant after unrolling) and composes the step with the pose.  Fewer than 6 pairs or a refused pivot leave the pose.
+__global__ __launch_bounds__(kThreads) void icp_plane_fit_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
+                                                                 const float *__restrict__ normals, long long n_stride,
+                                                                 const float *__restrict__ positive, long long b_stride, int Nb,
+                                                                 const int32_t *__restrict__ b_count,
+                                                                 const int32_t *__restrict__ nn, double *__restrict__ pose) {
+  __shared__ double s_red[kThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  const float *pa = anchor + (long long)p * Na * a_stride, *pn = normals + (long long)p * Na * n_stride;
+  const float *pb = positive + (long long)p * Nb * b_stride;
+  const int32_t *row = nn + (long long)p * Nb;
+  double rt[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) rt[e] = pose[(long long)p * 12 + e];
+  double cnt = 0.0, sm[3] = {0.0, 0.0, 0.0};
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    double n[3], m[3];
+    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
+      const float *y = pb + (long long)j * b_stride;
+      icp_move(rt, y[0], y[1], y[2], m);
+      cnt += 1.0;
+      sm[0] += m[0]; sm[1] += m[1]; sm[2] += m[2];
+    }
+  }
+  const int npl = (int)block_sum_256<double>(cnt, s_red);
+  if (npl < 6) return;  // the pose stays as it was (workgroup-uniform)
+  double c[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) c[r] = block_sum_256<double>(sm[r], s_red) / (double)npl;
+  double H[21], g[6];  // H: the upper triangle, row by row
+#pragma unroll
+  for (int e = 0; e < 21; ++e) H[e] = 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) g[e] = 0.0;
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    double n[3], m[3];
+    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
+      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
+      icp_move(rt, y[0], y[1], y[2], m);
+      const double q0 = m[0] - c[0], q1 = m[1] - c[1], q2 = m[2] - c[2];
+      const double a[6] = {q1 * n[2] - q2 * n[1], q2 * n[0] - q0 * n[2], q0 * n[1] - q1 * n[0], n[0], n[1], n[2]};
+      const double dx = (double)x[0] - m[0], dy = (double)x[1] - m[1], dz = (double)x[2] - m[2];
+      const double res = (dx * n[0] + dy * n[1]) + dz * n[2];
+      int e = 0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) {
+#pragma unroll
+        for (int k = r; k < 6; ++k) H[e++] += a[r] * a[k];
+        g[r] += a[r] * res;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 21; ++e) H[e] = block_sum_256<double>(H[e], s_red);
+#pragma unroll
+  for (int e = 0; e < 6; ++e) g[e] = block_sum_256<double>(g[e], s_red);
+  if (tid == 0) icp_solve_compose(H, g, rt, c, pose + (long long)p * 12);
 }
 
 // num_plane and rmse_plane of the last association under the returned pose (the sums in the fit's order)
@@ -505,6 +518,174 @@ __global__ __launch_bounds__(kThreads) void icp_plane_stats_kernel(const float *
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------ gicp fit
+// N block sums at once, each by block_sum_256's tree (the wave's xor butterfly 32 .. 1, then ((w0 + w1) + w2) + w3), behind
+// one pair of barriers instead of N.  s_red holds 4 * N doubles.
+template <int N>
+__device__ __forceinline__ void block_sums_256(double *v, double *s_red) {
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[e] += __shfl_xor(v[e], off, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) s_red[4 * e + wave] = v[e];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < N; ++e) v[e] = s_red[4 * e] + s_red[4 * e + 1] + s_red[4 * e + 2] + s_red[4 * e + 3];
+}
+
+// What a pair of the generalized fit carries (include/dh3d_hip.h dh3d_icp_refine_gicp F_gicp, steps 3 to 5): the weight matrix
+// M = (C_A + C_B)^-1 as its six entries 00 01 02 11 12 22, and whether both normals are non-zero.
+struct GicpPair {
+  double M[6];
+  bool planar;
+};
+
+// C = I - f v v^T as the entries 00 01 02 11 12 22, f = (1 - epsilon) / (v . v) or 0 for a zero v; returns v . v > 0
+__device__ __forceinline__ bool gicp_cov(double v0, double v1, double v2, double one_m_eps, double *C) {
+  const double s = (v0 * v0 + v1 * v1) + v2 * v2;
+  const double f = s > 0.0 ? one_m_eps / s : 0.0;
+  const double a0 = f * v0, a1 = f * v1, a2 = f * v2;
+  C[0] = 1.0 - a0 * v0; C[1] = 0.0 - a0 * v1; C[2] = 0.0 - a0 * v2;
+  C[3] = 1.0 - a1 * v1; C[4] = 0.0 - a1 * v2; C[5] = 1.0 - a2 * v2;
+  return s > 0.0;
+}
+
+__device__ __forceinline__ GicpPair gicp_pair(const float *na, const float *kb, const double *rt, double one_m_eps) {
+  double CA[6], CB[6], W[6], u[3];
+  const double k0 = kb[0], k1 = kb[1], k2 = kb[2];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) u[r] = (rt[4 * r] * k0 + rt[4 * r + 1] * k1) + rt[4 * r + 2] * k2;
+  const bool pa = gicp_cov(na[0], na[1], na[2], one_m_eps, CA);
+  const bool pb = gicp_cov(u[0], u[1], u[2], one_m_eps, CB);
+#pragma unroll
+  for (int e = 0; e < 6; ++e) W[e] = CA[e] + CB[e];
+  // W = [[0 1 2], [1 3 4], [2 4 5]]; M = adj(W) / det(W)
+  const double c00 = W[3] * W[5] - W[4] * W[4], c01 = W[2] * W[4] - W[1] * W[5], c02 = W[1] * W[4] - W[2] * W[3];
+  const double c11 = W[0] * W[5] - W[2] * W[2], c12 = W[1] * W[2] - W[0] * W[4], c22 = W[0] * W[3] - W[1] * W[1];
+  const double det = (W[0] * c00 + W[1] * c01) + W[2] * c02;
+  GicpPair g;
+  g.M[0] = c00 / det; g.M[1] = c01 / det; g.M[2] = c02 / det;
+  g.M[3] = c11 / det; g.M[4] = c12 / det; g.M[5] = c22 / det;
+  g.planar = pa && pb;
+  return g;
+}
+
+// One 256-lane workgroup per pair (include/dh3d_hip.h dh3d_icp_refine_gicp F_gicp): the centroid c of the moved positives of
+// all pairs, then per pair the weight matrix M and the 21 + 6 float64 sums of H = sum J^T M J and g = sum J^T M d, each
+// lane over its j in ascending order; all 27 reduced in one LDS pass (block_sums_256); lane 0 solves and composes as the
+// plane fit does.  Fewer than 3 pairs or a refused pivot leave the pose.
+__global__ __launch_bounds__(kThreads) void icp_gicp_fit_kernel(
+    const float *__restrict__ anchor, long long a_stride, int Na, const float *__restrict__ a_normals, long long an_stride,
+    const float *__restrict__ positive, long long b_stride, int Nb, const float *__restrict__ b_normals, long long bn_stride,
+    const int32_t *__restrict__ b_count, const int32_t *__restrict__ nn, double one_m_eps, double *__restrict__ pose) {
+  __shared__ double s_red[27 * (kThreads / 64)];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  const float *pa = anchor + (long long)p * Na * a_stride, *pan = a_normals + (long long)p * Na * an_stride;
+  const float *pb = positive + (long long)p * Nb * b_stride, *pbn = b_normals + (long long)p * Nb * bn_stride;
+  const int32_t *row = nn + (long long)p * Nb;
+  double rt[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) rt[e] = pose[(long long)p * 12 + e];
+  double sm[4] = {0.0, 0.0, 0.0, 0.0};  // the count, then the moved points
+  for (int j = tid; j < nb; j += kThreads) {
+    if (row[j] >= 0) {
+      const float *y = pb + (long long)j * b_stride;
+      double m[3];
+      icp_move(rt, y[0], y[1], y[2], m);
+      sm[0] += 1.0;
+      sm[1] += m[0]; sm[2] += m[1]; sm[3] += m[2];
+    }
+  }
+  block_sums_256<4>(sm, s_red);
+  const int ng = (int)sm[0];
+  if (ng < 3) return;  // the pose stays as it was (workgroup-uniform)
+  const double c[3] = {sm[1] / (double)ng, sm[2] / (double)ng, sm[3] / (double)ng};
+  double S[27];  // H: the upper triangle, row by row; then g
+#pragma unroll
+  for (int e = 0; e < 27; ++e) S[e] = 0.0;
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    if (i >= 0) {
+      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
+      double m[3];
+      icp_move(rt, y[0], y[1], y[2], m);
+      const GicpPair w = gicp_pair(pan + (long long)i * an_stride, pbn + (long long)j * bn_stride, rt, one_m_eps);
+      const double *M = w.M;
+      const double Mr[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
+      const double q0 = m[0] - c[0], q1 = m[1] - c[1], q2 = m[2] - c[2];
+      const double d[3] = {(double)x[0] - m[0], (double)x[1] - m[1], (double)x[2] - m[2]};
+      double b[6][3];  // b_v = M j_v
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        b[0][r] = Mr[r][2] * q1 - Mr[r][1] * q2;
+        b[1][r] = Mr[r][0] * q2 - Mr[r][2] * q0;
+        b[2][r] = Mr[r][1] * q0 - Mr[r][0] * q1;
+        b[3][r] = Mr[r][0]; b[4][r] = Mr[r][1]; b[5][r] = Mr[r][2];
+      }
+      int e = 0;
+#pragma unroll
+      for (int u = 0; u < 6; ++u) {
+#pragma unroll
+        for (int v = u; v < 6; ++v) {  // j_u . b_v
+          const double h = u == 0 ? q1 * b[v][2] - q2 * b[v][1] : u == 1 ? q2 * b[v][0] - q0 * b[v][2]
+                         : u == 2 ? q0 * b[v][1] - q1 * b[v][0] : b[v][u - 3];
+          S[e++] += h;
+        }
+        S[21 + u] += (b[u][0] * d[0] + b[u][1] * d[1]) + b[u][2] * d[2];
+      }
+    }
+  }
+  block_sums_256<27>(S, s_red);
+  if (tid == 0) icp_solve_compose(S, S + 21, rt, c, pose + (long long)p * 12);
+}
+
+// num_planar and rmse_gicp of the last association under the returned pose (the sums in the fit's order)
+__global__ __launch_bounds__(kThreads) void icp_gicp_stats_kernel(
+    const float *__restrict__ anchor, long long a_stride, int Na, const float *__restrict__ a_normals, long long an_stride,
+    const float *__restrict__ positive, long long b_stride, int Nb, const float *__restrict__ b_normals, long long bn_stride,
+    const int32_t *__restrict__ b_count, const int32_t *__restrict__ nn, double one_m_eps, const double *__restrict__ pose,
+    int32_t *__restrict__ num_planar, double *__restrict__ rmse_gicp) {
+  __shared__ double s_red[3 * (kThreads / 64)];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
+  const float *pa = anchor + (long long)p * Na * a_stride, *pan = a_normals + (long long)p * Na * an_stride;
+  const float *pb = positive + (long long)p * Nb * b_stride, *pbn = b_normals + (long long)p * Nb * bn_stride;
+  const int32_t *row = nn + (long long)p * Nb;
+  double rt[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) rt[e] = pose[(long long)p * 12 + e];
+  double s[3] = {0.0, 0.0, 0.0};  // pairs, planar pairs, d . (M d)
+  for (int j = tid; j < nb; j += kThreads) {
+    const int i = row[j];
+    if (i >= 0) {
+      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
+      double m[3];
+      icp_move(rt, y[0], y[1], y[2], m);
+      const GicpPair w = gicp_pair(pan + (long long)i * an_stride, pbn + (long long)j * bn_stride, rt, one_m_eps);
+      const double *M = w.M;
+      const double d0 = (double)x[0] - m[0], d1 = (double)x[1] - m[1], d2 = (double)x[2] - m[2];
+      const double e0 = (M[0] * d0 + M[1] * d1) + M[2] * d2, e1 = (M[1] * d0 + M[3] * d1) + M[4] * d2;
+      const double e2 = (M[2] * d0 + M[4] * d1) + M[5] * d2;
+      s[0] += 1.0;
+      s[1] += w.planar ? 1.0 : 0.0;
+      s[2] += (d0 * e0 + d1 * e1) + d2 * e2;
+    }
+  }
+  block_sums_256<3>(s, s_red);
+  if (tid == 0) {
+    const int n = (int)s[0];
+    num_planar[p] = (int)s[1];
+    rmse_gicp[p] = n > 0 ? sqrt(s[2] / (double)n) : quiet_nan();
+  }
+}
+
 // ----------------------------------------------------------------------------------------------------------- workspace
 struct IcpWs {
   double *pose;    // [P, 12] the working pose
@@ -537,17 +718,20 @@ DH3D_API size_t dh3d_icp_refine_ws_bytes(int P, int Na, int Nb) {
   return icp_served(P, Na, Nb) ? carve_bytes<IcpWs>(P, Na, Nb) : 0;
 }
 
-// The launches of both entries: normals == nullptr is the point-to-point fit, else the point-to-plane fit and its two outputs.
+// The launches of the three entries: normals == nullptr is the point-to-point fit; normals alone the point-to-plane fit and
+// its two outputs (num_plane, rmse_plane); with pos_normals the generalized fit at epsilon, the two outputs then being
+// num_planar and rmse_gicp.
 static int icp_run(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *normals,
                    long long normals_stride, const float *positive, long long positive_stride, const int32_t *positive_count,
-                   const double *Rt0, const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path,
-                   double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
-                   int32_t *num_plane, double *rmse_plane, void *workspace, void *stream) {
+                   const float *pos_normals, long long pos_normals_stride, double epsilon, const double *Rt0,
+                   const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path, double *Rt,
+                   int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid, int32_t *num_plane,
+                   double *rmse_plane, void *workspace, void *stream) {
   Carve carve(workspace);
   const IcpWs ws(carve, P, Na, Nb);
   const bool grid = (path == 0 ? dh3d_icp_plan(Na, Nb) : path) == 2;
   hipStream_t s = (hipStream_t)stream;
-  const double r2 = max_dist * max_dist;
+  const double r2 = max_dist * max_dist, one_m_eps = 1.0 - epsilon;
 
   hipLaunchKernelGGL(icp_init_kernel, dim3(dh3d_cdiv(P, 64)), dim3(64), 0, s, Rt0, valid0, P, ws.pose, valid);
   if (grid) {
@@ -567,13 +751,20 @@ static int icp_run(const float *anchor, long long anchor_stride, const int32_t *
     if (it < iterations && !normals)
       hipLaunchKernelGGL(icp_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, positive, positive_stride,
                          Nb, positive_count, nn, ws.pose);
+    else if (it < iterations && pos_normals)
+      hipLaunchKernelGGL(icp_gicp_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals, normals_stride,
+                         positive, positive_stride, Nb, pos_normals, pos_normals_stride, positive_count, nn, one_m_eps, ws.pose);
     else if (it < iterations)
       hipLaunchKernelGGL(icp_plane_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals,
                          normals_stride, positive, positive_stride, Nb, positive_count, nn, ws.pose);
   }
   hipLaunchKernelGGL(icp_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, positive, positive_stride, Nb,
                      positive_count, nn, ws.pose, Rt, num_corr, fitness, rmse);
-  if (normals)
+  if (pos_normals)
+    hipLaunchKernelGGL(icp_gicp_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals, normals_stride,
+                       positive, positive_stride, Nb, pos_normals, pos_normals_stride, positive_count, nn, one_m_eps, ws.pose,
+                       num_plane, rmse_plane);
+  else if (normals)
     hipLaunchKernelGGL(icp_plane_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals,
                        normals_stride, positive, positive_stride, Nb, positive_count, nn, ws.pose, num_plane, rmse_plane);
   return dh3d_launch_status();
@@ -591,8 +782,9 @@ DH3D_API int dh3d_icp_refine(const float *anchor, long long anchor_stride, const
   DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
   DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
                workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
-  return icp_run(anchor, anchor_stride, anchor_count, nullptr, 0, positive, positive_stride, positive_count, Rt0, valid0, P, Na,
-                 Nb, max_dist, iterations, path, Rt, nn, num_corr, fitness, rmse, valid, nullptr, nullptr, workspace, stream);
+  return icp_run(anchor, anchor_stride, anchor_count, nullptr, 0, positive, positive_stride, positive_count, nullptr, 0, 0.0,
+                 Rt0, valid0, P, Na, Nb, max_dist, iterations, path, Rt, nn, num_corr, fitness, rmse, valid, nullptr, nullptr,
+                 workspace, stream);
 }
 
 DH3D_API size_t dh3d_icp_refine_plane_ws_bytes(int P, int Na, int Nb) { return dh3d_icp_refine_ws_bytes(P, Na, Nb); }
@@ -613,6 +805,30 @@ DH3D_API int dh3d_icp_refine_plane(const float *anchor, long long anchor_stride,
   DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
                workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
   return icp_run(anchor, anchor_stride, anchor_count, anchor_normals, normals_stride, positive, positive_stride, positive_count,
-                 Rt0, valid0, P, Na, Nb, max_dist, iterations, path, Rt, nn, num_corr, fitness, rmse, valid, num_plane,
-                 rmse_plane, workspace, stream);
+                 nullptr, 0, 0.0, Rt0, valid0, P, Na, Nb, max_dist, iterations, path, Rt, nn, num_corr, fitness, rmse, valid,
+                 num_plane, rmse_plane, workspace, stream);
+}
+
+DH3D_API size_t dh3d_icp_refine_gicp_ws_bytes(int P, int Na, int Nb) { return dh3d_icp_refine_ws_bytes(P, Na, Nb); }
+
+DH3D_API int dh3d_icp_refine_gicp(const float *anchor, long long anchor_stride, const int32_t *anchor_count,
+                                  const float *anchor_normals, long long normals_stride, const float *positive_normals,
+                                  long long positive_normals_stride, const float *positive, long long positive_stride,
+                                  const int32_t *positive_count, const double *Rt0, const int32_t *valid0, int P, int Na, int Nb,
+                                  double max_dist, int iterations, int path, double epsilon, double *Rt, int32_t *nn,
+                                  int32_t *num_corr, double *fitness, double *rmse, int32_t *valid, int32_t *num_planar,
+                                  double *rmse_gicp, void *workspace, size_t workspace_bytes, void *stream) {
+  DH3D_REQUIRE(anchor && anchor_normals && positive_normals && positive && Rt0 && Rt && nn && num_corr && fitness && rmse &&
+               valid && num_planar && rmse_gicp);
+  DH3D_REQUIRE(P > 0 && Na > 0 && Nb > 0 && anchor_stride >= 3 && normals_stride >= 3 && positive_normals_stride >= 3 &&
+               positive_stride >= 3);
+  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
+  DH3D_REQUIRE(epsilon > 0.0 && epsilon <= 1.0);  // (NaN fails both)
+  DH3D_SUPPORTED(icp_served(P, Na, Nb) && iterations <= kMaxIter);
+  DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
+  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+               workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
+  return icp_run(anchor, anchor_stride, anchor_count, anchor_normals, normals_stride, positive, positive_stride, positive_count,
+                 positive_normals, positive_normals_stride, epsilon, Rt0, valid0, P, Na, Nb, max_dist, iterations, path, Rt, nn,
+                 num_corr, fitness, rmse, valid, num_planar, rmse_gicp, workspace, stream);
 }

@@ -16,6 +16,7 @@ sampler replaces randsample, whose stream cannot be reproduced).
     nrm = estimate_normals(anchor_points, k=16)                               # PCA normals, curvature, the ids used
     res = refine_icp_plane(anchor_points, positive_points, res["Rt"], res["valid"])  # point-to-plane: + num_plane, rmse_plane
     res = register_clouds(model, anchor_points, positive_points, refine={"method": "plane", "iterations": 5})
+    res = refine_icp_gicp(anchor_points, positive_points, res["Rt"], res["valid"])  # generalized ICP: + num_planar, rmse_gicp
     f = compute_fpfh(anchor_points, k=32)                                     # fpfh [P, N, 36], counts, normals, nbr
     res = register_fpfh(anchor_points, positive_points, refine=True)          # no model: normals -> FPFH -> match -> RANSAC -> ICP
     dt, ddeg = transform_errors(T_gt, res["Rt"], res["valid"])                # compareTransform, host float64
@@ -160,8 +161,10 @@ def refine_icp(anchor_points, positive_points, Rt, valid=None, anchor_count=None
     return _icp_call(anchor_points, positive_points, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, None)
 
 
-def _icp_call(anchor_points, positive_points, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, normals):
-    """The checks, the workspace and the call of refine_icp (normals None: dh3d_icp_refine) and refine_icp_plane."""
+def _icp_call(anchor_points, positive_points, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, normals,
+              positive_normals=None, epsilon=None):
+    """The checks, the workspace and the call of refine_icp (normals None: dh3d_icp_refine), refine_icp_plane and
+    refine_icp_gicp (positive_normals and epsilon given: dh3d_icp_refine_gicp)."""
     a = _rows(anchor_points, "anchor_points", 3)
     b = _rows(positive_points, "positive_points", 3)
     P, Na = a.shape[:2]
@@ -210,6 +213,16 @@ def _icp_call(anchor_points, positive_points, Rt, valid, anchor_count, positive_
         return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse)
     num_plane = torch.empty((P,), dtype=torch.int32, device=dev)
     rmse_plane = torch.empty((P,), dtype=torch.float64, device=dev)
+    if positive_normals is not None:
+        pn = positive_normals
+        with torch.cuda.device(dev):
+            L.check(lib.dh3d_icp_refine_gicp(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(normals), normals.stride(1), L.ptr(pn),
+                                             pn.stride(1), L.ptr(b), b.stride(1), L.ptr(bc), L.ptr(rt0), L.ptr(valid), P, Na, Nb,
+                                             max_dist, iterations, path, epsilon, L.ptr(out_rt), L.ptr(nn), L.ptr(num_corr),
+                                             L.ptr(fitness), L.ptr(rmse), L.ptr(ok), L.ptr(num_plane), L.ptr(rmse_plane),
+                                             L.ptr(ws), ws.numel(), L.stream_ptr()), "refine_icp_gicp")
+        return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse, num_planar=num_plane,
+                    rmse_gicp=rmse_plane)
     with torch.cuda.device(dev):
         L.check(lib.dh3d_icp_refine_plane(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(normals), normals.stride(1), L.ptr(b),
                                           b.stride(1), L.ptr(bc), L.ptr(rt0), L.ptr(valid), P, Na, Nb, max_dist, iterations,
@@ -278,13 +291,43 @@ def refine_icp_plane(anchor_points, positive_points, Rt, valid=None, anchor_coun
     compare -- plus num_plane [P] int32 (pairs with a normal in the last association) and rmse_plane [P] float64 (the rms
     residual along the normals; NaN without pairs).  No host sync: graph-capturable; the workspace is refine_icp's."""
     a = _rows(anchor_points, "anchor_points", 3)
-    if anchor_normals is None:
-        anchor_normals = estimate_normals(a, anchor_count, normals_k, viewpoint)["normals"]
-    nrm = _rows(anchor_normals, "anchor_normals", 3)
-    if tuple(nrm.shape[:2]) != tuple(a.shape[:2]) or nrm.device != a.device:
-        raise ValueError("anchor_normals must be [%d, %d, >=3] on %s, got %s on %s"
-                         % (a.shape[0], a.shape[1], a.device, tuple(nrm.shape), nrm.device))
+    nrm = _normals_of(a, anchor_normals, anchor_count, "anchor_normals", normals_k, viewpoint)
     return _icp_call(a, positive_points, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, nrm)
+
+
+def _normals_of(points, normals, count, name, normals_k, viewpoint):
+    """The normals [P, N, >=3] of a cloud batch: the caller's, read in place, or estimate_normals' when None."""
+    if normals is None:
+        normals = estimate_normals(points, count, normals_k, viewpoint)["normals"]
+    nrm = _rows(normals, name, 3)
+    if tuple(nrm.shape[:2]) != tuple(points.shape[:2]) or nrm.device != points.device:
+        raise ValueError("%s must be [%d, %d, >=3] on %s, got %s on %s"
+                         % (name, points.shape[0], points.shape[1], points.device, tuple(nrm.shape), nrm.device))
+    return nrm
+
+
+def refine_icp_gicp(anchor_points, positive_points, Rt, valid=None, anchor_count=None, positive_count=None, max_dist=1.0,
+                    iterations=20, path=0, anchor_normals=None, normals_k=16, viewpoint=(0., 0., 0.), positive_normals=None,
+                    epsilon=1e-3):
+    """Dense generalized (plane-to-plane) ICP, Segal, Haehnel & Thrun 2009: refine_icp's inputs, association, loop and
+    outputs with the fit that models both surfaces -- every point carries a covariance that is 1 across its normal and
+    `epsilon` (0 < epsilon <= 1) along it, and every pair is weighted by the inverse of the anchor's covariance plus the moved
+    positive's (a linearised 6 x 6 solve per iteration; include/dh3d_hip.h dh3d_icp_refine_gicp states every rule).
+    anchor_normals [P, Na, >=3] and positive_normals [P, Nb, >=3] float32 are read in place; None computes that cloud's with
+    estimate_normals(points, its count, normals_k, viewpoint).  Sign and length of a normal do not matter; a zero normal makes
+    its point isotropic and keeps it in the fit, so with all normals zero (or epsilon = 1) this is a linearised point-to-point
+    step.  The result is refine_icp's dict -- rmse stays the point-to-point one, so the three methods compare -- plus
+    num_planar [P] int32 (pairs of the last association whose normals are both non-zero) and rmse_gicp [P] float64 (the rms
+    of the weighted residual sqrt(d . M d); NaN without pairs).  No host sync: graph-capturable; the workspace is
+    refine_icp's."""
+    a = _rows(anchor_points, "anchor_points", 3)
+    b = _rows(positive_points, "positive_points", 3)
+    epsilon = float(epsilon)
+    if not 0.0 < epsilon <= 1.0:
+        raise ValueError("refine_icp_gicp: need 0 < epsilon <= 1, got %r" % (epsilon,))
+    an = _normals_of(a, anchor_normals, anchor_count, "anchor_normals", normals_k, viewpoint)
+    pn = _normals_of(b, positive_normals, positive_count, "positive_normals", normals_k, viewpoint)
+    return _icp_call(a, b, Rt, valid, anchor_count, positive_count, max_dist, iterations, path, an, pn, epsilon)
 
 
 FPFH_MAX_K, FPFH_COLS = 64, 36  # csrc/fpfh.hip kMaxK, kRow: 33 bins and three zero columns
@@ -390,7 +433,8 @@ def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None
     tensor or a pair (anchor, positive), e.g. farthest-point picks, -1 padded at the tail.  keypoints may be a pair too.
     refine: None, True or a dict of refine_pose keywords, on the full clouds.  Returns register_clouds' keys: ransac_rigid's
     dict plus match / dist (indices into the keypoint lists), and with refine Rt_ransac, fitness, rmse, num_corr_icp, nn (and
-    num_plane, rmse_plane); plus anchor_ids / positive_ids (the keypoint ids, None: all points).  No host sync."""
+    num_plane, rmse_plane with method="plane"; num_planar, rmse_gicp with method="gicp"); plus anchor_ids / positive_ids (the
+    keypoint ids, None: all points).  No host sync."""
     rkw = _refine_kw(refine)
     pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
     nv, kp, kid = pair(num_valid), pair(keypoints), pair(keypoint_ids)
@@ -418,21 +462,25 @@ def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None
         out["fitness"], out["rmse"], out["num_corr_icp"], out["nn"] = icp["fitness"], icp["rmse"], icp["num_corr"], icp["nn"]
         if "rmse_plane" in icp:
             out["num_plane"], out["rmse_plane"] = icp["num_plane"], icp["rmse_plane"]
+        if "rmse_gicp" in icp:
+            out["num_planar"], out["rmse_gicp"] = icp["num_planar"], icp["rmse_gicp"]
     return out
 
 
 def refine_pose(anchor_points, positive_points, Rt, valid=None, anchor_count=None, positive_count=None, method="point", **kw):
     """The dense refinement behind register_clouds / PlaceIndex.localize(refine=...): method "point" is refine_icp (its
-    keywords max_dist, iterations, path), "plane" is refine_icp_plane (those plus anchor_normals, normals_k, viewpoint)."""
-    if method not in ("point", "plane"):
-        raise ValueError('method must be "point" or "plane", got %r' % (method,))
-    fn = refine_icp if method == "point" else refine_icp_plane
+    keywords max_dist, iterations, path), "plane" is refine_icp_plane (those plus anchor_normals, normals_k, viewpoint),
+    "gicp" is refine_icp_gicp (those plus positive_normals, epsilon)."""
+    fns = {"point": refine_icp, "plane": refine_icp_plane, "gicp": refine_icp_gicp}
+    if method not in fns:
+        raise ValueError('method must be "point", "plane" or "gicp", got %r' % (method,))
+    fn = fns[method]
     return fn(anchor_points, positive_points, Rt, valid, anchor_count=anchor_count, positive_count=positive_count, **kw)
 
 
 def _refine_kw(refine):
     """refine: None / False (no refinement), True (refine_icp's defaults) or a dict of refine_pose keywords: refine_icp's,
-    or method="plane" and refine_icp_plane's."""
+    or method="plane" and refine_icp_plane's, or method="gicp" and refine_icp_gicp's."""
     if refine is None or refine is False:
         return None
     if refine is True:
@@ -448,7 +496,8 @@ def register_clouds(model, anchor_points, positive_points, num_valid=None, refin
     refine: None, True or a dict of refine_icp keywords -- the RANSAC pose is then refined by dense ICP of the full clouds
     (num_valid as the counts): Rt is the refined pose and the result gains Rt_ransac (the keypoint fit), fitness, rmse,
     num_corr_icp and nn; valid stays the RANSAC fit's.  A dict with method="plane" (and refine_icp_plane's keywords) refines
-    point-to-plane instead and adds num_plane and rmse_plane."""
+    point-to-plane instead and adds num_plane and rmse_plane; method="gicp" (and refine_icp_gicp's keywords) refines by
+    generalized ICP and adds num_planar and rmse_gicp."""
     if not getattr(model.config, "detection", False):
         raise ValueError("register_clouds needs a model with config.detection (the keypoint outputs)")
     rkw = _refine_kw(refine)
@@ -463,6 +512,8 @@ def register_clouds(model, anchor_points, positive_points, num_valid=None, refin
         out["fitness"], out["rmse"], out["num_corr_icp"], out["nn"] = icp["fitness"], icp["rmse"], icp["num_corr"], icp["nn"]
         if "rmse_plane" in icp:
             out["num_plane"], out["rmse_plane"] = icp["num_plane"], icp["rmse_plane"]
+        if "rmse_gicp" in icp:
+            out["num_planar"], out["rmse_gicp"] = icp["num_planar"], icp["rmse_gicp"]
     return out
 
 

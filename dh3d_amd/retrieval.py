@@ -193,7 +193,8 @@ class PlaceIndex:
         winner's stored cloud, gathered by place id on the device; a query without a winner goes in as invalid.  Rt is then
         the refined pose and the result gains Rt_ransac (the keypoint fit), fitness and rmse (the dense overlap: the check on
         the retrieved place); a dict with method="plane" refines point-to-plane (registration.refine_icp_plane's keywords;
-        the winner's normals are computed per call) and adds rmse_plane.  Needs an index built with points > 0 (else
+        the winner's normals are computed per call) and adds rmse_plane; method="gicp" refines by generalized ICP
+        (registration.refine_icp_gicp's keywords; both clouds' normals are computed per call) and adds rmse_gicp.  Needs an index built with points > 0 (else
         ValueError).  No host sync."""
         if not self.keypoints:
             raise ValueError("localize needs a PlaceIndex built with keypoints > 0")
@@ -243,6 +244,8 @@ class PlaceIndex:
             out["fitness"], out["rmse"] = icp["fitness"], icp["rmse"]
             if "rmse_plane" in icp:
                 out["rmse_plane"] = icp["rmse_plane"]
+            if "rmse_gicp" in icp:
+                out["rmse_gicp"] = icp["rmse_gicp"]
         return out
 
 
@@ -250,7 +253,7 @@ def relocalize_clouds(global_model, local_model, index, points, k=5, num_valid=N
     """Clouds [Q, N, 3] in, place ids and poses out: globaldesc from `global_model` (config.extract_global), kp_count /
     xyz_feat_att_nms from `local_model` (config.detection) -- two models, as the reference has two checkpoints -- then
     index.localize.  num_valid: None or int32 [Q].  refine: None, True or a dict of registration.refine_icp keywords (or
-    method="plane" and registration.refine_icp_plane's) -- the winner's pose is refined by dense ICP of `points` against the
+    method="plane" / "gicp" and registration.refine_icp_plane's / refine_icp_gicp's) -- the winner's pose is refined by dense ICP of `points` against the
     place's stored cloud (PlaceIndex(points=...))."""
     if not getattr(global_model.config, "extract_global", False):
         raise ValueError("relocalize_clouds needs a global_model with config.extract_global (the globaldesc output)")

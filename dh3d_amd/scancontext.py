@@ -192,7 +192,7 @@ def relocalize_scan_context(index, points, num_valid=None, center=None, k=1, can
     0 is the winner) plus Rt [Q, 3, 4] float64 (NaN where no place was found) and valid [Q] bool.  refine: None, True or a
     dict of registration.refine_pose keywords -- Rt is then refined by dense ICP of `points` against the winner's stored
     cloud (an index built with points > 0, else ValueError) and the result gains Rt_scan (the pose above), fitness and rmse
-    (and rmse_plane with method="plane").  No host sync."""
+    (and rmse_plane with method="plane", rmse_gicp with method="gicp").  No host sync."""
     rkw = registration._refine_kw(refine)
     if rkw is not None and not index.points:
         raise ValueError("relocalize_scan_context(refine=...) needs a ScanContextIndex built with points > 0 (the places' clouds)")
@@ -218,4 +218,6 @@ def relocalize_scan_context(index, points, num_valid=None, center=None, k=1, can
         out["fitness"], out["rmse"] = icp["fitness"], icp["rmse"]
         if "rmse_plane" in icp:
             out["rmse_plane"] = icp["rmse_plane"]
+        if "rmse_gicp" in icp:
+            out["rmse_gicp"] = icp["rmse_gicp"]
     return out

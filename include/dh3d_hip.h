@@ -1387,6 +1387,56 @@ int dh3d_scan_context(const float *xyz, long long xyz_stride, const int32_t *cou
 int dh3d_scan_context_distance(const float *qry, const float *map, const int32_t *map_count, const int32_t *cand, int Q, int R,
                                int C, int Nr, int Ns, double *dist, int32_t *shift, int32_t *order, void *stream);
 
+/* Dense generalized (plane-to-plane) ICP refinement (csrc/icp.hip) -- Generalized-ICP, Segal, Haehnel & Thrun, RSS 2009:
+ * dh3d_icp_refine with a third fit, which models both surfaces.  The inputs, the ASSOCIATION A, the LOOP (pose = Rt0;
+ * `iterations` times { nn = A(pose); pose = F_gicp(nn, pose) }; then nn = A(pose) once more), the paths, the plan, the limits,
+ * the validity rule and the independence guarantees are dh3d_icp_refine's, word for word.  In addition:
+ * INPUTS: the normal of anchor point i of pair p at anchor_normals + (p*Na + i) * normals_stride and the normal of positive
+ *   point j at positive_normals + (p*Nb + j) * positive_normals_stride (3 floats each, strides in elements, >= 3), as
+ *   dh3d_estimate_normals writes them.  Their sign and their length do not matter.  A zero normal makes its point isotropic
+ *   and does NOT take it out of the fit.  epsilon, 0 < epsilon <= 1: the covariance along a normal relative to 1 across it;
+ *   e1 = 1.0 - epsilon, rounded once.
+ * FIT F_gicp(nn, pose = [R | t]), float64 on the exact float32 values, every operation rounded on its own.  Symmetric 3 x 3
+ *   matrices keep the six entries uv = 00 01 02 11 12 22.  The pairs are the j < nb in ascending order with i = nn[j] >= 0;
+ *   n_g of them (= num_corr of that association).  n_g < 3: the pose stays as it was.  m_j = y'_j of the association under
+ *   the pose; c = (sum of m_j) / n_g.  Per pair:
+ *   cov(v) for a 3-vector v: s = (v_0*v_0 + v_1*v_1) + v_2*v_2; f = e1 / s when s > 0, else 0; a_u = f * v_u;
+ *     cov(v)_uv = I_uv - a_u * v_v (I_uv = 1.0 for u = v, else 0.0).  v is NON-ZERO iff s > 0.
+ *   C_A = cov(n), n = the normal of anchor i.  C_B = cov(u), u_r = (R_r0*k_0 + R_r1*k_1) + R_r2*k_2 for k = the normal of
+ *     positive j.  W_uv = C_A_uv + C_B_uv.
+ *   cof_00 = W_11*W_22 - W_12*W_12; cof_01 = W_02*W_12 - W_01*W_22; cof_02 = W_01*W_12 - W_02*W_11;
+ *     cof_11 = W_00*W_22 - W_02*W_02; cof_12 = W_01*W_02 - W_00*W_12; cof_22 = W_00*W_11 - W_01*W_01;
+ *     det = (W_00*cof_00 + W_01*cof_01) + W_02*cof_02 (>= 8 epsilon^3 in exact arithmetic); M_uv = cof_uv / det, M_vu = M_uv.
+ *   q = m_j - c and d = (double)x_i - m_j per axis.  The linearisation is F_plane's: a step s = (w, v) moves m_j by w x q + v,
+ *     the columns of J being j_0 = (0, -q_2, q_1), j_1 = (q_2, 0, -q_0), j_2 = (-q_1, q_0, 0), j_3 = e_0, j_4 = e_1, j_5 = e_2.
+ *   b_v = M j_v, written out per row r: b_0r = M_r2*q_1 - M_r1*q_2; b_1r = M_r0*q_2 - M_r2*q_0; b_2r = M_r1*q_0 - M_r0*q_1;
+ *     b_3r = M_r0; b_4r = M_r1; b_5r = M_r2.
+ *   h_uv = j_u . b_v for u <= v: u = 0: q_1*b_v2 - q_2*b_v1; u = 1: q_2*b_v0 - q_0*b_v2; u = 2: q_0*b_v1 - q_1*b_v0;
+ *     u >= 3: b_v,u-3.  e_u = (b_u0*d_0 + b_u1*d_1) + b_u2*d_2.
+ *   H_uv = sum of h_uv (u <= v, 21 sums), g_u = sum of e_u (6 sums).  Every sum (n_g's and c's three included): lane j % 256
+ *   over its j in ascending order from 0; then within each 64-lane wave l_i = l_i + l_(i xor 32), then xor 16, 8, 4, 2, 1;
+ *   then ((wave 0 + wave 1) + wave 2) + wave 3.
+ *   H s = g by F_plane's Cholesky with its pivot refusal (not finite or <= 1e-12 * max_u H_uu) and its non-finite-s refusal;
+ *   dR from w = s[0:3] and the new pose from dR, c and s[3:6] exactly as F_plane composes them.
+ * OUTPUTS: Rt, nn, num_corr, fitness, rmse (point-to-point: the three methods compare) and valid as dh3d_icp_refine gives
+ *   them; num_planar [P] int32 = the pairs of the last association with n and u both non-zero; rmse_gicp [P] float64 =
+ *   sqrt(sum of z / num_corr) under the returned pose with y_r = (M_r0*d_0 + M_r1*d_1) + M_r2*d_2 and z = (d_0*y_0 + d_1*y_1)
+ *   + d_2*y_2 (the sums in the fit's order), NaN when num_corr = 0.  A pair that is not valid comes back as from
+ *   dh3d_icp_refine, with num_planar 0 and rmse_gicp NaN.  Every element is written.  Rt may be Rt0.
+ * dh3d_icp_refine_gicp_ws_bytes (host only): the workspace, as dh3d_icp_refine_ws_bytes; the plan is dh3d_icp_plan.
+ * SIDE EFFECTS: caller's stream, one launch after the other (no parallel branches), no host sync, no allocation, no
+ *   floating-point atomics; graph-capturable.
+ * STATUS: dh3d_icp_refine's, with NULL anchor_normals / positive_normals / num_planar / rmse_gicp, a normals stride below 3
+ *   or an epsilon not in (0, 1] (NaN included) among the DH3D_ERR_INVALID_ARGUMENT cases.  NaN and infinite normals are
+ *   outside the contract. */
+size_t dh3d_icp_refine_gicp_ws_bytes(int P, int Na, int Nb);
+int dh3d_icp_refine_gicp(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *anchor_normals,
+                         long long normals_stride, const float *positive_normals, long long positive_normals_stride,
+                         const float *positive, long long positive_stride, const int32_t *positive_count, const double *Rt0,
+                         const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path, double epsilon,
+                         double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
+                         int32_t *num_planar, double *rmse_gicp, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,11 @@ prepare_clouds pads.  Pose errors are registration.transform_errors' (compareTra
 three |Euler angles| in degrees -- a start 2 degrees off about one axis reads as about 3).  "plane": on the demo pairs, the
 anchor normals at k = 16 (the kNN and the normals kernel timed apart), then point-to-plane ICP (registration.refine_icp_plane
 on given normals, cell lists) at 5, 10 and 20 iterations next to point-to-point at the same counts, each with its pose error
-against the truth; and both fits alone on eight-anchor clouds (the plane fit needs normals that span space).  Prints one JSON
-line.
+against the truth; and both fits alone on eight-anchor clouds (the plane fit needs normals that span space).  Generalized ICP
+(registration.refine_icp_gicp on given normals of both clouds, epsilon 1e-3) runs in the same pass at the same counts: its
+rows carry besides the positive normals' cost (kNN + normals kernel, positive_normals_us) and the time per iteration
+(iteration_us, against the same call at 0 iterations), and gicp_step8_us stands next to the other two fits'.  Prints one
+JSON line.
 
     python tools/icp_bench.py [--pairs 64] [--points 8192] [--iterations 20] [--iters 5] [--reg-pairs 8]
 """
@@ -71,8 +74,15 @@ def plane_rows(a, rng, demo_pairs, ypos, eye):
     nbr = batched_knn(tA, 16)[0]
     out["normals_us"] = timed(lambda: reg.estimate_normals(tA, nbr=nbr), a.iters)
     nrm = reg.estimate_normals(tA, nbr=nbr)["normals"]
+    out["positive_knn_us"] = timed(lambda: batched_knn(tY, 16), a.iters)
+    nbr_y = batched_knn(tY, 16)[0]
+    out["positive_normals_us"] = timed(lambda: reg.estimate_normals(tY, nbr=nbr_y), a.iters)
+    nrm_y = reg.estimate_normals(tY, nbr=nbr_y)["normals"]
     path = 2 if N <= reg.ICP_GRID_MAX else 1
-    for method, fn, kw in (("plane", reg.refine_icp_plane, dict(anchor_normals=nrm)), ("point", reg.refine_icp, {})):
+    gicp_kw = dict(anchor_normals=nrm, positive_normals=nrm_y, epsilon=1e-3)
+    gicp0 = timed(lambda: reg.refine_icp_gicp(tA, tY, tT0, iterations=0, path=path, **gicp_kw), a.iters)
+    for method, fn, kw in (("plane", reg.refine_icp_plane, dict(anchor_normals=nrm)), ("point", reg.refine_icp, {}),
+                           ("gicp", reg.refine_icp_gicp, gicp_kw)):
         for it in sorted({5, 10, T}):
             us = timed(lambda: fn(tA, tY, tT0, iterations=it, path=path, **kw), a.iters)
             r = fn(tA, tY, tT0, iterations=it, path=path, **kw)
@@ -81,13 +91,18 @@ def plane_rows(a, rng, demo_pairs, ypos, eye):
                        fitness=float(r["fitness"].mean()), rmse=float(r["rmse"].mean()))
             if method == "plane":
                 row["rmse_plane"] = float(r["rmse_plane"].mean())
+            if method == "gicp":
+                row.update(rmse_gicp=float(r["rmse_gicp"].mean()), iteration_us=(us - gicp0) / it,
+                           positive_normals_us=out["positive_knn_us"] + out["positive_normals_us"])
             out["%s_%d" % (method, it)] = row
     # both fits alone: eight anchors at the corners of a small cube with normals that span space; every positive pairs up
     t = lambda v: torch.from_numpy(v).cuda()
     corners = np.array([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], np.float32)
     eight = t(np.tile(0.25 * corners, (P, 1, 1)))
     n8 = t(np.tile(corners / np.float32(math.sqrt(3.0)), (P, 1, 1)))
-    for method, fn, kw in (("plane", reg.refine_icp_plane, dict(anchor_normals=n8)), ("point", reg.refine_icp, {})):
+    ny = reg.estimate_normals(ypos, k=16)["normals"]
+    for method, fn, kw in (("plane", reg.refine_icp_plane, dict(anchor_normals=n8)), ("point", reg.refine_icp, {}),
+                           ("gicp", reg.refine_icp_gicp, dict(anchor_normals=n8, positive_normals=ny))):
         f0 = timed(lambda: fn(eight, ypos, eye, max_dist=10.0, iterations=0, path=1, **kw), a.iters)
         fT = timed(lambda: fn(eight, ypos, eye, max_dist=10.0, iterations=T, path=1, **kw), a.iters)
         out["%s_step8_us" % method] = (fT - f0) / T     # one 8-anchor scan + one fit
