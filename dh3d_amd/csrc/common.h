@@ -58,6 +58,26 @@ __device__ __forceinline__ T block_sum_256(T v, T *s_red) {
   return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
+// N block sums at once, in place, each by block_sum_256's tree (the wave's xor butterfly 32 .. 1, then ((w0 + w1) + w2) + w3:
+// the same bits), behind one pair of barriers instead of N.  s_red holds 4 * N elements.
+template <int N, typename T>
+__device__ __forceinline__ void block_sums_256(T *v, T *s_red) {
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[e] += __shfl_xor(v[e], off, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) s_red[4 * e + wave] = v[e];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < N; ++e) v[e] = s_red[4 * e] + s_red[4 * e + 1] + s_red[4 * e + 2] + s_red[4 * e + 3];
+}
+
 // Folded training-mode BatchNorm coefficients: y = x * scale + shift with scale = gamma * rstd and shift = beta - mean *
 // scale in ONE rounding (explicit fmaf: contraction cannot differ between translation units).  Every pass of a site --
 // the finalize that stores (scale, shift) and the backward sums that only get (mean, rstd, gamma, beta) -- folds through

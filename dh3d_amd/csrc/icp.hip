@@ -29,24 +29,27 @@
 //                     clouds, the scan 1.52).  The sort sees the rows below anchor_count only: icp_pack_kernel hands it
 //                     row r % na in place of every row r >= na (such rows are never candidates: their index says so), so
 //                     the grid of a cloud padded with rows of 100000.0 is the grid of its points, not of its padding.
-//   icp_fit_kernel    one 256-lane workgroup per pair: the pairs (anchor[nn[j]], positive[j]) with nn[j] >= 0, lane j % 256
-//                     over ascending j, float64 block sums in a fixed tree (count and centroids, then B over the centred
-//                     pairs), lane 0 solves (rigid_fit.h: the functions of ransac_kernel's refit).  n < 3 leaves the pose.
-//   icp_stats_kernel  num_corr, fitness, rmse (the sum in the fit's order) and the outputs of invalid pairs.
-// Point-to-plane (dh3d_icp_refine_plane): the same launches with another fit and two more outputs.
-//   icp_plane_fit_kernel    one 256-lane workgroup per pair: the pairs whose anchor has a non-zero normal, the centroid of
-//                           their moved positives, 21 + 6 float64 block sums (H = sum a a^T, g = sum a r), lane 0 solves the
-//                           6 x 6 system by Cholesky in registers and composes the step with the pose.  Fewer than 6 pairs or
-//                           a refused pivot leave the pose.  224 VGPRs, no scratch; one workgroup per pair as icp_fit_kernel.
-//   icp_plane_stats_kernel  num_plane and rmse_plane.
-// Generalized / plane-to-plane (dh3d_icp_refine_gicp): the same launches with a third fit and its two outputs.
-//   icp_gicp_fit_kernel     one 256-lane workgroup per pair: every pair of nn, weighted by M = (C_A + C_B)^-1 of the two
-//                           normals' covariances (closed-form 3 x 3 inverse per pair), 21 + 6 float64 sums of H = sum J^T M J
-//                           and g = sum J^T M d reduced in ONE LDS pass (block_sums_256: the tree of block_sum_256 for all 27
-//                           behind two barriers, where the plane kernel pays 27 pairs), then icp_solve_compose, the plane
-//                           fit's Cholesky and composition.  138 VGPRs, no scratch, 864 bytes of LDS.
-//   icp_gicp_stats_kernel   num_planar and rmse_gicp.  60 VGPRs, no scratch.
-// Compiled without contraction (csrc/Makefile EXACT): the ids depend on every rounding of d2.
+// The fit and stats kernels, one 256-lane workgroup per cloud pair, share four helpers:
+//   IcpClouds           the batch as one argument block: clouds, normals (null for a method without them), strides, counts,
+//                       nn and the working pose.  icp_run fills it once; these kernels and icp_grid_kernel take it by value.
+//   icp_for_pairs       the walk over the pairs (anchor[nn[j]], positive[j]) with nn[j] >= 0: lane j % 256 over ascending j.
+//   block_sums_256<N>   (common.h) every sum of a kernel's pass in one reduction: a fixed tree behind two barriers.
+//   icp_moved_centroid  the first pass of the plane and the generalized fit: count and centroid of the moved positives of
+//                       the admitted pairs; icp_solve_compose is their last step (6 x 6 Cholesky in registers, the step
+//                       composed with the pose; a refused pivot leaves the pose).
+//   icp_fit_kernel          point-to-point: rigid_fit.h's block_rigid_fit_256 (ransac_kernel's refit) over the pairs -- 7 sums
+//                           (count, centroids), 10 sums (B over the centred pairs), lane 0 solves.  n < 3 leaves the pose.
+//                           80 VGPRs, 320 bytes of LDS.
+//   icp_stats_kernel        num_corr, fitness, rmse (the sum in the fit's order) and the outputs of invalid pairs.  32 VGPRs.
+//   icp_plane_fit_kernel    point-to-plane (dh3d_icp_refine_plane): the pairs whose anchor has a non-zero normal, 21 + 6 sums
+//                           (H = sum a a^T, g = sum a r).  Fewer than 6 pairs leave the pose.  126 VGPRs, 864 bytes of LDS.
+//   icp_plane_stats_kernel  num_plane and rmse_plane.  40 VGPRs.
+//   icp_gicp_fit_kernel     generalized / plane-to-plane (dh3d_icp_refine_gicp): every pair of nn, weighted by
+//                           M = (C_A + C_B)^-1 of the two normals' covariances (closed-form 3 x 3 inverse per pair), 21 + 6
+//                           sums (H = sum J^T M J, g = sum J^T M d).  Fewer than 3 pairs leave the pose.  126 VGPRs, 864
+//                           bytes of LDS.
+//   icp_gicp_stats_kernel   num_planar and rmse_gicp.  60 VGPRs.
+// None of them uses scratch.  Compiled without contraction (csrc/Makefile EXACT): the ids depend on every rounding of d2.
 #include <math.h>
 
 #include "cell_grid.h"
@@ -80,6 +83,45 @@ __device__ __forceinline__ double icp_d2(double x0, double x1, double x2, const 
   return (dx * dx + dy * dy) + dz * dz;
 }
 
+// A batch of P cloud pairs as the cell-list, fit and stats kernels take it (by value).  Strides are in elements; a count
+// that is null means all rows; the normals of a method that has none are null.
+struct IcpClouds {
+  const float *anchor, *a_normals, *positive, *b_normals;
+  long long a_stride, an_stride, b_stride, bn_stride;
+  int Na, Nb;
+  const int32_t *a_count, *b_count;
+  int32_t *nn;   // [P, Nb] the anchor of every positive point, -1: none
+  double *pose;  // [P, 12] the working pose (workspace)
+};
+
+// cloud pair p: its positive count and the first rows of its anchor, its positive and its ids
+struct IcpRows {
+  int nb;
+  const float *a, *b;
+  const int32_t *nn;
+};
+__device__ __forceinline__ IcpRows icp_rows(const IcpClouds &c, int p) {
+  return {c.b_count ? clamp_count(c.b_count[p], c.Nb) : c.Nb, c.anchor + (long long)p * c.Na * c.a_stride,
+          c.positive + (long long)p * c.Nb * c.b_stride, c.nn + (long long)p * c.Nb};
+}
+__device__ __forceinline__ const float *icp_anchor_normal(const IcpClouds &c, int p, int i) {
+  return c.a_normals + ((long long)p * c.Na + i) * c.an_stride;
+}
+__device__ __forceinline__ const float *icp_positive_normal(const IcpClouds &c, int p, int j) {
+  return c.b_normals + ((long long)p * c.Nb + j) * c.bn_stride;
+}
+
+// The pairs of cloud pair p, one 256-lane workgroup: body(i, j, x, y) for every j = lane, lane + 256, ... (ascending) with
+// i = nn[j] >= 0, x the anchor's row i and y the positive's row j.  Every sum over the pairs is a lane's sum in this order.
+template <typename Body>
+__device__ __forceinline__ void icp_for_pairs(const IcpClouds &c, int p, Body body) {
+  const IcpRows r = icp_rows(c, p);
+  for (int j = threadIdx.x; j < r.nb; j += kThreads) {
+    const int i = r.nn[j];
+    if (i >= 0) body(i, j, r.a + (long long)i * c.a_stride, r.b + (long long)j * c.b_stride);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- init
 // the working pose (workspace) and valid: a pair is valid when valid0 is not 0 and Rt0 is finite
 __global__ __launch_bounds__(64) void icp_init_kernel(const double *__restrict__ Rt0, const int32_t *__restrict__ valid0, int P,
@@ -110,6 +152,8 @@ __global__ __launch_bounds__(kThreads) void icp_pack_kernel(const float *__restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------- scan
+// (The one kernel that takes IcpClouds' fields one by one: with the block its loops compiled to the same instructions on
+// other registers and ran 0.8 % slower, the same in two runs -- 1583 and 1586 against 1571 and 1573 us per iteration.)
 __global__ __launch_bounds__(kThreads) void icp_scan_kernel(
     const float *__restrict__ anchor, long long a_stride, int Na, const int32_t *__restrict__ a_count,
     const float *__restrict__ positive, long long b_stride, int Nb, const int32_t *__restrict__ b_count,
@@ -165,23 +209,21 @@ __device__ __forceinline__ void icp_take(Best &b, const float4 rec, const double
 }
 
 __global__ __launch_bounds__(kThreads) void icp_grid_kernel(
-    const float4 *__restrict__ sorted, const float *__restrict__ gbox, const int *__restrict__ cells, int Na,
-    const int32_t *__restrict__ a_count, const float *__restrict__ positive, long long b_stride, int Nb,
-    const int32_t *__restrict__ b_count, const double *__restrict__ pose, const int32_t *__restrict__ valid, double r2,
-    double max_dist, int32_t *__restrict__ nn) {
+    const float4 *__restrict__ sorted, const float *__restrict__ gbox, const int *__restrict__ cells, IcpClouds c,
+    const int32_t *__restrict__ valid, double r2, double max_dist) {
   __shared__ unsigned s_dep[3][64];  // axis value -> its bits at their places in the cell's 12-bit code
-  const int p = blockIdx.y, j = blockIdx.x * kThreads + threadIdx.x;
-  const int na = a_count ? clamp_count(a_count[p], Na) : Na, nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
-  int32_t *out = nn + (long long)p * Nb;
+  const int p = blockIdx.y, j = blockIdx.x * kThreads + threadIdx.x, Na = c.Na, Nb = c.Nb;
+  const int na = c.a_count ? clamp_count(c.a_count[p], Na) : Na, nb = c.b_count ? clamp_count(c.b_count[p], Nb) : Nb;
+  int32_t *out = c.nn + (long long)p * Nb;
   if ((int)blockIdx.x * kThreads >= nb || na == 0 || !valid[p]) {  // (workgroup-uniform)
     if (j < Nb) out[j] = -1;
     return;
   }
   const bool live = j < nb;
-  const float *yr = positive + ((long long)p * Nb + (live ? j : 0)) * b_stride;
+  const float *yr = c.positive + ((long long)p * Nb + (live ? j : 0)) * c.b_stride;
   const float y0 = yr[0], y1 = yr[1], y2 = yr[2];
   double m[3];
-  icp_move(pose + (long long)p * 12, y0, y1, y2, m);
+  icp_move(c.pose + (long long)p * 12, y0, y1, y2, m);
   const float4 *sc = sorted + (size_t)p * Na;
   const CellGrid g = cell_grid(cells, p);
   const int *ct = g.ct;
@@ -249,88 +291,40 @@ __global__ __launch_bounds__(kThreads) void icp_grid_kernel(
 }
 
 // ----------------------------------------------------------------------------------------------------------------- fit
-__global__ __launch_bounds__(kThreads) void icp_fit_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
-                                                           const float *__restrict__ positive, long long b_stride, int Nb,
-                                                           const int32_t *__restrict__ b_count,
-                                                           const int32_t *__restrict__ nn, double *__restrict__ pose) {
-  __shared__ double s_red[kThreads / 64];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
-  const float *pa = anchor + (long long)p * Na * a_stride, *pb = positive + (long long)p * Nb * b_stride;
-  const int32_t *row = nn + (long long)p * Nb;
-  // least-squares fit on the pairs: float64 sums, each lane over its slots in order, then a fixed tree
-  double cnt = 0.0, sx[3] = {0.0, 0.0, 0.0}, sy[3] = {0.0, 0.0, 0.0};
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    if (i >= 0) {
-      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
-      cnt += 1.0;
-      sx[0] += x[0]; sx[1] += x[1]; sx[2] += x[2];
-      sy[0] += y[0]; sy[1] += y[1]; sy[2] += y[2];
-    }
-  }
-  const int n = (int)block_sum_256<double>(cnt, s_red);
-  if (n < 3) return;  // the pose stays as it was (workgroup-uniform)
-  double xc[3], yc[3];
-  for (int r = 0; r < 3; ++r) {
-    xc[r] = block_sum_256<double>(sx[r], s_red) / (double)n;
-    yc[r] = block_sum_256<double>(sy[r], s_red) / (double)n;
-  }
-  double B[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    if (i >= 0) {
-      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
-      accumulate_b(B, x[0] - xc[0], x[1] - xc[1], x[2] - xc[2], y[0] - yc[0], y[1] - yc[1], y[2] - yc[2]);
-    }
-  }
-  for (int e = 0; e < 10; ++e) B[e] = block_sum_256<double>(B[e], s_red);
-  if (tid == 0) {
-    double Rf[9], tf[3];
-    rotation_from_b(B, Rf);
-    translation(Rf, xc, yc, tf);
-    double *rt = pose + (long long)p * 12;
-    for (int r = 0; r < 3; ++r) {
-      rt[4 * r] = Rf[3 * r];
-      rt[4 * r + 1] = Rf[3 * r + 1];
-      rt[4 * r + 2] = Rf[3 * r + 2];
-      rt[4 * r + 3] = tf[r];
-    }
-  }
+__global__ __launch_bounds__(kThreads) void icp_fit_kernel(IcpClouds c) {
+  __shared__ double s_red[10 * (kThreads / 64)];
+  const int p = blockIdx.x;
+  const IcpRows r = icp_rows(c, p);
+  block_rigid_fit_256(r.nb, [&](int j, float *x, float *y) {  // (the slots of icp_for_pairs)
+    const int i = r.nn[j];
+    if (i < 0) return false;
+    const float *xa = r.a + (long long)i * c.a_stride, *yb = r.b + (long long)j * c.b_stride;
+    x[0] = xa[0]; x[1] = xa[1]; x[2] = xa[2];
+    y[0] = yb[0]; y[1] = yb[1]; y[2] = yb[2];
+    return true;
+  }, s_red, c.pose + (long long)p * 12);
 }
 
 // --------------------------------------------------------------------------------------------------------------- stats
-__global__ __launch_bounds__(kThreads) void icp_stats_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
-                                                             const float *__restrict__ positive, long long b_stride, int Nb,
-                                                             const int32_t *__restrict__ b_count,
-                                                             const int32_t *__restrict__ nn, const double *__restrict__ pose,
-                                                             double *__restrict__ Rt, int32_t *__restrict__ num_corr,
+__global__ __launch_bounds__(kThreads) void icp_stats_kernel(IcpClouds c, double *__restrict__ Rt, int32_t *__restrict__ num_corr,
                                                              double *__restrict__ fitness, double *__restrict__ rmse) {
-  __shared__ double s_red[kThreads / 64];
+  __shared__ double s_red[2 * (kThreads / 64)];
   const int p = blockIdx.x, tid = threadIdx.x;
-  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
-  const float *pa = anchor + (long long)p * Na * a_stride, *pb = positive + (long long)p * Nb * b_stride;
-  const int32_t *row = nn + (long long)p * Nb;
-  const double *rt = pose + (long long)p * 12;
-  double cnt = 0.0, sum = 0.0;
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    if (i >= 0) {
-      const float *x = pa + (long long)i * a_stride;
-      const float *y = pb + (long long)j * b_stride;
-      double m[3];
-      icp_move(rt, y[0], y[1], y[2], m);
-      cnt += 1.0;
-      sum += icp_d2(x[0], x[1], x[2], m);
-    }
-  }
-  const int n = (int)block_sum_256<double>(cnt, s_red);
-  sum = block_sum_256<double>(sum, s_red);
+  const double *rt = c.pose + (long long)p * 12;
+  double s[2] = {0.0, 0.0};  // pairs, d2
+  icp_for_pairs(c, p, [&](int, int, const float *x, const float *y) {
+    double m[3];
+    icp_move(rt, y[0], y[1], y[2], m);
+    s[0] += 1.0;
+    s[1] += icp_d2(x[0], x[1], x[2], m);
+  });
+  block_sums_256<2>(s, s_red);
   if (tid < 12) Rt[(long long)p * 12 + tid] = rt[tid];  // (NaN where the pair is not valid: icp_init_kernel)
   if (tid == 0) {
+    const int n = (int)s[0], nb = icp_rows(c, p).nb;
     num_corr[p] = n;
     fitness[p] = (double)n / (double)(nb > 1 ? nb : 1);
-    rmse[p] = n > 0 ? sqrt(sum / (double)n) : quiet_nan();
+    rmse[p] = n > 0 ? sqrt(s[1] / (double)n) : quiet_nan();
   }
 }
 
@@ -418,127 +412,90 @@ __device__ __forceinline__ void icp_solve_compose(const double *H, const double 
   }
 }
 
+// The first pass of F_plane and F_gicp: the count of the pairs that admit(i) takes and the centroid `cen` of their moved
+// positives (one reduction).  False, to every lane, when they are fewer than `least`: the pose then stays as it was.
+template <typename Admit>
+__device__ __forceinline__ bool icp_moved_centroid(const IcpClouds &c, int p, const double *rt, Admit admit, int least,
+                                                   double *s_red, double *cen) {
+  double sm[4] = {0.0, 0.0, 0.0, 0.0};  // the count, then the moved points
+  icp_for_pairs(c, p, [&](int i, int, const float *, const float *y) {
+    if (!admit(i)) return;
+    double m[3];
+    icp_move(rt, y[0], y[1], y[2], m);
+    sm[0] += 1.0;
+    sm[1] += m[0]; sm[2] += m[1]; sm[3] += m[2];
+  });
+  block_sums_256<4>(sm, s_red);
+  const int n = (int)sm[0];
+  if (n < least) return false;  // (workgroup-uniform)
+#pragma unroll
+  for (int r = 0; r < 3; ++r) cen[r] = sm[1 + r] / (double)n;
+  return true;
+}
+
+// r = n . (x - m)
+__device__ __forceinline__ double icp_plane_residual(const float *x, const double *m, const double *n) {
+  const double dx = (double)x[0] - m[0], dy = (double)x[1] - m[1], dz = (double)x[2] - m[2];
+  return (dx * n[0] + dy * n[1]) + dz * n[2];
+}
+
 // One 256-lane workgroup per pair (include/dh3d_hip.h dh3d_icp_refine_plane F_plane): the centroid c of the moved positives
 // of the pairs, then the 21 + 6 float64 sums of H = sum a a^T and g = sum a r over a = [(m - c) x n ; n], r = n . (x - m),
-// each lane over its j in ascending order and a fixed tree; lane 0 solves H s = g by Cholesky (registers: every index is a
-// constant after unrolling) and composes the step with the pose.  Fewer than 6 pairs or a refused pivot leave the pose.
-__global__ __launch_bounds__(kThreads) void icp_plane_fit_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
-                                                                 const float *__restrict__ normals, long long n_stride,
-                                                                 const float *__restrict__ positive, long long b_stride, int Nb,
-                                                                 const int32_t *__restrict__ b_count,
-                                                                 const int32_t *__restrict__ nn, double *__restrict__ pose) {
-  __shared__ double s_red[kThreads / 64];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
-  const float *pa = anchor + (long long)p * Na * a_stride, *pn = normals + (long long)p * Na * n_stride;
-  const float *pb = positive + (long long)p * Nb * b_stride;
-  const int32_t *row = nn + (long long)p * Nb;
-  double rt[12];
+// reduced at once; lane 0 solves and composes (icp_solve_compose).  Fewer than 6 pairs or a refused pivot leave the pose.
+__global__ __launch_bounds__(kThreads) void icp_plane_fit_kernel(IcpClouds c) {
+  __shared__ double s_red[27 * (kThreads / 64)];
+  const int p = blockIdx.x;
+  double rt[12], cen[3], n[3];
 #pragma unroll
-  for (int e = 0; e < 12; ++e) rt[e] = pose[(long long)p * 12 + e];
-  double cnt = 0.0, sm[3] = {0.0, 0.0, 0.0};
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    double n[3], m[3];
-    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
-      const float *y = pb + (long long)j * b_stride;
-      icp_move(rt, y[0], y[1], y[2], m);
-      cnt += 1.0;
-      sm[0] += m[0]; sm[1] += m[1]; sm[2] += m[2];
+  for (int e = 0; e < 12; ++e) rt[e] = c.pose[(long long)p * 12 + e];
+  const auto planar = [&](int i) { return icp_plane_pair(icp_anchor_normal(c, p, i), n); };
+  if (!icp_moved_centroid(c, p, rt, planar, 6, s_red, cen)) return;
+  double S[27];  // H: the upper triangle, row by row; then g
+#pragma unroll
+  for (int e = 0; e < 27; ++e) S[e] = 0.0;
+  icp_for_pairs(c, p, [&](int i, int, const float *x, const float *y) {
+    if (!planar(i)) return;
+    double m[3];
+    icp_move(rt, y[0], y[1], y[2], m);
+    const double q0 = m[0] - cen[0], q1 = m[1] - cen[1], q2 = m[2] - cen[2];
+    const double a[6] = {q1 * n[2] - q2 * n[1], q2 * n[0] - q0 * n[2], q0 * n[1] - q1 * n[0], n[0], n[1], n[2]};
+    const double res = icp_plane_residual(x, m, n);
+    int e = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+#pragma unroll
+      for (int k = r; k < 6; ++k) S[e++] += a[r] * a[k];
+      S[21 + r] += a[r] * res;
     }
-  }
-  const int npl = (int)block_sum_256<double>(cnt, s_red);
-  if (npl < 6) return;  // the pose stays as it was (workgroup-uniform)
-  double c[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) c[r] = block_sum_256<double>(sm[r], s_red) / (double)npl;
-  double H[21], g[6];  // H: the upper triangle, row by row
-#pragma unroll
-  for (int e = 0; e < 21; ++e) H[e] = 0.0;
-#pragma unroll
-  for (int e = 0; e < 6; ++e) g[e] = 0.0;
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    double n[3], m[3];
-    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
-      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
-      icp_move(rt, y[0], y[1], y[2], m);
-      const double q0 = m[0] - c[0], q1 = m[1] - c[1], q2 = m[2] - c[2];
-      const double a[6] = {q1 * n[2] - q2 * n[1], q2 * n[0] - q0 * n[2], q0 * n[1] - q1 * n[0], n[0], n[1], n[2]};
-      const double dx = (double)x[0] - m[0], dy = (double)x[1] - m[1], dz = (double)x[2] - m[2];
-      const double res = (dx * n[0] + dy * n[1]) + dz * n[2];
-      int e = 0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-#pragma unroll
-        for (int k = r; k < 6; ++k) H[e++] += a[r] * a[k];
-        g[r] += a[r] * res;
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 21; ++e) H[e] = block_sum_256<double>(H[e], s_red);
-#pragma unroll
-  for (int e = 0; e < 6; ++e) g[e] = block_sum_256<double>(g[e], s_red);
-  if (tid == 0) icp_solve_compose(H, g, rt, c, pose + (long long)p * 12);
+  });
+  block_sums_256<27>(S, s_red);
+  if (threadIdx.x == 0) icp_solve_compose(S, S + 21, rt, cen, c.pose + (long long)p * 12);
 }
 
 // num_plane and rmse_plane of the last association under the returned pose (the sums in the fit's order)
-__global__ __launch_bounds__(kThreads) void icp_plane_stats_kernel(const float *__restrict__ anchor, long long a_stride, int Na,
-                                                                   const float *__restrict__ normals, long long n_stride,
-                                                                   const float *__restrict__ positive, long long b_stride,
-                                                                   int Nb, const int32_t *__restrict__ b_count,
-                                                                   const int32_t *__restrict__ nn, const double *__restrict__ pose,
-                                                                   int32_t *__restrict__ num_plane, double *__restrict__ rmse_plane) {
-  __shared__ double s_red[kThreads / 64];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
-  const float *pa = anchor + (long long)p * Na * a_stride, *pn = normals + (long long)p * Na * n_stride;
-  const float *pb = positive + (long long)p * Nb * b_stride;
-  const int32_t *row = nn + (long long)p * Nb;
-  const double *rt = pose + (long long)p * 12;
-  double cnt = 0.0, sum = 0.0;
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
+__global__ __launch_bounds__(kThreads) void icp_plane_stats_kernel(IcpClouds c, int32_t *__restrict__ num_plane,
+                                                                   double *__restrict__ rmse_plane) {
+  __shared__ double s_red[2 * (kThreads / 64)];
+  const int p = blockIdx.x;
+  const double *rt = c.pose + (long long)p * 12;
+  double s[2] = {0.0, 0.0};  // pairs with a normal, r^2
+  icp_for_pairs(c, p, [&](int i, int, const float *x, const float *y) {
     double n[3], m[3];
-    if (i >= 0 && icp_plane_pair(pn + (long long)i * n_stride, n)) {
-      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
-      icp_move(rt, y[0], y[1], y[2], m);
-      const double dx = (double)x[0] - m[0], dy = (double)x[1] - m[1], dz = (double)x[2] - m[2];
-      const double res = (dx * n[0] + dy * n[1]) + dz * n[2];
-      cnt += 1.0;
-      sum += res * res;
-    }
-  }
-  const int npl = (int)block_sum_256<double>(cnt, s_red);
-  sum = block_sum_256<double>(sum, s_red);
-  if (tid == 0) {
+    if (!icp_plane_pair(icp_anchor_normal(c, p, i), n)) return;
+    icp_move(rt, y[0], y[1], y[2], m);
+    const double res = icp_plane_residual(x, m, n);
+    s[0] += 1.0;
+    s[1] += res * res;
+  });
+  block_sums_256<2>(s, s_red);
+  if (threadIdx.x == 0) {
+    const int npl = (int)s[0];
     num_plane[p] = npl;
-    rmse_plane[p] = npl > 0 ? sqrt(sum / (double)npl) : quiet_nan();
+    rmse_plane[p] = npl > 0 ? sqrt(s[1] / (double)npl) : quiet_nan();
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------ gicp fit
-// N block sums at once, each by block_sum_256's tree (the wave's xor butterfly 32 .. 1, then ((w0 + w1) + w2) + w3), behind
-// one pair of barriers instead of N.  s_red holds 4 * N doubles.
-template <int N>
-__device__ __forceinline__ void block_sums_256(double *v, double *s_red) {
-#pragma unroll
-  for (int e = 0; e < N; ++e) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[e] += __shfl_xor(v[e], off, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int e = 0; e < N; ++e) s_red[4 * e + wave] = v[e];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < N; ++e) v[e] = s_red[4 * e] + s_red[4 * e + 1] + s_red[4 * e + 2] + s_red[4 * e + 3];
-}
-
 // What a pair of the generalized fit carries (include/dh3d_hip.h dh3d_icp_refine_gicp F_gicp, steps 3 to 5): the weight matrix
 // M = (C_A + C_B)^-1 as its six entries 00 01 02 11 12 22, and whether both normals are non-zero.
 struct GicpPair {
@@ -577,109 +534,73 @@ __device__ __forceinline__ GicpPair gicp_pair(const float *na, const float *kb, 
 }
 
 // One 256-lane workgroup per pair (include/dh3d_hip.h dh3d_icp_refine_gicp F_gicp): the centroid c of the moved positives of
-// all pairs, then per pair the weight matrix M and the 21 + 6 float64 sums of H = sum J^T M J and g = sum J^T M d, each
-// lane over its j in ascending order; all 27 reduced in one LDS pass (block_sums_256); lane 0 solves and composes as the
-// plane fit does.  Fewer than 3 pairs or a refused pivot leave the pose.
-__global__ __launch_bounds__(kThreads) void icp_gicp_fit_kernel(
-    const float *__restrict__ anchor, long long a_stride, int Na, const float *__restrict__ a_normals, long long an_stride,
-    const float *__restrict__ positive, long long b_stride, int Nb, const float *__restrict__ b_normals, long long bn_stride,
-    const int32_t *__restrict__ b_count, const int32_t *__restrict__ nn, double one_m_eps, double *__restrict__ pose) {
+// all pairs, then per pair the weight matrix M and the 21 + 6 float64 sums of H = sum J^T M J and g = sum J^T M d, reduced
+// at once; lane 0 solves and composes as the plane fit does.  Fewer than 3 pairs or a refused pivot leave the pose.
+__global__ __launch_bounds__(kThreads) void icp_gicp_fit_kernel(IcpClouds c, double one_m_eps) {
   __shared__ double s_red[27 * (kThreads / 64)];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
-  const float *pa = anchor + (long long)p * Na * a_stride, *pan = a_normals + (long long)p * Na * an_stride;
-  const float *pb = positive + (long long)p * Nb * b_stride, *pbn = b_normals + (long long)p * Nb * bn_stride;
-  const int32_t *row = nn + (long long)p * Nb;
-  double rt[12];
+  const int p = blockIdx.x;
+  double rt[12], cen[3];
 #pragma unroll
-  for (int e = 0; e < 12; ++e) rt[e] = pose[(long long)p * 12 + e];
-  double sm[4] = {0.0, 0.0, 0.0, 0.0};  // the count, then the moved points
-  for (int j = tid; j < nb; j += kThreads) {
-    if (row[j] >= 0) {
-      const float *y = pb + (long long)j * b_stride;
-      double m[3];
-      icp_move(rt, y[0], y[1], y[2], m);
-      sm[0] += 1.0;
-      sm[1] += m[0]; sm[2] += m[1]; sm[3] += m[2];
-    }
-  }
-  block_sums_256<4>(sm, s_red);
-  const int ng = (int)sm[0];
-  if (ng < 3) return;  // the pose stays as it was (workgroup-uniform)
-  const double c[3] = {sm[1] / (double)ng, sm[2] / (double)ng, sm[3] / (double)ng};
+  for (int e = 0; e < 12; ++e) rt[e] = c.pose[(long long)p * 12 + e];
+  if (!icp_moved_centroid(c, p, rt, [](int) { return true; }, 3, s_red, cen)) return;
   double S[27];  // H: the upper triangle, row by row; then g
 #pragma unroll
   for (int e = 0; e < 27; ++e) S[e] = 0.0;
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    if (i >= 0) {
-      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
-      double m[3];
-      icp_move(rt, y[0], y[1], y[2], m);
-      const GicpPair w = gicp_pair(pan + (long long)i * an_stride, pbn + (long long)j * bn_stride, rt, one_m_eps);
-      const double *M = w.M;
-      const double Mr[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
-      const double q0 = m[0] - c[0], q1 = m[1] - c[1], q2 = m[2] - c[2];
-      const double d[3] = {(double)x[0] - m[0], (double)x[1] - m[1], (double)x[2] - m[2]};
-      double b[6][3];  // b_v = M j_v
+  icp_for_pairs(c, p, [&](int i, int j, const float *x, const float *y) {
+    double m[3];
+    icp_move(rt, y[0], y[1], y[2], m);
+    const GicpPair w = gicp_pair(icp_anchor_normal(c, p, i), icp_positive_normal(c, p, j), rt, one_m_eps);
+    const double *M = w.M;
+    const double Mr[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
+    const double q0 = m[0] - cen[0], q1 = m[1] - cen[1], q2 = m[2] - cen[2];
+    const double d[3] = {(double)x[0] - m[0], (double)x[1] - m[1], (double)x[2] - m[2]};
+    double b[6][3];  // b_v = M j_v
 #pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        b[0][r] = Mr[r][2] * q1 - Mr[r][1] * q2;
-        b[1][r] = Mr[r][0] * q2 - Mr[r][2] * q0;
-        b[2][r] = Mr[r][1] * q0 - Mr[r][0] * q1;
-        b[3][r] = Mr[r][0]; b[4][r] = Mr[r][1]; b[5][r] = Mr[r][2];
-      }
-      int e = 0;
-#pragma unroll
-      for (int u = 0; u < 6; ++u) {
-#pragma unroll
-        for (int v = u; v < 6; ++v) {  // j_u . b_v
-          const double h = u == 0 ? q1 * b[v][2] - q2 * b[v][1] : u == 1 ? q2 * b[v][0] - q0 * b[v][2]
-                         : u == 2 ? q0 * b[v][1] - q1 * b[v][0] : b[v][u - 3];
-          S[e++] += h;
-        }
-        S[21 + u] += (b[u][0] * d[0] + b[u][1] * d[1]) + b[u][2] * d[2];
-      }
+    for (int r = 0; r < 3; ++r) {
+      b[0][r] = Mr[r][2] * q1 - Mr[r][1] * q2;
+      b[1][r] = Mr[r][0] * q2 - Mr[r][2] * q0;
+      b[2][r] = Mr[r][1] * q0 - Mr[r][0] * q1;
+      b[3][r] = Mr[r][0]; b[4][r] = Mr[r][1]; b[5][r] = Mr[r][2];
     }
-  }
+    int e = 0;
+#pragma unroll
+    for (int u = 0; u < 6; ++u) {
+#pragma unroll
+      for (int v = u; v < 6; ++v) {  // j_u . b_v
+        const double h = u == 0 ? q1 * b[v][2] - q2 * b[v][1] : u == 1 ? q2 * b[v][0] - q0 * b[v][2]
+                       : u == 2 ? q0 * b[v][1] - q1 * b[v][0] : b[v][u - 3];
+        S[e++] += h;
+      }
+      S[21 + u] += (b[u][0] * d[0] + b[u][1] * d[1]) + b[u][2] * d[2];
+    }
+  });
   block_sums_256<27>(S, s_red);
-  if (tid == 0) icp_solve_compose(S, S + 21, rt, c, pose + (long long)p * 12);
+  if (threadIdx.x == 0) icp_solve_compose(S, S + 21, rt, cen, c.pose + (long long)p * 12);
 }
 
 // num_planar and rmse_gicp of the last association under the returned pose (the sums in the fit's order)
-__global__ __launch_bounds__(kThreads) void icp_gicp_stats_kernel(
-    const float *__restrict__ anchor, long long a_stride, int Na, const float *__restrict__ a_normals, long long an_stride,
-    const float *__restrict__ positive, long long b_stride, int Nb, const float *__restrict__ b_normals, long long bn_stride,
-    const int32_t *__restrict__ b_count, const int32_t *__restrict__ nn, double one_m_eps, const double *__restrict__ pose,
-    int32_t *__restrict__ num_planar, double *__restrict__ rmse_gicp) {
+__global__ __launch_bounds__(kThreads) void icp_gicp_stats_kernel(IcpClouds c, double one_m_eps, int32_t *__restrict__ num_planar,
+                                                                  double *__restrict__ rmse_gicp) {
   __shared__ double s_red[3 * (kThreads / 64)];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const int nb = b_count ? clamp_count(b_count[p], Nb) : Nb;
-  const float *pa = anchor + (long long)p * Na * a_stride, *pan = a_normals + (long long)p * Na * an_stride;
-  const float *pb = positive + (long long)p * Nb * b_stride, *pbn = b_normals + (long long)p * Nb * bn_stride;
-  const int32_t *row = nn + (long long)p * Nb;
+  const int p = blockIdx.x;
   double rt[12];
 #pragma unroll
-  for (int e = 0; e < 12; ++e) rt[e] = pose[(long long)p * 12 + e];
+  for (int e = 0; e < 12; ++e) rt[e] = c.pose[(long long)p * 12 + e];
   double s[3] = {0.0, 0.0, 0.0};  // pairs, planar pairs, d . (M d)
-  for (int j = tid; j < nb; j += kThreads) {
-    const int i = row[j];
-    if (i >= 0) {
-      const float *x = pa + (long long)i * a_stride, *y = pb + (long long)j * b_stride;
-      double m[3];
-      icp_move(rt, y[0], y[1], y[2], m);
-      const GicpPair w = gicp_pair(pan + (long long)i * an_stride, pbn + (long long)j * bn_stride, rt, one_m_eps);
-      const double *M = w.M;
-      const double d0 = (double)x[0] - m[0], d1 = (double)x[1] - m[1], d2 = (double)x[2] - m[2];
-      const double e0 = (M[0] * d0 + M[1] * d1) + M[2] * d2, e1 = (M[1] * d0 + M[3] * d1) + M[4] * d2;
-      const double e2 = (M[2] * d0 + M[4] * d1) + M[5] * d2;
-      s[0] += 1.0;
-      s[1] += w.planar ? 1.0 : 0.0;
-      s[2] += (d0 * e0 + d1 * e1) + d2 * e2;
-    }
-  }
+  icp_for_pairs(c, p, [&](int i, int j, const float *x, const float *y) {
+    double m[3];
+    icp_move(rt, y[0], y[1], y[2], m);
+    const GicpPair w = gicp_pair(icp_anchor_normal(c, p, i), icp_positive_normal(c, p, j), rt, one_m_eps);
+    const double *M = w.M;
+    const double d0 = (double)x[0] - m[0], d1 = (double)x[1] - m[1], d2 = (double)x[2] - m[2];
+    const double e0 = (M[0] * d0 + M[1] * d1) + M[2] * d2, e1 = (M[1] * d0 + M[3] * d1) + M[4] * d2;
+    const double e2 = (M[2] * d0 + M[4] * d1) + M[5] * d2;
+    s[0] += 1.0;
+    s[1] += w.planar ? 1.0 : 0.0;
+    s[2] += (d0 * e0 + d1 * e1) + d2 * e2;
+  });
   block_sums_256<3>(s, s_red);
-  if (tid == 0) {
+  if (threadIdx.x == 0) {
     const int n = (int)s[0];
     num_planar[p] = (int)s[1];
     rmse_gicp[p] = n > 0 ? sqrt(s[2] / (double)n) : quiet_nan();
@@ -718,55 +639,62 @@ DH3D_API size_t dh3d_icp_refine_ws_bytes(int P, int Na, int Nb) {
   return icp_served(P, Na, Nb) ? carve_bytes<IcpWs>(P, Na, Nb) : 0;
 }
 
-// The launches of the three entries: normals == nullptr is the point-to-point fit; normals alone the point-to-plane fit and
-// its two outputs (num_plane, rmse_plane); with pos_normals the generalized fit at epsilon, the two outputs then being
-// num_planar and rmse_gicp.
-static int icp_run(const float *anchor, long long anchor_stride, const int32_t *anchor_count, const float *normals,
-                   long long normals_stride, const float *positive, long long positive_stride, const int32_t *positive_count,
-                   const float *pos_normals, long long pos_normals_stride, double epsilon, const double *Rt0,
-                   const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path, double *Rt,
-                   int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid, int32_t *num_plane,
-                   double *rmse_plane, void *workspace, void *stream) {
+// What the three entries refuse alike; each adds its own normals, strides, outputs and epsilon ahead of this (all of them
+// invalid-argument refusals, as the first three here, so the order between them decides nothing).
+static int icp_check(const IcpClouds &c, const double *Rt0, int P, double max_dist, int iterations, int path, const double *Rt,
+                     const int32_t *num_corr, const double *fitness, const double *rmse, const int32_t *valid,
+                     const void *workspace, size_t workspace_bytes) {
+  DH3D_REQUIRE(c.anchor && c.positive && Rt0 && Rt && c.nn && num_corr && fitness && rmse && valid);
+  DH3D_REQUIRE(P > 0 && c.Na > 0 && c.Nb > 0 && c.a_stride >= 3 && c.b_stride >= 3);
+  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
+  DH3D_SUPPORTED(icp_served(P, c.Na, c.Nb) && iterations <= kMaxIter);
+  DH3D_SUPPORTED(path != 2 || c.Na <= kGridMaxNa);
+  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+               workspace_bytes >= carve_bytes<IcpWs>(P, c.Na, c.Nb));
+  return DH3D_OK;
+}
+
+// The launches of the three entries, after icp_check: without normals the point-to-point fit; with the anchor's alone the
+// point-to-plane fit and its two outputs (num_plane, rmse_plane); with both clouds' the generalized fit at epsilon, the two
+// outputs then being num_planar and rmse_gicp.
+static int icp_run(IcpClouds c, double epsilon, const double *Rt0, const int32_t *valid0, int P, double max_dist, int iterations,
+                   int path, double *Rt, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid, int32_t *num_extra,
+                   double *rmse_extra, void *workspace, void *stream) {
   Carve carve(workspace);
-  const IcpWs ws(carve, P, Na, Nb);
-  const bool grid = (path == 0 ? dh3d_icp_plan(Na, Nb) : path) == 2;
+  const IcpWs ws(carve, P, c.Na, c.Nb);
+  const bool grid = (path == 0 ? dh3d_icp_plan(c.Na, c.Nb) : path) == 2;
   hipStream_t s = (hipStream_t)stream;
   const double r2 = max_dist * max_dist, one_m_eps = 1.0 - epsilon;
+  const dim3 fit(P), lanes(kThreads);
+  c.pose = ws.pose;
 
   hipLaunchKernelGGL(icp_init_kernel, dim3(dh3d_cdiv(P, 64)), dim3(64), 0, s, Rt0, valid0, P, ws.pose, valid);
   if (grid) {
-    hipLaunchKernelGGL(icp_pack_kernel, dim3(dh3d_cdiv(Na, kThreads), P), dim3(kThreads), 0, s, anchor, anchor_stride, Na,
-                       anchor_count, ws.packed);
-    const int st = dh3d_spatial_sort_cells(ws.packed, P, Na, reinterpret_cast<float *>(ws.sorted), ws.gbox, ws.cells, stream);
+    hipLaunchKernelGGL(icp_pack_kernel, dim3(dh3d_cdiv(c.Na, kThreads), P), lanes, 0, s, c.anchor, c.a_stride, c.Na, c.a_count,
+                       ws.packed);
+    const int st = dh3d_spatial_sort_cells(ws.packed, P, c.Na, reinterpret_cast<float *>(ws.sorted), ws.gbox, ws.cells, stream);
     if (st != DH3D_OK) return st;
   }
-  const dim3 agrid(dh3d_cdiv(Nb, kThreads), P);
+  const dim3 agrid(dh3d_cdiv(c.Nb, kThreads), P);
   for (int it = 0; it <= iterations; ++it) {
     if (grid)
-      hipLaunchKernelGGL(icp_grid_kernel, agrid, dim3(kThreads), 0, s, ws.sorted, ws.gbox, ws.cells, Na, anchor_count,
-                         positive, positive_stride, Nb, positive_count, ws.pose, valid, r2, max_dist, nn);
+      hipLaunchKernelGGL(icp_grid_kernel, agrid, lanes, 0, s, ws.sorted, ws.gbox, ws.cells, c, valid, r2, max_dist);
     else
-      hipLaunchKernelGGL(icp_scan_kernel, agrid, dim3(kThreads), 0, s, anchor, anchor_stride, Na, anchor_count, positive,
-                         positive_stride, Nb, positive_count, ws.pose, valid, r2, nn);
-    if (it < iterations && !normals)
-      hipLaunchKernelGGL(icp_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, positive, positive_stride,
-                         Nb, positive_count, nn, ws.pose);
-    else if (it < iterations && pos_normals)
-      hipLaunchKernelGGL(icp_gicp_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals, normals_stride,
-                         positive, positive_stride, Nb, pos_normals, pos_normals_stride, positive_count, nn, one_m_eps, ws.pose);
-    else if (it < iterations)
-      hipLaunchKernelGGL(icp_plane_fit_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals,
-                         normals_stride, positive, positive_stride, Nb, positive_count, nn, ws.pose);
+      hipLaunchKernelGGL(icp_scan_kernel, agrid, lanes, 0, s, c.anchor, c.a_stride, c.Na, c.a_count, c.positive, c.b_stride,
+                         c.Nb, c.b_count, c.pose, valid, r2, c.nn);
+    if (it == iterations) break;
+    if (!c.a_normals)
+      hipLaunchKernelGGL(icp_fit_kernel, fit, lanes, 0, s, c);
+    else if (c.b_normals)
+      hipLaunchKernelGGL(icp_gicp_fit_kernel, fit, lanes, 0, s, c, one_m_eps);
+    else
+      hipLaunchKernelGGL(icp_plane_fit_kernel, fit, lanes, 0, s, c);
   }
-  hipLaunchKernelGGL(icp_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, positive, positive_stride, Nb,
-                     positive_count, nn, ws.pose, Rt, num_corr, fitness, rmse);
-  if (pos_normals)
-    hipLaunchKernelGGL(icp_gicp_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals, normals_stride,
-                       positive, positive_stride, Nb, pos_normals, pos_normals_stride, positive_count, nn, one_m_eps, ws.pose,
-                       num_plane, rmse_plane);
-  else if (normals)
-    hipLaunchKernelGGL(icp_plane_stats_kernel, dim3(P), dim3(kThreads), 0, s, anchor, anchor_stride, Na, normals,
-                       normals_stride, positive, positive_stride, Nb, positive_count, nn, ws.pose, num_plane, rmse_plane);
+  hipLaunchKernelGGL(icp_stats_kernel, fit, lanes, 0, s, c, Rt, num_corr, fitness, rmse);
+  if (c.b_normals)
+    hipLaunchKernelGGL(icp_gicp_stats_kernel, fit, lanes, 0, s, c, one_m_eps, num_extra, rmse_extra);
+  else if (c.a_normals)
+    hipLaunchKernelGGL(icp_plane_stats_kernel, fit, lanes, 0, s, c, num_extra, rmse_extra);
   return dh3d_launch_status();
 }
 
@@ -775,15 +703,11 @@ DH3D_API int dh3d_icp_refine(const float *anchor, long long anchor_stride, const
                              const int32_t *valid0, int P, int Na, int Nb, double max_dist, int iterations, int path,
                              double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
                              void *workspace, size_t workspace_bytes, void *stream) {
-  DH3D_REQUIRE(anchor && positive && Rt0 && Rt && nn && num_corr && fitness && rmse && valid);
-  DH3D_REQUIRE(P > 0 && Na > 0 && Nb > 0 && anchor_stride >= 3 && positive_stride >= 3);
-  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
-  DH3D_SUPPORTED(icp_served(P, Na, Nb) && iterations <= kMaxIter);
-  DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
-  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-               workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
-  return icp_run(anchor, anchor_stride, anchor_count, nullptr, 0, positive, positive_stride, positive_count, nullptr, 0, 0.0,
-                 Rt0, valid0, P, Na, Nb, max_dist, iterations, path, Rt, nn, num_corr, fitness, rmse, valid, nullptr, nullptr,
+  const IcpClouds c{anchor, nullptr, positive, nullptr, anchor_stride, 0, positive_stride, 0, Na, Nb, anchor_count,
+                    positive_count, nn, nullptr};
+  const int st = icp_check(c, Rt0, P, max_dist, iterations, path, Rt, num_corr, fitness, rmse, valid, workspace, workspace_bytes);
+  if (st != DH3D_OK) return st;
+  return icp_run(c, 0.0, Rt0, valid0, P, max_dist, iterations, path, Rt, num_corr, fitness, rmse, valid, nullptr, nullptr,
                  workspace, stream);
 }
 
@@ -796,17 +720,13 @@ DH3D_API int dh3d_icp_refine_plane(const float *anchor, long long anchor_stride,
                                    double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
                                    int32_t *num_plane, double *rmse_plane, void *workspace, size_t workspace_bytes,
                                    void *stream) {
-  DH3D_REQUIRE(anchor && anchor_normals && positive && Rt0 && Rt && nn && num_corr && fitness && rmse && valid && num_plane &&
-               rmse_plane);
-  DH3D_REQUIRE(P > 0 && Na > 0 && Nb > 0 && anchor_stride >= 3 && normals_stride >= 3 && positive_stride >= 3);
-  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
-  DH3D_SUPPORTED(icp_served(P, Na, Nb) && iterations <= kMaxIter);
-  DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
-  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-               workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
-  return icp_run(anchor, anchor_stride, anchor_count, anchor_normals, normals_stride, positive, positive_stride, positive_count,
-                 nullptr, 0, 0.0, Rt0, valid0, P, Na, Nb, max_dist, iterations, path, Rt, nn, num_corr, fitness, rmse, valid,
-                 num_plane, rmse_plane, workspace, stream);
+  const IcpClouds c{anchor, anchor_normals, positive, nullptr, anchor_stride, normals_stride, positive_stride, 0, Na, Nb,
+                    anchor_count, positive_count, nn, nullptr};
+  DH3D_REQUIRE(anchor_normals && normals_stride >= 3 && num_plane && rmse_plane);
+  const int st = icp_check(c, Rt0, P, max_dist, iterations, path, Rt, num_corr, fitness, rmse, valid, workspace, workspace_bytes);
+  if (st != DH3D_OK) return st;
+  return icp_run(c, 0.0, Rt0, valid0, P, max_dist, iterations, path, Rt, num_corr, fitness, rmse, valid, num_plane, rmse_plane,
+                 workspace, stream);
 }
 
 DH3D_API size_t dh3d_icp_refine_gicp_ws_bytes(int P, int Na, int Nb) { return dh3d_icp_refine_ws_bytes(P, Na, Nb); }
@@ -818,17 +738,13 @@ DH3D_API int dh3d_icp_refine_gicp(const float *anchor, long long anchor_stride, 
                                   double max_dist, int iterations, int path, double epsilon, double *Rt, int32_t *nn,
                                   int32_t *num_corr, double *fitness, double *rmse, int32_t *valid, int32_t *num_planar,
                                   double *rmse_gicp, void *workspace, size_t workspace_bytes, void *stream) {
-  DH3D_REQUIRE(anchor && anchor_normals && positive_normals && positive && Rt0 && Rt && nn && num_corr && fitness && rmse &&
-               valid && num_planar && rmse_gicp);
-  DH3D_REQUIRE(P > 0 && Na > 0 && Nb > 0 && anchor_stride >= 3 && normals_stride >= 3 && positive_normals_stride >= 3 &&
-               positive_stride >= 3);
-  DH3D_REQUIRE(max_dist > 0.0 && isfinite(max_dist) && iterations >= 0 && path >= 0 && path <= 2);
+  const IcpClouds c{anchor, anchor_normals, positive, positive_normals, anchor_stride, normals_stride, positive_stride,
+                    positive_normals_stride, Na, Nb, anchor_count, positive_count, nn, nullptr};
+  DH3D_REQUIRE(anchor_normals && positive_normals && normals_stride >= 3 && positive_normals_stride >= 3 && num_planar &&
+               rmse_gicp);
   DH3D_REQUIRE(epsilon > 0.0 && epsilon <= 1.0);  // (NaN fails both)
-  DH3D_SUPPORTED(icp_served(P, Na, Nb) && iterations <= kMaxIter);
-  DH3D_SUPPORTED(path != 2 || Na <= kGridMaxNa);
-  DH3D_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
-               workspace_bytes >= carve_bytes<IcpWs>(P, Na, Nb));
-  return icp_run(anchor, anchor_stride, anchor_count, anchor_normals, normals_stride, positive, positive_stride, positive_count,
-                 positive_normals, positive_normals_stride, epsilon, Rt0, valid0, P, Na, Nb, max_dist, iterations, path, Rt, nn,
-                 num_corr, fitness, rmse, valid, num_planar, rmse_gicp, workspace, stream);
+  const int st = icp_check(c, Rt0, P, max_dist, iterations, path, Rt, num_corr, fitness, rmse, valid, workspace, workspace_bytes);
+  if (st != DH3D_OK) return st;
+  return icp_run(c, epsilon, Rt0, valid0, P, max_dist, iterations, path, Rt, num_corr, fitness, rmse, valid, num_planar,
+                 rmse_gicp, workspace, stream);
 }

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_kernel(
   __shared__ int s_wave[kRansacWaves];
   __shared__ int s_cnt[kRansacThreads];
   __shared__ int s_done, s_win, s_kstar;
-  __shared__ double s_red[kRansacWaves];
+  __shared__ double s_red[10 * kRansacWaves];  // block_rigid_fit_256
   const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
   Corr s;
   s.x0 = s_dyn;
@@ -272,37 +272,13 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_kernel(
     return;
   }
 
-  // (4) least-squares refit on the inliers: float64 sums, each lane over its slots in order, then a fixed tree
-  double sx[3] = {0.0, 0.0, 0.0}, sy[3] = {0.0, 0.0, 0.0};
-  for (int j = tid; j < n; j += kRansacThreads) {
-    if (n == 3 || is_inlier(s, j, R, t, thr)) {
-      sx[0] += s.x0[j]; sx[1] += s.x1[j]; sx[2] += s.x2[j];
-      sy[0] += s.y0[j]; sy[1] += s.y1[j]; sy[2] += s.y2[j];
-    }
-  }
-  double xc[3], yc[3];
-  for (int r = 0; r < 3; ++r) {
-    xc[r] = block_sum_256<double>(sx[r], s_red) / (double)count;
-    yc[r] = block_sum_256<double>(sy[r], s_red) / (double)count;
-  }
-  double B[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int j = tid; j < n; j += kRansacThreads) {
-    if (n == 3 || is_inlier(s, j, R, t, thr))
-      accumulate_b(B, s.x0[j] - xc[0], s.x1[j] - xc[1], s.x2[j] - xc[2], s.y0[j] - yc[0], s.y1[j] - yc[1],
-                   s.y2[j] - yc[2]);
-  }
-  for (int e = 0; e < 10; ++e) B[e] = block_sum_256<double>(B[e], s_red);
-  if (tid == 0) {
-    double Rf[9], tf[3];
-    rotation_from_b(B, Rf);
-    translation(Rf, xc, yc, tf);
-    for (int r = 0; r < 3; ++r) {
-      rt[4 * r] = Rf[3 * r];
-      rt[4 * r + 1] = Rf[3 * r + 1];
-      rt[4 * r + 2] = Rf[3 * r + 2];
-      rt[4 * r + 3] = tf[r];
-    }
-  }
+  // (4) least-squares refit on the inliers (count of them: at least 3 here)
+  block_rigid_fit_256(n, [&](int j, float *x, float *y) {
+    if (n != 3 && !is_inlier(s, j, R, t, thr)) return false;
+    x[0] = s.x0[j]; x[1] = s.x1[j]; x[2] = s.x2[j];
+    y[0] = s.y0[j]; y[1] = s.y1[j]; y[2] = s.y2[j];
+    return true;
+  }, s_red, rt);
 }
 
 size_t ransac_lds_bytes(int Ma) { return (size_t)Ma * (6 * sizeof(float) + sizeof(int)); }

@@ -1,8 +1,11 @@
 // The float64 rigid fit of estimateRigidTransform.m that csrc/registration.hip (RANSAC trial models and the refit) and
 // csrc/icp.hip (the fit of every ICP iteration) share: one copy, one set of roundings.  Both files are built without
-// contraction (csrc/Makefile EXACT).  The block sums of the refits are common.h's block_sum_256<double>.
+// contraction (csrc/Makefile EXACT).  block_rigid_fit_256 is the fit of a workgroup over many pairs: RANSAC's refit on the
+// inliers and the fit of a point-to-point ICP iteration.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "common.h"
 
 namespace {
 
@@ -157,6 +160,44 @@ __device__ __forceinline__ double smallest_eigenvector_3(const double *Cu, doubl
 // t = xc - R yc
 __device__ __forceinline__ void translation(const double *R, const double *xc, const double *yc, double *t) {
   for (int r = 0; r < 3; ++r) t[r] = xc[r] - (R[3 * r] * yc[0] + R[3 * r + 1] * yc[1] + R[3 * r + 2] * yc[2]);
+}
+
+// The least-squares fit of a 256-lane workgroup over the pairs of `slots` slots: pair(j, x, y) fills slot j's anchor x[3]
+// and positive y[3] and returns true, or returns false for a slot without a pair.  Float64 sums, each lane over its slots
+// j = lane, lane + 256, ... in order, then block_sums_256's fixed tree: the count and the centroids, then B over the centred
+// pairs; lane 0 solves and writes the 3 x 4 rt.  Returns the number of pairs to every lane; fewer than 3 leave rt as it
+// was (workgroup-uniform).  s_red: 40 doubles.
+template <typename Pair>
+__device__ __forceinline__ int block_rigid_fit_256(int slots, Pair pair, double *s_red, double *rt) {
+  float x[3], y[3];
+  double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // the count, the anchors, the positives
+  for (int j = threadIdx.x; j < slots; j += 256) {
+    if (pair(j, x, y)) {
+      s[0] += 1.0;
+      s[1] += x[0]; s[2] += x[1]; s[3] += x[2];
+      s[4] += y[0]; s[5] += y[1]; s[6] += y[2];
+    }
+  }
+  block_sums_256<7>(s, s_red);
+  const int n = (int)s[0];
+  if (n < 3) return n;
+  const double xc[3] = {s[1] / (double)n, s[2] / (double)n, s[3] / (double)n};
+  const double yc[3] = {s[4] / (double)n, s[5] / (double)n, s[6] / (double)n};
+  double B[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = threadIdx.x; j < slots; j += 256) {
+    if (pair(j, x, y)) accumulate_b(B, x[0] - xc[0], x[1] - xc[1], x[2] - xc[2], y[0] - yc[0], y[1] - yc[1], y[2] - yc[2]);
+  }
+  block_sums_256<10>(B, s_red);
+  if (threadIdx.x == 0) {
+    double Rf[9], tf[3];
+    rotation_from_b(B, Rf);
+    translation(Rf, xc, yc, tf);
+    for (int r = 0; r < 3; ++r) {
+      for (int k = 0; k < 3; ++k) rt[4 * r + k] = Rf[3 * r + k];
+      rt[4 * r + 3] = tf[r];
+    }
+  }
+  return n;
 }
 
 }  // namespace

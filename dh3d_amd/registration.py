@@ -204,33 +204,25 @@ def _icp_call(anchor_points, positive_points, Rt, valid, anchor_count, positive_
     fitness = torch.empty((P,), dtype=torch.float64, device=dev)
     rmse = torch.empty((P,), dtype=torch.float64, device=dev)
     ok = torch.empty((P,), dtype=torch.int32, device=dev)
+    # per method: the entry, what it takes between anchor_count and the positive and behind `path`, its two extra outputs
+    nrm = lambda t: (L.ptr(t), t.stride(1))
     if normals is None:
-        with torch.cuda.device(dev):
-            L.check(lib.dh3d_icp_refine(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(b), b.stride(1), L.ptr(bc), L.ptr(rt0),
-                                        L.ptr(valid), P, Na, Nb, max_dist, iterations, path, L.ptr(out_rt), L.ptr(nn),
-                                        L.ptr(num_corr), L.ptr(fitness), L.ptr(rmse), L.ptr(ok), L.ptr(ws), ws.numel(),
-                                        L.stream_ptr()), "refine_icp")
-        return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse)
-    num_plane = torch.empty((P,), dtype=torch.int32, device=dev)
-    rmse_plane = torch.empty((P,), dtype=torch.float64, device=dev)
-    if positive_normals is not None:
-        pn = positive_normals
-        with torch.cuda.device(dev):
-            L.check(lib.dh3d_icp_refine_gicp(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(normals), normals.stride(1), L.ptr(pn),
-                                             pn.stride(1), L.ptr(b), b.stride(1), L.ptr(bc), L.ptr(rt0), L.ptr(valid), P, Na, Nb,
-                                             max_dist, iterations, path, epsilon, L.ptr(out_rt), L.ptr(nn), L.ptr(num_corr),
-                                             L.ptr(fitness), L.ptr(rmse), L.ptr(ok), L.ptr(num_plane), L.ptr(rmse_plane),
-                                             L.ptr(ws), ws.numel(), L.stream_ptr()), "refine_icp_gicp")
-        return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse, num_planar=num_plane,
-                    rmse_gicp=rmse_plane)
+        what, entry, more, tail, extra = "refine_icp", lib.dh3d_icp_refine, (), (), ()
+    elif positive_normals is None:
+        what, entry, more, tail = "refine_icp_plane", lib.dh3d_icp_refine_plane, nrm(normals), ()
+        extra = ("num_plane", "rmse_plane")
+    else:
+        what, entry, more, tail = "refine_icp_gicp", lib.dh3d_icp_refine_gicp, nrm(normals) + nrm(positive_normals), (epsilon,)
+        extra = ("num_planar", "rmse_gicp")
+    res = dict(Rt=out_rt, valid=ok, nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse)
+    for name, dtype in zip(extra, (torch.int32, torch.float64)):
+        res[name] = torch.empty((P,), dtype=dtype, device=dev)
     with torch.cuda.device(dev):
-        L.check(lib.dh3d_icp_refine_plane(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(normals), normals.stride(1), L.ptr(b),
-                                          b.stride(1), L.ptr(bc), L.ptr(rt0), L.ptr(valid), P, Na, Nb, max_dist, iterations,
-                                          path, L.ptr(out_rt), L.ptr(nn), L.ptr(num_corr), L.ptr(fitness), L.ptr(rmse),
-                                          L.ptr(ok), L.ptr(num_plane), L.ptr(rmse_plane), L.ptr(ws), ws.numel(),
-                                          L.stream_ptr()), "refine_icp_plane")
-    return dict(Rt=out_rt, valid=ok.bool(), nn=nn, num_corr=num_corr, fitness=fitness, rmse=rmse, num_plane=num_plane,
-                rmse_plane=rmse_plane)
+        L.check(entry(L.ptr(a), a.stride(1), L.ptr(ac), *more, L.ptr(b), b.stride(1), L.ptr(bc), L.ptr(rt0), L.ptr(valid), P, Na, Nb,
+                      max_dist, iterations, path, *tail, L.ptr(out_rt), L.ptr(nn), L.ptr(num_corr), L.ptr(fitness), L.ptr(rmse),
+                      L.ptr(ok), *(L.ptr(res[name]) for name in extra), L.ptr(ws), ws.numel(), L.stream_ptr()), what)
+    res["valid"] = ok.bool()
+    return res
 
 
 NORMALS_MAX_K = 64  # csrc/normals.hip kMaxK
@@ -457,14 +449,20 @@ def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None
     out["match"], out["dist"] = match, dist
     out["anchor_ids"], out["positive_ids"] = idl
     if rkw is not None:
-        icp = refine_pose(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv[0], positive_count=nv[1], **rkw)
-        out["Rt_ransac"], out["Rt"] = out["Rt"], icp["Rt"]
-        out["fitness"], out["rmse"], out["num_corr_icp"], out["nn"] = icp["fitness"], icp["rmse"], icp["num_corr"], icp["nn"]
-        if "rmse_plane" in icp:
-            out["num_plane"], out["rmse_plane"] = icp["num_plane"], icp["rmse_plane"]
-        if "rmse_gicp" in icp:
-            out["num_planar"], out["rmse_gicp"] = icp["num_planar"], icp["rmse_gicp"]
+        _merge_refinement(out, refine_pose(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv[0],
+                                           positive_count=nv[1], **rkw))
     return out
+
+
+def _merge_refinement(out, icp, before="Rt_ransac", dense=True):
+    """A refine_pose result `icp` into the registration result `out`, in place: Rt becomes the refined pose and the pose so
+    far moves to `before`; fitness and rmse, and the method's own rmse_plane / rmse_gicp.  dense (register_fpfh,
+    register_clouds): also num_corr_icp, nn and the method's count num_plane / num_planar."""
+    out[before], out["Rt"] = out["Rt"], icp["Rt"]
+    names = dict(fitness="fitness", rmse="rmse", rmse_plane="rmse_plane", rmse_gicp="rmse_gicp")
+    if dense:
+        names.update(num_corr="num_corr_icp", nn="nn", num_plane="num_plane", num_planar="num_planar")
+    out.update((names[k], v) for k, v in icp.items() if k in names)
 
 
 def refine_pose(anchor_points, positive_points, Rt, valid=None, anchor_count=None, positive_count=None, method="point", **kw):
@@ -507,13 +505,8 @@ def register_clouds(model, anchor_points, positive_points, num_valid=None, refin
     ob = model.forward(positive_points, fetch=fetch, num_valid=nv_b)
     out = register(oa["xyz_feat_att_nms"], oa["kp_count"], ob["xyz_feat_att_nms"], ob["kp_count"], **kw)
     if rkw is not None:
-        icp = refine_pose(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv_a, positive_count=nv_b, **rkw)
-        out["Rt_ransac"], out["Rt"] = out["Rt"], icp["Rt"]
-        out["fitness"], out["rmse"], out["num_corr_icp"], out["nn"] = icp["fitness"], icp["rmse"], icp["num_corr"], icp["nn"]
-        if "rmse_plane" in icp:
-            out["num_plane"], out["rmse_plane"] = icp["num_plane"], icp["rmse_plane"]
-        if "rmse_gicp" in icp:
-            out["num_planar"], out["rmse_gicp"] = icp["num_planar"], icp["rmse_gicp"]
+        _merge_refinement(out, refine_pose(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv_a,
+                                           positive_count=nv_b, **rkw))
     return out
 
 

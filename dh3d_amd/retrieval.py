@@ -240,12 +240,7 @@ class PlaceIndex:
             icp = registration.refine_pose(self.cloud.index_select(0, safe_place), query_cloud, out["Rt"], any_ok,
                                            anchor_count=self.cloud_count.index_select(0, safe_place),
                                            positive_count=query_cloud_count, **rkw)
-            out["Rt_ransac"], out["Rt"] = out["Rt"], icp["Rt"]
-            out["fitness"], out["rmse"] = icp["fitness"], icp["rmse"]
-            if "rmse_plane" in icp:
-                out["rmse_plane"] = icp["rmse_plane"]
-            if "rmse_gicp" in icp:
-                out["rmse_gicp"] = icp["rmse_gicp"]
+            registration._merge_refinement(out, icp, dense=False)
         return out
 
 

@@ -214,10 +214,5 @@ def relocalize_scan_context(index, points, num_valid=None, center=None, k=1, can
         icp = registration.refine_pose(index.places.cloud.index_select(0, safe), points, out["Rt"], valid,
                                        anchor_count=index.places.cloud_count.index_select(0, safe), positive_count=num_valid,
                                        **rkw)
-        out["Rt_scan"], out["Rt"] = out["Rt"], icp["Rt"]
-        out["fitness"], out["rmse"] = icp["fitness"], icp["rmse"]
-        if "rmse_plane" in icp:
-            out["rmse_plane"] = icp["rmse_plane"]
-        if "rmse_gicp" in icp:
-            out["rmse_gicp"] = icp["rmse_gicp"]
+        registration._merge_refinement(out, icp, before="Rt_scan", dense=False)
     return out

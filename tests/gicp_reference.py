@@ -106,18 +106,7 @@ def fit_gicp(anchor, a_normal, positive, b_normal, nn, Rt, epsilon=1e-3, order="
     if len(j) < 3:
         return None, info
     H, g, c = system(m, d, M, order)
-    with np.errstate(all="ignore"):
-        info["cond"] = float(np.linalg.cond(H))
-    s, info["pivot"] = pr.cholesky_solve(H, g)
-    if s is None or not np.isfinite(s).all():
-        return None, info
-    info["s"] = s
-    dR = pr.step_rotation(s[:3])
-    R, t = Rt[:, :3], Rt[:, 3]
-    Rn = np.stack([(dR[:, 0] * R[0, k] + dR[:, 1] * R[1, k]) + dR[:, 2] * R[2, k] for k in range(3)], axis=1)
-    u = t - c
-    tn = (((dR[:, 0] * u[0] + dR[:, 1] * u[1]) + dR[:, 2] * u[2]) + c) + s[3:]
-    return np.concatenate([Rn, tn[:, None]], axis=1), info
+    return pr.solve_compose(H, g, c, Rt, info)
 
 
 def gicp_stats(anchor, a_normal, positive, b_normal, nn, Rt, epsilon=1e-3, order="numpy"):
@@ -136,36 +125,14 @@ def icp_gicp(anchor, a_normal, positive, b_normal, Rt0, max_dist=1.0, iterations
     state with num_planar and rmse_gicp besides, and the margins gap / thr, cond (the largest cond(H) of a step taken), pivot
     (the smallest Cholesky pivot ratio of a step taken), refused (the largest pivot ratio that made a step with 3 or more pairs
     leave the pose; -inf without one) and det (the smallest det(W) of a fit)."""
-    anchor, positive = np.asarray(anchor, np.float32), np.asarray(positive, np.float32)
     a_normal, b_normal = np.asarray(a_normal, np.float32), np.asarray(b_normal, np.float32)
-    Na, Nb = len(anchor), len(positive)
-    na = Na if na is None else min(max(int(na), 0), Na)
-    nb = Nb if nb is None else min(max(int(nb), 0), Nb)
-    Rt = np.array(Rt0, np.float64)
-    out = dict(valid=bool(valid0) and bool(np.isfinite(Rt).all()), states=[], gap=np.inf, thr=np.inf, cond=0.0, pivot=np.inf,
-               refused=-np.inf, det=np.inf)
-    if not out["valid"]:
-        dead = dict(Rt=np.full((3, 4), np.nan), nn=np.full(Nb, -1, np.int32), num_corr=0, rmse=np.nan, fitness=0.0,
-                    num_planar=0, rmse_gicp=np.nan)
-        out["states"] = [dead] * (iterations + 1)
-        return out
-    for k in range(iterations + 1):
-        nn = np.full(Nb, -1, np.int32)
-        nn[:nb], d2, gap, thr = ir.associate(anchor[:na], positive[:nb], Rt, max_dist)
-        n = int((nn >= 0).sum())
-        out["gap"], out["thr"] = min(out["gap"], gap), min(out["thr"], thr)
-        npl, rg = gicp_stats(anchor, a_normal, positive, b_normal, nn, Rt, epsilon, order)
-        out["states"].append(dict(Rt=Rt.copy(), nn=nn, num_corr=n, fitness=n / max(nb, 1),
-                                  rmse=math.sqrt(d2[np.isfinite(d2)].sum() / n) if n else np.nan, num_planar=npl, rmse_gicp=rg))
-        if k < iterations:
-            new, info = fit_gicp(anchor, a_normal, positive, b_normal, nn, Rt, epsilon, order)
-            out["det"] = min(out["det"], info["det"])
-            if new is not None:
-                out["cond"], out["pivot"] = max(out["cond"], info["cond"]), min(out["pivot"], info["pivot"])
-                Rt = new
-            elif info["n_g"] >= 3:
-                out["refused"] = max(out["refused"], info["pivot"])
-    return out
+
+    def step(anchor, positive, nn, Rt, out):
+        new, info = fit_gicp(anchor, a_normal, positive, b_normal, nn, Rt, epsilon, order)
+        out["det"] = min(out["det"], info["det"])
+        return pr.take_step(out, new, info, info["n_g"] >= 3)
+    return ir.loop(anchor, positive, Rt0, step, lambda a, y, nn, Rt: gicp_stats(a, a_normal, y, b_normal, nn, Rt, epsilon, order),
+                   ("num_planar", "rmse_gicp"), dict(pr.SOLVE_MARGINS, det=np.inf), max_dist, iterations, na, nb, valid0)
 
 
 def is_clear(run):

@@ -134,6 +134,27 @@ def step_rotation(w):
     return (np.eye(3) + A * K) + B * K2
 
 
+def compose(Rt, s, c):
+    """The step s = (rotation vector, translation) about the centroid c composed with the pose Rt, in the header's order."""
+    dR = step_rotation(s[:3])
+    R, t = Rt[:, :3], Rt[:, 3]
+    Rn = np.stack([(dR[:, 0] * R[0, k] + dR[:, 1] * R[1, k]) + dR[:, 2] * R[2, k] for k in range(3)], axis=1)
+    u = t - c
+    tn = (((dR[:, 0] * u[0] + dR[:, 1] * u[1]) + dR[:, 2] * u[2]) + c) + s[3:]
+    return np.concatenate([Rn, tn[:, None]], axis=1)
+
+
+def solve_compose(H, g, c, Rt, info):
+    """The end of F_plane and F_gicp: (the new Rt or None on a refused pivot or a non-finite s, info with cond / pivot / s)."""
+    with np.errstate(all="ignore"):
+        info["cond"] = float(np.linalg.cond(H))
+    s, info["pivot"] = cholesky_solve(H, g)
+    if s is None or not np.isfinite(s).all():
+        return None, info
+    info["s"] = s
+    return compose(Rt, s, c), info
+
+
 def fit_plane(anchor, normal, positive, nn, Rt):
     """F_plane(nn, pose): (the new Rt [3, 4] or None when the pose stays, info dict n_pl / cond / pivot / s)."""
     j, a, r, c = rows(anchor, normal, positive, nn, Rt)
@@ -142,18 +163,7 @@ def fit_plane(anchor, normal, positive, nn, Rt):
         return None, info
     H = (a[:, :, None] * a[:, None, :]).sum(axis=0)
     g = (a * r[:, None]).sum(axis=0)
-    with np.errstate(all="ignore"):
-        info["cond"] = float(np.linalg.cond(H))
-    s, info["pivot"] = cholesky_solve(H, g)
-    if s is None or not np.isfinite(s).all():
-        return None, info
-    info["s"] = s
-    dR = step_rotation(s[:3])
-    R, t = Rt[:, :3], Rt[:, 3]
-    Rn = np.stack([(dR[:, 0] * R[0, k] + dR[:, 1] * R[1, k]) + dR[:, 2] * R[2, k] for k in range(3)], axis=1)
-    u = t - c
-    tn = (((dR[:, 0] * u[0] + dR[:, 1] * u[1]) + dR[:, 2] * u[2]) + c) + s[3:]
-    return np.concatenate([Rn, tn[:, None]], axis=1), info
+    return solve_compose(H, g, c, Rt, info)
 
 
 def plane_stats(anchor, normal, positive, nn, Rt):
@@ -166,35 +176,26 @@ def icp_plane(anchor, normal, positive, Rt0, max_dist=1.0, iterations=20, na=Non
     and rmse_plane besides, and the margins gap / thr, cond (the largest cond(H) of a step taken), pivot (the smallest
     Cholesky pivot ratio of a step taken) and refused (the largest pivot ratio that made a step with 6 or more pairs leave the
     pose; -inf without one)."""
-    anchor, positive = np.asarray(anchor, np.float32), np.asarray(positive, np.float32)
     normal = np.asarray(normal, np.float32)
-    Na, Nb = len(anchor), len(positive)
-    na = Na if na is None else min(max(int(na), 0), Na)
-    nb = Nb if nb is None else min(max(int(nb), 0), Nb)
-    Rt = np.array(Rt0, np.float64)
-    out = dict(valid=bool(valid0) and bool(np.isfinite(Rt).all()), states=[], gap=np.inf, thr=np.inf, cond=0.0, pivot=np.inf,
-               refused=-np.inf)
-    if not out["valid"]:
-        dead = dict(Rt=np.full((3, 4), np.nan), nn=np.full(Nb, -1, np.int32), num_corr=0, rmse=np.nan, fitness=0.0,
-                    num_plane=0, rmse_plane=np.nan)
-        out["states"] = [dead] * (iterations + 1)
-        return out
-    for k in range(iterations + 1):
-        nn = np.full(Nb, -1, np.int32)
-        nn[:nb], d2, gap, thr = ir.associate(anchor[:na], positive[:nb], Rt, max_dist)
-        n = int((nn >= 0).sum())
-        out["gap"], out["thr"] = min(out["gap"], gap), min(out["thr"], thr)
-        npl, rp = plane_stats(anchor, normal, positive, nn, Rt)
-        out["states"].append(dict(Rt=Rt.copy(), nn=nn, num_corr=n, fitness=n / max(nb, 1),
-                                  rmse=math.sqrt(d2[np.isfinite(d2)].sum() / n) if n else np.nan, num_plane=npl, rmse_plane=rp))
-        if k < iterations:
-            new, info = fit_plane(anchor, normal, positive, nn, Rt)
-            if new is not None:
-                out["cond"], out["pivot"] = max(out["cond"], info["cond"]), min(out["pivot"], info["pivot"])
-                Rt = new
-            elif info["n_pl"] >= 6:
-                out["refused"] = max(out["refused"], info["pivot"])
-    return out
+
+    def step(anchor, positive, nn, Rt, out):
+        new, info = fit_plane(anchor, normal, positive, nn, Rt)
+        return take_step(out, new, info, info["n_pl"] >= 6)
+    return ir.loop(anchor, positive, Rt0, step, lambda a, y, nn, Rt: plane_stats(a, normal, y, nn, Rt),
+                   ("num_plane", "rmse_plane"), SOLVE_MARGINS, max_dist, iterations, na, nb, valid0)
+
+
+SOLVE_MARGINS = dict(cond=0.0, pivot=np.inf, refused=-np.inf)  # where icp_plane's and icp_gicp's margins of the solve start
+
+
+def take_step(out, new, info, enough):
+    """The margins of a step of icp_plane / icp_gicp into the run `out`: cond and pivot of a step taken, refused of one that
+    had `enough` pairs and left the pose.  Returns new."""
+    if new is not None:
+        out["cond"], out["pivot"] = max(out["cond"], info["cond"]), min(out["pivot"], info["pivot"])
+    elif enough:
+        out["refused"] = max(out["refused"], info["pivot"])
+    return new
 
 
 def demo_normals(anchor, k=16, n=None):

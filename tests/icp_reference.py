@@ -59,18 +59,22 @@ def fit(anchor, positive, nn):
     return np.concatenate([R[0], t[0][:, None]], axis=1), float(g[0])
 
 
-def icp(anchor, positive, Rt0, max_dist=1.0, iterations=20, na=None, nb=None, valid0=True):
-    """dh3d_icp_refine on one pair: anchor [Na, 3], positive [Nb, 3] float32, Rt0 [3, 4].  Returns a dict: valid, states (a
-    list of iterations + 1 dicts Rt / nn [Nb] / num_corr / rmse / fitness: entry k is the result of the call with
-    iterations = k), and the margins gap / thr / eig over the whole run."""
+def loop(anchor, positive, Rt0, step, stats, extra, margins, max_dist, iterations, na, nb, valid0):
+    """The loop of the three rules on one pair: anchor [Na, 3], positive [Nb, 3] float32, Rt0 [3, 4].  step(anchor, positive,
+    nn, Rt, out) is the rule's fit: the new pose or None when the pose stays; it keeps its own margins in out, which start
+    as `margins`.  stats(anchor, positive, nn, Rt) gives the rule's two extra outputs, named by `extra` (all three empty for
+    the point rule).  Returns a dict: valid, states (a list of iterations + 1 dicts Rt / nn [Nb] / num_corr / rmse / fitness
+    and the extras: entry k is the result of the call with iterations = k), the association's margins gap / thr and the
+    fit's over the whole run."""
     anchor, positive = np.asarray(anchor, np.float32), np.asarray(positive, np.float32)
     Na, Nb = len(anchor), len(positive)
     na = Na if na is None else min(max(int(na), 0), Na)
     nb = Nb if nb is None else min(max(int(nb), 0), Nb)
     Rt = np.array(Rt0, np.float64)
-    out = dict(valid=bool(valid0) and bool(np.isfinite(Rt).all()), states=[], gap=np.inf, thr=np.inf, eig=np.inf)
+    out = dict(valid=bool(valid0) and bool(np.isfinite(Rt).all()), states=[], gap=np.inf, thr=np.inf, **margins)
     if not out["valid"]:
-        dead = dict(Rt=np.full((3, 4), np.nan), nn=np.full(Nb, -1, np.int32), num_corr=0, rmse=np.nan, fitness=0.0)
+        dead = dict(Rt=np.full((3, 4), np.nan), nn=np.full(Nb, -1, np.int32), num_corr=0, rmse=np.nan, fitness=0.0,
+                    **dict(zip(extra, (0, np.nan))))
         out["states"] = [dead] * (iterations + 1)
         return out
     for k in range(iterations + 1):
@@ -79,13 +83,23 @@ def icp(anchor, positive, Rt0, max_dist=1.0, iterations=20, na=None, nb=None, va
         n = int((nn >= 0).sum())
         out["gap"], out["thr"] = min(out["gap"], gap), min(out["thr"], thr)
         out["states"].append(dict(Rt=Rt.copy(), nn=nn, num_corr=n, fitness=n / max(nb, 1),
-                                  rmse=math.sqrt(d2[np.isfinite(d2)].sum() / n) if n else np.nan))
+                                  rmse=math.sqrt(d2[np.isfinite(d2)].sum() / n) if n else np.nan,
+                                  **dict(zip(extra, stats(anchor, positive, nn, Rt)))))
         if k < iterations:
-            f = fit(anchor, positive, nn)
-            if f is not None:
-                Rt, g = f
-                out["eig"] = min(out["eig"], g)
+            new = step(anchor, positive, nn, Rt, out)
+            Rt = Rt if new is None else new
     return out
+
+
+def icp(anchor, positive, Rt0, max_dist=1.0, iterations=20, na=None, nb=None, valid0=True):
+    """dh3d_icp_refine on one pair: loop's dict with the margin eig (the smallest relative eigen gap of a fit)."""
+    def step(anchor, positive, nn, Rt, out):
+        f = fit(anchor, positive, nn)
+        if f is None:
+            return None
+        out["eig"] = min(out["eig"], f[1])
+        return f[0]
+    return loop(anchor, positive, Rt0, step, lambda *a: (), (), dict(eig=np.inf), max_dist, iterations, na, nb, valid0)
 
 
 # ------------------------------------------------------------------------------------------------------------ fixtures

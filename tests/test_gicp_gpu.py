@@ -12,8 +12,6 @@ every pair of both batches below and every iteration count of ITERS, the largest
 100 x that is under 1e-9, so POSE_TOL = 1e-9.  rmse keeps the plane test's bound 1e-9 * (1 + 3 * big); rmse_gicp is
 that bound times sqrt(1 / (2 * epsilon)), the largest gain sqrt(lambda_max(M)) the whitening can apply to a residual
 (the eigenvalues of W = C_A + C_B lie in [2 epsilon, 2]); the two orders differed by 1.3e-14 in rmse_gicp."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -21,28 +19,16 @@ import torch
 import gicp_reference as gr
 import icp_plane_reference as pr
 import icp_reference as ir
+from icp_fixtures import _assert_same, _bits_equal, place_index, place_scene
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 N = 2048
 ITERS = (0, 1, 2, 5, 12)
 EPS = 1e-3
 POSE_TOL = 1e-9
 EYE = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)
 KEYS = ("Rt", "valid", "nn", "num_corr", "fitness", "rmse", "num_planar", "rmse_gicp")
-
-
-def _bits_equal(a, b):
-    if a.dtype == torch.float64:
-        return torch.equal(a.view(torch.int64), b.view(torch.int64))  # (bit for bit, NaN included)
-    return torch.equal(a, b)
-
-
-def _assert_same(got, exp, what):
-    assert set(got) == set(exp), what
-    for k in exp:
-        assert _bits_equal(got[k], exp[k]), (what, k)
 
 
 def _edge_pairs(seed):
@@ -284,35 +270,12 @@ def test_register_fpfh_passes_the_method_through(dev):
     assert "rmse_plane" not in got and "rmse_gicp" not in reg.register_fpfh(A, B, refine=True)
 
 
-def _place_rows(rng, pts, M=64, D=128):
-    rows = np.zeros((M, 3 + D + 1), np.float32)
-    d = rng.standard_normal((M, D))
-    rows[:, :3] = pts[rng.choice(len(pts), M, replace=False)]
-    rows[:, 3:3 + D] = d / np.linalg.norm(d, axis=1, keepdims=True)
-    return rows
-
-
 def test_localize_passes_the_method_through(dev):
     from dh3d_amd import registration as reg
-    from dh3d_amd import retrieval
-    rng = np.random.default_rng(24)
-    demo = np.load(os.path.join(HERE, "golden", "demo_clouds.npz"))
-    clouds = np.stack([demo[k][rng.permutation(len(demo[k]))[:N]] for k in ("local_268", "local_642")]).astype(np.float32)
-    rows = np.stack([_place_rows(rng, c) for c in clouds])
-    count = np.array([64, 60], np.int32)
-    g = rng.standard_normal((2, 256)).astype(np.float32)
-    g /= np.linalg.norm(g, axis=1, keepdims=True)
-    index = retrieval.PlaceIndex(dim=256, capacity=8, device=dev, keypoints=64, row_dim=rows.shape[2], points=N)
-    index.add(g, None, rows, count, cloud=clouds)
-    R, tr = ir.rotation((0.1, 0.2, 1.0), 0.6), np.array([3.0, -2.0, 0.5])
-    n = count[1]
-    qrows = np.zeros((1, 64, rows.shape[2]), np.float32)
-    perm = rng.permutation(n)
-    qrows[0, perm, :3] = (rows[1, :n, :3].astype(np.float64) - tr) @ R + rng.normal(0.0, 0.05, (n, 3))
-    qrows[0, perm, 3:131] = rows[1, :n, 3:131] + 0.01 * rng.standard_normal((n, 128)).astype(np.float32)
-    qcloud = ((clouds[1].astype(np.float64) - tr) @ R + rng.normal(0.0, 0.02, (N, 3)))[rng.permutation(N)][None].astype(np.float32)
+    s = place_scene(("local_268", "local_642"), N)
+    index, T = place_index(dev, s), s["T"]
     t = lambda v: torch.from_numpy(v).to(dev)
-    qd, qr, qc, qp = t(g[1:2]), t(qrows), torch.tensor([n], dtype=torch.int32, device=dev), t(qcloud)
+    qd, qr, qc, qp = t(s["g"][1:2]), t(s["qrows"]), torch.tensor([s["count"][1]], dtype=torch.int32, device=dev), t(s["qcloud"])
     plain = index.localize(qd, qr, qc, k=2)
     res = index.localize(qd, qr, qc, k=2, refine={"method": "gicp", "iterations": 5}, query_cloud=qp)
     assert res["place"].cpu().tolist() == [1]
@@ -321,7 +284,6 @@ def test_localize_passes_the_method_through(dev):
                           method="gicp", iterations=5)
     for k in ("Rt", "fitness", "rmse", "rmse_gicp"):
         assert _bits_equal(res[k], icp[k]), k
-    T = np.concatenate([R, tr[:, None]], axis=1)
     print("ransac", ir.pose_errors(plain["Rt"][0].cpu().numpy(), T), "gicp", ir.pose_errors(res["Rt"][0].cpu().numpy(), T),
           "fitness", float(res["fitness"][0]), "rmse_gicp", float(res["rmse_gicp"][0]))
     assert float(res["fitness"][0]) > 0.95 and np.isfinite(float(res["rmse_gicp"][0]))

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import icp_reference as ir
+from icp_fixtures import _assert_same, _bits_equal, place_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -17,18 +18,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 N = 2048
 ITERS = (0, 1, 2, 5, 30)
 EYE = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)
-
-
-def _bits_equal(a, b):
-    if a.dtype == torch.float64:
-        return torch.equal(a.view(torch.int64), b.view(torch.int64))  # (bit for bit, NaN included)
-    return torch.equal(a, b)
-
-
-def _assert_same(got, exp, what):
-    assert set(got) == set(exp), what
-    for k in exp:
-        assert _bits_equal(got[k], exp[k]), (what, k)
 
 
 def _edge_pairs(seed):
@@ -349,43 +338,21 @@ def test_register_clouds_with_and_without_refinement(dev, det_model):
             _assert_same(got, exp, refine)
 
 
-def _place_rows(rng, pts, M=64, D=128):
-    rows = np.zeros((M, 3 + D + 1), np.float32)
-    d = rng.standard_normal((M, D))
-    rows[:, :3] = pts[rng.choice(len(pts), M, replace=False)]
-    rows[:, 3:3 + D] = d / np.linalg.norm(d, axis=1, keepdims=True)
-    return rows
-
-
 def test_localize_refines_the_winner(dev):
     from dh3d_amd import registration as reg
     from dh3d_amd import retrieval
-    rng = np.random.default_rng(24)
-    demo = np.load(os.path.join(HERE, "golden", "demo_clouds.npz"))
-    clouds = np.stack([demo[k][rng.permutation(len(demo[k]))[:N]] for k in ("local_268", "local_642", "global_c")])
-    rows = np.stack([_place_rows(rng, c) for c in clouds])
-    count = np.array([64, 60, 64], np.int32)
-    g = rng.standard_normal((3, 256)).astype(np.float32)
-    g /= np.linalg.norm(g, axis=1, keepdims=True)
+    s = place_scene(("local_268", "local_642", "global_c"), N)
+    clouds, rows, count, g, T = s["clouds"], s["rows"], s["count"], s["g"], s["T"]
     index = retrieval.PlaceIndex(dim=256, capacity=8, device=dev, keypoints=64, row_dim=rows.shape[2], points=N)
     index.add(g[:1], None, rows[:1], count[:1], cloud=clouds[:1])
     index.add(g[1:], None, rows[1:], count[1:], cloud=torch.from_numpy(clouds[1:]).to(dev),
               cloud_count=np.array([N, N - 100], np.int32))
     assert index.cloud_count.cpu().tolist()[:3] == [N, N, N - 100] and torch.equal(index.cloud[1].cpu(), torch.from_numpy(clouds[1]))
-    # the queries: a moved copy of place 1 (5 cm noise on the keypoints, 2 cm on the cloud, both shuffled), and one without
-    # keypoints, which no candidate can fit
-    R, tr = ir.rotation((0.1, 0.2, 1.0), 0.6), np.array([3.0, -2.0, 0.5])
-    T = np.concatenate([R, tr[:, None]], axis=1)
-    n = count[1]
-    qrows = np.zeros((2, 64, rows.shape[2]), np.float32)
-    perm = rng.permutation(n)
-    qrows[0, perm, :3] = (rows[1, :n, :3].astype(np.float64) - tr) @ R + rng.normal(0.0, 0.05, (n, 3))
-    qrows[0, perm, 3:131] = rows[1, :n, 3:131] + 0.01 * rng.standard_normal((n, 128)).astype(np.float32)
-    qcloud = np.zeros((2, N, 3), np.float32)
-    qcloud[0] = ((clouds[1].astype(np.float64) - tr) @ R + rng.normal(0.0, 0.02, (N, 3)))[rng.permutation(N)]
-    qcloud[1] = qcloud[0]
+    # the queries: the scene's moved copy of place 1, and one without keypoints, which no candidate can fit
+    qrows = np.concatenate([s["qrows"], np.zeros_like(s["qrows"])])
+    qcloud = np.concatenate([s["qcloud"], s["qcloud"]])
     t = lambda v: torch.from_numpy(v).to(dev)
-    qd, qr, qc, qp = t(np.stack([g[1], g[2]])), t(qrows), torch.tensor([n, 0], dtype=torch.int32, device=dev), t(qcloud)
+    qd, qr, qc, qp = t(np.stack([g[1], g[2]])), t(qrows), torch.tensor([count[1], 0], dtype=torch.int32, device=dev), t(qcloud)
     plain = index.localize(qd, qr, qc, k=3)
     res = index.localize(qd, qr, qc, k=3, refine=True, query_cloud=qp)
     assert res["place"].cpu().tolist() == [1, -1]

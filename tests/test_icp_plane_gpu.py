@@ -13,6 +13,7 @@ import torch
 
 import icp_plane_reference as pr
 import icp_reference as ir
+from icp_fixtures import _assert_same, _bits_equal, place_index, place_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -21,18 +22,6 @@ N = 2048
 ITERS = (0, 1, 2, 5, 30)
 EYE = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)
 KEYS = ("Rt", "valid", "nn", "num_corr", "fitness", "rmse", "num_plane", "rmse_plane")
-
-
-def _bits_equal(a, b):
-    if a.dtype == torch.float64:
-        return torch.equal(a.view(torch.int64), b.view(torch.int64))  # (bit for bit, NaN included)
-    return torch.equal(a, b)
-
-
-def _assert_same(got, exp, what):
-    assert set(got) == set(exp), what
-    for k in exp:
-        assert _bits_equal(got[k], exp[k]), (what, k)
 
 
 def _edge_pairs(seed):
@@ -308,36 +297,12 @@ def test_register_clouds_passes_the_method_through(dev):
     assert "rmse_plane" not in point
 
 
-def _place_rows(rng, pts, M=64, D=128):
-    rows = np.zeros((M, 3 + D + 1), np.float32)
-    d = rng.standard_normal((M, D))
-    rows[:, :3] = pts[rng.choice(len(pts), M, replace=False)]
-    rows[:, 3:3 + D] = d / np.linalg.norm(d, axis=1, keepdims=True)
-    return rows
-
-
 def test_localize_passes_the_method_through(dev):
     from dh3d_amd import registration as reg
-    from dh3d_amd import retrieval
-    rng = np.random.default_rng(24)
-    demo = np.load(os.path.join(HERE, "golden", "demo_clouds.npz"))
-    clouds = np.stack([demo[k][rng.permutation(len(demo[k]))[:N]] for k in ("local_268", "local_642")]).astype(np.float32)
-    rows = np.stack([_place_rows(rng, c) for c in clouds])
-    count = np.array([64, 60], np.int32)
-    g = rng.standard_normal((2, 256)).astype(np.float32)
-    g /= np.linalg.norm(g, axis=1, keepdims=True)
-    index = retrieval.PlaceIndex(dim=256, capacity=8, device=dev, keypoints=64, row_dim=rows.shape[2], points=N)
-    index.add(g, None, rows, count, cloud=clouds)
-    R, tr = ir.rotation((0.1, 0.2, 1.0), 0.6), np.array([3.0, -2.0, 0.5])
-    T = np.concatenate([R, tr[:, None]], axis=1)
-    n = count[1]
-    qrows = np.zeros((1, 64, rows.shape[2]), np.float32)
-    perm = rng.permutation(n)
-    qrows[0, perm, :3] = (rows[1, :n, :3].astype(np.float64) - tr) @ R + rng.normal(0.0, 0.05, (n, 3))
-    qrows[0, perm, 3:131] = rows[1, :n, 3:131] + 0.01 * rng.standard_normal((n, 128)).astype(np.float32)
-    qcloud = ((clouds[1].astype(np.float64) - tr) @ R + rng.normal(0.0, 0.02, (N, 3)))[rng.permutation(N)][None].astype(np.float32)
+    s = place_scene(("local_268", "local_642"), N)
+    index, T = place_index(dev, s), s["T"]
     t = lambda v: torch.from_numpy(v).to(dev)
-    qd, qr, qc, qp = t(g[1:2]), t(qrows), torch.tensor([n], dtype=torch.int32, device=dev), t(qcloud)
+    qd, qr, qc, qp = t(s["g"][1:2]), t(s["qrows"]), torch.tensor([s["count"][1]], dtype=torch.int32, device=dev), t(s["qcloud"])
     plain = index.localize(qd, qr, qc, k=2)
     res = index.localize(qd, qr, qc, k=2, refine={"method": "plane", "iterations": 5}, query_cloud=qp)
     assert res["place"].cpu().tolist() == [1]
