@@ -883,12 +883,7 @@ __device__ __forceinline__ void ih_build_lists(const int *s_slot, int *s_loff) {
   __syncthreads();
   if (tid < 64) {  // exclusive prefix of the kIHCap = 64 counts
     const int c = s_cnt[tid];
-    int v = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(v, off, 64);
-      if (tid >= off) v += o;
-    }
+    const int v = wave_incl_scan(c);
     s_loff[tid] = v - c;
     if (tid == 63) s_loff[64] = v;
   }

@@ -19,6 +19,7 @@
 // rows, which a second pass adds per target in chunk order (cdna_hip_programming.md, Appendix B "Scatter / gather"):
 // the main gather skips such targets, so a kNN neighbourhood (in-degree ~K) pays two empty launches for it.
 #include "flex_common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -185,12 +186,7 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_kernel(int32_t *__restr
     for (int u = 0; u < 16; ++u) { a += d[u]; p += parts_of(d[u]); }
   }
   // inclusive scan of the (a, p) pairs over the workgroup
-  long long ia = a, ip = p;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long ua = __shfl_up(ia, o, 64), up = __shfl_up(ip, o, 64);
-    if (lane >= o) { ia += ua; ip += up; }
-  }
+  const long long ia = wave_incl_scan(a), ip = wave_incl_scan(p);
   if (lane == 63) { s_a[wave] = ia; s_b[wave] = ip; }
   __syncthreads();
   long long ba = 0, bp = 0, ta = 0, tp = 0;

@@ -489,12 +489,7 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
         const int i = tid * CH + c;
         if (i <= N) mine += s_cnt[i];
       }
-      unsigned inc = mine;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned up = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += up;
-      }
+      const unsigned inc = wave_incl_scan(mine);
       if (lane == 63) s_wsum[wave] = inc;
       __syncthreads();
       unsigned base = inc - mine;

@@ -8,12 +8,12 @@
 //                         K neighbours: a point is kept iff no neighbour inside the radius beats rank 0 and a' > thr.  The
 //                         point's key is (f32_order_bits(a') << 32) | i, or 0 when it is not kept;
 //   K3 nms_select_kernel  one 1024-lane workgroup per cloud: compact the non-zero keys (in place), radix-select the M-th
-//                         largest (8 passes of 8 bits over the survivors), bitonic-sort the <= M winners in LDS (keys are
-//                         unique -- the index sits in the low bits -- so the order is total), write count and ids.
+//                         largest, bitonic-sort the <= M winners in LDS (keys are unique -- the index sits in the low bits
+//                         -- so the order is total), write count and ids; all three steps are block_ops.h's.
 // Only comparisons, one f32 multiply and 1 - x: exact by construction (compiled without contraction, csrc/Makefile EXACT).
 #include "common.h"
 #include "keys.h"
-#include "wave_ops.h"
+#include "block_ops.h"
 #include "workspace.h"
 
 namespace {
@@ -89,82 +89,30 @@ __global__ __launch_bounds__(kSelThreads) void nms_select_kernel(unsigned long l
                                                                  int32_t *__restrict__ count, int32_t *__restrict__ inds) {
   __shared__ unsigned long long s_win[kMaxKeep];
   __shared__ int s_hist[256];
-  __shared__ int s_suf[256];
   __shared__ int s_wave[kSelWaves];
-  __shared__ int s_bin, s_above, s_n;
-  const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+  __shared__ int s_sel[2], s_n;
+  const int b = blockIdx.x, tid = threadIdx.x;
   unsigned long long *ck = keys + (long long)b * N;
 
   // (1) compact the non-zero keys to the front, in place, in index order: every store of a chunk lands below the chunk's
-  //     end and the chunk was read before the barrier
+  //     end and the chunk was read before the barriers of block_compact_slot
   int c = 0;
   for (int base = 0; base < N; base += kSelThreads) {
     const int i = base + tid;
     const unsigned long long key = i < N ? ck[i] : 0ull;
-    const unsigned long long bal = __ballot(key != 0ull);
-    if ((tid & 63) == 0) s_wave[w] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int q = 0; q < kSelWaves; ++q) {
-      const int v = s_wave[q];
-      off += q < w ? v : 0;
-      tot += v;
-    }
-    if (key) ck[c + off + __popcll(bal & lanes_below())] = key;
+    int tot;
+    const int slot = c + block_compact_slot<kSelThreads>(key != 0ull, s_wave, tot);
+    if (key) ck[slot] = key;
     c += tot;
-    __syncthreads();
   }
 
-  // (2) the M-th largest key (MSB-first radix select); with c <= M every survivor is a winner
+  // (2) the M-th largest key = the (c - M + 1)-th smallest; with c <= M every survivor is a winner
   unsigned long long thr = 1ull;
-  if (c > M) {
-    unsigned long long prefix = 0ull, mask = 0ull;
-    int rem = M;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-      if (tid < 256) s_hist[tid] = 0;
-      __syncthreads();
-      for (int base = 0; base < c; base += kSelThreads) {
-        const int j = base + tid;
-        const unsigned long long key = j < c ? ck[j] : 0ull;
-        const bool in = j < c && (key & mask) == prefix;
-        const int bin = (int)((key >> shift) & 255ull);
-        // a whole wave in one bin (the scores' top bits mostly agree): one LDS atomic instead of 64 on one address
-        const unsigned long long act = __ballot(in);
-        const int first = __shfl(bin, __builtin_ffsll((long long)act) - 1);  // the bin of the lowest lane in the subset
-        const unsigned long long same = __ballot(in && bin == first);
-        if (act && same == act) {
-          if (in && (same & lanes_below()) == 0ull) atomicAdd(&s_hist[first], __popcll(act));
-        } else if (in) {
-          atomicAdd(&s_hist[bin], 1);
-        }
-      }
-      __syncthreads();
-      if (tid < 256) s_suf[tid] = s_hist[tid];
-      __syncthreads();
-      for (int off = 1; off < 256; off <<= 1) {  // s_suf[t] = sum of s_hist[t..255]
-        const int v = (tid < 256 && tid + off < 256) ? s_suf[tid + off] : 0;
-        __syncthreads();
-        if (tid < 256) s_suf[tid] += v;
-        __syncthreads();
-      }
-      if (tid < 256) {
-        const int above = s_suf[tid] - s_hist[tid];
-        if (above < rem && rem <= s_suf[tid]) {  // exactly one bin: the one where the count from the top reaches rem
-          s_bin = tid;
-          s_above = above;
-        }
-      }
-      __syncthreads();
-      rem -= s_above;
-      prefix |= (unsigned long long)s_bin << shift;
-      mask |= 255ull << shift;
-      __syncthreads();
-    }
-    thr = prefix;  // the M-th largest key itself: exactly M keys are >= it
-  }
+  if (c > M)  // exactly M keys are >= it: the keys are distinct
+    thr = block_radix_select<kSelThreads>(c, c - M + 1, [&](int j, bool &) { return ck[j]; }, s_hist, s_sel).key;
   const int nw = c < M ? c : M;
 
-  // (3) the winners into LDS (any order), padded with zeros to a power of two, bitonic-sorted descending
+  // (3) the winners into LDS (any order), bitonic-sorted descending
   if (tid == 0) s_n = 0;
   __syncthreads();
   for (int base = 0; base < c; base += kSelThreads) {
@@ -178,26 +126,7 @@ __global__ __launch_bounds__(kSelThreads) void nms_select_kernel(unsigned long l
     const int slot = slot0 + __popcll(bal & lanes_below());
     if (win && slot < nw) s_win[slot] = key;  // (exactly nw winners; the bound only guards the LDS buffer)
   }
-  int P = 1;
-  while (P < nw) P <<= 1;
-  for (int j = nw + tid; j < P; j += kSelThreads) s_win[j] = 0ull;
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int jj = k >> 1; jj > 0; jj >>= 1) {
-      for (int x = tid; x < P; x += kSelThreads) {
-        const int y = x ^ jj;
-        if (y > x) {
-          const unsigned long long u = s_win[x], v = s_win[y];
-          const bool desc = (x & k) == 0;
-          if (desc ? (u < v) : (u > v)) {
-            s_win[x] = v;
-            s_win[y] = u;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  block_sort<kSelThreads>(s_win, nw, [](unsigned long long x, unsigned long long y) { return x > y; });
   for (int j = tid; j < M; j += kSelThreads)
     inds[(long long)b * M + j] = j < nw ? (int32_t)(unsigned)(s_win[j] & 0xffffffffull) : -1;
   if (tid == 0) count[b] = nw;

@@ -26,7 +26,7 @@
 // over c (this file is built with -ffp-contract=off).  NaN / infinite inputs are outside the contract.
 #include "common.h"
 #include "keys.h"
-#include "wave_ops.h"
+#include "block_ops.h"
 
 namespace {
 
@@ -178,23 +178,6 @@ struct XyzRow {  // the distances of one query to a cloud of n points of c compo
   }
 };
 
-// ascending bitonic sort of s[0 .. P) (P a power of two) by the workgroup; barriers inside, one after
-__device__ void block_sort64(u64 *s, int P) {
-  for (int k2 = 2; k2 <= P; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      __syncthreads();
-      for (int i = threadIdx.x; i < P; i += kRowThreads) {
-        const int l = i ^ j;
-        if (l > i) {
-          const u64 a = s[i], c = s[l];
-          if ((a > c) == ((i & k2) == 0)) { s[i] = c; s[l] = a; }
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
-
 // FULL: write the whole row (values + ids, dh3d_select_top_k); otherwise its first k columns (val, idx of dh3d_knn_point).
 // Dynamic LDS: u64 key[P] | unsigned wk[T] | int wi[T], T = k + kk, P a power of two >= max(2 kk, 512).
 template <class SRC, bool FULL>
@@ -214,8 +197,8 @@ __device__ __forceinline__ void topk_row(const SRC &src, int n, int k, int P, fl
     __syncthreads();
     u64 tau = kNoKey;
     auto compact = [&](int have) {
-      for (int i = have + tid; i < P; i += kRowThreads) s_key[i] = kNoKey;
-      block_sort64(s_key, P);
+      for (int i = have + tid; i < kk; i += kRowThreads) s_key[i] = kNoKey;  // (a cut before kk keys have arrived)
+      block_sort<kRowThreads>(s_key, max(have, kk));
       tau = s_key[kk - 1];
       if (tid == 0) s_cnt = kk;
       __syncthreads();
@@ -235,11 +218,11 @@ __device__ __forceinline__ void topk_row(const SRC &src, int n, int k, int P, fl
     __syncthreads();
     compact(have);
     // ---- the kk chosen in position order
-    for (int i = tid; i < P; i += kRowThreads) {
+    for (int i = tid; i < kk; i += kRowThreads) {
       const u64 v = s_key[i];
-      s_key[i] = i < kk ? (v << 32) | (v >> 32) : kNoKey;
+      s_key[i] = (v << 32) | (v >> 32);
     }
-    block_sort64(s_key, P);
+    block_sort<kRowThreads>(s_key, kk);
   }
   // ---- stage 2: the walk on C, by the first wave; walk position t < k is row position t, k + i the i-th chosen
   for (int t = tid; t < T; t += kRowThreads) {

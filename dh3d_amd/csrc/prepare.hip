@@ -22,12 +22,13 @@
 //   stage 2   the same table keyed by cells of edge radius * (1 + 2^-20) over the stage-1 points (lists only); a point walks
 //             the 27 cells around its own and leaves as soon as it has counted more than nb_points.
 //   stage 3   float64 centroid by a fixed tree (tile partial sums, then the tiles in order); the targetnum smallest
-//             (d2, index) by a radix select on the double's bit pattern, 8 bits a pass, one workgroup per cloud; ties on the
+//             (d2, index) by a radix select on the double's bit pattern (block_ops.h), one workgroup per cloud; ties on the
 //             threshold go to the lowest indices through the same prefix scan that compacts.
 // All three compactions: per-tile counts, a scan of the tile counts per cloud, in-tile ranks by a workgroup scan.
 // This file is built with -ffp-contract=off: the double expressions below are evaluated as written.
 #include "common.h"
 #include "keys.h"
+#include "block_ops.h"
 #include "workspace.h"
 
 namespace {
@@ -76,24 +77,6 @@ Ws make_layout(Carve &c, int B, int N) {
 
 __device__ __forceinline__ double sqdist(double dx, double dy, double dz) { return (dx * dx + dy * dy) + dz * dz; }
 
-// Exclusive prefix of v over the workgroup of kThreads; total to every thread.  s_w: 4 ints of LDS.
-__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int &total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += o;
-  }
-  __syncthreads();
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += s_w[w];
-  total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  return base + inc - v;
-}
-
 // The flags (0, 1 or 2) of this thread's kPer consecutive points and their exclusive in-tile ranks, flag 1 in the low and
 // flag 2 in the high 16 bits (a tile holds 1024 points: neither field overflows).
 __device__ __forceinline__ void tile_ranks(const int *flag, int n, int i0, int (&f)[kPer], int (&r)[kPer], int *s_w) {
@@ -105,7 +88,7 @@ __device__ __forceinline__ void tile_ranks(const int *flag, int n, int i0, int (
     loc += (f[e] == 1) + ((f[e] == 2) << 16);
   }
   int total;
-  const int base = block_excl_scan(loc, s_w, total);
+  const int base = block_excl_scan<kThreads>(loc, s_w, total);
 #pragma unroll
   for (int e = 0; e < kPer; ++e) r[e] += base;
 }
@@ -233,8 +216,8 @@ __global__ __launch_bounds__(kThreads) void prep_tile_sums_kernel(Ws w, int st_n
     one += f == 1, two += f == 2;
   }
   int t1, t2;
-  block_excl_scan(one, s_w, t1);
-  block_excl_scan(two, s_w, t2);
+  block_excl_scan<kThreads>(one, s_w, t1);
+  block_excl_scan<kThreads>(two, s_w, t2);
   if (threadIdx.x == 0) {
     int *ts = w.tsum + ((size_t)b * w.T + blockIdx.x) * 2;
     ts[0] = t1, ts[1] = t2;
@@ -248,8 +231,8 @@ __global__ __launch_bounds__(kThreads) void prep_tile_scan_kernel(Ws w, int st_t
   const int *ts = w.tsum + (size_t)b * w.T * 2;
   const int a = t < w.T ? ts[t * 2] : 0, c = t < w.T ? ts[t * 2 + 1] : 0;
   int ta, tc;
-  const int ea = block_excl_scan(a, s_w, ta);
-  const int ec = block_excl_scan(c, s_w, tc);
+  const int ea = block_excl_scan<kThreads>(a, s_w, ta);
+  const int ec = block_excl_scan<kThreads>(c, s_w, tc);
   if (t < w.T) {
     int *to = w.toff + ((size_t)b * w.T + t) * 2;
     to[0] = ea, to[1] = ec;
@@ -300,24 +283,6 @@ __global__ __launch_bounds__(kThreads) void prep_voxel_kernel(Ws w, const float 
   }
 }
 
-// ascending bitonic sort of a[0 .. c) by the workgroup, any c: every comparator puts the minimum at the lower position
-// (flip, then disperse), so positions >= c act as +inf and their comparators are skipped
-__device__ void block_sort_int(int *a, int c) {
-  for (int k2 = 2; k2 < 2 * c; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < c; i += kThreads) {
-        const int l = j == (k2 >> 1) ? i ^ (k2 - 1) : i ^ j;
-        if (l > i && l < c) {
-          const int x = a[i], y = a[l];
-          if (x > y) a[i] = y, a[l] = x;
-        }
-      }
-      __threadfence_block();
-      __syncthreads();
-    }
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void prep_big_voxel_kernel(Ws w, const float *__restrict__ raw) {
   __shared__ int s_m[kBigLds];
   const int b = blockIdx.y;
@@ -331,10 +296,9 @@ __global__ __launch_bounds__(kThreads) void prep_big_voxel_kernel(Ws w, const fl
     __syncthreads();
     if (c <= kBigLds) {
       for (int k = threadIdx.x; k < c; k += kThreads) s_m[k] = m[k];
-      __syncthreads();
       m = s_m;
     }
-    block_sort_int(m, c);
+    block_sort<kThreads>(m, c);  // (in LDS, or in place in the member array)
     if (threadIdx.x < 3) {                               // one axis per thread, each in member order
       const float *p = raw + pb * 3 + threadIdx.x;
       double s = 0.0;
@@ -418,10 +382,8 @@ __global__ __launch_bounds__(kThreads) void prep_survivors_kernel(Ws w) {
 // take; flag = 1 below the threshold, 2 on it.  Elsewhere every survivor gets flag 1 (prep_output_kernel cuts at
 // targetnum).
 __global__ __launch_bounds__(kSelThreads) void prep_select_kernel(Ws w, int targetnum, int sortby, double *__restrict__ centroid) {
-  __shared__ int s_hist[256];
+  __shared__ int s_hist[256], s_sel[2];
   __shared__ double s_c[3];
-  __shared__ u64 s_prefix;
-  __shared__ int s_k;
   const int b = blockIdx.x, tid = threadIdx.x;
   int *st = w.st + b * ST_INTS;
   const int m = st[ST_ERR] ? 0 : st[ST_N2];
@@ -445,27 +407,9 @@ __global__ __launch_bounds__(kSelThreads) void prep_select_kernel(Ws w, int targ
   for (int i = tid; i < m; i += kSelThreads)
     key[i] = (u64)__double_as_longlong(sqdist((double)p[(size_t)i * 3] - cx, (double)p[(size_t)i * 3 + 1] - cy,
                                               (double)p[(size_t)i * 3 + 2] - cz));
-  if (tid == 0) s_prefix = 0, s_k = targetnum;
-  __threadfence_block();
-  __syncthreads();
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    if (tid < 256) s_hist[tid] = 0;
-    __syncthreads();
-    const u64 prefix = s_prefix;
-    for (int i = tid; i < m; i += kSelThreads) {
-      const u64 k = key[i];
-      if (shift == 56 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&s_hist[(int)(k >> shift) & 255], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int k = s_k, d = 0;
-      for (; d < 255 && s_hist[d] < k; ++d) k -= s_hist[d];
-      s_k = k, s_prefix = prefix | ((u64)d << shift);
-    }
-    __syncthreads();
-  }
-  const u64 tau = s_prefix;
-  if (tid == 0) st[ST_NEED] = s_k;
+  const BlockSelected sel = block_radix_select<kSelThreads>(m, targetnum, [&](int i, bool &) { return key[i]; }, s_hist, s_sel);
+  const u64 tau = sel.key;
+  if (tid == 0) st[ST_NEED] = sel.need;
   for (int i = tid; i < m; i += kSelThreads) flag[i] = key[i] < tau ? 1 : key[i] == tau ? 2 : 0;
 }
 

@@ -6,8 +6,8 @@
 //   tuple_counts_kernel   grid ceil(M / 256), 256 threads, a place per thread; the live places stream through LDS in tiles
 //                         of 256 positions, read as broadcasts.  The only O(M^2) piece; it runs once per map.
 //   draw_select_kernel    one workgroup of 1024: the number of eligible places, the Q-th smallest stream-15 key among them by
-//                         a radix select (8 bits a pass, keys recomputed on every pass, as pairs.hip's block_select -- here
-//                         under a predicate), then a stable compaction of the chosen (key, id) into the workspace.
+//                         a radix select (block_ops.h; the keys recomputed on every pass, as in pairs.hip -- here under
+//                         a predicate), then a stable compaction of the chosen (key, id) into the workspace.
 //   draw_rank_kernel      grid ceil(Q / 256): a chosen place's slot is the number of chosen keys below its own.
 //   sample_tuples_kernel  one 256-thread workgroup per query slot.  Pass 1: the four waves each stream a quarter of the
 //                         places (16 B per lane, coalesced), test d2 against the two radii and keep one sorted 64-entry list
@@ -24,7 +24,7 @@
 // survivors arrived.  Compiled without contraction (csrc/Makefile EXACT): every id depends on the roundings of d2 and D2.
 #include "common.h"
 #include "keys.h"
-#include "wave_ops.h"
+#include "block_ops.h"
 #include "workspace.h"
 
 namespace {
@@ -95,8 +95,9 @@ __global__ __launch_bounds__(kBig) void draw_select_kernel(const int32_t *__rest
                                                            int num_neg, const u64 *__restrict__ seed, u64 *__restrict__ ws_key,
                                                            int32_t *__restrict__ ws_id, int32_t *__restrict__ ws_chosen,
                                                            int32_t *__restrict__ ok) {
-  __shared__ unsigned s_hist[256], s_sel[2], s_w[kBig / 64], s_total;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int s_hist[256], s_sel[2], s_w[kBig / 64];
+  __shared__ unsigned s_total;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int n = count ? clamp_count(*count, M) : M;
   const u64 h = stream_h(*seed, kQueryKeys, 0u);
   auto eligible = [&](int i) { return i < n && n_pos[i] >= num_pos && n_neg[i] >= num_neg; };
@@ -116,45 +117,20 @@ __global__ __launch_bounds__(kBig) void draw_select_kernel(const int32_t *__rest
 
   // the want-th smallest key of the eligible places: the keys are distinct (splitmix64 is a bijection), so exactly `want`
   // of them are <= the result
-  u64 prefix = 0;
-  unsigned k = want;
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    if (tid < 256) s_hist[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += kBig) {
-      if (!eligible(i)) continue;
-      const u64 key = splitmix64(h + (u64)i);
-      if (shift == 56 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&s_hist[(unsigned)(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      unsigned before = 0, bin = 0;
-      while (before + s_hist[bin] < k) before += s_hist[bin], ++bin;  // (k <= the candidates' number: bin stays below 256)
-      s_sel[0] = bin, s_sel[1] = k - before;
-    }
-    __syncthreads();
-    prefix |= (u64)s_sel[0] << shift;
-    k = s_sel[1];
-    __syncthreads();  // s_sel is read before the next pass overwrites it
-  }
+  const u64 thr = block_radix_select<kBig>(n, (int)want, [&](int i, bool &valid) {
+    valid = eligible(i);
+    return splitmix64(h + (u64)i);
+  }, s_hist, s_sel).key;
 
   int run = 0;
   for (int c = 0; c * kBig < n; ++c) {
     const int i = c * kBig + tid;
     const u64 key = splitmix64(h + (u64)i);
-    const bool sel = eligible(i) && key <= prefix;
-    const u64 mask = __ballot(sel);
-    if (lane == 0) s_w[wave] = (unsigned)__popcll(mask);
-    __syncthreads();
-    int at = run + __popcll(mask & lanes_below()), all = 0;
-    for (int w = 0; w < kBig / 64; ++w) {
-      const int v = (int)s_w[w];
-      if (w < wave) at += v;
-      all += v;
-    }
+    const bool sel = eligible(i) && key <= thr;
+    int all;
+    const int at = run + block_compact_slot<kBig>(sel, s_w, all);
     if (sel && at < Q) ws_key[at] = key, ws_id[at] = i;
     run += all;
-    __syncthreads();
   }
 }
 

@@ -102,6 +102,18 @@ __device__ __forceinline__ unsigned long long lanes_below() {
   return lane ? (~0ull >> (64 - lane)) : 0ull;
 }
 
+// Inclusive prefix sum of v over the wave (int, unsigned, long long).
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const T o = __shfl_up(v, off, 64);
+    if (lane >= off) v += o;
+  }
+  return v;
+}
+
 // Orders the LDS traffic of ONE wave: what a lane wrote before is visible to every lane of the wave after.
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

@@ -178,4 +178,7 @@ def tie_cases():
         # voxels of 5000, 300 and 20 members (clusters 0.09 wide, each inside one cell): the three ways the members are ordered
         "crowded_voxels": (crowd, dict(targetnum=1024, voxel_size=0.2, radius=1.0, nb_points=4)),
         "m_equals_targetnum": (lattice(6, 0.5), dict(targetnum=216, voxel_size=0.2, radius=None)),
+        # 216 points in 9 exact tie groups of d2, the first and the last of 8: the select at k = 1, at k = a whole first
+        # group, and with the threshold inside the last group, taking 1 and 7 of its 8
+        **{"select_ties_k%d" % t: (lattice(6, 0.5), dict(targetnum=t, voxel_size=None, radius=None)) for t in (1, 8, 209, 215)},
     }

@@ -115,6 +115,11 @@ def test_more_and_fewer_survivors_than_m(dev):
     assert many.tolist() == [8, 8]
     one, _ = _check_vs_single(xyz, s, dev, max_keypoints=1)
     assert one.tolist() == [1, 1]
+    # the edge between "every survivor wins" and the select: M = c + 1 and c take all of cloud 0, c - 1 drops its last
+    c = int(few[0])
+    for m in (c - 1, c, c + 1):
+        edge, _ = _check_vs_single(xyz, s, dev, max_keypoints=m)
+        assert int(edge[0]) == min(c, m)
 
 
 def test_mixed_batch_with_an_all_zero_cloud(dev):

@@ -59,7 +59,7 @@ def _run_resample(dev, pts, ns, T, seed, dirty=0x5A):
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,Nsrc,T,ns", [
     (1, 300, 64, [65]), (5, 300, 64, [0, 1, 63, 64, 65]), (1, 1000, 64, [1000]), (5, 4200, 4096, [4099, 0, 4096, 4095, 4200]),
-    (1, 1, 1, [1]), (2, 1500, 3000, [1500, 7])])
+    (1, 1, 1, [1]), (2, 1500, 3000, [1500, 7]), (1, 300, 1, [300]), (1, 1100, 1025, [1026])])
 def test_resample_equals_restatement(dev, B, Nsrc, T, ns):
     from dh3d_amd import pairs
     pts, exp, exp_orig = _resample_case(B, Nsrc, T, ns, SEED)

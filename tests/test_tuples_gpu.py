@@ -186,10 +186,11 @@ def test_a_slot_does_not_depend_on_the_other_slots(dev):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,count,Q", [("grid", None, 450), ("grid", 500, 40), ("route", None, 620), ("route", 77, 5)])
+@pytest.mark.parametrize("name,count,Q", [("grid", None, 450), ("grid", 500, 40), ("route", None, 620), ("route", 77, 5),
+                                          ("grid", None, 1), ("grid", None, "eligible")])
 def test_counts_and_queries_are_the_restatement(dev, name, count, Q):
     """tuple_counts and draw_queries on the two maps; Q above the number of places that can be queries (412 on the grid,
-    600 on the route) takes the -1 / ok = 0 path."""
+    600 on the route) takes the -1 / ok = 0 path.  Q = 1 and Q = that number itself are the select's k = 1 and k = n."""
     from dh3d_amd import tuples
     pos = T.grid_positions() if name == "grid" else T.route_positions()
     M = pos.shape[0]
@@ -198,12 +199,17 @@ def test_counts_and_queries_are_the_restatement(dev, name, count, Q):
     cnt = None if count is None else torch.tensor([count], dtype=torch.int32, device=dev)
     n_pos, n_neg = tuples.tuple_counts(_T(_behind(pos, n), dev), cnt)
     assert np.array_equal(n_pos.cpu().numpy(), exp_pos) and np.array_equal(n_neg.cpu().numpy(), exp_neg)
+    eligible = int(((exp_pos[:n] >= 2) & (exp_neg[:n] >= 18)).sum())
+    if Q == "eligible":
+        Q = eligible
     for seed in (SEED, 1):
         exp_q, exp_ok = T.draw_queries(exp_pos, exp_neg, Q, 2, 18, count, seed)
         queries, ok = tuples.draw_queries(n_pos, n_neg, Q, 2, 18, count=cnt, seed=seed)
         assert np.array_equal(queries.cpu().numpy(), exp_q) and int(ok) == exp_ok
-    if count is None:
+    if count is None and Q > eligible:
         assert exp_ok == 0 and exp_q[-1] == -1 and exp_q[0] >= 0
+    elif count is None:
+        assert exp_ok == 1 and (exp_q >= 0).all() and len(set(exp_q.tolist())) == Q
 
 
 def _bank(dev, points, seed):
