@@ -5,22 +5,31 @@
 // shapes the exact-f32 MFMA form needs 15.4 us of matrix pipe per launch (B=8, N=8192, 64->64) against 4.6 us
 // of compulsory HBM time, and its gather / GEMM / store phases run back to back inside a workgroup.  Here:
 //   * one 768-thread workgroup per CU (three waves per SIMD: two producers + one consumer), looping over 32-point tiles of ONE XCD's contiguous tile range;
-//   * waves 0-7 PRODUCE (16 lanes per point): neighbour ids two rounds ahead, neighbour rows one round ahead
-//     (the next tile's loads are in flight while this one is reduced), the K-neighbour reduce in f32, the
-//     exact 3-way bf16 split, and the S tile into LDS as three bf16 planes (double buffered);
+//   * waves 0-7 PRODUCE, four channels per lane (16-byte gathers): neighbour ids and neighbour rows are requested ahead
+//     of the reduce that uses them, then the K-neighbour reduce in f32, the exact 3-way bf16 split, and the S tile into
+//     LDS as three bf16 planes (double buffered).
+//       64 -> 64: 16 lanes per point, a wave covers 4 points, all eight waves produce every tile; ids two rounds ahead,
+//         rows one round ahead; the two producers of a SIMD run opposite schedules (loads first / reduce first).
+//       32 -> 64: 8 lanes per point, a wave covers 8 points, so four waves -- one per SIMD -- cover a tile: waves 0-3
+//         produce the even tiles of the workgroup into S buffer 0, waves 4-7 the odd tiles into buffer 1.  A wave reduces
+//         in one tile period and requests its next tile's rows in the other, while the other group reduces.  The work
+//         per (point, neighbour) -- addresses, load instructions, ids, waits -- does not shrink with the channel count;
+//         eight lanes per point halve it.  The S tile is bit for bit what the 16-lane mapping writes.
 //   * waves 8-11 CONSUME: wave (cb, kh) owns K-half kh x column block cb of the concatenated weight, held in
 //     REGISTERS for the lifetime of the workgroup (no weight traffic in the steady state), multiplies with
 //     v_mfma_f32_32x32x16_bf16 (6 per K=16, two independent accumulator chains), and the two K-half partial
 //     tiles are summed through LDS (double buffered) with feature_bias + BatchNorm + activation applied in
 //     the 16-byte store.
-// One workgroup barrier per tile; results are deterministic.
+// One workgroup barrier per tile, taken by every wave; results are deterministic.
 //
-// What bounds it (measured, tools/coissue_probe.hip): on gfx950 an FP32 VALU instruction does NOT issue while
-// another wave's MFMA occupies the same SIMD -- FP VALU time and MFMA time add -- whereas integer VALU, LDS
-// and memory instructions do overlap with it.  So the design minimises FP instructions, not just total
-// instructions: neighbour offsets are computed ONCE per (point, neighbour) by one lane and broadcast with DPP
-// moves (not 16x redundantly), the bf16 split uses packed subtracts, and everything else the producers do
-// (addresses, masks, byte permutes, LDS writes, loads) runs in the shadow of the consumers' MFMAs.
+// What bounds it (measured, tools/coissue_probe2.hip): a SIMD issues one VALU-class instruction (VALU or
+// MFMA) per ~4.7 cycles whatever the number of waves.  Scalar-f32 and integer VALU work of one wave runs beside another
+// wave's MFMAs; a PACKED f32 instruction (v_pk_*_f32) occupies the matrix pipe and serialises with every wave's MFMAs
+// on the SIMD, and matrix-pipe work of a second wave starves behind a wave that streams MFMAs.  So the producers stay
+// off the matrix pipe (scalar f32 reduce and split, no SLP re-packing) and the design minimises VALU instructions:
+// neighbour offsets are computed once per (point, neighbour, component) and broadcast inside the fma itself
+// (v_fmac_f32_dpp: along the 16-lane row for 64 -> 64, within the quad for 32 -> 64), and addresses, masks, byte permutes,
+// LDS writes and loads are kept to one set per point.
 #include <type_traits>
 
 #include "bf16x3.h"
@@ -30,7 +39,7 @@ namespace {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTM = 32;   // points per tile
-constexpr int kPPR = 32;  // points per producer round (16 lanes per point, 8 producer waves)
+constexpr int kPPR = 32;  // points per producer round (64 -> 64: 8 waves x 4 points; 32 -> 64: one group of 4 waves x 8 points)
 constexpr int kProducers = 8 * 64, kThreads = kProducers + 256;
 
 template <int DIN, int DOUT>
@@ -39,13 +48,15 @@ struct X6Cfg {
   static constexpr int LD = KD + 8;                  // LDS leading dimension of a bf16 plane (elements)
   static constexpr int KB = KD / 16;                 // k-blocks of 16
   static constexpr int KBH = KB / 2;                 // k-blocks per consumer wave (one K-half)
-  static constexpr int VEC = DIN / 16;               // channels per producer lane
+  static constexpr int VEC = 4;                      // channels per producer lane (16-byte gathers)
+  static constexpr int LPP = DIN / VEC;              // producer lanes per point
+  static constexpr int NQ = LPP == 16 ? 2 : 8;       // neighbour coordinates a lane loads per round (see the producers)
   static constexpr int ROUNDS = kTM / kPPR;          // rounds per tile
   static constexpr int A_ELEMS = 3 * kTM * LD;       // bf16 elements per S buffer
   static constexpr int P_FLOATS = 4 * 8 * 64;        // floats per partial buffer: four consumer waves x half an accumulator tile
   static constexpr int B3_VEC = 2 * KB * 64;         // uint4 per third weight plane (two column blocks x KB fragments)
   static constexpr size_t LDS_BYTES = (size_t)2 * A_ELEMS * 2 + (size_t)2 * P_FLOATS * 4 + (size_t)B3_VEC * 16;
-  static_assert(DOUT == 64 && (VEC == 2 || VEC == 4) && KBH % 2 == 0 && LDS_BYTES <= 159 * 1024, "shape");
+  static_assert(DOUT == 64 && (LPP == 8 || LPP == 16) && KBH % 2 == 0 && LDS_BYTES <= 159 * 1024, "shape");
 };
 
 // LDS traffic of this wave done, then workgroup barrier.  Global loads stay in flight across it.
@@ -70,10 +81,6 @@ __device__ __forceinline__ void split3x2(const f32x2 v, unsigned &c1, unsigned &
   c3 = pack_hi16(t0, t1);
 }
 
-template <int VEC> struct LaneVec;
-template <> struct LaneVec<4> { typedef float4 type; };
-template <> struct LaneVec<2> { typedef float2 type; };
-
 // RAGGED: the last tile is partial (R % 32 != 0): stores are guarded, which costs the reduce its place in the
 // MFMA shadow (a guarded store is a branch); full-tile launches use the unguarded instantiation.
 template <int DIN, int DOUT, bool RAGGED>
@@ -81,7 +88,8 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
     const float *__restrict__ feat, const float *__restrict__ xyz, const int32_t *__restrict__ nbr,
     const uint4 *__restrict__ wp3, unsigned R, unsigned N, EpilogueArgs ep, float *__restrict__ out, int T) {
   using C = X6Cfg<DIN, DOUT>;
-  using FV = typename LaneVec<C::VEC>::type;
+  typedef float4 FV;
+  constexpr bool QUAD = C::LPP == 8;  // 32 -> 64: eight lanes per point, offsets per quad, two producer groups (below)
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
   unsigned short *s_A = reinterpret_cast<unsigned short *>(s_raw);           // [2][3][kTM][LD] bf16
   float *s_P = reinterpret_cast<float *>(s_raw + (size_t)2 * C::A_ELEMS * 2);  // [2][2][kTM][PLD] f32
@@ -97,26 +105,32 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
 
   if (wave < kProducers / 64) {
     // ------------------------------------------------------------------ producers
-    // FP32 VALU work only issues in the gaps of the consumers' MFMA stream: with the producers ahead in the issue
-    // arbitration those gaps open as soon as an FP instruction is ready instead of at the end of a GEMM burst
-    // (measured 26.9 -> 25.9 us per launch)
+    // The producers' VALU instructions share the SIMD's one VALU-class issue port with the consumer's MFMAs (~4.7 cycles
+    // per instruction, see the header): with the producers ahead in the issue arbitration a ready producer instruction
+    // goes out between two MFMAs instead of at the end of a GEMM burst (measured 26.9 -> 25.9 us per launch)
     __builtin_amdgcn_s_setprio(3);
-    const int prow = tid >> 4, lj = tid & 15;
+    // 64 -> 64: 16 lanes per point, a wave covers 4 points per round and all eight waves produce every tile.
+    // 32 -> 64: 8 lanes per point, a wave covers 8 points, four waves cover a tile.  Waves w and w + 4 share SIMD w % 4, so
+    // each group of four (grp = wave >> 2) has one wave per SIMD; group grp produces the tiles i with i % 2 == grp into S
+    // buffer i & 1 = grp, always its own, and a round g of a wave is its group's g-th tile.
+    const int grp = QUAD ? wave >> 2 : 0;
+    const int prow = QUAD ? (tid & 255) >> 3 : tid >> 4, lj = tid & (C::LPP - 1);
     const int c0 = lj * C::VEC;  // first channel of this lane
     const unsigned mrec = (unsigned)(0x100000000ULL / N);
-    const int G = cnt * C::ROUNDS;  // rounds of this workgroup
+    const int G = QUAD ? (cnt + 1 - grp) >> 1 : cnt * C::ROUNDS;  // rounds of this wave
     int nid[2][8], myid[2][2];
     FV fv[2][8];
-    float qd[2][2], pcd[2];
-    // neighbour offsets, one dword per lane (see compute): lane l of a point's 16 lanes is (slot a = (l >> 2) & 3,
-    // component i = l & 3) and holds [-, dx, dy, dz][i] of neighbours a and a + 4
+    float qd[2][C::NQ], pcd[2];
+    // neighbour offsets, one dword per lane (see compute).  16 lanes per point: lane l of a point is (slot a = (l >> 2) & 3,
+    // component i = l & 3) and holds [-, dx, dy, dz][i] of neighbours a and a + 4.  8 lanes per point: lane i of every quad
+    // holds [-, dx, dy, dz][i] of all eight neighbours.
     const int da = (tid >> 2) & 3, di = tid & 3;
     const int dcomp = di > 0 ? di - 1 : 0;   // (lanes with i = 0 are never read)
 
-    // rounds at or past G are dummies (row 0 again, into the idle buffer): the pipeline below then has no
-    // conditional loads -- a load under a branch is merged through register copies that wait for it
+    // rounds at or past G are dummies (row 0 again; 64 -> 64 reduces them into the idle buffer, 32 -> 64 only loads them):
+    // the pipeline below then has no conditional loads -- a load under a branch is merged through register copies that wait for it
     auto row_of = [&](int g, unsigned &n, bool &ok) {
-      const int i = g / C::ROUNDS, r = g % C::ROUNDS;
+      const int i = QUAD ? 2 * g + grp : g / C::ROUNDS, r = QUAD ? 0 : g % C::ROUNDS;
       n = (unsigned)(tbeg + i * S) * kTM + r * kPPR + prow;
       ok = (int)(g < G) & (int)(n < R);
       n = ok ? n : 0u;
@@ -128,8 +142,10 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
       const int4 a = ip[0], b = ip[1];
       nid[s][0] = a.x; nid[s][1] = a.y; nid[s][2] = a.z; nid[s][3] = a.w;
       nid[s][4] = b.x; nid[s][5] = b.y; nid[s][6] = b.z; nid[s][7] = b.w;
-      myid[s][0] = nbr[(size_t)n * 8 + da];
-      myid[s][1] = nbr[(size_t)n * 8 + 4 + da];
+      if constexpr (!QUAD) {
+        myid[s][0] = nbr[(size_t)n * 8 + da];
+        myid[s][1] = nbr[(size_t)n * 8 + 4 + da];
+      }
     };
     auto issue_feat = [&](int s, int g) {
       unsigned n; bool ok;
@@ -138,8 +154,12 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
       if (n - q * N >= N) ++q;
       const unsigned cloud0 = q * N;
       pcd[s] = xyz[(size_t)n * 3 + dcomp];
-      qd[s][0] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(xyz) + (size_t)((cloud0 + (unsigned)myid[s][0]) * 12u + (unsigned)dcomp * 4u));
-      qd[s][1] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(xyz) + (size_t)((cloud0 + (unsigned)myid[s][1]) * 12u + (unsigned)dcomp * 4u));
+      const int *cid = QUAD ? nid[s] : myid[s];  // the neighbours whose offsets this lane holds
+#pragma unroll
+      for (int k = 0; k < C::NQ; ++k) {
+        const unsigned g2 = cloud0 + (unsigned)cid[k];
+        qd[s][k] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(xyz) + (size_t)(g2 * 12u + (unsigned)dcomp * 4u));
+      }
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const unsigned g2 = cloud0 + (unsigned)nid[s][k];
@@ -149,25 +169,33 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
     };
     auto compute = [&](int s, int g) {
       // (rows past R and dummy rounds read point 0: finite values in S rows whose outputs are never stored)
-      const int i = g / C::ROUNDS, r = g % C::ROUNDS;
+      const int i = QUAD ? 2 * g + grp : g / C::ROUNDS, r = QUAD ? 0 : g % C::ROUNDS;
       // The K-neighbour reduce  S_c[ch] = sum_k [1, dx, dy, dz]_k[c] * f_k[ch]  in SCALAR f32 VALU instructions.  Measured
       // on gfx950 (tools/coissue_probe2.hip, profiles/r05_*_coissue_probe2.txt): scalar-f32 and integer VALU work of
       // one wave issues freely while another wave's MFMAs run; a packed-f32 instruction (v_pk_fma_f32) occupies the
       // matrix pipe; and ANY matrix-pipe instruction of a second wave (packed f32, or this reduce as
       // v_mfma_f32_4x4x1_16b_f32: 4x fewer issue slots) starves behind a wave that streams MFMAs back to back -- the
       // two waves' times add.  So the producers stay off the matrix pipe entirely.
-      // Lane (a, i) of a point's 16 lanes holds component i of [1, dx, dy, dz] for neighbours a (d0) and a + 4 (d1);
-      // component c of neighbour k is broadcast along the row from lane 4 (k & 3) + c.
-      float d0 = qd[s][0] - pcd[s], d1 = qd[s][1] - pcd[s];
+      // 16 lanes per point: lane (a, i) of a point holds component i of [1, dx, dy, dz] for neighbours a (d[0]) and a + 4
+      // (d[1]); component c of neighbour k is broadcast along the 16-lane DPP row from lane 4 (k & 3) + c.
+      // 8 lanes per point (two points per DPP row, so no row broadcast): lane i of every quad holds component i for neighbour
+      // k in d[k] -- eight subtractions instead of two -- and component c is broadcast within the quad (quad_perm:[c,c,c,c]).
+      // Either way every channel sees the same operands in the same order: the two mappings give the same bits.
+      float d[C::NQ];
+#pragma unroll
+      for (int k = 0; k < C::NQ; ++k) d[k] = qd[s][k] - pcd[s];
       // (a DPP read of a VGPR needs two wait states after the VALU write; the compiler cannot see into the asm below)
-      asm volatile("s_nop 1" : "+v"(d0), "+v"(d1));
+      if constexpr (QUAD)
+        asm volatile("s_nop 1" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]), "+v"(d[4]), "+v"(d[5]), "+v"(d[6]), "+v"(d[7]));
+      else
+        asm volatile("s_nop 1" : "+v"(d[0]), "+v"(d[1]));
       f32x2 acc[4][C::VEC / 2];  // [S0, Sx, Sy, Sz][channel pair]
-      // acc += bcast(row lane L of d) * f as ONE instruction: v_fmac_f32 with the DPP row broadcast on its first
+      // acc += bcast(lane L of d) * f as ONE instruction: v_fmac_f32 with the DPP broadcast (L: its control) on its first
       // source (the compiler keeps a separate v_mov_b32_dpp per broadcast value: 24 more VALU issue slots per round)
 #define DH3D_X6_FMAC_BCAST(ACC, D, F, L) \
-  asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:" #L " row_mask:0xf bank_mask:0xf" : "+v"(ACC) : "v"(D), "v"(F))
+  asm("v_fmac_f32_dpp %0, %1, %2 " L " row_mask:0xf bank_mask:0xf" : "+v"(ACC) : "v"(D), "v"(F))
 #define DH3D_X6_MUL_BCAST(ACC, D, F, L) \
-  asm("v_mul_f32_dpp %0, %1, %2 row_newbcast:" #L " row_mask:0xf bank_mask:0xf" : "=v"(ACC) : "v"(D), "v"(F))
+  asm("v_mul_f32_dpp %0, %1, %2 " L " row_mask:0xf bank_mask:0xf" : "=v"(ACC) : "v"(D), "v"(F))
 #define DH3D_X6_NEIGHBOUR_(KI, DS, LX, LY, LZ)                                                                   \
   {                                                                                                              \
     const float *fp = reinterpret_cast<const float *>(&fv[s][KI]);                                               \
@@ -189,10 +217,11 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
     }                                                                                                            \
   }
 #define DH3D_X6_NEIGHBOUR(KI)                                                                                    \
-  if (((KI) & 3) == 0) DH3D_X6_NEIGHBOUR_(KI, ((KI) < 4 ? d0 : d1), 1, 2, 3)                                      \
-  else if (((KI) & 3) == 1) DH3D_X6_NEIGHBOUR_(KI, ((KI) < 4 ? d0 : d1), 5, 6, 7)                                 \
-  else if (((KI) & 3) == 2) DH3D_X6_NEIGHBOUR_(KI, ((KI) < 4 ? d0 : d1), 9, 10, 11)                               \
-  else DH3D_X6_NEIGHBOUR_(KI, ((KI) < 4 ? d0 : d1), 13, 14, 15)
+  if constexpr (QUAD) DH3D_X6_NEIGHBOUR_(KI, d[KI], "quad_perm:[1,1,1,1]", "quad_perm:[2,2,2,2]", "quad_perm:[3,3,3,3]") \
+  else if (((KI) & 3) == 0) DH3D_X6_NEIGHBOUR_(KI, d[(KI) >> 2], "row_newbcast:1", "row_newbcast:2", "row_newbcast:3")   \
+  else if (((KI) & 3) == 1) DH3D_X6_NEIGHBOUR_(KI, d[(KI) >> 2], "row_newbcast:5", "row_newbcast:6", "row_newbcast:7")   \
+  else if (((KI) & 3) == 2) DH3D_X6_NEIGHBOUR_(KI, d[(KI) >> 2], "row_newbcast:9", "row_newbcast:10", "row_newbcast:11") \
+  else DH3D_X6_NEIGHBOUR_(KI, d[(KI) >> 2], "row_newbcast:13", "row_newbcast:14", "row_newbcast:15")
       DH3D_X6_NEIGHBOUR(0) DH3D_X6_NEIGHBOUR(1) DH3D_X6_NEIGHBOUR(2) DH3D_X6_NEIGHBOUR(3)
       DH3D_X6_NEIGHBOUR(4) DH3D_X6_NEIGHBOUR(5) DH3D_X6_NEIGHBOUR(6) DH3D_X6_NEIGHBOUR(7)
 #undef DH3D_X6_NEIGHBOUR
@@ -207,18 +236,45 @@ __global__ __launch_bounds__(kThreads) void flex_conv_x6_kernel(
         for (int h = 0; h < C::VEC / 2; ++h) {
           split3x2(acc[c][h], c1[h], c2[h], c3[h]);
         }
-        if (C::VEC == 4) {
-          *reinterpret_cast<uint2 *>(row + c * DIN) = make_uint2(c1[0], c1[C::VEC / 2 - 1]);
-          *reinterpret_cast<uint2 *>(row + c * DIN + kTM * C::LD) = make_uint2(c2[0], c2[C::VEC / 2 - 1]);
-          *reinterpret_cast<uint2 *>(row + c * DIN + 2 * kTM * C::LD) = make_uint2(c3[0], c3[C::VEC / 2 - 1]);
-        } else {
-          *reinterpret_cast<unsigned *>(row + c * DIN) = c1[0];
-          *reinterpret_cast<unsigned *>(row + c * DIN + kTM * C::LD) = c2[0];
-          *reinterpret_cast<unsigned *>(row + c * DIN + 2 * kTM * C::LD) = c3[0];
-        }
+        *reinterpret_cast<uint2 *>(row + c * DIN) = make_uint2(c1[0], c1[1]);
+        *reinterpret_cast<uint2 *>(row + c * DIN + kTM * C::LD) = make_uint2(c2[0], c2[1]);
+        *reinterpret_cast<uint2 *>(row + c * DIN + 2 * kTM * C::LD) = make_uint2(c3[0], c3[1]);
       }
     };
 
+    if constexpr (QUAD) {
+      // One schedule.  A wave has two tile periods per round: it reduces its tile in the period that ends with the tile's
+      // barrier, and requests the rows of its next round and the ids of two rounds after that one in the other period,
+      // while the other group reduces -- so on every SIMD one producer wants the VALU and the other the load path, which
+      // is what the two schedules of the 64 -> 64 kernel below arrange.  (Measured alone at 8 x 8192, profiles/x6_din32.txt: 15.1 us per
+      // launch; rows two rounds ahead 16.1 us -- a wave has only cnt / 2 rounds, and every round of lead is a dummy round of
+      // loads at the end; requests in front of the reduce instead of behind its barrier 16.2 us.)  Every wave takes every barrier: cnt + 1 in all, the first and the last outside the loop for the
+      // group they do not belong to.
+      issue_ids(0, 0);
+      issue_ids(1, 1);
+      issue_feat(0, 0);
+      issue_ids(0, 2);
+      if (grp) wg_barrier(0);  // tile 0 (group 0's) is staged
+      auto round = [&](int s, int gg) {
+        compute(s, gg);
+        wg_barrier(2 * gg + grp);  // tile 2 gg + grp is staged
+        issue_feat(s ^ 1, gg + 1);
+        issue_ids(s ^ 1, gg + 3);
+        wg_barrier(2 * gg + grp + 1);  // the other group's tile is staged, or (== cnt) the consumers' last partial tiles
+      };
+      // No exit test between a round's requests and the reduce that uses them: behind one, the compiler sinks the requests
+      // past the second barrier to just in front of that reduce (the barrier's memory clobber does not hold back loads
+      // through __restrict__ const pointers), and the round has no lead at all.  (A dummy round is loaded, never reduced:
+      // the consumers may be reading this group's buffer.)
+      int g = 0;
+      for (; g + 1 < G; g += 2) {
+        round(0, g);
+        round(1, g + 1);
+      }
+      if (g < G) round(0, g);
+      if ((cnt & 1) == grp) wg_barrier(cnt);
+      return;
+    }
     // Two schedules, one producer of each per SIMD.  Every producer does the same work per round -- reduce + split (VALU and matrix
     // pipe), then the gathers of a later round (address arithmetic, then the CU's one texture-address path) -- and the
     // workgroup barrier keeps the eight of them in step: with one schedule they all want the VALU in the first half of
