@@ -270,6 +270,9 @@ _SIGNATURES = {
     "dh3d_prob_sample_seeded": [c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_scan_context": [c_fp, c_ll, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_float, c_fp, c_fp, c_fp],
     "dh3d_scan_context_distance": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_iss_keypoints_ws_bytes": [c_int, c_int, c_int],
+    "dh3d_iss_keypoints": [c_fp, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_double, c_double, c_int, c_int, c_fp, c_fp, c_fp, c_fp,
+                           c_fp, c_fp, c_size_t, c_fp],
 }
 _RESTYPES = {
     "dh3d_arch": ctypes.c_char_p,
@@ -294,6 +297,7 @@ _RESTYPES = {
     "dh3d_retrieve_ws_bytes": c_size_t,
     "dh3d_resample_clouds_ws_bytes": c_size_t,
     "dh3d_draw_queries_ws_bytes": c_size_t,
+    "dh3d_iss_keypoints_ws_bytes": c_size_t,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

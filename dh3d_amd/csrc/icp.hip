@@ -26,9 +26,10 @@
 //                     crowded flag (cells[kCellFlag]) is NOT a reason to leave the cells: for one radius-bound neighbour a
 //                     dense cell costs its points and no more, while 64 unrelated lanes meet nearly every group between
 //                     them (sending crowded clouds to the groups measured 2.47 ms for 64 x 8192 x 8192 on the demo
-//                     clouds, the scan 1.52).  The sort sees the rows below anchor_count only: icp_pack_kernel hands it
-//                     row r % na in place of every row r >= na (such rows are never candidates: their index says so), so
-//                     the grid of a cloud padded with rows of 100000.0 is the grid of its points, not of its padding.
+//                     clouds, the scan 1.52).  The sort sees the rows below anchor_count only: cloud_pack_kernel
+//                     (cloud_pack.h, shared with iss.hip) hands it row r % na in place of every row r >= na (such rows are
+//                     never candidates: their index says so), so the grid of a cloud padded with rows of 100000.0 is the
+//                     grid of its points, not of its padding.
 // The fit and stats kernels, one 256-lane workgroup per cloud pair, share four helpers:
 //   IcpClouds           the batch as one argument block: clouds, normals (null for a method without them), strides, counts,
 //                       nn and the working pose.  icp_run fills it once; these kernels and icp_grid_kernel take it by value.
@@ -53,6 +54,7 @@
 #include <math.h>
 
 #include "cell_grid.h"
+#include "cloud_pack.h"
 #include "common.h"
 #include "keys.h"
 #include "rigid_fit.h"
@@ -136,19 +138,6 @@ __global__ __launch_bounds__(64) void icp_init_kernel(const double *__restrict__
   }
   for (int e = 0; e < 12; ++e) pose[(long long)p * 12 + e] = ok ? v[e] : quiet_nan();
   valid[p] = ok ? 1 : 0;
-}
-
-// anchor rows with an element stride -> [P, Na, 3] for the sort.  Row r >= na becomes a copy of row r % na: whatever lies
-// behind the count (prepare_clouds pads with 100000.0) stays out of the grid's extent, and the copies spread over the
-// cloud's cells instead of crowding one.  The copies keep their own index r >= na, which icp_take refuses.
-__global__ __launch_bounds__(kThreads) void icp_pack_kernel(const float *__restrict__ a, long long stride, int Na,
-                                                            const int32_t *__restrict__ a_count, float *__restrict__ out) {
-  const int p = blockIdx.y, r = blockIdx.x * kThreads + threadIdx.x;
-  if (r >= Na) return;
-  const int na = a_count ? clamp_count(a_count[p], Na) : Na;
-  const float *src = a + ((long long)p * Na + (r < na || na == 0 ? r : r % na)) * stride;
-  float *dst = out + ((long long)p * Na + r) * 3;
-  dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
 }
 
 // ---------------------------------------------------------------------------------------------------------------- scan
@@ -670,8 +659,8 @@ static int icp_run(IcpClouds c, double epsilon, const double *Rt0, const int32_t
 
   hipLaunchKernelGGL(icp_init_kernel, dim3(dh3d_cdiv(P, 64)), dim3(64), 0, s, Rt0, valid0, P, ws.pose, valid);
   if (grid) {
-    hipLaunchKernelGGL(icp_pack_kernel, dim3(dh3d_cdiv(c.Na, kThreads), P), lanes, 0, s, c.anchor, c.a_stride, c.Na, c.a_count,
-                       ws.packed);
+    hipLaunchKernelGGL(cloud_pack_kernel, dim3(dh3d_cdiv(c.Na, kPackThreads), P), dim3(kPackThreads), 0, s, c.anchor, c.a_stride,
+                       c.Na, c.a_count, ws.packed);
     const int st = dh3d_spatial_sort_cells(ws.packed, P, c.Na, reinterpret_cast<float *>(ws.sorted), ws.gbox, ws.cells, stream);
     if (st != DH3D_OK) return st;
   }

@@ -157,6 +157,18 @@ __device__ __forceinline__ double smallest_eigenvector_3(const double *Cu, doubl
   return low;
 }
 
+// The three eigenvalues of the symmetric C (upper triangle as above) in descending order l[0] >= l[1] >= l[2], for
+// csrc/iss.hip: smallest_eigenvector_3's solve with the vector dropped (the compiler removes the rotations' products).
+__device__ __forceinline__ void eigenvalues_3_descending(const double *Cu, double *l) {
+  double d[3], n[3];
+  smallest_eigenvector_3(Cu, d, n);
+  double a = d[0], b = d[1], c = d[2], t;
+  if (a < b) { t = a; a = b; b = t; }
+  if (b < c) { t = b; b = c; c = t; }
+  if (a < b) { t = a; a = b; b = t; }
+  l[0] = a; l[1] = b; l[2] = c;
+}
+
 // t = xc - R yc
 __device__ __forceinline__ void translation(const double *R, const double *xc, const double *yc, double *t) {
   for (int r = 0; r < 3; ++r) t[r] = xc[r] - (R[3 * r] * yc[0] + R[3 * r + 1] * yc[1] + R[3 * r + 2] * yc[2]);

@@ -19,6 +19,8 @@ sampler replaces randsample, whose stream cannot be reproduced).
     res = refine_icp_gicp(anchor_points, positive_points, res["Rt"], res["valid"])  # generalized ICP: + num_planar, rmse_gicp
     f = compute_fpfh(anchor_points, k=32)                                     # fpfh [P, N, 36], counts, normals, nbr
     res = register_fpfh(anchor_points, positive_points, refine=True)          # no model: normals -> FPFH -> match -> RANSAC -> ICP
+    kp = iss_keypoints(anchor_points, salient_radius=2.0, non_max_radius=1.5) # ISS detector: ids, count, saliency, ...
+    res = register_fpfh(anchor_points, positive_points, keypoints={"method": "iss"})  # ... in front of the FPFH registration
     dt, ddeg = transform_errors(T_gt, res["Rt"], res["valid"])                # compareTransform, host float64
     summary = summarize_registration(dt, ddeg, res["inlier_ratio"], res["trials"])
 """
@@ -391,11 +393,111 @@ def compute_fpfh(points, normals=None, num_valid=None, k=32, max_dist=None, nbr=
     return dict(fpfh=fpfh, counts=counts, normals=nrm, nbr=nbr)
 
 
+ISS_MAX_POINTS = 16384  # csrc/iss.hip kMaxN (the cell table of dh3d_spatial_sort_cells); its kMaxKeep is KEYPOINT_MAX
+_ISS_WS = {}  # (device, P, N, M) -> the uint8 workspace of dh3d_iss_keypoints (its content carries nothing between calls)
+
+
+def cloud_resolution(points, num_valid=None):
+    """The resolution of every cloud, [P] float32 on the device: the float64 mean over the valid rows of the distance to the
+    nearest other row (column 1 of utils.batched_knn(points, 2); with padding far away no padded row is a valid row's nearest),
+    0 for fewer than 2 valid rows.  points [P, N, >=3] float32 on the GPU, num_valid [P] int32 or None (all rows).  No host
+    sync."""
+    x = _rows(points, "points", 3)
+    P, N = x.shape[:2]
+    dev = x.device
+    cnt = None if num_valid is None else _count(num_valid, "num_valid", P, dev)
+    if N < 2:
+        return torch.zeros((P,), dtype=torch.float32, device=dev)
+    from .utils import batched_knn
+    with torch.cuda.device(dev):
+        near = batched_knn(x[:, :, :3].contiguous(), 2)[1][:, :, 1].to(torch.float64)
+    n = torch.full((P,), N, dtype=torch.int64, device=dev) if cnt is None else cnt.clamp(0, N).to(torch.int64)
+    inside = torch.arange(N, device=dev)[None, :] < n[:, None]
+    mean = torch.where(inside, near, torch.zeros_like(near)).sum(dim=1) / n.clamp(min=1).to(torch.float64)
+    return torch.where(n >= 2, mean, torch.zeros_like(mean)).to(torch.float32)
+
+
+def _iss_radius(r, name, P, dev):
+    """A radius of iss_keypoints as a [P] float32 device tensor: a number for all clouds, or the caller's tensor."""
+    if isinstance(r, torch.Tensor):
+        if r.dtype != torch.float32 or not r.is_cuda or tuple(r.shape) != (P,) or r.device != dev:
+            raise ValueError("%s must be a number or a float32 [%d] tensor on %s" % (name, P, dev))
+        return r
+    return torch.full((P,), float(r), dtype=torch.float32, device=dev)
+
+
+def iss_keypoints(points, num_valid=None, salient_radius=None, non_max_radius=None, gamma_21=0.975, gamma_32=0.975,
+                  min_neighbors=5, max_keypoints=4096, saliency=None, eigenvalues=False):
+    """ISS keypoints (Intrinsic Shape Signatures, Zhong 2009; Open3D's compute_iss_keypoints) of every cloud, on the device:
+    a point is salient where the float64 scatter of all points within salient_radius has eigenvalues l1 >= l2 >= l3 with l2 <
+    gamma_21 * l1 and l3 < gamma_32 * l2, its saliency being l3; it is a keypoint where no point within non_max_radius is more
+    salient (ties to the lowest index) and both balls hold at least min_neighbors points (include/dh3d_hip.h
+    dh3d_iss_keypoints states every rule).  points [P, N, >=3] float32 on the GPU (the first three columns are read; column
+    views are read in place), N <= 16384; num_valid [P] int32 or None (all rows).  A radius is a number, a [P] float32 device
+    tensor, or None: 6 x (salient) and 4 x (non-max) cloud_resolution(points, num_valid), computed on the device.
+    saliency [P, N] float32: the caller's saliencies in place of the eigenvalue rule (the suppression and the selection
+    alone).  Returns a dict of device tensors: ids [P, max_keypoints] int32 (the most salient first, -1 behind them: what
+    register_fpfh(keypoint_ids=...) takes), count [P] int32, saliency [P, N] float32, num_neighbors [P, N, 2] int32 (the
+    points within the salient and the non-max radius, the point itself counted), eigenvalues [P, N, 3] float64 (l1 l2 l3;
+    None unless asked for) and radii [P, 2] float32 as used.  No host sync: graph-capturable.  The workspace is kept per
+    (device, P, N, max_keypoints) and carries nothing between calls; calls of one shape belong on one stream."""
+    x = _rows(points, "points", 3)
+    P, N = x.shape[:2]
+    dev = x.device
+    cnt = None if num_valid is None else _count(num_valid, "num_valid", P, dev)
+    gamma_21, gamma_32, min_neighbors, M = float(gamma_21), float(gamma_32), int(min_neighbors), int(max_keypoints)
+    if not 0.0 < gamma_21 <= 1.0 or not 0.0 < gamma_32 <= 1.0:
+        raise ValueError("iss_keypoints: gamma_21 and gamma_32 must lie in (0, 1], got %r, %r" % (gamma_21, gamma_32))
+    if min_neighbors < 1:
+        raise ValueError("iss_keypoints: min_neighbors must be at least 1, got %d" % min_neighbors)
+    if N > ISS_MAX_POINTS:
+        raise ValueError("iss_keypoints: at most %d points per cloud, got %d" % (ISS_MAX_POINTS, N))
+    if not 1 <= M <= KEYPOINT_MAX:
+        raise ValueError("iss_keypoints: max_keypoints must lie in 1 .. %d, got %d" % (KEYPOINT_MAX, M))
+    sal_in = None
+    if saliency is not None:
+        sal_in = L.require_cuda_f32(saliency, "saliency", 2)
+        if tuple(sal_in.shape) != (P, N) or sal_in.device != dev:
+            raise ValueError("saliency must be float32 [%d, %d] on %s, got %s on %s" % (P, N, dev, tuple(sal_in.shape), sal_in.device))
+    if salient_radius is None or non_max_radius is None:
+        res = cloud_resolution(x, cnt)
+    rs = res * 6.0 if salient_radius is None else _iss_radius(salient_radius, "salient_radius", P, dev)
+    rn = res * 4.0 if non_max_radius is None else _iss_radius(non_max_radius, "non_max_radius", P, dev)
+    radii = torch.stack((rs, rn), dim=1).contiguous()
+    lib = L.lib()
+    key = (dev, P, N, M)
+    ws = _ISS_WS.get(key)
+    if ws is None:
+        nbytes = lib.dh3d_iss_keypoints_ws_bytes(P, N, M)
+        if nbytes == 0:
+            raise ValueError("iss_keypoints: shape P = %d, N = %d, max_keypoints = %d is not served" % (P, N, M))
+        ws = _ISS_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    sal = torch.empty((P, N), dtype=torch.float32, device=dev)
+    nbr = torch.empty((P, N, 2), dtype=torch.int32, device=dev)
+    lam = torch.empty((P, N, 3), dtype=torch.float64, device=dev) if eigenvalues else None
+    ids = torch.empty((P, M), dtype=torch.int32, device=dev)
+    count = torch.empty((P,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.dh3d_iss_keypoints(L.ptr(x), x.stride(1), L.ptr(cnt), L.ptr(radii), L.ptr(sal_in), P, N, gamma_21, gamma_32,
+                                       min_neighbors, M, L.ptr(sal), L.ptr(nbr), L.ptr(lam), L.ptr(ids), L.ptr(count), L.ptr(ws),
+                                       ws.numel(), L.stream_ptr()), "iss_keypoints")
+    return dict(ids=ids, count=count, saliency=sal, num_neighbors=nbr, eigenvalues=lam, radii=radii)
+
+
 def _fpfh_keypoints(x, cnt, keypoints, keypoint_ids, name):
     """The keypoints of register_fpfh on one batch of clouds: (ids [P, M] int32 or None for all points, count [P] int32)."""
     P, N = x.shape[:2]
     dev = x.device
     full = torch.full((P,), N, dtype=torch.int32, device=dev) if cnt is None else cnt.clamp(0, N)
+    if isinstance(keypoints, dict):  # a detector: {"method": "iss", ...iss_keypoints' keywords}
+        kw = dict(keypoints)
+        method = kw.pop("method", None)
+        if method != "iss":
+            raise ValueError('%s keypoints: method must be "iss", got %r' % (name, method))
+        if keypoint_ids is not None:
+            raise ValueError("%s: give a keypoint detector or keypoint_ids, not both" % name)
+        res = iss_keypoints(x, cnt, **kw)
+        return res["ids"], res["count"]
     if keypoint_ids is not None:
         ids = L.require_cuda_i32(keypoint_ids, name + " keypoint_ids", 2)
         if ids.shape[0] != P or ids.device != dev:
@@ -422,7 +524,9 @@ def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None
     the GPU.  num_valid: None, one int32 [P] tensor for both batches, or a pair (anchor, positive).  The keypoints of a cloud:
     every point when it has at most 4096 rows and nothing is asked; otherwise `keypoints` = M (default 4096) of them spread
     over the valid rows, ids[p, r] = (r * n_p) // M, computed on the device; or the caller's keypoint_ids -- one int32 [P, M]
-    tensor or a pair (anchor, positive), e.g. farthest-point picks, -1 padded at the tail.  keypoints may be a pair too.
+    tensor or a pair (anchor, positive), e.g. farthest-point picks, -1 padded at the tail.  keypoints may be a pair too, and
+    in place of a number a detector: {"method": "iss", ...iss_keypoints' keywords} runs iss_keypoints on the cloud (N <= 16384)
+    and goes on as with its ids as keypoint_ids.
     refine: None, True or a dict of refine_pose keywords, on the full clouds.  Returns register_clouds' keys: ransac_rigid's
     dict plus match / dist (indices into the keypoint lists), and with refine Rt_ransac, fitness, rmse, num_corr_icp, nn (and
     num_plane, rmse_plane with method="plane"; num_planar, rmse_gicp with method="gicp"); plus anchor_ids / positive_ids (the

@@ -1437,6 +1437,50 @@ int dh3d_icp_refine_gicp(const float *anchor, long long anchor_stride, const int
                          double *Rt, int32_t *nn, int32_t *num_corr, double *fitness, double *rmse, int32_t *valid,
                          int32_t *num_planar, double *rmse_gicp, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ISS keypoints (csrc/iss.hip) -- Intrinsic Shape Signatures, Zhong 2009, the model-free detector that Open3D offers as
+ * compute_iss_keypoints: a point is salient where the scatter of ALL points within a radius has three well separated
+ * eigenvalues, and a keypoint where no point within a second radius is more salient.  The rule follows Open3D 0.1x as
+ * remembered, not as read from a source on this tree; what rests on memory alone is marked INFERRED:
+ *   INFERRED  both radius tests are strict (d2 < r * r) and the point itself is a member of its own neighbourhoods;
+ *   INFERRED  the covariance is (sum e e^T) / m - mean mean^T over the members, the point itself included;
+ *   INFERRED  a point is salient iff l2 / l1 < gamma_21 and l3 / l2 < gamma_32 (here as products), its saliency being l3;
+ *   INFERRED  both neighbourhoods need at least min_neighbors members.
+ *   The project's own: ties of the suppression go to the lowest index (Open3D keeps both of two equal maxima, which gives
+ *   twin keypoints on clouds with exact duplicates), and at most M keypoints come back, the most salient first.
+ * INPUTS: point i of cloud p at xyz + (p*N + i) * stride (3 floats; the stride in elements, >= 3), finite below n =
+ *   clamp(count[p], 0, N); a NULL count means N.  radii [P, 2] float32 on the DEVICE: r_s (salient radius) and r_n (non-max
+ *   radius) of every cloud.  gamma_21, gamma_32 in (0, 1]; min_neighbors >= 1; 1 <= M <= 4096.
+ * 1 MEMBERSHIP, float32, every operation rounded on its own (no fused multiply-add): d = x_j - x_i per axis, d2 = (dx*dx +
+ *   dy*dy) + dz*dz; j is in S_i iff j < n and d2 < r_s * r_s (the product in float32), in T_i iff j < n and d2 < r_n * r_n.
+ *   i is a member of both (d2 = 0).  A radius that is <= 0 or NaN has no members.  num_nbr[p, i] = (|S_i|, |T_i|).
+ * 2 MOMENTS, float64: for j in S_i, e = (double)x_j - (double)x_i per axis (NOT the float32 d of step 1); S1 = sum of e,
+ *   S2 = sum of e e^T, m = |S_i|; C = S2 / m - (S1 / m)(S1 / m)^T.  l1 >= l2 >= l3: the eigenvalues of C by the cyclic
+ *   Jacobi of dh3d_estimate_normals (csrc/rigid_fit.h), sorted.  The order of the sums is not part of the rule: the
+ *   eigenvalues carry an error of a few m * 2^-53 * r_s^2.
+ * 3 SALIENCY, float32: s_i = (float)l3 if m >= min_neighbors and l2 < gamma_21 * l1 and l3 < gamma_32 * l2 and l3 > 0 (the
+ *   products in float64), else +0.  Rows i >= n: 0.
+ * 4 KEYPOINT: i < n is one iff s_i > 0 and |T_i| >= min_neighbors and no j in T_i, j != i, has s_j > s_i or (s_j == s_i and
+ *   j < i).  A saliency that is <= 0 or NaN is never a candidate and never suppresses.
+ * 5 OUTPUT: the keypoints by (s descending, index ascending), the first min(M, their number) of them: ids [P, M] int32, -1
+ *   behind them; kp_count [P] = the number written.
+ * saliency_in [P, N] float32 or NULL.  Given: steps 2 and 3 are skipped, s_i = saliency_in[p, i] for i < n (0 behind), the
+ *   counts of step 1 are computed all the same, and lam, if asked for, is written as 0.
+ * OUTPUTS: saliency [P, N] float32; num_nbr [P, N, 2] int32 (0 for rows i >= n); lam [P, N, 3] float64 or NULL: l1 l2 l3 of
+ *   every row i < n with m >= 1, else 0; ids and kp_count.  Every element of every output is written, for n = 0 too.  A
+ *   cloud's result does not depend on the batch, on the workspace's content or on the run.
+ * dh3d_iss_keypoints_ws_bytes (host only; the shape alone): bytes of the caller-owned workspace (16-byte aligned, no clearing
+ *   needed); 0 for a shape the call refuses.
+ * SIDE EFFECTS: caller's stream, one launch after the other (pack, dh3d_spatial_sort_cells, moments, suppression, select; no
+ *   parallel branches), no host sync, no allocation, no floating-point atomics; graph-capturable.
+ * STATUS: NULL pointers (count, saliency_in and lam excepted), a stride below 3, P / N / M <= 0, min_neighbors < 1, a gamma
+ *   not in (0, 1] (NaN included), a misaligned or too small workspace: DH3D_ERR_INVALID_ARGUMENT.  N > 16384 (the cell table),
+ *   P > 65535, M > 4096: DH3D_ERR_UNSUPPORTED.  Both before any launch.  Non-finite coordinates below n are outside the
+ *   contract. */
+size_t dh3d_iss_keypoints_ws_bytes(int P, int N, int M);
+int dh3d_iss_keypoints(const float *xyz, long long stride, const int32_t *count, const float *radii, const float *saliency_in,
+                       int P, int N, double gamma_21, double gamma_32, int min_neighbors, int M, float *saliency,
+                       int32_t *num_nbr, double *lam, int32_t *ids, int32_t *kp_count, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
