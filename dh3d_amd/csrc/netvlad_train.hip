@@ -82,8 +82,17 @@ __global__ __launch_bounds__(256) void nv_walk_kernel(const NvArgs a) {
   const int bi = xcd + 8 * (seq / a.nblk), blk = seq % a.nblk;
   if (bi >= a.B) return;
   const int n = a.n, m = a.m;
-  if (a.mask && !a.mask[bi]) {  // a padding cloud: no statistics, zero gradients
-    if (MODE == 2 && tid < kP && blk * kP + tid < n) a.datt[(size_t)bi * n + blk * kP + tid] = 0.f;
+  if (a.mask && !a.mask[bi]) {  // a padding cloud: no statistics, zero gradients, and zero rows in what this pass writes
+    const size_t r0 = (size_t)bi * n + (size_t)blk * kP;  // (the blocks of a cloud cover its rows kP at a time)
+    const int live = min(kP, n - blk * kP);
+    float *rows = MODE == 0 ? a.s : MODE == 1 ? a.p : MODE == 2 ? a.dz : nullptr;
+    if (rows)
+      for (int e = tid; e < live * 64; e += 256) rows[r0 * 64 + e] = 0.f;
+    if (tid < live) {
+      if (MODE == 0) a.rinv[r0 + tid] = 0.f;
+      if (MODE == 2) { a.datt[r0 + tid] = 0.f; a.t2[r0 + tid] = 0.f; }
+      if (MODE == 3) a.q[r0 + tid] = 0.f;
+    }
     return;
   }
   if (tid < kP) { s_f0[tid] = 0.f; s_f1[tid] = 0.f; s_f2[tid] = 0.f; }  // (padding points keep these)

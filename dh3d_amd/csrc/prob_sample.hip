@@ -152,6 +152,7 @@ __global__ __launch_bounds__(kScanThreads) void prob_cumsum_kernel(int n, const 
     comp = tt - (r2 - run);
     run = r2;
   }
+  for (int i = nb + tid; i < n; i += kScanThreads) cum[i] = 0.f;  // behind the row's count: no sums, but every element is written
 }
 
 // One draw on the sums of one row, in LDS or in global memory (the caller's pointer decides after inlining).

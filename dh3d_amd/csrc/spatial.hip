@@ -64,8 +64,8 @@ __device__ __forceinline__ unsigned deal_grid_bits(const float ext[3], int nb[3]
 // cells (may be NULL): per cloud kCellInts ints, the slots of cell_grid.h -- [0, 4096]: first sorted position of every grid
 // cell in the order of the cells' 12-bit codes (the top 12 bits of the sort key; an empty cell's entry = the next cell's),
 // [4096] = N; [4100..4105] as floats: the grid's origin (x, y, z) and the quantisation scale 2^(nb + 2) / extent per axis (a
-// cell = 4 quantisation steps); [4107]: the bit schedule (12 x 2 bits, step 0 = the code's top bit).  The key computation
-// below is the expression cell_grid.h's grid_cell restates for the table's readers.
+// cell = 4 quantisation steps); [4107]: the bit schedule (12 x 2 bits, step 0 = the code's top bit); the slots in between
+// and behind: 0.  The key computation below is the expression cell_grid.h's grid_cell restates for the table's readers.
 template <int PPT>
 __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__restrict__ xyz, int N,
                                                                int npad, float4 *__restrict__ sorted,
@@ -123,6 +123,9 @@ __global__ __launch_bounds__(kThreads) void spatial_sort_kernel(const float *__r
     hd[0] = lo[0]; hd[1] = lo[1]; hd[2] = lo[2];
     hd[3] = scale[0]; hd[4] = scale[1]; hd[5] = scale[2];
     ct[kCellSched] = (int)sched;
+    // the slots no field uses: 0, so that the table is a function of the cloud alone (fps.hip copies them to a subset's)
+    ct[kCellCopy] = ct[kCellCopy + 1] = ct[kCellCopy + 2] = 0;
+    for (int c = kCellSched + 1; c < kCellInts; ++c) ct[c] = 0;
   }
   // (near-)cubic clouds get the plain Morton code of rounds 1-4 from three bit-spreads; any other schedule goes through
   // per-axis deposit tables in LDS (a table build, a barrier and three look-ups per point: ~2.5 us at 8 x 8192)

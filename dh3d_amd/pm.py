@@ -265,7 +265,7 @@ def prob_sample(inp, inpr):
 
 def prob_sample_seeded(inp, m, count, seed):
     """inp [b,n] float32 weights, count [b] int32 or None, seed a 1-element int64 GPU tensor -> (ids [b,m] int32, cum [b,n]):
-    include/dh3d_hip.h dh3d_prob_sample_seeded.  cum holds the sums of a row's first count[b] entries only."""
+    include/dh3d_hip.h dh3d_prob_sample_seeded.  cum holds the sums of a row's first count[b] entries, zeros behind them."""
     p = _prob_rows(inp, "prob_sample_seeded")
     m = int(m)
     if m < 1 or m > PROB_SAMPLE_MAX_M:

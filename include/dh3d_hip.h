@@ -355,6 +355,7 @@ int dh3d_knn_sorted(const float *sorted, const float *gbox, int B, int N, int K,
  *   [4107]        the bit SCHEDULE: 12 x 2 bits, field s (bits 2s, 2s+1) = the axis (0 x, 1 y, 2 z) that grid-code bit
  *                 11 - s belongs to -- field 0 is the code's MOST significant bit; within an axis the bits appear in the
  *                 code from that axis' most significant cell-coordinate bit downwards.  0x186186 = z y x z y x ... (cube).
+ *   [4097..4099], [4108..4111]  no field: written as 0 (every int of the table is written by the call)
  * To decode cell code c into per-axis cell coordinates: walk s = 0..11, append bit (c >> (11 - s)) & 1 to the coordinate of
  * axis (sched >> 2s) & 3.  A table written by an ABI <= 3 sort (no schedule, scale 64 / extent) must not be handed to an
  * ABI 4 dh3d_knn_grid.  (The device-side definitions -- slots, header decode, cell map, cell code -- live in
@@ -798,7 +799,8 @@ int dh3d_three_interpolate_bwd_sorted(int b, int n, int c, int m, const float *g
  * three_interpolate (core/backbones.py:89-100), csrc/netvlad_train.hip: c [B*m,256] are the sampled rows, cw = c Wc and
  * E = c dV^T GEMMs on them; s / p / dz [B*n,64], rinv / att / datt / t2 / q [B*n] live on the fine points (by original
  * point index); idx / dist = dh3d_three_nn of the fine points [B,n,3], order = dh3d_spatial_sort records of the fine
- * clouds [B,n,4] (NULL: index order), mask [B] bytes (NULL: every cloud).  m <= 1024.
+ * clouds [B,n,4] (NULL: index order), mask [B] bytes (NULL: every cloud).  m <= 1024.  A masked (padding) cloud takes no
+ * part in any sum, and its rows of every per-point output (s, rinv, p, dz, datt, t2, q) are written as 0.
  *   fwd_stats : s = rinv * interp(cw), rinv = rsqrt(max(|interp(c)|^2, 1e-12)), part [2][B][64] f64 = per-cloud column
  *               sums / sums of squares of s (zeroed by the CALLER)
  *   fwd_assign: p = softmax(s*scale + shift), asum [B,64] = sum_n p*att, Ap [B*m,64] = interp^T(p*att*rinv) (both zeroed
@@ -1326,7 +1328,7 @@ int dh3d_sample_tuples(const double *pos, const int32_t *count, int M, const int
  * dh3d_prob_sample_seeded -- the draws are made on the device by the scheme of "Training batches", stream 16:
  *     r_in(b, j) = (float)((u(16, b, j) >> 40) + 1) * 2^-24       exact in float32, in (0, 1]: q > 0
  *   count: NULL, or a device pointer [b]: row b is its entries 0 .. n_b-1 with n_b = clamp(count[b], 0, n) (NULL: n_b = n);
- *   entries at or beyond n_b are never read, and temp holds the sums of the first n_b entries only.  n_b == 0, or a total
+ *   entries at or beyond n_b are never read, and temp holds the sums of the first n_b entries, then zeros.  n_b == 0, or a total
  *   cum[n_b-1] that is not > 0: every id of the row is -1.  Otherwise no id has weight 0 as long as the sums before it are
  *   exact (q > 0 and the walk stops at the first cum >= q).  seed is a DEVICE pointer to one uint64, as there. */
 int dh3d_prob_sample(int b, int n, int m, const float *inp_p, const float *inp_r, float *temp, int32_t *out, void *stream);

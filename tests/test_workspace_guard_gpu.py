@@ -1,9 +1,10 @@
 """GPU: no entry point writes past the workspace size it asks for.  Each of them runs once over a buffer of need + 4096
-bytes whose tail holds a byte pattern, told workspace_bytes = need, at the smallest shape that puts every segment of its
+bytes filled with a byte pattern, told workspace_bytes = need, at the smallest shape that puts every segment of its
 layout (csrc/workspace.h) in use: the tail must come back untouched, and the outputs must equal a second run over a
-workspace twice as large -- bit for bit where the op has no f32 atomics, within the op's own test's tolerance for the
-gradients that are summed by atomics (flex_conv: tests/test_backward_gpu.py, 1e-4 of the largest entry; FlexDeconv's
-weight gradients: tests/test_flex_deconv_gpu.py, rtol = atol = 1e-3)."""
+workspace twice as large that starts from zero bytes instead (a segment read before it is written shows) -- bit for
+bit where the op has no f32 atomics, within the op's own test's tolerance for the gradients that are summed by atomics
+(flex_conv: tests/test_backward_gpu.py, 1e-4 of the largest entry; FlexDeconv's weight gradients:
+tests/test_flex_deconv_gpu.py, rtol = atol = 1e-3)."""
 import numpy as np
 import pytest
 import torch
@@ -23,7 +24,9 @@ def guarded(dev, query, shape, launch, atomic=()):
     need = getattr(_lib.lib(), query)(*shape)
     assert need > 0, (query, shape)
     small = torch.full((need + TAIL,), PATTERN, dtype=torch.uint8, device=dev)
-    large = torch.full((2 * need,), PATTERN, dtype=torch.uint8, device=dev)
+    # the second workspace starts from other bytes: an output that depends on what a workspace held before the call
+    # differs between the two runs
+    large = torch.zeros((2 * need,), dtype=torch.uint8, device=dev)
     got = launch(small.data_ptr(), need)
     exp = launch(large.data_ptr(), 2 * need)
     torch.cuda.synchronize()
