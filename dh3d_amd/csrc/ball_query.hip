@@ -16,7 +16,7 @@
 #include <float.h>
 #include <math.h>
 
-#include "cell_grid.h"
+#include "cell_walk.h"
 #include "common.h"
 #include "wave_ops.h"
 
@@ -107,8 +107,8 @@ __global__ __launch_bounds__(64) void ball_scan_kernel(const float *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ cell lists
-constexpr int kGridWaves = 4;       // queries per workgroup
-constexpr int kGridMaxCells = 512;  // a ball whose box meets more cells restarts over the 64-point group boxes
+constexpr int kGridWaves = 4;  // queries per workgroup; a ball whose box meets more than kWalkMaxCells cells (cell_walk.h)
+                               // goes over the 64-point group boxes
 
 __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
     const float4 *__restrict__ sorted, const float *__restrict__ gbox, const int *__restrict__ cells,
@@ -121,8 +121,7 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
   unsigned *bits = s_dyn + wave * (64 * wpl + 128);
   int *s_pre = reinterpret_cast<int *>(bits + 64 * wpl), *s_beg = s_pre + 64;
   for (int i = 0; i < wpl; ++i) bits[i * 64 + lane] = 0u;
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the zeroes are in place before any lane's atomicOr
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();  // the zeroes are in place before any lane's atomicOr
 
   const float4 *sc = sorted + (size_t)b * n;
   const size_t qrow = (size_t)b * m + j;
@@ -150,8 +149,10 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
       const int a = sched_axis(g.sched, s);
       g.nb[0] += (int)(a == 0); g.nb[1] += (int)(a == 1); g.nb[2] += (int)(a == 2);
     }
-    // the cells the ball's axis-aligned box meets.  A hit has |q - p| < r (1 + 5 * 2^-24) on every axis; the margin also
-    // covers the two roundings of q -+ r -+ margin, and the cell function is monotone (cell_grid.h grid_cell)
+    // The cells the ball's axis-aligned box meets: cell_walk.h's ball_cells, to the letter (its comment has the argument
+    // for the margin).  Written out here because with the shared function the kernel's preamble came out 3 instructions
+    // longer (1490 against 1487; the loops are the same) and cube_m1024_r0.1_k32 of tools/ball_query_bench.py measured 12.60
+    // us against 12.48 with a spread of 0.08: over the bar by one tick of the timer (profiles/cell_walk.txt section 4).
     int c0[3], cn[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
       cn[a] = grid_cell(g, a, (q[a] + r) + marg) - c0[a] + 1;
     }
     const int total = cn[0] * cn[1] * cn[2];
-    if (!ct[kCellFlag] && total <= kGridMaxCells) {
+    if (!ct[kCellFlag] && total <= kWalkMaxCells) {
       for (int t0 = 0; t0 < total; t0 += 64) {
         // a lane per cell: its range of the order; then the ranges of the 64 cells flattened, a lane per record
         const int t = t0 + lane;
@@ -171,16 +172,10 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
           beg = max(ct[code], 0);
           len = max(min(ct[code + 1], n) - beg, 0);
         }
-        int inc = len;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const int up = __shfl_up(inc, off, 64);
-          if (lane >= off) inc += up;
-        }
+        const int inc = wave_incl_scan(len);
         s_pre[lane] = inc;
         s_beg[lane] = beg - (inc - len);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_sync();
         const int recs = __builtin_amdgcn_readlane(inc, 63);
         for (int rr = lane; rr < recs; rr += 64) {
           int o = 0;  // the first cell whose inclusive prefix exceeds rr
@@ -189,8 +184,7 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
             if (s_pre[o + step - 1] <= rr) o += step;
           test(s_beg[o] + rr);
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_sync();
       }
     } else {
       // crowded cloud or wide ball: every 64-point group of the order whose box the ball meets (1e-5 relative margin on
@@ -216,8 +210,7 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
       }
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();
 
   // ---- read out: lane l owns the words [l * wpl, (l + 1) * wpl) -- ascending indices across the wave
   int c = 0;
@@ -227,12 +220,7 @@ __global__ __launch_bounds__(64 * kGridWaves) void ball_grid_kernel(
     c += __popc(w);
     if (w) lowest = (unsigned)((lane * wpl + i) * 32 + __builtin_ctz(w));
   }
-  int inc = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += up;
-  }
+  const int inc = wave_incl_scan(c);
   const int hits = __builtin_amdgcn_readlane(inc, 63);
   const int cnt = min(hits, nsample);
   int32_t *row = idx + qrow * nsample;

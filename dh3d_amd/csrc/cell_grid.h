@@ -1,8 +1,8 @@
 // The cell table of dh3d_spatial_sort_cells (include/dh3d_hip.h states the layout for callers), device side: the slots, the
 // header's decode, the cell of a coordinate and the table index of a cell.  One definition each: spatial.hip writes the
-// table, knn.hip, ball_query.hip, icp.hip, pointnet2.hip and fps.hip read it, and tests/spatial_reference.py pins every
-// slot bit for bit -- a reader with its own copy that differs in a clamp, a slot or a bit position returns a wrong
-// neighbour on one kind of cloud only.
+// table, knn.hip, ball_query.hip, icp.hip, iss.hip, pointnet2.hip and fps.hip read it, and tests/spatial_reference.py pins
+// every slot bit for bit -- a reader with its own copy that differs in a clamp, a slot or a bit position returns a wrong
+// neighbour on one kind of cloud only.  (cell_walk.h: what the radius searches do with the table.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -22,7 +22,8 @@
 //                     in a loop for every cell, ~400 instructions that almost every step of a wave paid for some lane.
 //                     Candidates are compared by (d2, original index), so the order of the walk does not matter.  A box of
 //                     more than 512 cells takes the 64-point groups of the order whose box the ball meets instead: the
-//                     loop over the groups is wave-uniform, the records of a group are read as broadcasts.  The sort's
+//                     loop over the groups is wave-uniform, the records of a group are read as broadcasts.  The walk
+//                     itself is cell_walk.h's cell_walk, shared with iss.hip; the float64 box and reach test are here.  The sort's
 //                     crowded flag (cells[kCellFlag]) is NOT a reason to leave the cells: for one radius-bound neighbour a
 //                     dense cell costs its points and no more, while 64 unrelated lanes meet nearly every group between
 //                     them (sending crowded clouds to the groups measured 2.47 ms for 64 x 8192 x 8192 on the demo
@@ -53,7 +54,7 @@
 // None of them uses scratch.  Compiled without contraction (csrc/Makefile EXACT): the ids depend on every rounding of d2.
 #include <math.h>
 
-#include "cell_grid.h"
+#include "cell_walk.h"
 #include "cloud_pack.h"
 #include "common.h"
 #include "keys.h"
@@ -67,7 +68,6 @@ constexpr int kMaxPoints = 131072;  // Na, Nb
 constexpr int kMaxPairs = 65535;
 constexpr int kMaxIter = 256;
 constexpr int kGridMaxNa = 16384;   // dh3d_spatial_sort_cells
-constexpr int kGridMaxCells = 512;  // a box that meets more cells walks the 64-point groups
 constexpr int kThreads = 256;
 constexpr int kChunk = 1024;        // anchors staged per step of the scan
 
@@ -215,67 +215,33 @@ __global__ __launch_bounds__(kThreads) void icp_grid_kernel(
   icp_move(c.pose + (long long)p * 12, y0, y1, y2, m);
   const float4 *sc = sorted + (size_t)p * Na;
   const CellGrid g = cell_grid(cells, p);
-  const int *ct = g.ct;
-  if (threadIdx.x < 192) {  // the deposit tables
-    const int ax = threadIdx.x >> 6;
-    s_dep[ax][threadIdx.x & 63] =
-        cell_deposit(g.sched, ax, threadIdx.x & 63, kGridSteps, ax == 0 ? g.nb[0] : ax == 1 ? g.nb[1] : g.nb[2], kGridSteps - 1);
-  }
-  __syncthreads();
+  cell_deposit_tables(g, s_dep);
   // The cells that the box y' +- max_dist meets.  An anchor x that the float64 test accepts has dx * dx <= d2 < max_dist^2
   // up to three float64 roundings, so |x - y'| < max_dist (1 + 2^-50) on every axis.  The box edge y' -+ (max_dist + marg)
   // is formed in float64 (2 roundings of 2^-53) and rounded to float32 (2^-24 relative to |y'| + max_dist + marg at most);
   // marg = (max_dist + |y'|) * 1e-6 is 16 times that, so the float32 edge still lies outside x, which is a float32 itself.
   // The cell function is the sort's own and monotone in its argument (cell_grid.h grid_cell): cell(lower edge) <= cell(x)
   // <= cell(upper edge).
-  int c0[3], cn[3];
+  CellBox box;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const double marg = (max_dist + fabs(m[a])) * 1e-6;
-    c0[a] = grid_cell(g, a, (float)((m[a] - max_dist) - marg));
-    cn[a] = grid_cell(g, a, (float)((m[a] + max_dist) + marg)) - c0[a] + 1;
+    box.c0[a] = grid_cell(g, a, (float)((m[a] - max_dist) - marg));
+    box.cn[a] = grid_cell(g, a, (float)((m[a] + max_dist) + marg)) - box.c0[a] + 1;
   }
-  const int total = cn[0] * cn[1] * cn[2];
-  const bool by_cells = total <= kGridMaxCells;
+  // The walk (cell_walk.h cell_walk).  A group of a wide box is walked when the ball can reach its box: the test is float64
+  // on the exact box, and an accepted anchor lies in its group's box, so the box distance is at most its d2 (up to the
+  // roundings that the 1e-9 margin covers).
   Best b{r2, -1};
-  if (live && by_cells) {
-    // one step = one read: the next cell's range while the lane has none, else the next record
-    int pos = 0, end = 0, ox = 0, oy = 0, oz = 0;
-    while (pos < end || oz < cn[2]) {
-      if (pos < end) {
-        icp_take(b, sc[pos++], m, na);
-      } else {
-        const unsigned code = s_dep[0][c0[0] + ox] | s_dep[1][c0[1] + oy] | s_dep[2][c0[2] + oz];
-        if (++ox == cn[0]) {
-          ox = 0;
-          if (++oy == cn[1]) { oy = 0; ++oz; }
-        }
-        pos = max(ct[code], 0);
-        end = min(ct[code + 1], Na);
-      }
-    }
-  }
-  // wide box: every 64-point group of the order whose box the ball can reach.  The test is float64 on the
-  // exact box: an accepted anchor lies in its group's box, so the box distance is at most its d2 (up to the roundings that
-  // the 1e-9 margin covers).  Wave-uniform loop; a lane that walked its cells only skips the records.
-  if (__any(live && !by_cells)) {
-    const int NG = (Na + 63) / 64;
-    const float *gb = gbox + (size_t)p * NG * 8;
-    for (int g = 0; g < NG; ++g) {
-      const float4 lo = *reinterpret_cast<const float4 *>(gb + (size_t)g * 8);
-      const float4 hi = *reinterpret_cast<const float4 *>(gb + (size_t)g * 8 + 4);
-      const double dx = fmax(fmax((double)lo.x - m[0], m[0] - (double)hi.x), 0.0);
-      const double dy = fmax(fmax((double)lo.y - m[1], m[1] - (double)hi.y), 0.0);
-      const double dz = fmax(fmax((double)lo.z - m[2], m[2] - (double)hi.z), 0.0);
-      const bool meet = live && !by_cells && ((dx * dx + dy * dy) + dz * dz) * (1.0 - 1e-9) < r2;
-      if (!__any(meet)) continue;
-      const int len = min(64, Na - g * 64);
-      for (int e = 0; e < len; ++e) {
-        const float4 rec = sc[g * 64 + e];
-        if (meet) icp_take(b, rec, m, na);
-      }
-    }
-  }
+  cell_walk(sc, gbox + (size_t)p * ((Na + 63) / 64) * 8, g.ct, Na, s_dep, box, live, [&](const float4 lo, const float4 hi) {
+    const double dx = fmax(fmax((double)lo.x - m[0], m[0] - (double)hi.x), 0.0);
+    const double dy = fmax(fmax((double)lo.y - m[1], m[1] - (double)hi.y), 0.0);
+    const double dz = fmax(fmax((double)lo.z - m[2], m[2] - (double)hi.z), 0.0);
+    return ((dx * dx + dy * dy) + dz * dz) * (1.0 - 1e-9) < r2;
+  }, [&](int, const float4 rec) {
+    icp_take(b, rec, m, na);
+    return true;
+  });
   if (j < Nb) out[j] = live ? b.i : -1;
 }
 

@@ -5,14 +5,12 @@
 // for another: graph-capturable.
 //   cloud_pack_kernel   (cloud_pack.h, icp.hip's) rows behind the count become copies of rows below it, then
 //                       dh3d_spatial_sort_cells builds the cell table once per call.
-//   iss_walk            the one walk both kernels make, LANE = POINT as icp_grid_kernel's: every lane walks the cells that
-//                       the box x_i +- r meets (cell_grid.h grid_cell is monotone; the margin covers the float32 roundings
-//                       of the membership test) with counters, a cell's code from three per-axis deposit tables in LDS, one
-//                       step = one read, the next cell's range or the next 16-byte record.  A box of more than 512 cells
-//                       takes the 64-point groups whose gbox the ball meets: a wave-uniform loop, the records read as
-//                       broadcasts.  The lanes of a workgroup are 256 consecutive points OF THE SORTED ORDER, so the lanes
-//                       of a wave are neighbours walking the same few cells.  The sort's crowded flag is not looked at: a
-//                       dense cell costs its records and no more (not measured against the group walk on crowded clouds).
+//   iss_walk            the one walk both kernels make, LANE = POINT: cell_walk.h's cell_walk (icp_grid_kernel's too) over
+//                       the cells that the box x_i +- r meets (ball_cells), a box of more than 512 cells over the 64-point
+//                       groups whose gbox the ball meets.  The lanes of a workgroup are 256 consecutive points OF THE SORTED
+//                       ORDER, so the lanes of a wave are neighbours walking the same few cells.  The sort's crowded flag
+//                       is not looked at: a dense cell costs its records and no more (not measured against the group walk
+//                       on crowded clouds).
 //                       The other form, WAVE = QUERY (ball_grid_kernel's: a lane per cell for the ranges, the ranges
 //                       flattened, a lane per record, a butterfly for the wave's eleven sums, the solve lane = point after
 //                       64 walks), was built first and lost: 1.77 ms against 1.19 ms for the whole call on 64 x 8192 street
@@ -25,7 +23,7 @@
 //   iss_nms_kernel      the same walk at r_n over the saliencies in sorted order (written by the moments kernel next to the
 //                       records' order); only points with a positive saliency walk, and a lane stops at the first
 //                       neighbour that beats it.  A 64-bit key per point, (ordered bits of s) << 32 | ~index, or 0 when the
-//                       point is not kept.  27 VGPRs, 768 bytes of LDS, no scratch.
+//                       point is not kept.  29 VGPRs, 768 bytes of LDS, no scratch.
 //   iss_select_kernel   one 1024-lane workgroup per cloud, block_ops.h's compaction, radix select of the M-th largest key and
 //                       LDS sort, as keypoints.hip's nms_select_kernel; ~index in the low bits makes the lowest index the
 //                       largest key among equal saliencies.  32 VGPRs, 33.9 KiB of LDS, no scratch.
@@ -33,7 +31,7 @@
 #include <math.h>
 
 #include "block_ops.h"
-#include "cell_grid.h"
+#include "cell_walk.h"
 #include "cloud_pack.h"
 #include "common.h"
 #include "keys.h"
@@ -47,7 +45,6 @@ constexpr int kMaxN = 16384;        // dh3d_spatial_sort_cells
 constexpr int kMaxClouds = 65535;
 constexpr int kMaxKeep = 4096;      // M limit: the winners' sort buffer in LDS (32 KiB)
 constexpr int kThreads = 256;
-constexpr int kBoxMaxCells = 512;   // a box that meets more cells walks the 64-point groups
 constexpr int kSelThreads = 1024;
 constexpr int kSelWaves = kSelThreads / 64;
 
@@ -79,12 +76,7 @@ __device__ __forceinline__ IssLane iss_lane(const float4 *sorted, const float *g
   const float rs = radii[2 * p], rn = radii[2 * p + 1];
   L.rs = rs > 0.f ? rs : 0.f;
   L.rn = rn > 0.f ? rn : 0.f;
-  if (threadIdx.x < 192) {  // axis value -> its bits at their places in the cell's 12-bit code
-    const int ax = threadIdx.x >> 6;
-    s_dep[ax][threadIdx.x & 63] = cell_deposit(L.g.sched, ax, threadIdx.x & 63, kGridSteps,
-                                               ax == 0 ? L.g.nb[0] : ax == 1 ? L.g.nb[1] : L.g.nb[2], kGridSteps - 1);
-  }
-  __syncthreads();
+  cell_deposit_tables(L.g, s_dep);  // axis value -> its bits at their places in the cell's 12-bit code
   L.s = blockIdx.x * kThreads + threadIdx.x;
   const float4 rec = L.sc[L.s < N ? L.s : 0];
   L.k = L.s < N ? __float_as_int(rec.w) : -1;
@@ -92,62 +84,18 @@ __device__ __forceinline__ IssLane iss_lane(const float4 *sorted, const float *g
   return L;
 }
 
-// The walk of one lane around its point at radius r: take(pos, record) for every sorted position whose record can pass the
-// float32 test d2 < r * r (and for others; never twice), until take returns false.  Every lane of the wave must call it
-// (the group walk is a wave-uniform loop); a lane whose `walks` is false takes nothing.  A record that passes has
-// |x - q| < r (1 + 5 * 2^-24) on every axis; the margin also covers the two roundings of q -+ r -+ margin, and the cell
-// function is monotone (cell_grid.h grid_cell).
+// The walk of one lane around its point at radius r (cell_walk.h cell_walk states the contract): take(pos, record) for
+// every sorted position whose record can pass the float32 test d2 < r * r, and for others, until take returns false.  A
+// group is walked when the ball meets its box: 1e-5 relative margin on the box distance, as ball_grid_kernel's; it dwarfs
+// the roundings of both chains.
 template <class Take>
 __device__ __forceinline__ void iss_walk(const IssLane &L, const unsigned (*s_dep)[64], bool walks, float r, Take take) {
-  const int N = L.N;
-  const int *ct = L.g.ct;
-  int c0[3], cn[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float marg = r * 1e-5f + fabsf(L.q[a]) * 1e-6f;
-    c0[a] = grid_cell(L.g, a, (L.q[a] - r) - marg);
-    cn[a] = grid_cell(L.g, a, (L.q[a] + r) + marg) - c0[a] + 1;
-  }
-  const bool by_cells = cn[0] * cn[1] * cn[2] <= kBoxMaxCells;  // (the product: at most the grid's 4096 cells)
-  if (walks && by_cells) {
-    // one step = one read: the next cell's range while the lane has none, else the next record
-    int pos = 0, end = 0, ox = 0, oy = 0, oz = 0;
-    while (pos < end || oz < cn[2]) {
-      if (pos < end) {
-        if (!take(pos, L.sc[pos])) break;
-        ++pos;
-      } else {
-        const unsigned code = s_dep[0][c0[0] + ox] | s_dep[1][c0[1] + oy] | s_dep[2][c0[2] + oz];
-        if (++ox == cn[0]) {
-          ox = 0;
-          if (++oy == cn[1]) { oy = 0; ++oz; }
-        }
-        pos = max(ct[code], 0);
-        end = min(ct[code + 1], N);
-      }
-    }
-  }
-  // wide box: every 64-point group of the order whose box the ball meets (1e-5 relative margin on the box distance, as
-  // ball_grid_kernel's; it dwarfs the roundings of both chains).  Wave-uniform loop; a lane that walked its cells only
-  // skips the records.
-  bool more = walks && !by_cells;
-  if (__any(more)) {
-    const int NG = (N + 63) / 64;
-    const float r2hi = r * r * 1.000001f;
-    for (int gi = 0; gi < NG; ++gi) {
-      const float4 lo = *reinterpret_cast<const float4 *>(L.gb + (size_t)gi * 8);
-      const float4 hi = *reinterpret_cast<const float4 *>(L.gb + (size_t)gi * 8 + 4);
-      const float dx = fmaxf(fmaxf(lo.x - L.q[0], L.q[0] - hi.x), 0.f), dy = fmaxf(fmaxf(lo.y - L.q[1], L.q[1] - hi.y), 0.f),
-                  dz = fmaxf(fmaxf(lo.z - L.q[2], L.q[2] - hi.z), 0.f);
-      const bool meet = more && ((dx * dx + dy * dy) + dz * dz) * 0.99999f <= r2hi;
-      if (!__any(meet)) continue;
-      const int len = min(64, N - gi * 64);
-      for (int e = 0; e < len; ++e) {
-        const float4 c = L.sc[gi * 64 + e];
-        if (meet && more) more = take(gi * 64 + e, c);
-      }
-    }
-  }
+  const float r2hi = r * r * 1.000001f;
+  cell_walk(L.sc, L.gb, L.g.ct, L.N, s_dep, ball_cells(L.g, L.q, r), walks, [&](const float4 lo, const float4 hi) {
+    const float dx = fmaxf(fmaxf(lo.x - L.q[0], L.q[0] - hi.x), 0.f), dy = fmaxf(fmaxf(lo.y - L.q[1], L.q[1] - hi.y), 0.f),
+                dz = fmaxf(fmaxf(lo.z - L.q[2], L.q[2] - hi.z), 0.f);
+    return ((dx * dx + dy * dy) + dz * dz) * 0.99999f <= r2hi;
+  }, take);
 }
 
 // ------------------------------------------------------------------------------------------------------------- moments

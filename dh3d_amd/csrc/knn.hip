@@ -24,7 +24,7 @@
 
 #include <type_traits>
 
-#include "cell_grid.h"
+#include "cell_walk.h"
 #include "common.h"
 #include "keys.h"
 #include "wave_ops.h"
@@ -1205,11 +1205,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   // the table index of cell (ax, ay, az): every axis' cell number with its bits at their places in the code (per
   // workgroup, in LDS: 64 entries per axis)
   unsigned (*s_ctab)[64] = reinterpret_cast<unsigned (*)[64]>(s_raw);   // [3][64]
-  if (threadIdx.x < 192) {
-    const int a = threadIdx.x >> 6;
-    s_ctab[a][threadIdx.x & 63] = cell_deposit(g.sched, a, threadIdx.x & 63, kGridSteps - D, nc[a], kGridSteps - 1);
-  }
-  __syncthreads();
+  cell_deposit_tables(g.sched, nc[0], nc[1], nc[2], kGridSteps - D, s_ctab);
   auto tab_code = [&](int ax, int ay, int az) { return s_ctab[0][ax & 63] | s_ctab[1][ay & 63] | s_ctab[2][az & 63]; };
   KnnState<8> st;
 #pragma unroll
@@ -1278,10 +1274,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     for (int k = 0; k < fit; ++k) s_list[qs][off + k] = (unsigned short)(beg + k);
     for (int k = max(fit, 0); k < len; ++k) direct(beg + k);
   };
-  auto lds_order = [&]() {  // (a row is wave-private and a wave's LDS operations complete in order: this pins the compiler)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  };
+  // (wave_lds_sync below: a row is wave-private and a wave's LDS operations complete in order: it pins the compiler)
   // Pass 0's pool is ~48 candidates of which 8 are wanted, the list is empty and the bound infinite: offered one by one,
   // every slot pays the square root, the rank code and the insertion (some lane of the wave always inserts).  So the pool
   // is SCREENED first, on squared distances alone (the rule written out above knn_small_kernel):
@@ -1315,7 +1308,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
       float4 r[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) r[u] = sc[row[min(k0 + sub + u * L, ns - 1)]];
-      lds_order();  // (a padded slot reads the last index: before its owner replaces it)
+      wave_lds_sync();  // (a padded slot reads the last index: before its owner replaces it)
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int i = k0 + sub + u * L;
@@ -1331,7 +1324,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     U = fmaxf(U, __int_as_float(knn_dpp_i32<0xB1>(__float_as_int(U))));  // quad_perm [1,0,3,2]
     U = fmaxf(U, __int_as_float(knn_dpp_i32<0x4E>(__float_as_int(U))));  // quad_perm [2,3,0,1]
     const float thr = __fmul_rn(U, 1.000001f);
-    lds_order();
+    wave_lds_sync();
     int c = 0;  // survivors of the query so far
 #pragma unroll 1
     for (int k0 = 0; k0 < ns; k0 += 4 * L) {
@@ -1342,7 +1335,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
         s[u] = s2v[k0 + sub + u * L];
         id[u] = row[k0 + sub + u * L];
       }
-      lds_order();  // (all sixteen slots are read before one of them is written)
+      wave_lds_sync();  // (all sixteen slots are read before one of them is written)
       int n = 0, at[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -1362,7 +1355,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
           row[first + at[u]] = id[u];
         }
       c += knn_dpp_i32<0xFF>(p);  // quad_perm [3,3,3,3]
-      lds_order();
+      wave_lds_sync();
     }
     // one entry ahead of the insertion; lanes past the end drop out (an entry read past c is stale and never offered)
     float s_n = s2v[sub];
@@ -1379,7 +1372,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     return screen ? 0 : min(T, kGridCap);
   };
   auto drain = [&](auto screen) __attribute__((always_inline)) {
-    lds_order();
+    wave_lds_sync();
     int total;
     if constexpr (decltype(screen)::value) total = drain_screened();
     else total = min(s_cnt[qs], kGridCap);
@@ -1400,7 +1393,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
         knn_offer<8, false>(st, ok[u] ? s2 : __builtin_nanf(""), __float_as_int(r[u].w), lad);
       }
     }
-    lds_order();
+    wave_lds_sync();
   };
   // One column (dy, dz: offsets + 2) of the 5 x 5 x 5 block, the cells at the x offsets of TMASK: ranges of all of them in
   // flight together (no load under the per-cell branches), then the box tests and the pooling.

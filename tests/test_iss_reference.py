@@ -80,6 +80,22 @@ def test_grid_paths_of_the_fixtures():
     assert (cells <= 512).any() and (cells > 512).any()       # both walks in one launch
 
 
+def test_cube_wide_runs_both_walks_in_one_wave():
+    """csrc/cell_walk.h's walk has two halves, a lane's cells and the wave-uniform group loop; the case that can go wrong is
+    a wave that runs both, with the suppression's early exits.  The lanes of a wave are 64 consecutive sorted positions: at
+    both radii of `cube-wide` (the moments kernel walks at max(r_s, r_n), the suppression at r_n) at least half of the 32
+    waves hold a lane at or below the 512-cell limit and a lane above it, so the bit-equal count and selection tests on
+    this fixture run the mixed wave."""
+    X, n, r_s, r_n, _ = ref.case("cube-wide")
+    assert n == len(X) == 2048
+    order = ref.sr.restate(ref.packed(X, n))["order"]         # sorted position -> point
+    for r in (max(r_s, r_n), r_n):
+        wide = (ref.grid_facts(X, n, r)[1][order] > 512).reshape(32, 64)
+        mixed = int((wide.any(1) & ~wide.all(1)).sum())
+        print("r = %.1f: waves with both walks %d of 32, points above the limit %.0f %%" % (r, mixed, 100.0 * wide.mean()))
+        assert mixed >= 16
+
+
 def test_lattice_has_pairs_on_the_shell():
     X, n, r_s, r_n, res = ref.case("lattice")
     assert ref.shell_pairs(X, n, r_s) > 1000 and ref.shell_pairs(X, n, r_n) > 1000
