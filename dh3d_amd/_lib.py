@@ -83,6 +83,8 @@ _SIGNATURES = {
     "dh3d_flex_conv_pm_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp,
                               c_size_t, c_fp, c_fp, c_fp, c_fp],
     "dh3d_gemm_is_split": [c_int, c_int, c_int, c_int, c_int],
+    "dh3d_gemm_plan": [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                       ctypes.POINTER(c_int)],
     "dh3d_gemm_tn_f32": [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp],
     "dh3d_gemm_nn_f32": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp],
     "dh3d_gemm_tn_f32_batched": [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp],

@@ -508,59 +508,78 @@ __global__ __launch_bounds__(256) void gemm_shortk_kernel(const float *__restric
 
 struct GemmBatch { int n; long long sA, sB, sC, sBias; };
 
-// reduction chunks of a product (> 1: the split partials meet in f32 atomics on a zeroed C)
-int gemm_chunks(bool ta, int M, int N, int K, int batch, int wgs) {
-  if (batch == 1 && ((!ta && M <= kSkM && K <= kSkK && K % 4 == 0) || (ta && K <= kSkM))) return 1;  // plain-FMA kernels
-  const int BN = N <= 64 ? 64 : 128;
-  const int gm = dh3d_cdiv(M, 128), gn = dh3d_cdiv(N, BN);
-  int chunks = dh3d_cdiv(wgs, gm * gn * batch);
-  const int maxc = dh3d_cdiv(K, ta ? 64 : 256);  // [M,K] operands: only long reductions are worth the atomics
-  chunks = chunks > maxc ? maxc : chunks;
-  return chunks < 1 ? 1 : chunks;
+// The ONE dispatch decision: gemm_launch runs it, dh3d_gemm_is_split and dh3d_gemm_plan report it.
+//   kernel: DH3D_GEMM_* of include/dh3d_hip.h (rows: 1..4 = RB, the rows in use in blocks of eight)
+//   stage : reduction steps per LDS stage (1: the plain-FMA kernels, which take the whole reduction in one pass)
+//   kchunk: reduction steps per workgroup, a multiple of the stage; chunks = ceil(K / kchunk) of them (> 1: the partials
+//           meet in f32 atomics on a zeroed C)
+//   split : what dh3d_gemm_is_split answers -- the chunk count BEFORE bias / leading dimension / C1 are looked at and
+//           before kchunk is rounded up (rounding only lowers the count, and never to 1: chunks > 1 implies split)
+struct GemmPlan { int kernel, chunks, kchunk, stage, split; };
+
+GemmPlan gemm_plan(bool ta, int M, int N, int K, int batch, int lda, bool c1, bool bias) {
+  GemmPlan p;
+  const bool narrow = N <= 64;
+  // one tiny dimension: the plain-FMA kernels above
+  const bool tiny = batch == 1 && ((!ta && M <= kSkM && K <= kSkK && K % 4 == 0) || (ta && K <= kSkM));
+  // tile: 128 x 128 (or 128 x 64 for narrow N); the reduction is split so that ~3 workgroups per CU exist.  Workgroups
+  // aimed at: the split partials meet in f32 atomics (~0.3 T/s chip-wide), so the long-reduction tn form wants fewer,
+  // longer chunks (measured: 384 beats 768 by 10-25 % there)
+  int chunks = 1;
+  if (!tiny) {
+    const int wgs = ta ? 384 : 768;
+    const int gm = dh3d_cdiv(M, 128), gn = dh3d_cdiv(N, narrow ? 64 : 128);
+    chunks = dh3d_cdiv(wgs, gm * gn * batch);
+    const int maxc = dh3d_cdiv(K, ta ? 64 : 256);  // [M,K] operands: only long reductions are worth the atomics
+    chunks = chunks > maxc ? maxc : chunks;
+    chunks = chunks < 1 ? 1 : chunks;
+  }
+  p.split = chunks > 1 ? 1 : 0;
+  if (tiny && !c1) {
+    p.chunks = 1; p.kchunk = K; p.stage = 1;
+    if (!ta && lda % 4 == 0) { p.kernel = M <= 8 ? 1 : M <= 16 ? 2 : M <= 24 ? 3 : 4; return p; }
+    if (ta && !bias) { p.kernel = DH3D_GEMM_SHORTK; return p; }
+  }
+  if (bias) chunks = 1;
+  // products of >= 2^26 multiply-adds with K % 32 == 0 go to the bf16x6 kernel (f32-accurate); small or odd-K ones stay on
+  // the exact-f32 pipe
+  const bool x6 = K % 32 == 0 && (double)M * N * K * batch >= 67108864.0 &&
+                  (ta || (lda % 4 == 0 && (double)M * lda < 1073741824.0));
+  // stage depth (measured, tools/gemm_bench.py): 16 for the 128-wide tiles (four workgroups per CU), 32 for N <= 64
+  // (the A stream dominates: whole 128-byte lines per row)
+  p.stage = !x6 ? kKC : narrow ? 32 : 16;
+  const int kgran = x6 ? 32 : p.stage;  // chunk granularity: whole stages of either depth
+  p.kchunk = dh3d_cdiv(K, chunks);
+  p.kchunk = (p.kchunk + kgran - 1) / kgran * kgran;  // multiple of the stage depth: float4 loads of the [M,K] operand stay aligned
+  p.chunks = dh3d_cdiv(K, p.kchunk);
+  p.kernel = x6 ? (narrow ? DH3D_GEMM_X6_NARROW : DH3D_GEMM_X6_WIDE) : (narrow ? DH3D_GEMM_F32_NARROW : DH3D_GEMM_F32_WIDE);
+  return p;
 }
 
 int gemm_launch(bool ta, const float *A, int lda, const float *B, int ldb, float *C, int ldc, int M, int N, int K,
                 float *C1, int rows0, bool accumulate, hipStream_t s, const float *colbias = nullptr,
                 GemmBatch bt = GemmBatch{1, 0, 0, 0, 0}) {
-  if (bt.n == 1 && !C1) {  // one tiny dimension: the plain-FMA kernels above
-    if (!ta && M <= kSkM && K <= kSkK && K % 4 == 0 && lda % 4 == 0) {
-      const size_t lds = sizeof(float) * (kSkM * ((K + 63) / 64 * 64) + 4 * kSkM * 64);
+  const GemmPlan p = gemm_plan(ta, M, N, K, bt.n, lda, C1 != nullptr, colbias != nullptr);
+  if (p.kernel <= DH3D_GEMM_ROWS4) {
+    const size_t lds = sizeof(float) * (kSkM * ((K + 63) / 64 * 64) + 4 * kSkM * 64);
 #define DH3D_ROWS(RBV)                                                                                                 \
   do {                                                                                                                 \
     DH3D_ALLOW_BIG_LDS(gemm_rows_kernel<RBV>);                                                                         \
     hipLaunchKernelGGL(gemm_rows_kernel<RBV>, dim3(dh3d_cdiv(N, 64)), dim3(256), lds, s, A, lda, B, ldb, C, ldc, M, N, \
                        K, accumulate ? 1 : 0, colbias);                                                                \
   } while (0)
-      if (M <= 8) DH3D_ROWS(1); else if (M <= 16) DH3D_ROWS(2); else if (M <= 24) DH3D_ROWS(3); else DH3D_ROWS(4);
+    if (p.kernel == 1) DH3D_ROWS(1); else if (p.kernel == 2) DH3D_ROWS(2); else if (p.kernel == 3) DH3D_ROWS(3); else DH3D_ROWS(4);
 #undef DH3D_ROWS
-      return dh3d_launch_status();
-    }
-    if (ta && K <= kSkM && !colbias) {
-      hipLaunchKernelGGL(gemm_shortk_kernel, dim3(dh3d_cdiv(N, 64), dh3d_cdiv(M, 64)), dim3(256), 0, s, A, lda, B, ldb, C,
-                         ldc, M, N, K, accumulate ? 1 : 0);
-      return dh3d_launch_status();
-    }
+    return dh3d_launch_status();
   }
-  // tile: 128 x 128 (or 128 x 64 for narrow N); the reduction is split so that ~3 workgroups per CU exist
-  const bool narrow = N <= 64;
-  const int BM = 128, BN = narrow ? 64 : 128;
-  const int gm = dh3d_cdiv(M, BM), gn = dh3d_cdiv(N, BN);
-  // workgroups aimed at: the split partials meet in f32 atomics (~0.3 T/s chip-wide), so the long-reduction tn form
-  // wants fewer, longer chunks (measured: 384 beats 768 by 10-25 % there)
-  const int wgs = ta ? 384 : 768;
-  int chunks = gemm_chunks(ta, M, N, K, bt.n, wgs);
-  if (colbias) chunks = 1;
-  // products of >= 2^26 multiply-adds with K % 32 == 0 go to the bf16x6 kernel (f32-accurate); small or odd-K ones stay on
-  // the exact-f32 pipe
-  const bool x6 = K % 32 == 0 && (double)M * N * K * bt.n >= 67108864.0 &&
-                  (ta || (lda % 4 == 0 && (double)M * lda < 1073741824.0));
-  // stage depth (measured, tools/gemm_bench.py): 16 for the 128-wide tiles (four workgroups per CU), 32 for N <= 64
-  // (the A stream dominates: whole 128-byte lines per row)
-  const int kc = !x6 ? kKC : narrow ? 32 : 16;
-  const int kgran = x6 ? 32 : kc;  // chunk granularity: whole stages of either depth
-  int kchunk = dh3d_cdiv(K, chunks);
-  kchunk = (kchunk + kgran - 1) / kgran * kgran;  // multiple of the stage depth: float4 loads of the [M,K] operand stay aligned
-  chunks = dh3d_cdiv(K, kchunk);
+  if (p.kernel == DH3D_GEMM_SHORTK) {
+    hipLaunchKernelGGL(gemm_shortk_kernel, dim3(dh3d_cdiv(N, 64), dh3d_cdiv(M, 64)), dim3(256), 0, s, A, lda, B, ldb, C,
+                       ldc, M, N, K, accumulate ? 1 : 0);
+    return dh3d_launch_status();
+  }
+  const bool x6 = p.kernel >= DH3D_GEMM_X6_NARROW, narrow = N <= 64;
+  const int gm = dh3d_cdiv(M, 128), gn = dh3d_cdiv(N, narrow ? 64 : 128);
+  const int chunks = p.chunks, kchunk = p.kchunk, kc = p.stage;
   const int atomic = (chunks > 1 || accumulate) ? 1 : 0;
   if (colbias && atomic) return DH3D_ERR_UNSUPPORTED;
   if ((long long)chunks * bt.n > 65535) return DH3D_ERR_UNSUPPORTED;
@@ -614,7 +633,24 @@ int dh3d_internal_transpose32(const void *in, void *out, int Bt, int R, int Cc, 
 // accumulate = 1, adds them onto what the caller put there: a caller that owns a zeroed arena passes accumulate = 1 and
 // saves the fill).  ta: 1 = the tn form.  Pure function of the shape.
 DH3D_API int dh3d_gemm_is_split(int ta, int M, int N, int K, int batch) {
-  return gemm_chunks(ta != 0, M, N, K, batch > 0 ? batch : 1, ta ? 384 : 768) > 1 ? 1 : 0;
+  return gemm_plan(ta != 0, M, N, K, batch > 0 ? batch : 1, ta ? M : K, false, false).split;
+}
+
+// The kernel, the reduction chunks and the steps per chunk that the four entry points below take for a shape (ta: 1 = the
+// tn form; batch > 1: the batched forms; with_bias: nn with a colbias) -- gemm_plan as they call it.  0, with the three
+// outputs 0, where they refuse the shape.  Pure function of the shape.
+DH3D_API int dh3d_gemm_plan(int ta, int M, int N, int K, int batch, int with_bias, int *chunks, int *kchunk, int *stage) {
+  GemmPlan p = GemmPlan{0, 0, 0, 0, 0};
+  const bool ok = M > 0 && N > 0 && K > 0 && batch > 0 && N % 4 == 0 &&
+                  (ta ? M % 4 == 0 && M / 128 <= 65535 && !with_bias : K % 4 == 0 && dh3d_cdiv(M, 128) <= 65535);
+  if (ok) {
+    p = gemm_plan(ta != 0, M, N, K, batch, ta ? M : K, false, with_bias != 0);
+    if ((long long)p.chunks * batch > 65535) p = GemmPlan{0, 0, 0, 0, 0};
+  }
+  if (chunks) *chunks = p.chunks;
+  if (kchunk) *kchunk = p.kchunk;
+  if (stage) *stage = p.stage;
+  return p.kernel;
 }
 
 DH3D_API int dh3d_gemm_tn_f32(const float *A, const float *B, int K, int M, int N, int accumulate, float *C,

@@ -4,6 +4,8 @@ Thin, allocation-only wrappers: each function validates shapes, allocates the ou
 enqueues one C-ABI call on the current stream.  No function here has a CPU or eager-torch fallback.
 """
 
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -1046,6 +1048,19 @@ def flex_conv_bwd(features, xyz, nbr, theta, bias, grad_out, center_rank0=False,
                                           Dout, 1 if center_rank0 else 0, L.ptr(ws), ws_bytes, L.ptr(gf), L.ptr(gt),
                                           L.ptr(gb), L.stream_ptr()), "flex_conv_pm_bwd")
     return gf, gt, gb
+
+
+GEMM_KERNELS = {1: "rows1", 2: "rows2", 3: "rows3", 4: "rows4", 5: "shortk", 6: "f32_narrow", 7: "f32_wide",
+                8: "x6_narrow", 9: "x6_wide"}   # include/dh3d_hip.h DH3D_GEMM_*
+
+
+def gemm_plan(ta, M, N, K, batch=1, bias=False):
+    """The kernel of csrc/gemm.hip that gemm_tn (ta) / gemm_nn and their batched forms take for a shape, and its cut of the
+    reduction (host only): (kernel name, chunks, kchunk, stage) -- dh3d_gemm_plan.  None where they refuse the shape."""
+    c, kc, st = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    r = L.lib().dh3d_gemm_plan(1 if ta else 0, int(M), int(N), int(K), int(batch), 1 if bias else 0, ctypes.byref(c),
+                               ctypes.byref(kc), ctypes.byref(st))
+    return None if r == 0 else (GEMM_KERNELS[r], c.value, kc.value, st.value)
 
 
 def gemm_tn(A, B, out=None, accumulate=False):

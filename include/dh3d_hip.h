@@ -677,6 +677,20 @@ int dh3d_flex_conv_pm_bwd(const float *features, const float *xyz, const int32_t
 /* 1 when the product's reduction is split over workgroups (C is then zeroed by the call and the partials added with f32
  * atomics; with accumulate = 1 they are added onto the caller's C -- a caller holding zeroed memory saves the fill). */
 int dh3d_gemm_is_split(int ta /* 1: tn form */, int M, int N, int K, int batch);
+/* Which kernel of csrc/gemm.hip serves a shape at the four GEMM entry points, and how its reduction is cut: the decision
+ * the launcher itself runs.  batch > 1: the batched forms; with_bias: nn with a colbias.  *chunks workgroups along the
+ * reduction take *kchunk steps each (the last one the remainder), *kchunk a multiple of *stage, the reduction steps per LDS
+ * stage (1 for the plain-FMA kernels, which take the whole reduction in one pass); any of the three may be NULL.  0, and
+ * zeros, for a shape the entry points refuse.  chunks > 1 implies dh3d_gemm_is_split; a bias implies chunks == 1.
+ * Host only; looks at the shape alone, never at the data. */
+#define DH3D_GEMM_ROWS1 1      /* gemm_rows_kernel<RB>: nn, M <= 32, K <= 512; id = RB = ceil(M / 8), 1 .. 4 */
+#define DH3D_GEMM_ROWS4 4
+#define DH3D_GEMM_SHORTK 5     /* gemm_shortk_kernel: tn, K <= 32 */
+#define DH3D_GEMM_F32_NARROW 6 /* gemm_f32_kernel, 128 x 64 tiles (N <= 64), stage 16 */
+#define DH3D_GEMM_F32_WIDE 7   /* gemm_f32_kernel, 128 x 128 tiles, stage 16 */
+#define DH3D_GEMM_X6_NARROW 8  /* gemm_x6_kernel, 128 x 64 tiles, stage 32: >= 2^26 multiply-adds, K % 32 == 0 */
+#define DH3D_GEMM_X6_WIDE 9    /* gemm_x6_kernel, 128 x 128 tiles, stage 16 */
+int dh3d_gemm_plan(int ta, int M, int N, int K, int batch, int with_bias, int *chunks, int *kchunk, int *stage);
 int dh3d_gemm_tn_f32(const float *A, const float *B, int K, int M, int N, int accumulate, float *C, void *stream);
 int dh3d_gemm_nn_f32(const float *A, const float *B, const float *colbias, int M, int K, int N, int accumulate,
                      float *C, void *stream);

@@ -125,6 +125,33 @@ def test_flex_conv_fwd_plan_is_the_dispatchers_choice():
     assert plan(1 << 14, 1 << 16, 8, 3, 64, 64) == 0 and plan(1 << 13, 1 << 14, 8, 3, 4, 4) == 0   # beyond 32-bit indices
 
 
+def test_gemm_plan_is_the_launchers_choice():
+    """dh3d_gemm_plan (host only): the kernel of csrc/gemm.hip and the cut of the reduction that the GEMM entry points take
+    for a shape -- ids 1 .. 4 gemm_rows_kernel<RB>, 5 gemm_shortk_kernel, 6 / 7 gemm_f32_kernel narrow / wide, 8 / 9
+    gemm_x6_kernel narrow / wide, 0 a shape they refuse.  tests/test_gemm_plan.py sweeps it."""
+    from dh3d_amd import _lib
+    lib = _lib.lib()
+    header = open(os.path.join(ROOT, "include", "dh3d_hip.h")).read()
+    assert re.search(r"\bint\s+dh3d_gemm_plan\s*\(", header) and "dh3d_gemm_plan" in _lib.EXPORTED_SYMBOLS
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "dh3d_gemm_plan")
+    assert lib.dh3d_abi_version() == 4 == _lib.ABI_VERSION                                   # an addition only
+
+    def plan(ta, M, N, K, batch=1, bias=0):
+        c, kc, st = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+        r = lib.dh3d_gemm_plan(ta, M, N, K, batch, bias, ctypes.byref(c), ctypes.byref(kc), ctypes.byref(st))
+        return r, c.value, kc.value, st.value
+
+    assert plan(0, 22, 256, 256) == (3, 1, 256, 1) and plan(1, 256, 256, 22) == (5, 1, 22, 1)     # the [clouds, 256] layers
+    assert plan(0, 33, 68, 36) == (7, 1, 48, 16) and plan(1, 68, 60, 33) == (6, 1, 48, 16)
+    assert plan(1, 132, 68, 70) == (7, 2, 48, 16) and plan(0, 129, 132, 1000) == (7, 4, 256, 16)
+    assert plan(0, 256, 128, 2048) == (9, 8, 256, 16) and plan(0, 256, 128, 2048, 1, 1) == (9, 1, 2048, 16)
+    assert plan(0, 512, 64, 2048) == (8, 8, 256, 32) and plan(1, 132, 132, 4128) == (9, 65, 64, 16)
+    assert plan(0, 130, 68, 512, 16) == (9, 2, 256, 16) and plan(1, 64, 132, 1024, 8) == (9, 16, 64, 16)
+    assert plan(0, 64, 64, 66) == (0, 0, 0, 0) and plan(1, 66, 64, 64) == (0, 0, 0, 0) and plan(1, 64, 64, 64, 1, 1)[0] == 0
+    for ta, M, N, K, b in ((0, 256, 128, 2048, 1), (1, 132, 68, 70, 1), (0, 129, 132, 1000, 1)):
+        assert lib.dh3d_gemm_is_split(ta, M, N, K, b) == 1                                  # chunks > 1 implies is_split
+
+
 def test_library_was_built_from_this_tree():
     """The loaded library carries the hash of the sources it was compiled from (csrc/Makefile SRC_HASH -> dh3d_source_hash):
     a stale .so that travelled with the tree (built artefacts are git-ignored, not gpurun-ignored) fails here."""
