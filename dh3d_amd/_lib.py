@@ -236,6 +236,8 @@ _SIGNATURES = {
                           c_fp, c_fp, c_size_t, c_fp],
     "dh3d_gather_rows": [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_int, c_fp, c_fp],
     "dh3d_match_descriptors": [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp],
+    "dh3d_match_descriptors2": [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_int, c_int, c_int, c_int, c_float, c_int, c_fp, c_fp,
+                                c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_ransac_rigid": [c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_int, c_int, c_int, c_double, c_double, c_int, c_u64,
                           c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_icp_plan": [c_int, c_int],

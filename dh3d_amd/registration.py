@@ -8,6 +8,8 @@ GetEulerAngles and a success / inlier-ratio / trial / RTE / RRE summary.  Here a
 sampler replaces randsample, whose stream cannot be reproduced).
 
     match, dist = match_descriptors(anchor_desc, anchor_count, positive_desc, positive_count)
+    m2 = match_descriptors2(anchor_desc, anchor_count, positive_desc, positive_count, ratio=0.9, mutual=True)  # nn1, nn2, match, ...
+    res = register(anchor_rows, anchor_count, positive_rows, positive_count, match={"ratio": 0.9, "mutual": True})
     res = ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count)       # Rt, valid, inliers, ... (no host sync)
     res = register(anchor_rows, anchor_count, positive_rows, positive_count)  # rows as xyz_feat_att_nms / _nms_res.bin
     res = register_clouds(model, anchor_points, positive_points)              # forward (config.detection) + register
@@ -59,11 +61,8 @@ def _check_m(M, name):
         raise ValueError("%s: at most %d keypoints per cloud, got %d" % (name, KEYPOINT_MAX, M))
 
 
-def match_descriptors(anchor_desc, anchor_count, positive_desc, positive_count):
-    """Nearest positive descriptor of every anchor keypoint (pdist2(pos, anc, 'smallest', 1)): anchor_desc [P, Ma, D] and
-    positive_desc [P, Mb, D] float32 (column views such as rows[:, :, 3:131] are read in place), counts [P] int32 ->
-    (match [P, Ma] int32, the lowest positive id at the smallest distance, -1 past anchor_count or when the pair has no
-    positive; dist [P, Ma] float32, +inf there).  D <= 256, a multiple of 4; Ma, Mb <= 4096."""
+def _descriptor_pair(anchor_desc, anchor_count, positive_desc, positive_count):
+    """The checked inputs of match_descriptors / match_descriptors2 and their shape: a, ac, b, bc, P, Ma, Mb, D."""
     a = _rows(anchor_desc, "anchor_desc", 1)
     b = _rows(positive_desc, "positive_desc", 1)
     P, Ma, D = a.shape
@@ -76,11 +75,53 @@ def match_descriptors(anchor_desc, anchor_count, positive_desc, positive_count):
     _check_m(Mb, "positive_desc")
     ac = _count(anchor_count, "anchor_count", P, a.device)
     bc = _count(positive_count, "positive_count", P, a.device)
+    return a, ac, b, bc, P, Ma, Mb, D
+
+
+def match_descriptors(anchor_desc, anchor_count, positive_desc, positive_count):
+    """Nearest positive descriptor of every anchor keypoint (pdist2(pos, anc, 'smallest', 1)): anchor_desc [P, Ma, D] and
+    positive_desc [P, Mb, D] float32 (column views such as rows[:, :, 3:131] are read in place), counts [P] int32 ->
+    (match [P, Ma] int32, the lowest positive id at the smallest distance, -1 past anchor_count or when the pair has no
+    positive; dist [P, Ma] float32, +inf there).  D <= 256, a multiple of 4; Ma, Mb <= 4096."""
+    a, ac, b, bc, P, Ma, Mb, D = _descriptor_pair(anchor_desc, anchor_count, positive_desc, positive_count)
     match = torch.empty((P, Ma), dtype=torch.int32, device=a.device)
     dist = torch.empty((P, Ma), dtype=torch.float32, device=a.device)
     L.check(L.lib().dh3d_match_descriptors(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(b), b.stride(1), L.ptr(bc), P, Ma, Mb, D,
                                            L.ptr(match), L.ptr(dist), L.stream_ptr()), "match_descriptors")
     return match, dist
+
+
+def match_descriptors2(anchor_desc, anchor_count, positive_desc, positive_count, ratio=None, mutual=False):
+    """match_descriptors with the second neighbour, Lowe's ratio test and the mutual check (include/dh3d_hip.h
+    dh3d_match_descriptors2 states every rule).  Inputs and limits as match_descriptors.  ratio: None (no test) or a number
+    in (0, 1]: a row is kept when S1 < float32(ratio * ratio) * S2 on the float32 sums of squares (strict: ratio = 1 rejects
+    exact ties; a lone candidate is kept).  mutual: keep a row only when its positive's nearest anchor is that row.
+    Returns a dict of device tensors: nn1 / nn2 [P, Ma] int32 and dist1 / dist2 [P, Ma] float32 (the two nearest positives,
+    ties to the lowest id; -1 / +inf where there is none; nn1 / dist1 are match_descriptors' results bit for bit), match
+    [P, Ma] int32 (nn1 where the row is kept, else -1), num_kept [P] int32, and with mutual=True rev [P, Mb] int32 /
+    rev_dist [P, Mb] float32 (every positive's nearest anchor; without mutual the reverse search is not run).  No host
+    sync: graph-capturable."""
+    a, ac, b, bc, P, Ma, Mb, D = _descriptor_pair(anchor_desc, anchor_count, positive_desc, positive_count)
+    ratio2 = 0.0
+    if ratio is not None:
+        ratio = float(ratio)
+        if not 0.0 < ratio <= 1.0:
+            raise ValueError("ratio must be None or in (0, 1], got %r" % (ratio,))
+        ratio2 = float(np.float32(ratio * ratio))
+    mutual = bool(mutual)
+    dev = a.device
+    new = lambda M, dtype: torch.empty((P, M), dtype=dtype, device=dev)
+    out = dict(nn1=new(Ma, torch.int32), dist1=new(Ma, torch.float32), nn2=new(Ma, torch.int32), dist2=new(Ma, torch.float32),
+               match=new(Ma, torch.int32), num_kept=torch.empty((P,), dtype=torch.int32, device=dev))
+    if mutual:
+        out["rev"], out["rev_dist"] = new(Mb, torch.int32), new(Mb, torch.float32)
+    with torch.cuda.device(dev):
+        L.check(L.lib().dh3d_match_descriptors2(L.ptr(a), a.stride(1), L.ptr(ac), L.ptr(b), b.stride(1), L.ptr(bc), P, Ma, Mb, D,
+                                                ratio2, int(mutual), L.ptr(out["nn1"]), L.ptr(out["dist1"]), L.ptr(out["nn2"]),
+                                                L.ptr(out["dist2"]), L.ptr(out.get("rev")), L.ptr(out.get("rev_dist")),
+                                                L.ptr(out["match"]), L.ptr(out["num_kept"]), L.stream_ptr()),
+                "match_descriptors2")
+    return out
 
 
 def ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=1.0, confidence=0.99, max_trials=10000, seed=0):
@@ -123,17 +164,42 @@ def ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=1.0, c
                 num_corr=num_corr)
 
 
-def register(anchor_rows, anchor_count, positive_rows, positive_count, desc_dim=128, **ransac_kw):
+def _match_options(match):
+    """register's / register_fpfh's match=: None (dh3d_match_descriptors) or a dict of match_descriptors2's ratio / mutual."""
+    if match is None:
+        return None
+    if not isinstance(match, dict) or set(match) - {"ratio", "mutual"}:
+        raise ValueError("match must be None or a dict with the keys ratio and mutual, got %r" % (match,))
+    return dict(match)
+
+
+def _match_and_fit(desc_a, anchor_count, desc_b, positive_count, xyz_a, xyz_b, match, ransac_kw):
+    """Descriptors to poses: match_descriptors (match None) or match_descriptors2 (a dict of its options, whose outputs join
+    the result), then ransac_rigid on the ids."""
+    opts = _match_options(match)
+    if opts is None:
+        ids, dist = match_descriptors(desc_a, anchor_count, desc_b, positive_count)
+        more = {}
+    else:
+        more = match_descriptors2(desc_a, anchor_count, desc_b, positive_count, **opts)
+        ids, dist = more["match"], more["dist1"]
+    out = ransac_rigid(xyz_a, xyz_b, ids, anchor_count, **ransac_kw)
+    out.update(more)
+    out["match"], out["dist"] = ids, dist
+    return out
+
+
+def register(anchor_rows, anchor_count, positive_rows, positive_count, desc_dim=128, match=None, **ransac_kw):
     """Keypoint rows in, poses out: rows [P, M, C >= 3 + desc_dim] float32 as the model's xyz_feat_att_nms (C = 132) or a
     _nms_res.bin (utils.load_descriptor_bin) give them -- [x, y, z, descriptor(, score)] -- with counts [P] int32.  Matches
     every anchor keypoint to its nearest positive descriptor, then ransac_rigid (keyword arguments threshold, confidence,
-    max_trials, seed).  Returns ransac_rigid's dict plus match / dist; everything stays on the device, no host sync."""
+    max_trials, seed).  Returns ransac_rigid's dict plus match / dist; everything stays on the device, no host sync.
+    match: None, or a dict of match_descriptors2's options, e.g. {"ratio": 0.9, "mutual": True} ({}: that entry, no
+    filter): RANSAC then sees only the kept rows, match is the filtered list, dist is dist1 (of every row, kept or not) and
+    match_descriptors2's other outputs (nn1, nn2, dist1, dist2, num_kept, with mutual rev / rev_dist) join the result."""
     a = _rows(anchor_rows, "anchor_rows", 3 + int(desc_dim))
     b = _rows(positive_rows, "positive_rows", 3 + int(desc_dim))
-    match, dist = match_descriptors(a[:, :, 3:3 + desc_dim], anchor_count, b[:, :, 3:3 + desc_dim], positive_count)
-    out = ransac_rigid(a, b, match, anchor_count, **ransac_kw)
-    out["match"], out["dist"] = match, dist
-    return out
+    return _match_and_fit(a[:, :, 3:3 + desc_dim], anchor_count, b[:, :, 3:3 + desc_dim], positive_count, a, b, match, ransac_kw)
 
 
 ICP_MAX_POINTS, ICP_MAX_ITERATIONS, ICP_GRID_MAX = 131072, 256, 16384  # csrc/icp.hip kMaxPoints, kMaxIter, kGridMaxNa
@@ -527,11 +593,14 @@ def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None
     tensor or a pair (anchor, positive), e.g. farthest-point picks, -1 padded at the tail.  keypoints may be a pair too, and
     in place of a number a detector: {"method": "iss", ...iss_keypoints' keywords} runs iss_keypoints on the cloud (N <= 16384)
     and goes on as with its ids as keypoint_ids.
+    match (a keyword beside ransac_rigid's): None, or a dict of match_descriptors2's options as register takes it
+    ({"ratio": 0.9, "mutual": True}); a pair the filters leave fewer than three correspondences comes back valid=False.
     refine: None, True or a dict of refine_pose keywords, on the full clouds.  Returns register_clouds' keys: ransac_rigid's
     dict plus match / dist (indices into the keypoint lists), and with refine Rt_ransac, fitness, rmse, num_corr_icp, nn (and
     num_plane, rmse_plane with method="plane"; num_planar, rmse_gicp with method="gicp"); plus anchor_ids / positive_ids (the
     keypoint ids, None: all points).  No host sync."""
     rkw = _refine_kw(refine)
+    match = ransac_kw.pop("match", None)
     pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
     nv, kp, kid = pair(num_valid), pair(keypoints), pair(keypoint_ids)
     rows, cnts, idl = [], [], []
@@ -548,9 +617,7 @@ def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None
         rows.append((xyz, desc))
         cnts.append(kc)
         idl.append(ids)
-    match, dist = match_descriptors(rows[0][1], cnts[0], rows[1][1], cnts[1])
-    out = ransac_rigid(rows[0][0], rows[1][0], match, cnts[0], **ransac_kw)
-    out["match"], out["dist"] = match, dist
+    out = _match_and_fit(rows[0][1], cnts[0], rows[1][1], cnts[1], rows[0][0], rows[1][0], match, ransac_kw)
     out["anchor_ids"], out["positive_ids"] = idl
     if rkw is not None:
         _merge_refinement(out, refine_pose(anchor_points, positive_points, out["Rt"], out["valid"], anchor_count=nv[0],
@@ -599,7 +666,8 @@ def register_clouds(model, anchor_points, positive_points, num_valid=None, refin
     (num_valid as the counts): Rt is the refined pose and the result gains Rt_ransac (the keypoint fit), fitness, rmse,
     num_corr_icp and nn; valid stays the RANSAC fit's.  A dict with method="plane" (and refine_icp_plane's keywords) refines
     point-to-plane instead and adds num_plane and rmse_plane; method="gicp" (and refine_icp_gicp's keywords) refines by
-    generalized ICP and adds num_planar and rmse_gicp."""
+    generalized ICP and adds num_planar and rmse_gicp.  Other keywords go to register: desc_dim, match={"ratio": ...,
+    "mutual": ...} and ransac_rigid's."""
     if not getattr(model.config, "detection", False):
         raise ValueError("register_clouds needs a model with config.detection (the keypoint outputs)")
     rkw = _refine_kw(refine)

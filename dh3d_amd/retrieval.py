@@ -195,7 +195,8 @@ class PlaceIndex:
         the retrieved place); a dict with method="plane" refines point-to-plane (registration.refine_icp_plane's keywords;
         the winner's normals are computed per call) and adds rmse_plane; method="gicp" refines by generalized ICP
         (registration.refine_icp_gicp's keywords; both clouds' normals are computed per call) and adds rmse_gicp.  Needs an index built with points > 0 (else
-        ValueError).  No host sync."""
+        ValueError).  Other keywords go to registration.register: ransac_rigid's, and match={"ratio": ..., "mutual": ...} (the
+        ratio test and the mutual check ahead of RANSAC).  No host sync."""
         if not self.keypoints:
             raise ValueError("localize needs a PlaceIndex built with keypoints > 0")
         rkw = registration._refine_kw(refine)
@@ -249,7 +250,8 @@ def relocalize_clouds(global_model, local_model, index, points, k=5, num_valid=N
     xyz_feat_att_nms from `local_model` (config.detection) -- two models, as the reference has two checkpoints -- then
     index.localize.  num_valid: None or int32 [Q].  refine: None, True or a dict of registration.refine_icp keywords (or
     method="plane" / "gicp" and registration.refine_icp_plane's / refine_icp_gicp's) -- the winner's pose is refined by dense ICP of `points` against the
-    place's stored cloud (PlaceIndex(points=...))."""
+    place's stored cloud (PlaceIndex(points=...)).  Other keywords go to index.localize and from there to
+    registration.register: match={"ratio": ..., "mutual": ...} filters the correspondences ahead of RANSAC."""
     if not getattr(global_model.config, "extract_global", False):
         raise ValueError("relocalize_clouds needs a global_model with config.extract_global (the globaldesc output)")
     if not getattr(local_model.config, "detection", False):

@@ -939,6 +939,29 @@ int dh3d_gather_rows(const float *src, int B, int N, int C, const int32_t *inds,
 int dh3d_match_descriptors(const float *anchor_desc, long long anchor_stride, const int32_t *anchor_count,
                            const float *positive_desc, long long positive_stride, const int32_t *positive_count, int P, int Ma,
                            int Mb, int D, int32_t *match, float *dist, void *stream);
+/* The two nearest positives of every anchor, the nearest anchor of every positive, and Lowe's ratio test and the mutual
+ * (cross) check on them (csrc/match.hip).  Inputs, strides, counts and limits as dh3d_match_descriptors; a = clamp(anchor_count
+ * [p], 0, Ma), b = clamp(positive_count[p], 0, Mb), and S(i, j) is that entry's f32 sum over d ascending of (a_d - b_d)^2, no
+ * fma contraction (S = +inf or NaN is no neighbour).  For every pair p:
+ *   nn1, nn2 [P, Ma]     the two smallest (S, j) over j < b in lexicographic order: ties go to the lowest id, duplicate
+ *                        positives give nn2 the next id at the same S; -1 where there is none (i >= a, b = 0, b = 1 for nn2);
+ *   dist1, dist2 [P, Ma] sqrtf of those sums, +inf where the id is -1.  nn1 / dist1 equal dh3d_match_descriptors' match /
+ *                        dist bit for bit;
+ *   rev, rev_dist [P, Mb] the smallest (S, i) over i < a of every positive j < b, else -1 / +inf (S is symmetric in f32).
+ *                        Both may be NULL when mutual == 0: the reverse search is then not run;
+ *   match [P, Ma]        nn1[i] if the row is kept, else -1.  Kept: nn1 >= 0; and ratio2 <= 0 or S1 < ratio2 * S2 (f32, one
+ *                        rounded product, strict; S2 = +inf without a second neighbour: a lone candidate is kept, an exact
+ *                        tie at ratio2 = 1 is not); and mutual == 0 or rev[nn1[i]] == i.  ratio2 is the SQUARE of Lowe's
+ *                        ratio: the test is on the sums, nothing depends on sqrtf;
+ *   num_kept [P]         how many rows of match are >= 0.
+ * Every element of every output is written.  A pair's result depends neither on the batch nor on the run: the f32 MFMA only
+ * screens which pairs the rule evaluates (a proved bound, csrc/match.hip), the ids and sums are the rule's, merged by integer
+ * minima.  No workspace, no host sync, graph-capturable.  Errors as dh3d_match_descriptors; also DH3D_ERR_INVALID_ARGUMENT
+ * for ratio2 > 1 or NaN, for only one of rev / rev_dist, and for mutual != 0 without them. */
+int dh3d_match_descriptors2(const float *anchor_desc, long long anchor_stride, const int32_t *anchor_count,
+                            const float *positive_desc, long long positive_stride, const int32_t *positive_count, int P, int Ma,
+                            int Mb, int D, float ratio2, int mutual, int32_t *nn1, float *dist1, int32_t *nn2, float *dist2,
+                            int32_t *rev, float *rev_dist, int32_t *match, int32_t *num_kept, void *stream);
 /* RANSAC rigid registration of P cloud pairs (ransacfitRt.m over ransac.m and estimateRigidTransform.m with isdegenerate = 0,
  * batched; csrc/registration.hip).  One workgroup per pair; no workspace (the correspondences are staged in LDS).
  * Coordinates: anchor point i of pair p at anchor_xyz + (p*Ma + i) * anchor_stride (3 floats), positive point j at

@@ -119,13 +119,16 @@ def main():
             Y[p] = ((X[p].astype(np.float64) - t) @ R + rng.normal(0.0, 0.02, (N, 3)))[rng.permutation(N)]
             T[p] = np.concatenate([R, t[:, None]], axis=1)
         y = torch.from_numpy(Y).cuda()
-        for label, kw in (("register_fpfh", {}), ("register_fpfh_refined", dict(refine=True))):
+        for label, kw in (("register_fpfh", {}), ("register_fpfh_refined", dict(refine=True)),
+                          ("register_fpfh_ratio_mutual", dict(match={"ratio": 0.9, "mutual": True}))):
             us = timed(lambda: reg.register_fpfh(x[:q], y, **kw), a.iters)
             out = reg.register_fpfh(x[:q], y, **kw)
             dt, dd = reg.transform_errors(T, out["Rt"], out["valid"])
             res[label] = dict(pairs=q, keypoints=int(out["match"].shape[1]), us=us, valid=int(out["valid"].sum()),
                               dt_mean=float(dt.mean()), dt_max=float(dt.max()), ddeg_mean=float(dd.mean()), ddeg_max=float(dd.max()),
                               inlier_ratio=float(out["inlier_ratio"].mean()), trials=float(out["trials"].float().mean()))
+            if "num_kept" in out:  # the correspondences the ratio test and the mutual check leave to RANSAC
+                res[label]["kept"] = float(out["num_kept"].float().mean())
     line = json.dumps(res)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "fpfh_bench.json"), "w") as f:

@@ -3,7 +3,14 @@ and dh3d_ransac_rigid separately, with device events around `iters` back-to-back
 depends on the trial count, so three inlier shares are timed: 0.5 (10-40 trials: one round of 256), 0.2 (~570 trials:
 three rounds) and 0 (max_trials + 1 = 10001 trials: 40 rounds, the worst case).  Prints one JSON line.
 
-    python tools/registration_bench.py [--pairs 64] [--keypoints 512] [--iters 20]
+dh3d_match_descriptors2 (csrc/match.hip) is timed beside the plain matcher at 64 x 512 x 512 x 128 and 8 x 4096 x 4096 x 36,
+`--reps` windows of `iters` calls each, the variants alternating inside a repetition: one plain call, two (the second with
+the roles swapped: what a mutual check costs without the new entry), the new entry forward only (match={}) and with both
+filters.  Each figure is the median over the repetitions with its spread (max - min); `ok` says whether the new call stays
+within the plain matcher's time plus that matcher's spread.  ransac_rigid is then timed on the unfiltered and on the
+filtered ids of fixtures whose outliers carry unrelated descriptors.  That part is also written to --out.
+
+    python tools/registration_bench.py [--pairs 64] [--keypoints 512] [--iters 20] [--reps 5] [--out profiles/match2_bench.json]
 """
 import argparse
 import json
@@ -30,6 +37,62 @@ def rows(rng, P, M, D, inlier_share):
     return torch.from_numpy(ra).cuda(), torch.from_numpy(rb).cuda()
 
 
+def desc_rows(rng, P, M, D, inlier_share, noise=0.03):
+    """As rows, but an outlier's positive also carries an unrelated descriptor, and the true partners differ by `noise` per
+    component: what the ratio test and the mutual check are there to tell apart."""
+    ra, rb = rows(rng, P, M, D, 1.0)
+    out = torch.from_numpy(rng.random((P, M)) >= inlier_share).cuda()
+    unrelated = torch.from_numpy(rng.standard_normal((P, M, D)).astype(np.float32)).cuda()
+    unrelated /= unrelated.norm(dim=-1, keepdim=True)
+    rb[:, :, 3:3 + D] += noise * torch.from_numpy(rng.standard_normal((P, M, D)).astype(np.float32)).cuda()
+    rb[:, :, 3:3 + D] = torch.where(out[:, :, None], unrelated, rb[:, :, 3:3 + D])
+    rb[:, :, :3] = torch.where(out[:, :, None], torch.from_numpy((rng.random((P, M, 3)) * 40 - 20).astype(np.float32)).cuda(),
+                               rb[:, :, :3])
+    return ra, rb
+
+
+def match2_times(rng, P, M, D, iters, reps):
+    """The four matcher variants on one shape, alternating inside every repetition: median and spread in us."""
+    ra, rb = desc_rows(rng, P, M, D, 0.5)
+    a, b = ra[:, :, 3:3 + D], rb[:, :, 3:3 + D]
+    cnt = torch.full((P,), M, dtype=torch.int32, device="cuda")
+    variants = dict(
+        plain_one=lambda: reg.match_descriptors(a, cnt, b, cnt),
+        plain_two=lambda: (reg.match_descriptors(a, cnt, b, cnt), reg.match_descriptors(b, cnt, a, cnt)),
+        match2_forward=lambda: reg.match_descriptors2(a, cnt, b, cnt),
+        match2_ratio_mutual=lambda: reg.match_descriptors2(a, cnt, b, cnt, ratio=0.9, mutual=True))
+    runs = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, fn in variants.items():
+            runs[k].append(timed(fn, iters))
+    row = dict(pairs=P, keypoints=M, desc_dim=D, iters=iters, reps=reps)
+    for k, v in runs.items():
+        row[k + "_us"] = dict(median=float(np.median(v)), spread=float(max(v) - min(v)))
+    med = lambda k: row[k + "_us"]["median"]
+    row["forward_ok"] = med("match2_forward") <= med("plain_one") + row["plain_one_us"]["spread"]
+    row["both_ok"] = med("match2_ratio_mutual") <= med("plain_two") + row["plain_two_us"]["spread"]
+    row["kept"] = float(reg.match_descriptors2(a, cnt, b, cnt, ratio=0.9, mutual=True)["num_kept"].float().mean())
+    return row
+
+
+def ransac_on_filtered(rng, P, M, D, iters):
+    """ransac_rigid on the plain ids and on the ratio + mutual ids of the outlier fixtures."""
+    cnt = torch.full((P,), M, dtype=torch.int32, device="cuda")
+    res = {}
+    for share in (0.5, 0.2):
+        ra, rb = desc_rows(rng, P, M, D, share)
+        a, b = ra[:, :, 3:3 + D], rb[:, :, 3:3 + D]
+        plain, _ = reg.match_descriptors(a, cnt, b, cnt)
+        kept = reg.match_descriptors2(a, cnt, b, cnt, ratio=0.9, mutual=True)
+        row = dict(kept=float(kept["num_kept"].float().mean()))
+        for label, ids in (("unfiltered", plain), ("filtered", kept["match"])):
+            out = reg.ransac_rigid(ra, rb, ids, cnt)
+            row[label] = dict(us=timed(lambda: reg.ransac_rigid(ra, rb, ids, cnt), iters), valid=int(out["valid"].sum()),
+                              trials=float(out["trials"].float().mean()), inlier_ratio=float(out["inlier_ratio"].mean()))
+        res["inliers%g" % share] = row
+    return res
+
+
 def timed(fn, iters):
     fn()
     torch.cuda.synchronize()
@@ -47,6 +110,9 @@ def main():
     ap.add_argument("--pairs", type=int, default=64)
     ap.add_argument("--keypoints", type=int, default=512)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                  "match2_bench.json"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
     P, M, D = a.pairs, a.keypoints, 128
@@ -63,6 +129,13 @@ def main():
         us = timed(lambda: reg.ransac_rigid(ra, rb, match, cnt), max(1, a.iters // (10 if share == 0 else 1)))
         res["ransac_inliers%g" % share] = dict(us=us, trials_min=int(trials.min()), trials_max=int(trials.max()))
     res["register_us"] = timed(lambda: reg.register(ra, cnt, rb, cnt), max(1, a.iters // 10))
+    m2 = dict(shape_512x128=match2_times(rng, 64, 512, 128, a.iters, a.reps),
+              shape_4096x36=match2_times(rng, 8, 4096, 36, a.iters, a.reps),
+              ransac=ransac_on_filtered(rng, P, M, D, a.iters))
+    res["match2"] = m2
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(json.dumps(m2) + "\n")
     print(json.dumps(res))
 
 
