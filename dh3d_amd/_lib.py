@@ -42,6 +42,7 @@ _SIGNATURES = {
     "dh3d_stage_copy": [c_fp, c_fp, c_size_t, c_int, c_fp],
     "dh3d_knn_bruteforce": [c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp],
     "dh3d_knn_bruteforce_xyz": [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp],
+    "dh3d_knn_bruteforce_plan": [c_int, c_int, c_int, c_int],
     "dh3d_flex_conv_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp],
     "dh3d_flex_conv_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp,
                            c_fp, c_fp, c_fp],
@@ -130,6 +131,7 @@ _SIGNATURES = {
     "dh3d_three_interpolate_bwd": [c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_spatial_sort": [c_fp, c_int, c_int, c_fp, c_fp, c_fp],
     "dh3d_knn_sorted": [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp],
+    "dh3d_knn_sorted_plan": [c_int, c_int, c_int],
     "dh3d_spatial_sort_cells": [c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp],
     "dh3d_knn_grid": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp],
     "dh3d_knn_grid_plan": [c_int, c_int, c_int],

@@ -913,24 +913,58 @@ __global__ __launch_bounds__(256) void knn_small_kernel(const float *__restrict_
   }
 }
 
+// What every kNN entry of this file takes beyond positive sizes: the K-lists hold 64 keys, a cloud is a grid row.
+constexpr int kKnnMaxK = 64, kKnnMaxB = 65535;
+
+// The K-list width (KMAX) of the lane-per-query kernels: knn_kernel here, knn_sorted_kernel below.
+static int knn_list_width(int K) { return K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : K <= 32 ? 32 : 64; }
+
+// The launch plan of dh3d_knn_bruteforce (Dp = 3) and dh3d_knn_bruteforce_xyz -- the one place knn_launch's thresholds
+// live (knn_launch runs it, dh3d_knn_bruteforce_plan reports it).
+//   cpl > 0: knn_small_kernel<cpl> (a wave per query, 64 * cpl >= N candidates in registers), q queries per wave;
+//   cpl = 0: knn_kernel<kmax> (a lane per query).
+struct KnnPlan {
+  int cpl, q, kmax;
+};
+static KnnPlan knn_plan(int B, int N, int K) {
+  KnnPlan p{0, 0, 0};
+  if (N <= 2048) {
+    p.cpl = N <= 512 ? 8 : N <= 1024 ? 16 : 32;
+    p.q = (long long)B * N <= 16384 ? 2 : 4;  // <= 4 waves per SIMD with two queries per wave
+    return p;
+  }
+  p.kmax = knn_list_width(K);
+  return p;
+}
+
+// The K-list width of knn_anydp_kernel (Dp != 3, up to the 16 coordinates its staging tile holds).
+constexpr int kAnyDpMax = 16;
+static int knn_anydp_width(int K) { return K <= 8 ? 8 : K <= 16 ? 16 : 64; }
+
 template <bool XYZ>
 int knn_launch(const float *pos, int B, int N, int K, int32_t *nn, float *dist, hipStream_t s) {
   const KnnLadder lad = knn_ladder(N);
-  if (N <= 2048) {  // wave-per-query kernel
-    const int Q = (long long)B * N <= 16384 ? 2 : 4;  // <= 4 waves per SIMD with two queries per wave
-    dim3 sgrid(dh3d_cdiv(N, 4 * Q), B), sblock(256);
-    if (N <= 512) hipLaunchKernelGGL((knn_small_kernel<8, XYZ>), sgrid, sblock, 0, s, pos, N, K, lad, nn, dist, Q);
-    else if (N <= 1024) hipLaunchKernelGGL((knn_small_kernel<16, XYZ>), sgrid, sblock, 0, s, pos, N, K, lad, nn, dist, Q);
-    else hipLaunchKernelGGL((knn_small_kernel<32, XYZ>), sgrid, sblock, 0, s, pos, N, K, lad, nn, dist, Q);
-    return dh3d_launch_status();
+  const KnnPlan p = knn_plan(B, N, K);
+  if (p.cpl > 0) {  // wave-per-query kernel
+    dim3 sgrid(dh3d_cdiv(N, 4 * p.q), B), sblock(256);
+#define DH3D_SMALL_CASE(CPL)                                                                                     \
+  if (p.cpl == CPL) {                                                                                            \
+    hipLaunchKernelGGL((knn_small_kernel<CPL, XYZ>), sgrid, sblock, 0, s, pos, N, K, lad, nn, dist, p.q);        \
+    return dh3d_launch_status();                                                                                 \
+  }
+    DH3D_SMALL_CASE(8) DH3D_SMALL_CASE(16) DH3D_SMALL_CASE(32)
+#undef DH3D_SMALL_CASE
+    return DH3D_ERR_UNSUPPORTED;  // (a plan without a kernel)
   }
   dim3 grid(dh3d_cdiv(N, kQueriesPerBlock), B), block(kQueriesPerBlock);
-  if (K <= 4) hipLaunchKernelGGL((knn_kernel<4, XYZ>), grid, block, 0, s, pos, N, K, lad, nn, dist);
-  else if (K <= 8) hipLaunchKernelGGL((knn_kernel<8, XYZ>), grid, block, 0, s, pos, N, K, lad, nn, dist);
-  else if (K <= 16) hipLaunchKernelGGL((knn_kernel<16, XYZ>), grid, block, 0, s, pos, N, K, lad, nn, dist);
-  else if (K <= 32) hipLaunchKernelGGL((knn_kernel<32, XYZ>), grid, block, 0, s, pos, N, K, lad, nn, dist);
-  else hipLaunchKernelGGL((knn_kernel<64, XYZ>), grid, block, 0, s, pos, N, K, lad, nn, dist);
-  return dh3d_launch_status();
+#define DH3D_LANE_CASE(KM)                                                                                       \
+  if (p.kmax == KM) {                                                                                            \
+    hipLaunchKernelGGL((knn_kernel<KM, XYZ>), grid, block, 0, s, pos, N, K, lad, nn, dist);                      \
+    return dh3d_launch_status();                                                                                 \
+  }
+  DH3D_LANE_CASE(4) DH3D_LANE_CASE(8) DH3D_LANE_CASE(16) DH3D_LANE_CASE(32) DH3D_LANE_CASE(64)
+#undef DH3D_LANE_CASE
+  return DH3D_ERR_UNSUPPORTED;
 }
 
 // Any position dimension (the reference loops over Dp, knn_bruteforce_kernel_gpu.cu.cc:98-107; DH3D itself only ever
@@ -988,42 +1022,72 @@ __global__ __launch_bounds__(256) void knn_anydp_kernel(const float *__restrict_
 DH3D_API int dh3d_knn_bruteforce(const float *positions, int B, int Dp, int N, int K, int32_t *nn,
                                  float *dist, void *stream) {
   DH3D_REQUIRE(positions && nn && dist && B > 0 && N > 0 && K > 0 && Dp > 0);
-  DH3D_SUPPORTED(K <= 64 && B <= 65535);
+  DH3D_SUPPORTED(K <= kKnnMaxK && B <= kKnnMaxB);
   if (Dp == 3) return knn_launch<false>(positions, B, N, K, nn, dist, (hipStream_t)stream);
-  DH3D_SUPPORTED(Dp <= 16);  // (any Dp upstream; the staging tile here holds 16 coordinates)
+  DH3D_SUPPORTED(Dp <= kAnyDpMax);  // (any Dp upstream; the staging tile here holds 16 coordinates)
   const KnnLadder lad = knn_ladder(N);
   dim3 grid(dh3d_cdiv(N, 256), B), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (K <= 8) hipLaunchKernelGGL(knn_anydp_kernel<8>, grid, block, 0, s, positions, Dp, N, K, lad, nn, dist);
-  else if (K <= 16) hipLaunchKernelGGL(knn_anydp_kernel<16>, grid, block, 0, s, positions, Dp, N, K, lad, nn, dist);
-  else hipLaunchKernelGGL(knn_anydp_kernel<64>, grid, block, 0, s, positions, Dp, N, K, lad, nn, dist);
-  return dh3d_launch_status();
+  const int km = knn_anydp_width(K);
+#define DH3D_ANYDP_CASE(KM)                                                                                      \
+  if (km == KM) {                                                                                                \
+    hipLaunchKernelGGL(knn_anydp_kernel<KM>, grid, block, 0, s, positions, Dp, N, K, lad, nn, dist);             \
+    return dh3d_launch_status();                                                                                 \
+  }
+  DH3D_ANYDP_CASE(8) DH3D_ANYDP_CASE(16) DH3D_ANYDP_CASE(64)
+#undef DH3D_ANYDP_CASE
+  return DH3D_ERR_UNSUPPORTED;  // (a width without a kernel)
 }
 
 DH3D_API int dh3d_knn_bruteforce_xyz(const float *xyz, int B, int N, int K, int32_t *nn, float *dist,
                                      void *stream) {
   DH3D_REQUIRE(xyz && nn && dist && B > 0 && N > 0 && K > 0);
-  DH3D_SUPPORTED(K <= 64 && B <= 65535);
+  DH3D_SUPPORTED(K <= kKnnMaxK && B <= kKnnMaxB);
   return knn_launch<true>(xyz, B, N, K, nn, dist, (hipStream_t)stream);
+}
+
+// The kernel dh3d_knn_bruteforce runs for [B, Dp, N] positions and K neighbours (dh3d_knn_bruteforce_xyz: Dp = 3), from
+// the launchers' own functions; host only.  family * 65536 + a * 256 + b, or -1 where the entry refuses the shape:
+//   family 1, a = CPL (8 / 16 / 32), b = Q (2 / 4): knn_small_kernel<CPL>, Q queries per wave   (Dp = 3, N <= 2048)
+//   family 2, a = 0, b = KMAX (4 .. 64):            knn_kernel<KMAX>                            (Dp = 3, N > 2048)
+//   family 3, a = 0, b = KMAX (8 / 16 / 64):        knn_anydp_kernel<KMAX>                      (Dp != 3, Dp <= 16)
+DH3D_API int dh3d_knn_bruteforce_plan(int B, int Dp, int N, int K) {
+  if (!(B > 0 && N > 0 && K > 0 && Dp > 0) || !(K <= kKnnMaxK && B <= kKnnMaxB)) return -1;
+  if (Dp != 3) return Dp <= kAnyDpMax ? 3 * 65536 + knn_anydp_width(K) : -1;
+  const KnnPlan p = knn_plan(B, N, K);
+  return p.cpl > 0 ? 1 * 65536 + p.cpl * 256 + p.q : 2 * 65536 + p.kmax;
+}
+
+// The launch plan of dh3d_knn_sorted (and of dh3d_knn_grid's gated second launch) -- the one place knn_sorted_launch's
+// thresholds live (knn_sorted_launch runs it, dh3d_knn_sorted_plan reports it).
+//   s: waves per query group, knn_split_kernel<kmax, s>; 0 = the one-wave kernel, knn_sorted_kernel<kmax>.
+struct KnnSortedPlan {
+  int s, kmax;
+};
+static KnnSortedPlan knn_sorted_plan(int B, int N, int K) {
+  // waves per query group: as many as keep the chip at <= ~4 waves per SIMD, where the search turns from latency- to
+  // issue-bound (MI355X: 8x8192 0.194 -> 0.109 ms at 4; 32x4096 0.178 -> 0.147 at 2)
+  const long long groups = (long long)((N + 63) / 64) * B;
+  KnnSortedPlan p{groups <= 256 ? 8 : groups <= 1280 ? 4 : groups <= 4096 ? 2 : 0, knn_list_width(K)};
+  if (p.kmax > 16) p.s = 0;                 // the split kernels keep lists of up to 16
+  if (p.s == 8 && p.kmax == 4) p.kmax = 8;  // (no <4, 8> instantiation: K <= 4 runs the width-8 kernel there)
+  return p;
 }
 
 static int knn_sorted_launch(const float *sorted, const float *gbox, int B, int N, int K, int32_t *nn, float *dist,
                              const int *gate, void *stream) {
   DH3D_REQUIRE(sorted && gbox && nn && dist && B > 0 && N > 0 && K > 0);
-  DH3D_SUPPORTED(K <= 64 && B <= 65535);
+  DH3D_SUPPORTED(K <= kKnnMaxK && B <= kKnnMaxB);
   const KnnLadder lad = knn_ladder(N);
   const int NG = (N + 63) / 64;
   dim3 grid(dh3d_cdiv(NG, kSortedWaves), B), block(64 * kSortedWaves);
   hipStream_t s = (hipStream_t)stream;
   const float4 *so = reinterpret_cast<const float4 *>(sorted);
-  // waves per query group (0 = the one-wave kernel): as many as keep the chip at <= ~4 waves per SIMD, where the
-  // search turns from latency- to issue-bound (MI355X: 8x8192 0.194 -> 0.109 ms at 4; 32x4096 0.178 -> 0.147 at 2)
-  const long long groups = (long long)NG * B;
-  const int S = groups <= 256 ? 8 : groups <= 1280 ? 4 : groups <= 4096 ? 2 : 0;
-  if (S > 0 && K <= 16) {
+  const KnnSortedPlan p = knn_sorted_plan(B, N, K);
+  if (p.s > 0) {
     dim3 sgrid(NG, B);
 #define DH3D_SPLIT_CASE(KM, SS)                                                                               \
-  if (K <= KM && S == SS) {                                                                                  \
+  if (p.kmax == KM && p.s == SS) {                                                                           \
     hipLaunchKernelGGL((knn_split_kernel<KM, SS>), sgrid, dim3(64 * SS), 0, s, so, gbox, N, K, lad, nn, dist, gate); \
     return dh3d_launch_status();                                                                             \
   }
@@ -1031,18 +1095,30 @@ static int knn_sorted_launch(const float *sorted, const float *gbox, int B, int 
     DH3D_SPLIT_CASE(8, 2) DH3D_SPLIT_CASE(8, 4) DH3D_SPLIT_CASE(8, 8)
     DH3D_SPLIT_CASE(16, 2) DH3D_SPLIT_CASE(16, 4) DH3D_SPLIT_CASE(16, 8)
 #undef DH3D_SPLIT_CASE
+    return DH3D_ERR_UNSUPPORTED;  // (a plan without a kernel)
   }
-  if (K <= 4) hipLaunchKernelGGL((knn_sorted_kernel<4>), grid, block, 0, s, so, gbox, N, K, lad, nn, dist, gate);
-  else if (K <= 8) hipLaunchKernelGGL((knn_sorted_kernel<8>), grid, block, 0, s, so, gbox, N, K, lad, nn, dist, gate);
-  else if (K <= 16) hipLaunchKernelGGL((knn_sorted_kernel<16>), grid, block, 0, s, so, gbox, N, K, lad, nn, dist, gate);
-  else if (K <= 32) hipLaunchKernelGGL((knn_sorted_kernel<32>), grid, block, 0, s, so, gbox, N, K, lad, nn, dist, gate);
-  else hipLaunchKernelGGL((knn_sorted_kernel<64>), grid, block, 0, s, so, gbox, N, K, lad, nn, dist, gate);
-  return dh3d_launch_status();
+#define DH3D_SORTED_CASE(KM)                                                                                  \
+  if (p.kmax == KM) {                                                                                        \
+    hipLaunchKernelGGL((knn_sorted_kernel<KM>), grid, block, 0, s, so, gbox, N, K, lad, nn, dist, gate);      \
+    return dh3d_launch_status();                                                                             \
+  }
+  DH3D_SORTED_CASE(4) DH3D_SORTED_CASE(8) DH3D_SORTED_CASE(16) DH3D_SORTED_CASE(32) DH3D_SORTED_CASE(64)
+#undef DH3D_SORTED_CASE
+  return DH3D_ERR_UNSUPPORTED;
 }
 
 DH3D_API int dh3d_knn_sorted(const float *sorted, const float *gbox, int B, int N, int K, int32_t *nn,
                              float *dist, void *stream) {
   return knn_sorted_launch(sorted, gbox, B, N, K, nn, dist, nullptr, stream);
+}
+
+// The kernel dh3d_knn_sorted launches for (B, N, K), from the launcher's own function; host only.  S * 256 + KMAX, or -1
+// where dh3d_knn_sorted refuses the shape.  S = 8 / 4 / 2: knn_split_kernel<KMAX, S>, S waves per 64-query group
+// (KMAX 4 / 8 / 16; 8 / 16 at S = 8); S = 0: knn_sorted_kernel<KMAX>, one wave per group (KMAX 4 .. 64).
+DH3D_API int dh3d_knn_sorted_plan(int B, int N, int K) {
+  if (!(B > 0 && N > 0 && K > 0) || !(K <= kKnnMaxK && B <= kKnnMaxB)) return -1;
+  const KnnSortedPlan p = knn_sorted_plan(B, N, K);
+  return p.s * 256 + p.kmax;
 }
 
 // ------------------------------------------------------------------------------------------------ cell-list kNN

@@ -13,14 +13,42 @@ from . import _lib as L
 ACT_NONE, ACT_RELU, ACT_SIGMOID = L.ACT_NONE, L.ACT_RELU, L.ACT_SIGMOID
 
 
-def knn_xyz(xyz, k):
-    """xyz [B,N,3] -> (nbr [B,N,K] int32, dist [B,N,K]); same function as ops.knn_bruteforce."""
+def _knn_out(what, out, B, N, k, device):
+    """The (nn, dist) a kNN wrapper writes: fresh tensors, or the caller's `out` pair after validation."""
+    if out is None:
+        return (torch.empty((B, N, k), dtype=torch.int32, device=device),
+                torch.empty((B, N, k), dtype=torch.float32, device=device))
+    nn, dist = out
+    for t, dt, name in ((nn, torch.int32, "nn"), (dist, torch.float32, "dist")):
+        if tuple(t.shape) != (B, N, k) or t.dtype != dt or t.device != device or not t.is_contiguous():
+            raise ValueError("%s: out %s must be contiguous %s [%d, %d, %d] on %s, got %s %s on %s"
+                             % (what, name, dt, B, N, k, device, t.dtype, tuple(t.shape), t.device))
+    return nn, dist
+
+
+def knn_xyz(xyz, k, out=None):
+    """xyz [B,N,3] -> (nbr [B,N,K] int32, dist [B,N,K]); same function as ops.knn_bruteforce.
+    out: optional (nn int32 [B,N,K], dist float32 [B,N,K]), contiguous on the device, to write into."""
     x = L.require_cuda_f32(xyz, "xyz", 3)
     B, N, _ = x.shape
-    nn = torch.empty((B, N, k), dtype=torch.int32, device=x.device)
-    dist = torch.empty((B, N, k), dtype=torch.float32, device=x.device)
+    nn, dist = _knn_out("knn_xyz", out, B, N, k, x.device)
     L.check(L.lib().dh3d_knn_bruteforce_xyz(L.ptr(x), B, N, k, L.ptr(nn), L.ptr(dist), L.stream_ptr()), "knn_xyz")
     return nn, dist
+
+
+KNN_FAMILIES = {1: "small", 2: "lane", 3: "anydp"}
+
+
+def knn_plan(B, N, k, Dp=3):
+    """The kernel knn_xyz / ops.knn_bruteforce run for B clouds of N points in Dp dimensions (host only;
+    dh3d_knn_bruteforce_plan): ("small", CPL, Q) a wave per query, CPL candidates per lane and Q queries per wave
+    (N <= 2048); ("lane", KMAX) a lane per query with a K-list of KMAX; ("anydp", KMAX) the kernel for Dp != 3.  None where
+    the entry refuses the shape."""
+    r = L.lib().dh3d_knn_bruteforce_plan(int(B), int(Dp), int(N), int(k))
+    if r < 0:
+        return None
+    family, a, b = KNN_FAMILIES[r >> 16], (r >> 8) & 255, r & 255
+    return (family, a, b) if family == "small" else (family, b)
 
 
 def spatial_sort(xyz):
@@ -54,15 +82,7 @@ def knn_grid(srt, gbox, cells, k, out=None):
     """kNN by cell lists on the three outputs of spatial_sort_cells(); same (nbr [B,N,K], dist) as knn_xyz bit for bit.
     K <= 8.  out: optional (nn int32 [B,N,K], dist float32 [B,N,K]), contiguous on the device, to write into."""
     B, N, _ = srt.shape
-    if out is None:
-        nn = torch.empty((B, N, k), dtype=torch.int32, device=srt.device)
-        dist = torch.empty((B, N, k), dtype=torch.float32, device=srt.device)
-    else:
-        nn, dist = out
-        for t, dt, name in ((nn, torch.int32, "nn"), (dist, torch.float32, "dist")):
-            if tuple(t.shape) != (B, N, k) or t.dtype != dt or t.device != srt.device or not t.is_contiguous():
-                raise ValueError("knn_grid: out %s must be contiguous %s [%d, %d, %d] on %s, got %s %s on %s"
-                                 % (name, dt, B, N, k, srt.device, t.dtype, tuple(t.shape), t.device))
+    nn, dist = _knn_out("knn_grid", out, B, N, k, srt.device)
     L.check(L.lib().dh3d_knn_grid(L.ptr(srt), L.ptr(gbox), L.ptr(cells), B, N, k, L.ptr(nn), L.ptr(dist), L.stream_ptr()), "knn_grid")
     return nn, dist
 
@@ -76,14 +96,22 @@ def knn_grid_plan(B, N, k):
     return None if r < 0 else (r % 16, r // 16)
 
 
-def knn_sorted(srt, gbox, k):
-    """kNN from spatial_sort() output; same (nbr [B,N,K], dist) as knn_xyz, original indexing."""
+def knn_sorted(srt, gbox, k, out=None):
+    """kNN from spatial_sort() output; same (nbr [B,N,K], dist) as knn_xyz, original indexing.
+    out: optional (nn int32 [B,N,K], dist float32 [B,N,K]), contiguous on the device, to write into."""
     B, N, _ = srt.shape
-    nn = torch.empty((B, N, k), dtype=torch.int32, device=srt.device)
-    dist = torch.empty((B, N, k), dtype=torch.float32, device=srt.device)
+    nn, dist = _knn_out("knn_sorted", out, B, N, k, srt.device)
     L.check(L.lib().dh3d_knn_sorted(L.ptr(srt), L.ptr(gbox), B, N, k, L.ptr(nn), L.ptr(dist), L.stream_ptr()),
             "knn_sorted")
     return nn, dist
+
+
+def knn_sorted_plan(B, N, k):
+    """The kernel knn_sorted launches for B clouds of N points and K neighbours (host only; dh3d_knn_sorted_plan):
+    (S, KMAX).  S = 8 / 4 / 2: knn_split_kernel<KMAX, S>, S waves per 64-query group (G = B * ceil(N / 64) <= 256 / 1280 /
+    4096 and K <= 16); S = 0: the one-wave knn_sorted_kernel<KMAX>.  None where knn_sorted refuses the shape."""
+    r = L.lib().dh3d_knn_sorted_plan(int(B), int(N), int(k))
+    return None if r < 0 else (r // 256, r % 256)
 
 
 def _ball_args(radius, nsample, xyz1, xyz2, what):

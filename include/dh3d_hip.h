@@ -75,7 +75,7 @@ int dh3d_stage_copy(const void *src, void *dst, size_t bytes, int device_to_devi
 /* KnnBruteforce -- replaces KnnBruteforceFunctor<GPUDevice,float,int>
  * (user_ops/kernels/knn_bruteforce_kernel_gpu.cu.cc:163-228; op user_ops/ops/knn_bruteforce.cc:11-35).
  * positions [B,Dp,N] -> nn [B,N,K] int32, dist [B,N,K] (Euclidean, ascending; self at rank 0).
- * Bit-exact ids incl. the CUB tie order.  Dp must be 3, 1 <= K <= 64.  N > 8192 (unsupported
+ * Bit-exact ids incl. the CUB tie order.  1 <= Dp <= 16 (Dp = 3: the fast kernels), 1 <= K <= 64.  N > 8192 (unsupported
  * upstream) is accepted with the ladder continued as (1024, ceil(N/1024)). */
 int dh3d_knn_bruteforce(const float *positions, int B, int Dp, int N, int K, int32_t *nn,
                         float *dist, void *stream);
@@ -84,6 +84,14 @@ int dh3d_knn_bruteforce(const float *positions, int B, int Dp, int N, int K, int
  * core/model.py:146); saves the transpose of core/model.py:157. */
 int dh3d_knn_bruteforce_xyz(const float *xyz, int B, int N, int K, int32_t *nn, float *dist,
                             void *stream);
+/* The kernel dh3d_knn_bruteforce runs for (B, Dp, N, K) -- dh3d_knn_bruteforce_xyz: Dp = 3 -- from the same functions the
+ * launchers use; host only, no GPU needed.  Returns family * 65536 + a * 256 + b, or -1 where the entry would refuse the
+ * shape (K > 64, B > 65535, Dp > 16, a size <= 0):
+ *   family 1 (Dp = 3, N <= 2048): a wave per query.  a = CPL, the candidates per lane (8: N <= 512, 16: N <= 1024, 32),
+ *            b = Q, the queries per wave (2 while B * N <= 16384, else 4);
+ *   family 2 (Dp = 3, N > 2048):  a lane per query.  a = 0, b = KMAX, the K-list width (4 / 8 / 16 / 32 / 64 >= K);
+ *   family 3 (Dp != 3):           the any-Dp kernel.  a = 0, b = KMAX (8 / 16 / 64 >= K). */
+int dh3d_knn_bruteforce_plan(int B, int Dp, int N, int K);
 
 /* FlexConv -- replaces FlexConvFunctor<GPUDevice,float> (flex_conv_kernel_gpu.cu.cc:392-441;
  * op user_ops/ops/flex_conv.cc:25-83).  Argument order is the functor's:
@@ -338,6 +346,13 @@ int dh3d_spatial_sort(const float *xyz, int B, int N, float *sorted, float *gbox
  * indices, rows are in original query order); candidate groups whose box is provably too far are skipped. */
 int dh3d_knn_sorted(const float *sorted, const float *gbox, int B, int N, int K, int32_t *nn, float *dist,
                     void *stream);
+/* The kernel dh3d_knn_sorted launches for (B, N, K), from the same function the launcher uses; host only, no GPU needed.
+ * Returns S * 256 + KMAX, or -1 where dh3d_knn_sorted would refuse the shape (K > 64, B > 65535, a size <= 0).
+ * G = B * ceil(N / 64) query groups decide S, the waves that share one group's scan: 8 (G <= 256), 4 (G <= 1280),
+ * 2 (G <= 4096), 0 = the one-wave kernel (beyond, and for every K > 16).  KMAX is the K-list width of the kernel that is
+ * actually instantiated: 4 / 8 / 16 at S = 4 and 2, 8 / 16 at S = 8 (K <= 4 runs the width-8 kernel there), 4 / 8 / 16 /
+ * 32 / 64 at S = 0. */
+int dh3d_knn_sorted_plan(int B, int N, int K);
 
 /* dh3d_spatial_sort that also writes the CELL TABLE of a 4096-cell grid over each cloud's bounding box: cells
  * [B, DH3D_CELL_INTS] int32.  The sort key is an 18-bit code; its top 12 bits are the GRID code, and since ABI 4 those 12

@@ -41,6 +41,8 @@ def test_invalid_arguments_are_status_codes_not_crashes():
     assert lib.dh3d_farthest_point_sample(1, 20000, 8, one, z, one, z) == 2  # N > 16384
     assert lib.dh3d_farthest_point_sample(1, 64, 0, one, z, one, z) == 1     # npoint <= 0 (tf_sampling.cpp:100)
     assert lib.dh3d_flex_conv_pm_fwd(one, one, one, one, 1, 64, 8, 48, 64, None, one, z) == 2
+    assert lib.dh3d_knn_bruteforce_xyz(one, 65536, 8, 4, one, one, z) == 2   # B > 65535: a cloud is a grid row
+    assert lib.dh3d_knn_sorted(one, one, 65536, 8, 4, one, one, z) == 2
     assert lib.dh3d_netvlad_workspace_bytes(4, 1024, 128, 64) == 0
     assert lib.dh3d_netvlad_workspace_bytes(4, 1024, 256, 64) > 0
 
@@ -87,6 +89,45 @@ def test_knn_grid_plan_is_the_launchers_choice():
     for N in (64, 1000, 3904, 4031, 4096, 8000, 16384):
         codes = [plan(B, N, 8)[0] for B in range(1, 300)]
         assert codes == sorted(codes, reverse=True), N
+
+
+def test_knn_sorted_plan_is_the_launchers_choice():
+    """dh3d_knn_sorted_plan (host only): the kernel dh3d_knn_sorted launches, (S, KMAX) -- S waves per 64-query group by
+    G = B * ceil(N / 64) (8 up to 256, 4 up to 1280, 2 up to 4096) on knn_split_kernel<KMAX, S>, S = 0 the one-wave
+    knn_sorted_kernel<KMAX> beyond and for every K > 16.  tests/test_knn_plan.py sweeps it."""
+    from dh3d_amd import _lib, pm
+    header = open(os.path.join(ROOT, "include", "dh3d_hip.h")).read()
+    assert re.search(r"\bint\s+dh3d_knn_sorted_plan\s*\(", header) and "dh3d_knn_sorted_plan" in _lib.EXPORTED_SYMBOLS
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "dh3d_knn_sorted_plan")
+    assert _lib.lib().dh3d_abi_version() == 4 == _lib.ABI_VERSION                             # an addition only
+    plan = pm.knn_sorted_plan
+    assert plan(8, 8192, 8) == (4, 8) and plan(32, 4096, 8) == (2, 8)          # the shipped batches: G 1024, 2048
+    assert plan(4, 4096, 12) == (8, 16) and plan(257, 50, 12) == (4, 16)       # G 256, 257
+    assert plan(20, 4096, 4) == (4, 4) and plan(21, 3904, 4) == (2, 4)         # G 1280, 1281
+    assert plan(64, 4096, 16) == (2, 16) and plan(241, 1088, 16) == (0, 16)    # G 4096, 4097
+    assert plan(1, 64, 3) == (8, 8)                                            # K <= 4 at S = 8: <8, 8> is what exists
+    assert plan(1, 64, 17) == (0, 32) and plan(1, 64, 33) == (0, 64) and plan(300, 1000, 64) == (0, 64)
+    assert plan(1, 64, 65) is None and plan(65536, 64, 8) is None and plan(0, 64, 8) is None and plan(1, 0, 8) is None
+    assert plan(65535, 64, 8) == (0, 8)
+
+
+def test_knn_bruteforce_plan_is_the_launchers_choice():
+    """dh3d_knn_bruteforce_plan (host only): the kernel dh3d_knn_bruteforce / _xyz run -- ("small", CPL, Q) a wave per query
+    up to 2048 points, ("lane", KMAX) a lane per query beyond, ("anydp", KMAX) for Dp != 3.  tests/test_knn_plan.py sweeps it."""
+    from dh3d_amd import _lib, pm
+    header = open(os.path.join(ROOT, "include", "dh3d_hip.h")).read()
+    assert re.search(r"\bint\s+dh3d_knn_bruteforce_plan\s*\(", header) and "dh3d_knn_bruteforce_plan" in _lib.EXPORTED_SYMBOLS
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "dh3d_knn_bruteforce_plan")
+    assert _lib.lib().dh3d_abi_version() == 4 == _lib.ABI_VERSION                             # an addition only
+    plan = pm.knn_plan
+    assert plan(8, 1024, 8) == ("small", 16, 2) and plan(32, 512, 8) == ("small", 8, 2)       # the model's sampled sets
+    assert plan(33, 512, 8) == ("small", 8, 4) and plan(9, 2048, 12) == ("small", 32, 4)
+    assert plan(1, 513, 8) == ("small", 16, 2) and plan(1, 1025, 8) == ("small", 32, 2)
+    assert plan(1, 2049, 4) == ("lane", 4) and plan(8, 8192, 8) == ("lane", 8) and plan(1, 3000, 33) == ("lane", 64)
+    assert plan(2, 300, 8, Dp=1) == ("anydp", 8) and plan(2, 300, 9, Dp=16) == ("anydp", 16)
+    assert plan(2, 300, 17, Dp=2) == ("anydp", 64)
+    assert plan(1, 64, 65) is None and plan(65536, 64, 8) is None and plan(1, 64, 8, Dp=17) is None
+    assert plan(0, 64, 8) is None and plan(1, 64, 8, Dp=0) is None
 
 
 def test_flex_conv_fwd_plan_is_the_dispatchers_choice():
