@@ -242,6 +242,8 @@ _SIGNATURES = {
                                 c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_ransac_rigid": [c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_int, c_int, c_int, c_double, c_double, c_int, c_u64,
                           c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
+    "dh3d_gnc_rigid": [c_fp, c_ll, c_fp, c_ll, c_fp, c_fp, c_int, c_int, c_int, c_double, c_double, c_int, c_int,
+                       c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],
     "dh3d_icp_plan": [c_int, c_int],
     "dh3d_icp_refine_ws_bytes": [c_int, c_int, c_int],
     "dh3d_icp_refine": [c_fp, c_ll, c_fp, c_fp, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_double, c_int, c_int, c_fp,

@@ -101,6 +101,60 @@ struct Corr {  // the compacted correspondences in LDS (f32, exact in f64)
   int *id;
 };
 
+// the seven arrays of Ma rows each in the kernel's dynamic LDS (corr_lds_bytes)
+__device__ __forceinline__ Corr corr_carve(float *s_dyn, int Ma) {
+  Corr s;
+  s.x0 = s_dyn;
+  s.x1 = s.x0 + Ma;
+  s.x2 = s.x1 + Ma;
+  s.y0 = s.x2 + Ma;
+  s.y1 = s.y0 + Ma;
+  s.y2 = s.y1 + Ma;
+  s.id = reinterpret_cast<int *>(s.y2 + Ma);
+  return s;
+}
+
+// The staging that ransac_kernel and gnc_kernel share, by a 256-lane workgroup: pair p's valid correspondences (i < a_count,
+// 0 <= match < Mb) compacted in anchor order into s, s.id their anchor rows; clears the pair's row of the inlier mask.
+// Returns their number n to every lane, behind a barrier.  s_wave: kRansacWaves ints.
+__device__ __forceinline__ int stage_corr(const Corr &s, int *s_wave, const float *__restrict__ axyz, long long a_stride, int Ma,
+                                          const int32_t *__restrict__ a_count, const float *__restrict__ bxyz,
+                                          long long b_stride, int Mb, const int32_t *__restrict__ match, int p,
+                                          uint8_t *__restrict__ inliers) {
+  const int tid = threadIdx.x, w = tid >> 6;
+  const int na = clamp_count(a_count[p], Ma);
+  int n = 0;
+  for (int base = 0; base < Ma; base += kRansacThreads) {
+    const int i = base + tid;
+    int m = -1;
+    if (i < Ma) {
+      inliers[(long long)p * Ma + i] = 0;
+      if (i < na) m = match[(long long)p * Ma + i];
+    }
+    const bool ok = m >= 0 && m < Mb;
+    const unsigned long long bal = __ballot(ok);
+    if ((tid & 63) == 0) s_wave[w] = __popcll(bal);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int q = 0; q < kRansacWaves; ++q) {
+      const int v = s_wave[q];
+      off += q < w ? v : 0;
+      tot += v;
+    }
+    if (ok) {
+      const int slot = n + off + __popcll(bal & lanes_below());
+      const float *xa = axyz + ((long long)p * Ma + i) * a_stride;
+      const float *xb = bxyz + ((long long)p * Mb + m) * b_stride;
+      s.x0[slot] = xa[0]; s.x1[slot] = xa[1]; s.x2[slot] = xa[2];
+      s.y0[slot] = xb[0]; s.y1[slot] = xb[1]; s.y2[slot] = xb[2];
+      s.id[slot] = i;
+    }
+    n += tot;
+    __syncthreads();
+  }
+  return n;
+}
+
 // the model of the sample (j0, j1, j2): centroid = (sum in sample order) / 3, B over the centred points in sample order
 __device__ void fit3(const Corr &s, int j0, int j1, int j2, double *R, double *t) {
   const int js[3] = {j0, j1, j2};
@@ -145,47 +199,11 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_kernel(
   __shared__ int s_cnt[kRansacThreads];
   __shared__ int s_done, s_win, s_kstar;
   __shared__ double s_red[10 * kRansacWaves];  // block_rigid_fit_256
-  const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
-  Corr s;
-  s.x0 = s_dyn;
-  s.x1 = s.x0 + Ma;
-  s.x2 = s.x1 + Ma;
-  s.y0 = s.x2 + Ma;
-  s.y1 = s.y0 + Ma;
-  s.y2 = s.y1 + Ma;
-  s.id = reinterpret_cast<int *>(s.y2 + Ma);
+  const int p = blockIdx.x, tid = threadIdx.x;
+  Corr s = corr_carve(s_dyn, Ma);
 
   // (1) compact the valid correspondences (i < a_count, 0 <= match < Mb) in anchor order; clear the mask row
-  const int na = clamp_count(a_count[p], Ma);
-  int n = 0;
-  for (int base = 0; base < Ma; base += kRansacThreads) {
-    const int i = base + tid;
-    int m = -1;
-    if (i < Ma) {
-      inliers[(long long)p * Ma + i] = 0;
-      if (i < na) m = match[(long long)p * Ma + i];
-    }
-    const bool ok = m >= 0 && m < Mb;
-    const unsigned long long bal = __ballot(ok);
-    if ((tid & 63) == 0) s_wave[w] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int q = 0; q < kRansacWaves; ++q) {
-      const int v = s_wave[q];
-      off += q < w ? v : 0;
-      tot += v;
-    }
-    if (ok) {
-      const int slot = n + off + __popcll(bal & lanes_below());
-      const float *xa = axyz + ((long long)p * Ma + i) * a_stride;
-      const float *xb = bxyz + ((long long)p * Mb + m) * b_stride;
-      s.x0[slot] = xa[0]; s.x1[slot] = xa[1]; s.x2[slot] = xa[2];
-      s.y0[slot] = xb[0]; s.y1[slot] = xb[1]; s.y2[slot] = xb[2];
-      s.id[slot] = i;
-    }
-    n += tot;
-    __syncthreads();
-  }
+  const int n = stage_corr(s, s_wave, axyz, a_stride, Ma, a_count, bxyz, b_stride, Mb, match, p, inliers);
   if (tid == 0 && num_corr) num_corr[p] = n;
   double *rt = Rt + (long long)p * 12;
   if (n < 3) {  // ransacfitRt.m: no model
@@ -281,7 +299,145 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_kernel(
   }, s_red, rt);
 }
 
-size_t ransac_lds_bytes(int Ma) { return (size_t)Ma * (6 * sizeof(float) + sizeof(int)); }
+// ------------------------------------------------------------------------------------------------------------- GNC
+
+constexpr int kGncMaxIter = 1024;
+
+// The weights a fit uses are not stored: they are a function of the fit before it (R, t) and of that fit's mu, and both
+// passes of block_weighted_rigid_fit_256 recompute them.  unit: the first fit, every w = 1.
+struct GncWeights {
+  double R[9], t[3], mu;
+  bool unit;
+};
+
+// the centred pair j (X = x - xc, Y = y - yc) and its weight (mu / (|X - (R Y + t)|^2 + mu))^2
+__device__ __forceinline__ double gnc_pair(const Corr &s, int j, const double *xc, const double *yc, const GncWeights &g,
+                                           double *X, double *Y) {
+  X[0] = (double)s.x0[j] - xc[0]; X[1] = (double)s.x1[j] - xc[1]; X[2] = (double)s.x2[j] - xc[2];
+  Y[0] = (double)s.y0[j] - yc[0]; Y[1] = (double)s.y1[j] - yc[1]; Y[2] = (double)s.y2[j] - yc[2];
+  if (g.unit) return 1.0;
+  const double e0 = X[0] - ((g.R[0] * Y[0] + g.R[1] * Y[1] + g.R[2] * Y[2]) + g.t[0]);
+  const double e1 = X[1] - ((g.R[3] * Y[0] + g.R[4] * Y[1] + g.R[5] * Y[2]) + g.t[1]);
+  const double e2 = X[2] - ((g.R[6] * Y[0] + g.R[7] * Y[1] + g.R[8] * Y[2]) + g.t[2]);
+  const double q = g.mu / ((e0 * e0 + e1 * e1 + e2 * e2) + g.mu);
+  return q * q;
+}
+
+// One 256-lane workgroup per pair, the whole schedule in one launch (include/dh3d_hip.h dh3d_gnc_rigid states the rule):
+// stage the correspondences as RANSAC does, centre them, then per fit two block reductions (the weighted centroids, then B)
+// with lane 0's 4 x 4 Jacobi behind them.  Every decision of the loop is taken by every lane on the same float64 values.
+__global__ __launch_bounds__(kRansacThreads) void gnc_kernel(
+    const float *__restrict__ axyz, long long a_stride, int Ma, const int32_t *__restrict__ a_count,
+    const float *__restrict__ bxyz, long long b_stride, int Mb, const int32_t *__restrict__ match, double thr, double division,
+    int settle, int max_iter, double *__restrict__ Rt, double *__restrict__ weights, int32_t *__restrict__ valid,
+    uint8_t *__restrict__ inliers, int32_t *__restrict__ num_inliers, int32_t *__restrict__ num_corr,
+    int32_t *__restrict__ iterations) {
+  extern __shared__ float s_dyn[];
+  __shared__ int s_wave[kRansacWaves];
+  __shared__ double s_red[10 * kRansacWaves];  // block_weighted_rigid_fit_256
+  __shared__ double s_pose[12];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  Corr s = corr_carve(s_dyn, Ma);
+  for (int i = tid; i < Ma; i += kRansacThreads) weights[(long long)p * Ma + i] = 0.0;  // (rows that are no correspondence)
+  const int n = stage_corr(s, s_wave, axyz, a_stride, Ma, a_count, bxyz, b_stride, Mb, match, p, inliers);
+  double *rt = Rt + (long long)p * 12;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  if (n < 3) {  // no model
+    if (tid < 12) rt[tid] = nan;
+    if (tid == 0) {
+      valid[p] = 0;
+      num_inliers[p] = 0;
+      num_corr[p] = n;
+      iterations[p] = 0;
+    }
+    return;
+  }
+
+  // the centroids, and D2 = the largest squared norm of a centred point (a NaN term is skipped: v > D2 is false)
+  double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = tid; j < n; j += kRansacThreads) {
+    c[0] += s.x0[j]; c[1] += s.x1[j]; c[2] += s.x2[j];
+    c[3] += s.y0[j]; c[4] += s.y1[j]; c[5] += s.y2[j];
+  }
+  block_sums_256<6>(c, s_red);
+  const double xc[3] = {c[0] / (double)n, c[1] / (double)n, c[2] / (double)n};
+  const double yc[3] = {c[3] / (double)n, c[4] / (double)n, c[5] / (double)n};
+  GncWeights g;
+  g.unit = true;
+  g.mu = 0.0;
+  for (int e = 0; e < 9; ++e) g.R[e] = 0.0;
+  for (int e = 0; e < 3; ++e) g.t[e] = 0.0;
+  double D2 = 0.0;
+  for (int j = tid; j < n; j += kRansacThreads) {
+    double X[3], Y[3];
+    gnc_pair(s, j, xc, yc, g, X, Y);
+    const double vx = X[0] * X[0] + X[1] * X[1] + X[2] * X[2], vy = Y[0] * Y[0] + Y[1] * Y[1] + Y[2] * Y[2];
+    if (vx > D2) D2 = vx;
+    if (vy > D2) D2 = vy;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_xor(D2, off, 64);
+    if (o > D2) D2 = o;
+  }
+  __syncthreads();  // (s_red: the centroid sums have been read)
+  if ((tid & 63) == 0) s_red[tid >> 6] = D2;
+  __syncthreads();
+  for (int q = 0; q < kRansacWaves; ++q) D2 = s_red[q] > D2 ? s_red[q] : D2;  // (a maximum: the same bits in any order)
+
+  const double d2 = thr * thr;
+  double mu = D2 > d2 ? D2 : d2;
+  double R[9], t[3];
+  int k = 0, at = 0;
+  for (;;) {
+    block_weighted_rigid_fit_256(n, [&](int j, double *X, double *Y) { return gnc_pair(s, j, xc, yc, g, X, Y); }, s_red,
+                                 s_pose);
+    for (int e = 0; e < 9; ++e) R[e] = s_pose[e];
+    for (int e = 0; e < 3; ++e) t[e] = s_pose[9 + e];
+    ++k;
+    if (mu == d2) ++at;
+    if (at > settle || k >= max_iter) break;
+    for (int e = 0; e < 9; ++e) g.R[e] = R[e];
+    for (int e = 0; e < 3; ++e) g.t[e] = t[e];
+    g.mu = mu;
+    g.unit = false;
+    mu = mu / division;
+    mu = mu > d2 ? mu : d2;
+  }
+
+  // the pose in the clouds' own coordinates, the weights of the last fit, the inlier mask of the pose
+  double tf[3];
+  translation(R, xc, yc, tf);
+  bool finite = true;
+  for (int e = 0; e < 3; ++e) {
+    tf[e] = tf[e] + t[e];
+    finite = finite && isfinite(tf[e]);
+  }
+  for (int e = 0; e < 9; ++e) finite = finite && isfinite(R[e]);
+  int cnt = 0;
+  for (int j = tid; j < n; j += kRansacThreads) {
+    double X[3], Y[3];
+    weights[(long long)p * Ma + s.id[j]] = gnc_pair(s, j, xc, yc, g, X, Y);
+    if (is_inlier(s, j, R, tf, thr)) {
+      inliers[(long long)p * Ma + s.id[j]] = 1;
+      ++cnt;
+    }
+  }
+  const int count = (int)block_sum_256<double>((double)cnt, s_red);
+  const bool ok = finite && count >= 3;
+  if (tid == 0) {
+    num_inliers[p] = count;
+    num_corr[p] = n;
+    iterations[p] = k;
+    valid[p] = ok;
+    for (int r = 0; r < 3; ++r) {
+      for (int q = 0; q < 3; ++q) rt[4 * r + q] = ok ? R[3 * r + q] : nan;
+      rt[4 * r + 3] = ok ? tf[r] : nan;
+    }
+  }
+}
+
+size_t corr_lds_bytes(int Ma) { return (size_t)Ma * (6 * sizeof(float) + sizeof(int)); }
 
 }  // namespace
 
@@ -312,11 +468,34 @@ DH3D_API int dh3d_ransac_rigid(const float *anchor_xyz, long long anchor_stride,
   static bool lds_cap_set = false;
   if (!lds_cap_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ransac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)ransac_lds_bytes(kMaxKp));
+                              (int)corr_lds_bytes(kMaxKp));
     lds_cap_set = true;
   }
-  hipLaunchKernelGGL(ransac_kernel, dim3(P), dim3(kRansacThreads), ransac_lds_bytes(Ma), (hipStream_t)stream, anchor_xyz,
+  hipLaunchKernelGGL(ransac_kernel, dim3(P), dim3(kRansacThreads), corr_lds_bytes(Ma), (hipStream_t)stream, anchor_xyz,
                      anchor_stride, Ma, anchor_count, positive_xyz, positive_stride, Mb, match, threshold, confidence,
                      max_trials, seed, Rt, valid, inliers, num_inliers, trials, num_corr);
+  return dh3d_launch_status();
+}
+
+DH3D_API int dh3d_gnc_rigid(const float *anchor_xyz, long long anchor_stride, const float *positive_xyz,
+                            long long positive_stride, const int32_t *match, const int32_t *anchor_count, int P, int Ma, int Mb,
+                            double threshold, double division, int settle, int max_iterations, double *Rt, double *weights,
+                            int32_t *valid, uint8_t *inliers, int32_t *num_inliers, int32_t *num_corr, int32_t *iterations,
+                            void *stream) {
+  DH3D_REQUIRE(anchor_xyz && positive_xyz && match && anchor_count && Rt && weights && valid && inliers && num_inliers &&
+               num_corr && iterations);
+  DH3D_REQUIRE(P > 0 && Ma > 0 && Mb > 0 && anchor_stride >= 3 && positive_stride >= 3);
+  DH3D_REQUIRE(threshold > 0.0 && division > 1.0 && settle >= 0 && max_iterations >= 1 && max_iterations <= kGncMaxIter);
+  DH3D_SUPPORTED(Ma <= kMaxKp && Mb <= kMaxKp && P <= 65535);
+  // the dynamic-LDS cap as dh3d_ransac_rigid sets it (and not DH3D_ALLOW_BIG_LDS, for the reason given there)
+  static bool lds_cap_set = false;
+  if (!lds_cap_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gnc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)corr_lds_bytes(kMaxKp));
+    lds_cap_set = true;
+  }
+  hipLaunchKernelGGL(gnc_kernel, dim3(P), dim3(kRansacThreads), corr_lds_bytes(Ma), (hipStream_t)stream, anchor_xyz,
+                     anchor_stride, Ma, anchor_count, positive_xyz, positive_stride, Mb, match, threshold, division, settle,
+                     max_iterations, Rt, weights, valid, inliers, num_inliers, num_corr, iterations);
   return dh3d_launch_status();
 }

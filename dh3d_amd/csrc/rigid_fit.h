@@ -212,4 +212,43 @@ __device__ __forceinline__ int block_rigid_fit_256(int slots, Pair pair, double 
   return n;
 }
 
+// The weighted fit of a 256-lane workgroup over `slots` pairs (the fit of every graduated non-convexity iteration,
+// include/dh3d_hip.h dh3d_gnc_rigid): pair(j, X, Y) fills slot j's anchor X[3] and positive Y[3] in float64 and returns the
+// pair's weight w.  W = sum w, cx = (sum w X) / W, cy = (sum w Y) / W, B = sum of w * (the pair's accumulate_b term on
+// (X - cx, Y - cy)), R = rotation_from_b(B), t = cx - R cy.  Each lane sums its slots j = lane, lane + 256, ... in order,
+// then block_sums_256's fixed tree; pair is called twice per slot (nothing is kept between the two passes).  Lane 0 solves
+// and leaves R (row-major, 9) and t (3) in s_pose; every lane may read them on return (a barrier stands before it).
+// s_red: 40 doubles, s_pose: 12 doubles; both may be used again right away.
+template <typename Pair>
+__device__ __forceinline__ void block_weighted_rigid_fit_256(int slots, Pair pair, double *s_red, double *s_pose) {
+  double X[3], Y[3];
+  double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // W, the weighted anchors, the weighted positives
+  for (int j = threadIdx.x; j < slots; j += 256) {
+    const double w = pair(j, X, Y);
+    s[0] += w;
+    s[1] += w * X[0]; s[2] += w * X[1]; s[3] += w * X[2];
+    s[4] += w * Y[0]; s[5] += w * Y[1]; s[6] += w * Y[2];
+  }
+  block_sums_256<7>(s, s_red);
+  const double cx[3] = {s[1] / s[0], s[2] / s[0], s[3] / s[0]};
+  const double cy[3] = {s[4] / s[0], s[5] / s[0], s[6] / s[0]};
+  double B[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = threadIdx.x; j < slots; j += 256) {
+    const double w = pair(j, X, Y);
+    double T[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    accumulate_b(T, X[0] - cx[0], X[1] - cx[1], X[2] - cx[2], Y[0] - cy[0], Y[1] - cy[1], Y[2] - cy[2]);
+#pragma unroll
+    for (int e = 0; e < 10; ++e) B[e] += w * T[e];
+  }
+  block_sums_256<10>(B, s_red);
+  if (threadIdx.x == 0) {
+    double Rf[9], tf[3];
+    rotation_from_b(B, Rf);
+    translation(Rf, cx, cy, tf);
+    for (int e = 0; e < 9; ++e) s_pose[e] = Rf[e];
+    for (int e = 0; e < 3; ++e) s_pose[9 + e] = tf[e];
+  }
+  __syncthreads();
+}
+
 }  // namespace

@@ -5,12 +5,20 @@ The reference does this step in MATLAB, one pair at a time (evaluate/local_eval/
 eval_align.m): pdist2(pos_desc, anc_desc, 'smallest', 1), ransacfitRt with a 1.0 m threshold, then compareTransform /
 GetEulerAngles and a success / inlier-ratio / trial / RTE / RRE summary.  Here a batch of pairs stays on the GPU until a
 [P, 3, 4] pose and a few counts per pair come out; include/dh3d_hip.h dh3d_ransac_rigid states every rule (the splitmix64
-sampler replaces randsample, whose stream cannot be reproduced).
+sampler replaces randsample, whose stream cannot be reproduced).  Beside RANSAC stands a deterministic estimator on the same
+correspondences, gnc_rigid (dh3d_gnc_rigid: graduated non-convexity on the Geman-McClure objective by re-weighted float64
+fits): no seed, and a fit count that depends on the extent of the correspondences and the threshold, not on the inlier
+share (the time follows it within a few per cent: the eigen-solve of a fit sweeps until it has converged).  It is a local
+method with a good track record, not a guarantee.  estimator="gnc" selects it in register, register_clouds and
+register_fpfh (and through their keywords in PlaceIndex.localize and relocalize_clouds); the default stays "ransac".
+relocalize_scan_context has no keypoint fit to select: its pose comes from the Scan Context yaw and ICP.
 
     match, dist = match_descriptors(anchor_desc, anchor_count, positive_desc, positive_count)
     m2 = match_descriptors2(anchor_desc, anchor_count, positive_desc, positive_count, ratio=0.9, mutual=True)  # nn1, nn2, match, ...
     res = register(anchor_rows, anchor_count, positive_rows, positive_count, match={"ratio": 0.9, "mutual": True})
     res = ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count)       # Rt, valid, inliers, ... (no host sync)
+    res = gnc_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=0.5)  # the same keys + weights, iterations
+    res = register(anchor_rows, anchor_count, positive_rows, positive_count, estimator="gnc", threshold=0.5)
     res = register(anchor_rows, anchor_count, positive_rows, positive_count)  # rows as xyz_feat_att_nms / _nms_res.bin
     res = register_clouds(model, anchor_points, positive_points)              # forward (config.detection) + register
     res = refine_icp(anchor_points, positive_points, res["Rt"], res["valid"])  # dense ICP: Rt, fitness, rmse, nn, ...
@@ -124,13 +132,8 @@ def match_descriptors2(anchor_desc, anchor_count, positive_desc, positive_count,
     return out
 
 
-def ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=1.0, confidence=0.99, max_trials=10000, seed=0):
-    """ransacfitRt on every pair: correspondences anchor_xyz[p, i] <-> positive_xyz[p, match[p, i]] for i < anchor_count[p]
-    with 0 <= match < Mb; the model maps positive into anchor coordinates (anchor ~ R positive + t).  anchor_xyz [P, Ma, >=3]
-    and positive_xyz [P, Mb, >=3] float32 (the first three columns are read; keypoint rows are read in place).  Returns a
-    dict of device tensors: Rt [P, 3, 4] float64 (NaN where not valid), valid [P] bool, inliers [P, Ma] bool (the winning
-    hypothesis' mask), num_inliers [P] int32, inlier_ratio [P] float64 (num_inliers / n, 0 when n = 0), trials [P] int32,
-    num_corr [P] int32 (n).  No host sync: graph-capturable."""
+def _corr_inputs(anchor_xyz, positive_xyz, match, anchor_count):
+    """The checked inputs of ransac_rigid / gnc_rigid and their shape: ax, bx, m, ac, P, Ma, Mb."""
     ax = _rows(anchor_xyz, "anchor_xyz", 3)
     bx = _rows(positive_xyz, "positive_xyz", 3)
     P, Ma = ax.shape[:2]
@@ -143,6 +146,17 @@ def ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=1.0, c
     if tuple(m.shape) != (P, Ma) or m.device != ax.device:
         raise ValueError("match must be int32 [%d, %d] on %s, got %s" % (P, Ma, ax.device, tuple(m.shape)))
     ac = _count(anchor_count, "anchor_count", P, ax.device)
+    return ax, bx, m, ac, P, Ma, Mb
+
+
+def ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=1.0, confidence=0.99, max_trials=10000, seed=0):
+    """ransacfitRt on every pair: correspondences anchor_xyz[p, i] <-> positive_xyz[p, match[p, i]] for i < anchor_count[p]
+    with 0 <= match < Mb; the model maps positive into anchor coordinates (anchor ~ R positive + t).  anchor_xyz [P, Ma, >=3]
+    and positive_xyz [P, Mb, >=3] float32 (the first three columns are read; keypoint rows are read in place).  Returns a
+    dict of device tensors: Rt [P, 3, 4] float64 (NaN where not valid), valid [P] bool, inliers [P, Ma] bool (the winning
+    hypothesis' mask), num_inliers [P] int32, inlier_ratio [P] float64 (num_inliers / n, 0 when n = 0), trials [P] int32,
+    num_corr [P] int32 (n).  No host sync: graph-capturable."""
+    ax, bx, m, ac, P, Ma, Mb = _corr_inputs(anchor_xyz, positive_xyz, match, anchor_count)
     threshold, confidence, max_trials, seed = float(threshold), float(confidence), int(max_trials), int(seed)
     if not threshold > 0.0 or not 0.0 < confidence < 1.0 or not 0 <= max_trials < (1 << 30):
         raise ValueError("need threshold > 0, 0 < confidence < 1 and 0 <= max_trials < 2^30, got %r, %r, %r"
@@ -164,6 +178,64 @@ def ransac_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=1.0, c
                 num_corr=num_corr)
 
 
+GNC_MAX_ITERATIONS = 1024  # csrc/registration.hip kGncMaxIter
+
+
+def gnc_rigid(anchor_xyz, positive_xyz, match, anchor_count, threshold=1.0, division=1.4, settle=8, max_iterations=64):
+    """A deterministic robust fit of every pair, beside ransac_rigid and on its inputs: graduated non-convexity on the
+    Geman-McClure objective (Fast Global Registration's, solved by re-weighted closed-form float64 fits; include/dh3d_hip.h
+    dh3d_gnc_rigid states every rule).  No sampling and no seed; the number of fits depends only on the extent of the
+    correspondences and the threshold, not on the inlier share (RANSAC's trial count, and with it its time, does).  It is a local method with a
+    good track record, not a guarantee: from the least-squares start it can settle on a wrong pose when outliers dominate.
+    threshold: the residual scale the weights end at, and the inlier distance (ransac_rigid's meaning and default);
+    division > 1: the factor mu shrinks by per fit; settle >= 0: further fits once mu has reached threshold^2;
+    1 <= max_iterations <= 1024 ends the schedule early (1: the plain least-squares fit).  Returns ransac_rigid's keys --
+    Rt [P, 3, 4] float64 (NaN where not valid), valid [P] bool, inliers [P, Ma] bool (residual < threshold under Rt),
+    num_inliers, inlier_ratio, num_corr -- plus weights [P, Ma] float64 (the weights of the last fit in anchor row order, 0
+    for rows that are no correspondence) and iterations [P] int32 (the fits run).  trials is the same tensor as iterations:
+    summarize_registration(..., res["trials"]) and other callers read a count of model fits from either estimator.  No
+    host sync, no workspace: graph-capturable."""
+    ax, bx, m, ac, P, Ma, Mb = _corr_inputs(anchor_xyz, positive_xyz, match, anchor_count)
+    threshold, division, settle, max_iterations = float(threshold), float(division), int(settle), int(max_iterations)
+    if not threshold > 0.0 or not division > 1.0 or settle < 0 or not 1 <= max_iterations <= GNC_MAX_ITERATIONS:
+        raise ValueError("need threshold > 0, division > 1, settle >= 0 and 1 <= max_iterations <= %d, got %r, %r, %r, %r"
+                         % (GNC_MAX_ITERATIONS, threshold, division, settle, max_iterations))
+    dev = ax.device
+    Rt = torch.empty((P, 3, 4), dtype=torch.float64, device=dev)
+    weights = torch.empty((P, Ma), dtype=torch.float64, device=dev)
+    valid = torch.empty((P,), dtype=torch.int32, device=dev)
+    inliers = torch.empty((P, Ma), dtype=torch.bool, device=dev)
+    num_inliers = torch.empty((P,), dtype=torch.int32, device=dev)
+    num_corr = torch.empty((P,), dtype=torch.int32, device=dev)
+    iterations = torch.empty((P,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().dh3d_gnc_rigid(L.ptr(ax), ax.stride(1), L.ptr(bx), bx.stride(1), L.ptr(m), L.ptr(ac), P, Ma, Mb,
+                                       threshold, division, settle, max_iterations, L.ptr(Rt), L.ptr(weights), L.ptr(valid),
+                                       L.ptr(inliers), L.ptr(num_inliers), L.ptr(num_corr), L.ptr(iterations), L.stream_ptr()),
+                "gnc_rigid")
+        ratio = num_inliers.to(torch.float64) / num_corr.clamp(min=1).to(torch.float64)
+        return dict(Rt=Rt, valid=valid.bool(), inliers=inliers, num_inliers=num_inliers, inlier_ratio=ratio, trials=iterations,
+                    num_corr=num_corr, weights=weights, iterations=iterations)
+
+
+_ESTIMATORS = {"ransac": (ransac_rigid, ("threshold", "confidence", "max_trials", "seed")),
+               "gnc": (gnc_rigid, ("threshold", "division", "settle", "max_iterations"))}
+
+
+def _estimator(fit_kw):
+    """The estimator of register / register_fpfh / register_clouds out of their keywords: pops estimator= ("ransac", the
+    default, or "gnc") and returns (the fit, the remaining keywords), which must be that estimator's own."""
+    kw = dict(fit_kw)
+    name = kw.pop("estimator", "ransac")
+    if name not in _ESTIMATORS:
+        raise ValueError('estimator must be "ransac" or "gnc", got %r' % (name,))
+    fn, names = _ESTIMATORS[name]
+    bad = sorted(set(kw) - set(names))
+    if bad:
+        raise ValueError('estimator="%s" takes the keywords %s, got %s' % (name, ", ".join(names), ", ".join(bad)))
+    return fn, kw
+
+
 def _match_options(match):
     """register's / register_fpfh's match=: None (dh3d_match_descriptors) or a dict of match_descriptors2's ratio / mutual."""
     if match is None:
@@ -175,7 +247,9 @@ def _match_options(match):
 
 def _match_and_fit(desc_a, anchor_count, desc_b, positive_count, xyz_a, xyz_b, match, ransac_kw):
     """Descriptors to poses: match_descriptors (match None) or match_descriptors2 (a dict of its options, whose outputs join
-    the result), then ransac_rigid on the ids."""
+    the result), then on the ids the estimator that ransac_kw names (estimator="ransac", the default: ransac_rigid;
+    "gnc": gnc_rigid) with the rest of ransac_kw, which must be that estimator's keywords."""
+    fit, fit_kw = _estimator(ransac_kw)
     opts = _match_options(match)
     if opts is None:
         ids, dist = match_descriptors(desc_a, anchor_count, desc_b, positive_count)
@@ -183,7 +257,7 @@ def _match_and_fit(desc_a, anchor_count, desc_b, positive_count, xyz_a, xyz_b, m
     else:
         more = match_descriptors2(desc_a, anchor_count, desc_b, positive_count, **opts)
         ids, dist = more["match"], more["dist1"]
-    out = ransac_rigid(xyz_a, xyz_b, ids, anchor_count, **ransac_kw)
+    out = fit(xyz_a, xyz_b, ids, anchor_count, **fit_kw)
     out.update(more)
     out["match"], out["dist"] = ids, dist
     return out
@@ -194,9 +268,12 @@ def register(anchor_rows, anchor_count, positive_rows, positive_count, desc_dim=
     _nms_res.bin (utils.load_descriptor_bin) give them -- [x, y, z, descriptor(, score)] -- with counts [P] int32.  Matches
     every anchor keypoint to its nearest positive descriptor, then ransac_rigid (keyword arguments threshold, confidence,
     max_trials, seed).  Returns ransac_rigid's dict plus match / dist; everything stays on the device, no host sync.
+    estimator="gnc" (default "ransac") fits with gnc_rigid instead: the keywords are then its threshold, division, settle,
+    max_iterations, and the result gains weights / iterations; a keyword of the other estimator is a ValueError.
     match: None, or a dict of match_descriptors2's options, e.g. {"ratio": 0.9, "mutual": True} ({}: that entry, no
     filter): RANSAC then sees only the kept rows, match is the filtered list, dist is dist1 (of every row, kept or not) and
     match_descriptors2's other outputs (nn1, nn2, dist1, dist2, num_kept, with mutual rev / rev_dist) join the result."""
+    _estimator(ransac_kw)  # (a wrong estimator or keyword is refused before anything is launched)
     a = _rows(anchor_rows, "anchor_rows", 3 + int(desc_dim))
     b = _rows(positive_rows, "positive_rows", 3 + int(desc_dim))
     return _match_and_fit(a[:, :, 3:3 + desc_dim], anchor_count, b[:, :, 3:3 + desc_dim], positive_count, a, b, match, ransac_kw)
@@ -585,8 +662,8 @@ def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None
                   refine=None, **ransac_kw):
     """Registration of cloud pairs from geometry alone, no model and no weights: compute_fpfh on both batches (normals by
     estimate_normals at k = 16, the k nearest neighbours of utils.batched_knn, max_dist as compute_fpfh's), match_descriptors
-    on the 36-column rows of the keypoints, ransac_rigid (its keywords threshold, confidence, max_trials, seed), and
-    refine_pose exactly as register_clouds wires it.  anchor_points [P, Na, >=3] and positive_points [P, Nb, >=3] float32 on
+    on the 36-column rows of the keypoints, ransac_rigid (its keywords threshold, confidence, max_trials, seed; or with
+    estimator="gnc" gnc_rigid and its keywords, as register takes them), and refine_pose exactly as register_clouds wires it.  anchor_points [P, Na, >=3] and positive_points [P, Nb, >=3] float32 on
     the GPU.  num_valid: None, one int32 [P] tensor for both batches, or a pair (anchor, positive).  The keypoints of a cloud:
     every point when it has at most 4096 rows and nothing is asked; otherwise `keypoints` = M (default 4096) of them spread
     over the valid rows, ids[p, r] = (r * n_p) // M, computed on the device; or the caller's keypoint_ids -- one int32 [P, M]
@@ -601,6 +678,7 @@ def register_fpfh(anchor_points, positive_points, num_valid=None, keypoints=None
     keypoint ids, None: all points).  No host sync."""
     rkw = _refine_kw(refine)
     match = ransac_kw.pop("match", None)
+    _estimator(ransac_kw)  # (a wrong estimator or keyword is refused before normals and FPFH are launched)
     pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
     nv, kp, kid = pair(num_valid), pair(keypoints), pair(keypoint_ids)
     rows, cnts, idl = [], [], []
@@ -667,10 +745,11 @@ def register_clouds(model, anchor_points, positive_points, num_valid=None, refin
     num_corr_icp and nn; valid stays the RANSAC fit's.  A dict with method="plane" (and refine_icp_plane's keywords) refines
     point-to-plane instead and adds num_plane and rmse_plane; method="gicp" (and refine_icp_gicp's keywords) refines by
     generalized ICP and adds num_planar and rmse_gicp.  Other keywords go to register: desc_dim, match={"ratio": ...,
-    "mutual": ...} and ransac_rigid's."""
+    "mutual": ...}, estimator= and that estimator's (ransac_rigid's by default)."""
     if not getattr(model.config, "detection", False):
         raise ValueError("register_clouds needs a model with config.detection (the keypoint outputs)")
     rkw = _refine_kw(refine)
+    _estimator({k: v for k, v in kw.items() if k not in ("desc_dim", "match")})  # (refused before the forwards run)
     nv_a, nv_b = num_valid if isinstance(num_valid, (tuple, list)) else (num_valid, num_valid)
     fetch = ("kp_count", "xyz_feat_att_nms")
     oa = model.forward(anchor_points, fetch=fetch, num_valid=nv_a)

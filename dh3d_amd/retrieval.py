@@ -196,7 +196,8 @@ class PlaceIndex:
         the winner's normals are computed per call) and adds rmse_plane; method="gicp" refines by generalized ICP
         (registration.refine_icp_gicp's keywords; both clouds' normals are computed per call) and adds rmse_gicp.  Needs an index built with points > 0 (else
         ValueError).  Other keywords go to registration.register: ransac_rigid's, and match={"ratio": ..., "mutual": ...} (the
-        ratio test and the mutual check ahead of RANSAC).  No host sync."""
+        ratio test and the mutual check ahead of RANSAC); estimator="gnc" and gnc_rigid's keywords fit every candidate with
+        the deterministic estimator instead.  No host sync."""
         if not self.keypoints:
             raise ValueError("localize needs a PlaceIndex built with keypoints > 0")
         rkw = registration._refine_kw(refine)

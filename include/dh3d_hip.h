@@ -1007,6 +1007,43 @@ int dh3d_ransac_rigid(const float *anchor_xyz, long long anchor_stride, const fl
                       const int32_t *match, const int32_t *anchor_count, int P, int Ma, int Mb, double threshold,
                       double confidence, int max_trials, unsigned long long seed, double *Rt, int32_t *valid,
                       uint8_t *inliers, int32_t *num_inliers, int32_t *trials, int32_t *num_corr, void *stream);
+/* Graduated non-convexity (GNC) rigid registration of P cloud pairs: the Geman-McClure objective of Fast Global
+ * Registration (Zhou, Park & Koltun, ECCV 2016) solved by iteratively re-weighted closed-form fits (Yang, Antonante,
+ * Tzoumas & Carlone, RA-L 2020, GNC-GM); csrc/registration.hip gnc_kernel.  A deterministic estimator beside
+ * dh3d_ransac_rigid: no sampling, no seed, and a fit count that depends only on the cloud's extent and the threshold.  It is
+ * a local method with a good record, not a guarantee.  One workgroup per pair, one launch, no workspace, no host sync, no
+ * atomics: graph-capturable.  Inputs, strides, the correspondences (anchors i < clamp(anchor_count[p], 0, Ma) with
+ * 0 <= match[p, i] < Mb, compacted in ascending i, n of them) and the model's direction (x ~ R y + t, x anchor, y positive)
+ * are dh3d_ransac_rigid's.  Everything below is float64 on the exact float64 values of the float32 inputs.
+ *   n < 3: no model (Rt NaN, valid 0, num_inliers 0, iterations 0, weights 0).
+ *   xc = (sum x) / n, yc = (sum y) / n;  X = x - xc, Y = y - yc
+ *   D2 = max over j of max(|X_j|^2, |Y_j|^2), taken as D2 = 0 then D2 = v where v > D2 (a NaN term is skipped);
+ *   d2 = threshold * threshold;  mu = D2 > d2 ? D2 : d2
+ *   w_j = 1;  at = 0;  k = 0
+ *   loop:
+ *       (R, t) = weighted_fit(w);  k += 1
+ *       if mu == d2: at += 1
+ *       if at > settle or k >= max_iterations: break
+ *       r_j = X_j - ((R Y_j) + t);  w_j = (mu / (|r_j|^2 + mu))^2
+ *       mu = mu / division;  mu = mu > d2 ? mu : d2
+ *   Rt = [R | (xc - R yc) + t]
+ *   weighted_fit: W = sum w, cx = (sum w X) / W, cy = (sum w Y) / W, B = sum over j of w_j * (A^T A of the pair
+ *     (X_j - cx, Y_j - cy), dh3d_ransac_rigid's A), R = quat2rot(the unit eigenvector of B's smallest eigenvalue, cyclic
+ *     Jacobi), t = cx - R cy.  Sums: each of the 256 lanes over its j = lane, lane + 256, ... in order, then a fixed tree.
+ * So the schedule runs m + settle + 1 fits, m the number of divisions that bring D2 down to d2 (0 when D2 <= d2), unless
+ * max_iterations ends it first; max_iterations = 1 is the plain least-squares fit.  The weights are never stored: w of fit
+ * k + 1 is recomputed from the pose of fit k and that fit's mu.
+ * Outputs, every element written: Rt [P, 3, 4] float64 (NaN where valid is 0); weights [P, Ma] float64 (the w the last fit
+ * used, at the anchor rows of the correspondences, 0 at every other row); inliers [P, Ma] uint8 (1 where
+ * sqrt(|x - (R y + t)|^2) < threshold under Rt, dh3d_ransac_rigid's inlier expression); num_inliers [P]; num_corr [P] = n;
+ * iterations [P] = k; valid [P] = n >= 3 and every entry of the pose finite and num_inliers >= 3.
+ * NULL pointers, P / Ma / Mb <= 0, a stride below 3, threshold <= 0, division <= 1, settle < 0, max_iterations outside
+ * 1 .. 1024 (NaN scalars included): DH3D_ERR_INVALID_ARGUMENT, checked first; then Ma or Mb > 4096 or P > 65535:
+ * DH3D_ERR_UNSUPPORTED. */
+int dh3d_gnc_rigid(const float *anchor_xyz, long long anchor_stride, const float *positive_xyz, long long positive_stride,
+                   const int32_t *match, const int32_t *anchor_count, int P, int Ma, int Mb, double threshold, double division,
+                   int settle, int max_iterations, double *Rt, double *weights, int32_t *valid, uint8_t *inliers,
+                   int32_t *num_inliers, int32_t *num_corr, int32_t *iterations, void *stream);
 
 /* Dense point-to-point ICP refinement of P registered cloud pairs (csrc/icp.hip): from a pose of dh3d_ransac_rigid to the
  * least-squares pose over the clouds' nearest-neighbour pairs, with the dense overlap of the result.

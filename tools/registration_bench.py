@@ -3,6 +3,12 @@ and dh3d_ransac_rigid separately, with device events around `iters` back-to-back
 depends on the trial count, so three inlier shares are timed: 0.5 (10-40 trials: one round of 256), 0.2 (~570 trials:
 three rounds) and 0 (max_trials + 1 = 10001 trials: 40 rounds, the worst case).  Prints one JSON line.
 
+dh3d_gnc_rigid runs on the same three fixtures (`gnc_inliers*`: median time and spread over `--reps` windows alternating
+with ransac_rigid, the fit count, validity, and both estimators' mean pose errors against the fixtures' truth) and on
+8 x 4096 correspondences, in windows of the same `--iters` calls on every fixture.  Its fit count depends on the extent and
+the threshold only: `gnc_iterations_equal` says whether the three fixtures ran the same fits, `gnc_times_agree` whether the
+three medians lie within the largest spread of their windows.
+
 dh3d_match_descriptors2 (csrc/match.hip) is timed beside the plain matcher at 64 x 512 x 512 x 128 and 8 x 4096 x 4096 x 36,
 `--reps` windows of `iters` calls each, the variants alternating inside a repetition: one plain call, two (the second with
 the roles swapped: what a mutual check costs without the new entry), the new entry forward only (match={}) and with both
@@ -75,8 +81,40 @@ def match2_times(rng, P, M, D, iters, reps):
     return row
 
 
+TRUTH = np.concatenate([np.eye(3), np.full((3, 1), -3.0)], axis=1)  # rows' pose: anchor = positive - 3
+
+
+def pose_errors(out):
+    """Mean translation / rotation error of a fit's poses against the fixtures' truth (transform_errors: a pair without a
+    pose counts 3 m / 6 deg, eval_align.m's catch), and how many pairs are valid."""
+    dt, dd = reg.transform_errors(np.broadcast_to(TRUTH, (out["Rt"].shape[0], 3, 4)), out["Rt"], out["valid"])
+    return dict(valid=int(out["valid"].sum()), rte_mean=float(dt.mean()), rre_mean=float(dd.mean()))
+
+
+def estimators(xa, xb, ids, cnt, iters, reps, ransac_iters=None):
+    """ransac_rigid and gnc_rigid on the same correspondences, alternating inside every repetition: each one's median time
+    and spread (max - min) in us over `reps` windows of `iters` calls (recorded in the entry), its validity and pose errors,
+    RANSAC's trials and GNC's fits.  ransac_iters: a shorter window for RANSAC alone, where it runs to its trial cap; GNC's
+    window is the same on every fixture, so that its times compare."""
+    fits = dict(ransac=lambda: reg.ransac_rigid(xa, xb, ids, cnt), gnc=lambda: reg.gnc_rigid(xa, xb, ids, cnt))
+    calls = dict(ransac=iters if ransac_iters is None else ransac_iters, gnc=iters)
+    runs = {k: [] for k in fits}
+    for _ in range(reps):
+        for k, fn in fits.items():
+            runs[k].append(timed(fn, calls[k]))
+    res = {}
+    for k, fn in fits.items():
+        out = fn()
+        res[k] = dict(us=float(np.median(runs[k])), us_spread=float(max(runs[k]) - min(runs[k])), iters=calls[k], reps=reps,
+                      **pose_errors(out))
+        fits_run = out["trials"].cpu().numpy()
+        res[k].update({"iterations_min" if k == "gnc" else "trials_min": int(fits_run.min()),
+                       "iterations_max" if k == "gnc" else "trials_max": int(fits_run.max())})
+    return res
+
+
 def ransac_on_filtered(rng, P, M, D, iters):
-    """ransac_rigid on the plain ids and on the ratio + mutual ids of the outlier fixtures."""
+    """ransac_rigid on the plain ids and on the ratio + mutual ids of the outlier fixtures; gnc_rigid beside it."""
     cnt = torch.full((P,), M, dtype=torch.int32, device="cuda")
     res = {}
     for share in (0.5, 0.2):
@@ -89,6 +127,9 @@ def ransac_on_filtered(rng, P, M, D, iters):
             out = reg.ransac_rigid(ra, rb, ids, cnt)
             row[label] = dict(us=timed(lambda: reg.ransac_rigid(ra, rb, ids, cnt), iters), valid=int(out["valid"].sum()),
                               trials=float(out["trials"].float().mean()), inlier_ratio=float(out["inlier_ratio"].mean()))
+            both = estimators(ra, rb, ids, cnt, iters, 3)
+            row[label].update(ransac_rte_mean=both["ransac"]["rte_mean"], ransac_rre_mean=both["ransac"]["rre_mean"],
+                              gnc=both["gnc"])
         res["inliers%g" % share] = row
     return res
 
@@ -128,6 +169,18 @@ def main():
         trials = out["trials"].cpu().numpy()
         us = timed(lambda: reg.ransac_rigid(ra, rb, match, cnt), max(1, a.iters // (10 if share == 0 else 1)))
         res["ransac_inliers%g" % share] = dict(us=us, trials_min=int(trials.min()), trials_max=int(trials.max()))
+        both = estimators(ra, rb, match, cnt, a.iters, a.reps, ransac_iters=max(1, a.iters // (10 if share == 0 else 1)))
+        res["gnc_inliers%g" % share] = dict(both["gnc"], ransac=both["ransac"])
+    # the two conditions on the GNC entries: one fit count for every inlier share, and therefore one time (within the
+    # spread of the repeated windows)
+    g = [res["gnc_inliers%g" % s] for s in (0.5, 0.2, 0.0)]
+    res["gnc_iterations_equal"] = len({(e["iterations_min"], e["iterations_max"]) for e in g}) == 1
+    res["gnc_times_agree"] = max(e["us"] for e in g) - min(e["us"] for e in g) <= max(e["us_spread"] for e in g)
+    # the pair that fills the staging: 8 x 4096 correspondences at 50 % inliers
+    ra4, rb4 = rows(np.random.default_rng(1), 8, 4096, 4, 0.5)  # (its own stream: the fixtures below stay what they were)
+    cnt4 = torch.full((8,), 4096, dtype=torch.int32, device="cuda")
+    ids4 = torch.arange(4096, dtype=torch.int32, device="cuda").repeat(8, 1)
+    res["gnc_8x4096_inliers0.5"] = estimators(ra4, rb4, ids4, cnt4, a.iters, a.reps)
     res["register_us"] = timed(lambda: reg.register(ra, cnt, rb, cnt), max(1, a.iters // 10))
     m2 = dict(shape_512x128=match2_times(rng, 64, 512, 128, a.iters, a.reps),
               shape_4096x36=match2_times(rng, 8, 4096, 36, a.iters, a.reps),
