@@ -21,6 +21,7 @@
 
 #include "cell_grid.h"
 #include "common.h"
+#include "group_box.h"
 #include "wave_ops.h"
 
 #pragma clang fp contract(off)
@@ -269,10 +270,7 @@ __global__ __launch_bounds__(64 * WAVES) void fps_list_kernel(const float4 *__re
     bool touched = false;
     for (int p0 = 0; p0 < npick; p0 += PP) {
       const float4 q = s_pick[min(p0 + pk, CAP - 1)];
-      const float ex = fmaxf(fmaxf(blx - q.x, q.x - bhx), 0.f);
-      const float ey = fmaxf(fmaxf(bly - q.y, q.y - bhy), 0.f);
-      const float ez = fmaxf(fmaxf(blz - q.z, q.z - bhz), 0.f);
-      const float bd = (ex * ex + ey * ey + ez * ez) * 0.99999f;
+      const float bd = point_box_gap2(blx, bly, blz, bhx, bhy, bhz, q.x, q.y, q.z);
       unsigned long long nd = __ballot(has_box && p0 + pk < npick && bd <= wmax);
       touched |= nd != 0ull;
       while (nd != 0ull) {  // the picks of this pass that reach the wave

@@ -26,6 +26,7 @@
 
 #include "cell_walk.h"
 #include "common.h"
+#include "group_box.h"
 #include "keys.h"
 #include "wave_ops.h"
 
@@ -82,6 +83,52 @@ struct KnnState {
   float bound;  // s > bound  =>  sqrt(s) > current K-th distance
 };
 
+constexpr u64 kKnnNoKey = ~0ull;  // an unfilled slot: above every real key
+template <int KMAX>
+__device__ __forceinline__ void knn_list_clear(KnnState<KMAX> &st) {  // (the bound stays)
+#pragma unroll
+  for (int i = 0; i < KMAX; ++i) st.keys[i] = kKnnNoKey;
+}
+// An empty list that takes everything.  knn_kernel and knn_sorted_kernel keep these two lines written out on purpose: with
+// the call in their place the compiler allocated both kernels differently (knn_sorted_kernel<32>: 203 -> 170 VGPRs, the
+// insertion's compares chained through vcc) and knn_sorted at K = 32, 8 x 8192, measured 0.606 -> 0.720 ms.
+template <int KMAX>
+__device__ __forceinline__ void knn_list_reset(KnnState<KMAX> &st) {
+  knn_list_clear(st);
+  st.bound = INFINITY;
+}
+
+// The screening bound that a list entry's distance gives, from the high word of its key: the (1 + 2^-20)-inflated square
+// of the distance -- a relative 2^-20 in s is 2^-21 in d, more than 3 ulp, so any s above it has sqrt(s) > d strictly.
+// An unfilled slot (or a NaN distance) gives none: false, and `out` is left as it is.
+__device__ __forceinline__ bool knn_inflated_sq(const unsigned key_hi, float &out) {
+  if (key_hi > 0x7f800000u) return false;
+  const float d = __uint_as_float(key_hi);
+  out = __fmul_rn(__fmul_rn(d, d), 1.000001f);
+  return true;
+}
+
+// One slot of the output.  Fewer than K points: the reference pads with id -1 / FLT_MAX (:110-111); otherwise the id is
+// the CUB rank tb turned back into the point's index (tb = (x % C_THREADS) * C_VPT + x / C_THREADS).
+__device__ __forceinline__ void knn_emit(const u64 key, const KnnLadder &lad, int32_t *nn, float *dist) {
+  if (key == kKnnNoKey) {
+    *nn = -1;
+    *dist = FLT_MAX;
+  } else {
+    const unsigned tb = (unsigned)key;
+    *nn = (int)(((tb % (unsigned)lad.cv) << lad.log2ct) + tb / (unsigned)lad.cv);
+    *dist = __uint_as_float((unsigned)(key >> 32));
+  }
+}
+// the first K entries of a lane's list
+template <int KMAX>
+__device__ __forceinline__ void knn_emit_list(const KnnState<KMAX> &st, int K, const KnnLadder &lad, int32_t *o_nn,
+                                              float *o_d) {
+#pragma unroll
+  for (int i = 0; i < KMAX; ++i)
+    if (i < K) knn_emit(st.keys[i], lad, o_nn + i, o_d + i);
+}
+
 // KEEP_MIN: the bound may already be tighter than this list's own K-th entry (knn_split_kernel)
 template <int KMAX, bool KEEP_MIN = false>
 __device__ __forceinline__ void knn_insert_key(KnnState<KMAX> &st, const u64 key) {
@@ -110,13 +157,8 @@ __device__ __forceinline__ void knn_insert_key(KnnState<KMAX> &st, const u64 key
         st.keys[i] = lt ? a : b;
       }
     }
-    const unsigned hb = (unsigned)(st.keys[KMAX - 1] >> 32);
-    if (hb <= 0x7f800000u) {
-      const float dk = __uint_as_float(hb);
-      // (1+2^-20)-inflated square of the K-th distance: any s above it has sqrt(s) > d_K.
-      const float nb = __fmul_rn(__fmul_rn(dk, dk), 1.000001f);
-      st.bound = KEEP_MIN ? fminf(st.bound, nb) : nb;
-    }
+    float nb;
+    if (knn_inflated_sq((unsigned)(st.keys[KMAX - 1] >> 32), nb)) st.bound = KEEP_MIN ? fminf(st.bound, nb) : nb;
   }
 }
 template <int KMAX, bool KEEP_MIN = false>
@@ -157,6 +199,120 @@ __device__ __forceinline__ float knn_min8(const f32x2 (&s)[4]) {
                fminf(fminf(s[2][0], s[2][1]), fminf(s[3][0], s[3][1])));
 }
 
+// The screen-and-queue step of the lane-per-query kernels, over the 32 candidates whose pair-SoA image starts at img:
+// candidates first .. first + 31 of the caller's numbering, real below `end` (padding is +inf).  24 broadcast LDS reads + 48 packed ops with nothing between them that
+// depends on the lane's list, so they pipeline; ONE wave-uniform test decides whether anybody needs the slow path (a
+// per-8 branch serialised every step behind its own LDS latency: 650-800 cycles/step measured with one wave per SIMD).
+// A survivor (s <= bound) is appended to the lane's queue as (bits(s), id_of(its number)): slot cnt of the
+// lane is q[cnt * qstride + col].  drain() -- the caller's: it empties every lane's queue into the lists and zeroes cnt, and
+// may tighten bound -- runs for the whole wave as soon as one queue could not take another eight.
+template <class IdOf, class Drain>
+__device__ __forceinline__ void knn_screen32(const float *img, uint2 *q, const int qstride, const int col, const bool valid,
+                                             const int first, const int end,
+                                             const f32x2 qx2, const f32x2 qy2, const f32x2 qz2, const float &bound, int &cnt,
+                                             IdOf id_of, Drain drain) {
+  f32x2 s[4][4];
+  float mn[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    knn_dist8(img + 2 * u * 12, qx2, qy2, qz2, s[u]);
+    mn[u] = knn_min8(s[u]);
+  }
+  const float m = fminf(fminf(mn[0], mn[1]), fminf(mn[2], mn[3]));
+  if (__any(valid && m <= bound)) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (valid && mn[u] <= bound) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          const float sv = s[u][t >> 1][t & 1];
+          if (sv <= bound && first + 8 * u + t < end) {
+            q[cnt * qstride + col] = make_uint2(__float_as_uint(sv), (unsigned)id_of(first + 8 * u + t));
+            ++cnt;
+          }
+        }
+      }
+      if (__any(cnt > kQueue - 8)) drain();  // wave-uniform
+    }
+  }
+}
+
+// The queue drain of the group-scanning kernels (slot i of a lane is q[i * 64 + lane]): ONE copy of the (long)
+// insertion per drain site, the next slot requested from LDS while this one is inserted.  Unrolled over the 16 slots
+// knn_sorted_kernel was > 100 KB of code (the drain is inlined at every site of the scan); the instruction cache coped with
+// that in the shipped build (0.2 % misses, profiles/r03_d_pmc_knn.txt) but not in the probe build, and nothing is gained
+// by the unrolling.
+template <int KMAX, bool KEEP_MIN>
+__device__ __forceinline__ void knn_drain_queue(KnnState<KMAX> &st, int &cnt, const uint2 *q, const int lane,
+                                                const KnnLadder &lad) {
+  const int deepest = -wave_min_i32(-cnt);
+  uint2 nxt = q[lane];
+#pragma unroll 1
+  for (int i = 0; i < deepest; ++i) {  // wave-uniform trip count
+    const uint2 e = nxt;
+    if (i + 1 < deepest) nxt = q[(i + 1) * 64 + lane];
+    if (i < cnt) knn_offer<KMAX, KEEP_MIN>(st, __uint_as_float(e.x), (int)e.y, lad);
+  }
+  cnt = 0;
+}
+
+// the lanes' records of a 64-record group (one each; padding is +inf) -> the wave's pair-SoA image and id strip
+__device__ __forceinline__ void knn_stage_group(float *my_c, int *my_id, const int lane, const float4 cr) {
+  my_c[cand4_slot(lane, 0)] = cr.x;
+  my_c[cand4_slot(lane, 1)] = cr.y;
+  my_c[cand4_slot(lane, 2)] = cr.z;
+  my_id[lane] = __float_as_int(cr.w);
+  __builtin_amdgcn_wave_barrier();
+}
+// One group of the sorted cloud (clen real records) through the screen: staged, then 32 candidates per step.
+template <class Drain>
+__device__ __forceinline__ void knn_scan_group(float *my_c, int *my_id, uint2 *my_q, const int lane, const float4 cr,
+                                               const int clen, const bool valid, const f32x2 qx2, const f32x2 qy2,
+                                               const f32x2 qz2, const float &bound, int &cnt, Drain drain) {
+  knn_stage_group(my_c, my_id, lane, cr);
+  for (int j = 0; j < clen; j += 32)
+    knn_screen32(my_c + (j >> 2) * 12, my_q, 64, lane, valid, j, clen, qx2, qy2, qz2, bound, cnt,
+                 [my_id](int i) { return my_id[i]; }, drain);
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The visit loop of a chunk walk: the candidate groups of `mask` (bit l = the group whose box lane l holds: clo, chi, and
+// bd = its gap to the query group's box), nearest to position gl first; the next group's records are prefetched while
+// this one is scanned.  group_of(l) names the group, load_group(g) fetches the lanes' records of it, scan_group(g, records)
+// evaluates it (and may tighten bound and wave_bound = the loosest bound of the wave's valid lanes).
+template <class GroupOf, class LoadGroup, class ScanGroup>
+__device__ __forceinline__ void knn_visit_groups(unsigned long long mask, const int gl, const float bd, const float4 &clo,
+                                                 const float4 &chi, const float4 &qr, const bool valid, const float &bound,
+                                                 const float &wave_bound, GroupOf group_of, LoadGroup load_group,
+                                                 ScanGroup scan_group) {
+  if (!mask) return;
+  int l = knn_pick_near(mask, gl);
+  mask &= ~(1ull << l);
+  float4 nxt = load_group(group_of(l));
+  while (true) {
+    const int lcur = l;
+    const float4 cr = nxt;
+    const bool more = mask != 0;
+    if (more) {
+      l = knn_pick_near(mask, gl);
+      mask &= ~(1ull << l);
+      nxt = load_group(group_of(l));
+    }
+    const float bdl = wave_bcast_f32(bd, lcur);
+    if (bdl <= wave_bound) {  // the bound may have tightened since the ballot
+      // box against box says "some query of the wave MIGHT reach the group" with the union of the 64 queries and
+      // the loosest of their bounds; the same test per query (point to box, own bound) is ~20 instructions
+      // against the ~450 of scanning the group, and decides most of the overlapping (tier 0) groups of a query
+      // group whose own box is large (Morton order jumps across the cloud inside it)
+      const float lx = wave_bcast_f32(clo.x, lcur), ly = wave_bcast_f32(clo.y, lcur), lz = wave_bcast_f32(clo.z, lcur);
+      const float hx = wave_bcast_f32(chi.x, lcur), hy = wave_bcast_f32(chi.y, lcur), hz = wave_bcast_f32(chi.z, lcur);
+      const float pd = point_box_gap2(lx, ly, lz, hx, hy, hz, qr.x, qr.y, qr.z);
+      if (__any(valid && pd <= bound)) scan_group(group_of(lcur), cr);
+    }
+    if (!more) break;
+  }
+}
+
 // XYZ_LAYOUT: false = positions [B,3,N] (op layout), true = xyz [B,N,3].
 template <int KMAX, bool XYZ_LAYOUT>
 __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__restrict__ pos, int N,
@@ -179,9 +335,19 @@ __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__re
 
   KnnState<KMAX> st;
 #pragma unroll
-  for (int i = 0; i < KMAX; ++i) st.keys[i] = ~0ull;
+  for (int i = 0; i < KMAX; ++i) st.keys[i] = kKnnNoKey;  // (written out, not knn_list_reset: see there)
   st.bound = INFINITY;
   int cnt = 0;
+  auto drain = [&]() {  // every lane's queue, as deep as the deepest
+    for (int i = 0; i < kQueue; ++i) {
+      if (!__any(i < cnt)) break;
+      if (i < cnt) {
+        const uint2 e = s_q[i * kQueriesPerBlock + tid];
+        knn_offer<KMAX>(st, __uint_as_float(e.x), (int)e.y, lad);
+      }
+    }
+    cnt = 0;
+  };
 
   for (int base = 0; base < N; base += kChunk) {
     const int len = min(kChunk, N - base);
@@ -199,47 +365,10 @@ __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__re
       }
     }
     __syncthreads();
-    // 32 candidates per iteration: 24 broadcast LDS reads + 48 packed ops with nothing between them that
-    // depends on the lane's list, so they pipeline; ONE wave-uniform test decides whether anybody needs the
-    // slow path (a per-8 branch serialised every step behind its own LDS latency: 650-800 cycles/step
-    // measured with one wave per SIMD).
     const int len32 = (len8 + 31) & ~31;  // the image is padded with +inf up to a multiple of 32
-    for (int j = 0; j < len32; j += 32) {
-      f32x2 s[4][4];
-      float mn[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        knn_dist8(s_c + ((j >> 2) + 2 * u) * 12, qx2, qy2, qz2, s[u]);
-        mn[u] = knn_min8(s[u]);
-      }
-      const float m = fminf(fminf(mn[0], mn[1]), fminf(mn[2], mn[3]));
-      if (__any(y < N && m <= st.bound)) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (y < N && mn[u] <= st.bound) {
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-              const float sv = s[u][t >> 1][t & 1];
-              const int x = base + j + 8 * u + t;
-              if (sv <= st.bound && x < N) {
-                s_q[cnt * kQueriesPerBlock + tid] = make_uint2(__float_as_uint(sv), (unsigned)x);
-                ++cnt;
-              }
-            }
-          }
-          if (__any(cnt > kQueue - 8)) {  // wave-uniform: drain every lane's queue
-            for (int i = 0; i < kQueue; ++i) {
-              if (!__any(i < cnt)) break;
-              if (i < cnt) {
-                const uint2 e = s_q[i * kQueriesPerBlock + tid];
-                knn_offer<KMAX>(st, __uint_as_float(e.x), (int)e.y, lad);
-              }
-            }
-            cnt = 0;
-          }
-        }
-      }
-    }
+    for (int j = 0; j < len32; j += 32)
+      knn_screen32(s_c + (j >> 2) * 12, s_q, kQueriesPerBlock, tid, y < N, base + j, N, qx2, qy2, qz2, st.bound, cnt,
+                   [](int x) { return x; }, drain);
   }
   for (int i = 0; i < kQueue; ++i) {  // final drain
     if (i < cnt) {
@@ -248,23 +377,7 @@ __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__re
     }
   }
 
-  if (y < N) {
-    int32_t *o_nn = nn + ((size_t)b * N + y) * K;
-    float *o_d = dist + ((size_t)b * N + y) * K;
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-      if (i < K) {
-        const unsigned tb = (unsigned)st.keys[i];
-        if (st.keys[i] == ~0ull) {  // fewer than K points: reference pads with id -1 / FLT_MAX (:110-111)
-          o_nn[i] = -1;
-          o_d[i] = FLT_MAX;
-        } else {
-          o_nn[i] = (int)(((tb % (unsigned)lad.cv) << lad.log2ct) + tb / (unsigned)lad.cv);
-          o_d[i] = __uint_as_float((unsigned)(st.keys[i] >> 32));
-        }
-      }
-    }
-  }
+  if (y < N) knn_emit_list(st, K, lad, nn + ((size_t)b * N + y) * K, dist + ((size_t)b * N + y) * K);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -273,8 +386,7 @@ __global__ __launch_bounds__(kQueriesPerBlock) void knn_kernel(const float *__re
 // a wave owns one group of 64 Morton-consecutive queries and walks the candidate groups nearest-first
 // (g, g+1, g-1, g+2, ...).  A candidate group is skipped when the squared distance between the two
 // bounding boxes exceeds every lane's current screening bound (which already over-estimates the K-th
-// distance); the 1e-5 relative margin on the box distance dwarfs the rounding of the f32 distance chain,
-// so a skipped candidate would also have failed the per-candidate screen.  Evaluated groups go through
+// distance): a skipped candidate would also have failed the per-candidate screen (group_box.h).  Evaluated groups go through
 // exactly the same screen / queue / 64-bit-key insertion as knn_kernel, so ids and distances are
 // bit-identical to it (tests).  Waves are independent: no block-level barrier.
 constexpr int kSortedWaves = 4;
@@ -309,64 +421,18 @@ __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const flo
 
   KnnState<KMAX> st;
 #pragma unroll
-  for (int i = 0; i < KMAX; ++i) st.keys[i] = ~0ull;
+  for (int i = 0; i < KMAX; ++i) st.keys[i] = kKnnNoKey;  // (written out, not knn_list_reset: see there)
   st.bound = INFINITY;
   int cnt = 0;
   float wave_bound = INFINITY;  // max over the wave's valid lanes of st.bound (refreshed after each drain)
 
   auto drain = [&]() {
-    // ONE copy of the (long) insertion per drain site, the next slot requested from LDS while this one is inserted.
-    // Unrolled over the 16 slots the kernel was > 100 KB of code (the drain is inlined at every site of the scan); the
-    // instruction cache coped with that in the shipped build (0.2 % misses, profiles/r03_d_pmc_knn.txt) but not in the
-    // probe build, and nothing is gained by the unrolling.
-    const int deepest = -wave_min_i32(-cnt);
-    uint2 nxt = my_q[lane];
-#pragma unroll 1
-    for (int i = 0; i < deepest; ++i) {  // wave-uniform trip count
-      const uint2 e = nxt;
-      if (i + 1 < deepest) nxt = my_q[(i + 1) * 64 + lane];
-      if (i < cnt) knn_offer<KMAX>(st, __uint_as_float(e.x), (int)e.y, lad);
-    }
-    cnt = 0;
+    knn_drain_queue<KMAX, false>(st, cnt, my_q, lane, lad);
     wave_bound = wave_max_f32(valid ? st.bound : 0.f);
   };
-
   // evaluate the 64 candidates of group gcc (records already in `cr`, one per lane)
   auto scan_group = [&](int gcc, const float4 cr) {
-    my_c[cand4_slot(lane, 0)] = cr.x;
-    my_c[cand4_slot(lane, 1)] = cr.y;
-    my_c[cand4_slot(lane, 2)] = cr.z;
-    my_id[lane] = __float_as_int(cr.w);
-    __builtin_amdgcn_wave_barrier();
-    const int clen = min(64, N - gcc * 64);
-    // 32 candidates per iteration, one wave-uniform test (see knn_kernel); padding records are +inf
-    for (int j = 0; j < clen; j += 32) {
-      f32x2 s[4][4];
-      float mn[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        knn_dist8(my_c + ((j >> 2) + 2 * u) * 12, qx2, qy2, qz2, s[u]);
-        mn[u] = knn_min8(s[u]);
-      }
-      const float m = fminf(fminf(mn[0], mn[1]), fminf(mn[2], mn[3]));
-      if (__any(valid && m <= st.bound)) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (valid && mn[u] <= st.bound) {
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-              const float sv = s[u][t >> 1][t & 1];
-              if (sv <= st.bound && j + 8 * u + t < clen) {
-                my_q[cnt * 64 + lane] = make_uint2(__float_as_uint(sv), (unsigned)my_id[j + 8 * u + t]);
-                ++cnt;
-              }
-            }
-          }
-          if (__any(cnt > kQueue - 8)) drain();
-        }
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    knn_scan_group(my_c, my_id, my_q, lane, cr, min(64, N - gcc * 64), valid, qx2, qy2, qz2, st.bound, cnt, drain);
   };
   auto load_group = [&](int gcc) { const int ci = gcc * 64 + lane; return ci < N ? sc[ci] : pad; };
 
@@ -389,63 +455,19 @@ __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const flo
       if (other) {
         clo = gb[gi * 2];
         chi = gb[gi * 2 + 1];
-        const float ex = fmaxf(fmaxf(clo.x - qhi.x, qlo.x - chi.x), 0.f);
-        const float ey = fmaxf(fmaxf(clo.y - qhi.y, qlo.y - chi.y), 0.f);
-        const float ez = fmaxf(fmaxf(clo.z - qhi.z, qlo.z - chi.z), 0.f);
-        bd = (ex * ex + ey * ey + ez * ez) * 0.99999f;
+        bd = group_box_gap2(clo, chi, qlo, qhi);
       }
-      unsigned long long mask =
+      const unsigned long long mask =
           tier == 0 ? __ballot(other && bd == 0.f) : __ballot(other && bd > 0.f && bd <= wave_bound);
-      if (!mask) continue;
-      int l = knn_pick_near(mask, gl);
-      mask &= ~(1ull << l);
-      float4 nxt = load_group(c0 + l);
-      while (true) {
-        const int lcur = l;
-        const float4 cr = nxt;
-        const bool more = mask != 0;
-        if (more) {
-          l = knn_pick_near(mask, gl);
-          mask &= ~(1ull << l);
-          nxt = load_group(c0 + l);
-        }
-        const float bdl = wave_bcast_f32(bd, lcur);
-        if (bdl <= wave_bound) {  // the bound may have tightened since the ballot
-          // box against box says "some query of the wave MIGHT reach the group" with the union of the 64 queries and
-          // the loosest of their bounds; the same test per query (point to box, own bound) is ~20 instructions
-          // against the ~450 of scanning the group, and decides most of the overlapping (tier 0) groups of a query
-          // group whose own box is large (Morton order jumps across the cloud inside it)
-          const float lx = wave_bcast_f32(clo.x, lcur), ly = wave_bcast_f32(clo.y, lcur), lz = wave_bcast_f32(clo.z, lcur);
-          const float hx = wave_bcast_f32(chi.x, lcur), hy = wave_bcast_f32(chi.y, lcur), hz = wave_bcast_f32(chi.z, lcur);
-          const float px = fmaxf(fmaxf(lx - qr.x, qr.x - hx), 0.f);
-          const float py = fmaxf(fmaxf(ly - qr.y, qr.y - hy), 0.f);
-          const float pz = fmaxf(fmaxf(lz - qr.z, qr.z - hz), 0.f);
-          const float pd = (px * px + py * py + pz * pz) * 0.99999f;
-          if (__any(valid && pd <= st.bound)) scan_group(c0 + lcur, cr);
-        }
-        if (!more) break;
-      }
+      knn_visit_groups(mask, gl, bd, clo, chi, qr, valid, st.bound, wave_bound, [c0](int l) { return c0 + l; }, load_group,
+                       scan_group);
     }
   }
   if (__any(cnt > 0)) drain();
 
   if (valid) {
-    const int y = __float_as_int(qr.w);  // original index of this query
-    int32_t *o_nn = nn + ((size_t)b * N + y) * K;
-    float *o_d = dist + ((size_t)b * N + y) * K;
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-      if (i < K) {
-        const unsigned tb = (unsigned)st.keys[i];
-        if (st.keys[i] == ~0ull) {
-          o_nn[i] = -1;
-          o_d[i] = FLT_MAX;
-        } else {
-          o_nn[i] = (int)(((tb % (unsigned)lad.cv) << lad.log2ct) + tb / (unsigned)lad.cv);
-          o_d[i] = __uint_as_float((unsigned)(st.keys[i] >> 32));
-        }
-      }
-    }
+    const size_t y = (size_t)b * N + __float_as_int(qr.w);  // original index of this query
+    knn_emit_list(st, K, lad, nn + y * K, dist + y * K);
   }
 }
 
@@ -463,6 +485,10 @@ __global__ __launch_bounds__(64 * kSortedWaves) void knn_sorted_kernel(const flo
 // The body is a device function over a raw LDS block (knn_split_lds_bytes<S>()): knn_split_kernel gives it a block of its
 // own, knn_grid_kernel ALIASES it with its candidate lists and serves a crowded cloud in the same launch (round 6: the
 // pruned scan as a second launch behind the cell lists was a 4.8 us no-op on every uniform cloud, and vice versa).
+// The contract with those callers: the body is entered by whole groups of S waves (wave0 = the group's first), and a group
+// may share its workgroup with another group or with idle waves (knn_grid_kernel<4, 2>: two groups of two).  Its
+// __syncthreads() are the WORKGROUP's, so the number it executes must not depend on data -- 2 + 2 log2(S), whatever the
+// cloud -- and it must not return early: every wave of a group that enters runs to the end.
 template <int S>
 __host__ __device__ constexpr int knn_split_lds_bytes() {
   return S * (64 * 3 * 4 + kQueue * 64 * 8 + 64 * 4 + 64 * 4 + 64 * 4);
@@ -497,9 +523,7 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
   const float4 qlo = gb[g * 2], qhi = gb[g * 2 + 1];
 
   KnnState<KMAX> st;
-#pragma unroll
-  for (int i = 0; i < KMAX; ++i) st.keys[i] = ~0ull;
-  st.bound = INFINITY;
+  knn_list_reset(st);
   int cnt = 0;
   float wave_bound = INFINITY;
   s_share[wave][lane] = INFINITY;
@@ -520,65 +544,17 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
   };
 
   auto drain = [&]() {
-    const int deepest = -wave_min_i32(-cnt);
-    uint2 nxt = my_q[lane];
-#pragma unroll 1
-    for (int i = 0; i < deepest; ++i) {  // one copy of the insertion per site (code size, see knn_sorted_kernel)
-      const uint2 e = nxt;
-      if (i + 1 < deepest) nxt = my_q[(i + 1) * 64 + lane];
-      if (i < cnt) knn_offer<KMAX, true>(st, __uint_as_float(e.x), (int)e.y, lad);
-    }
-    cnt = 0;
+    knn_drain_queue<KMAX, true>(st, cnt, my_q, lane, lad);
     // publish my R-th distance, take the largest of everyone's
-    const unsigned hb = (unsigned)(st.keys[R] >> 32);
     float mx = INFINITY;
-    if (hb <= 0x7f800000u) {
-      const float dr = __uint_as_float(hb);
-      mx = __fmul_rn(__fmul_rn(dr, dr), 1.000001f);
-    }
+    knn_inflated_sq((unsigned)(st.keys[R] >> 32), mx);
     s_share[wave][lane] = mx;
-    const unsigned hk = (unsigned)(st.keys[KMAX - 1] >> 32);
-    if (hk <= 0x7f800000u) {
-      const float dk = __uint_as_float(hk);
-      s_kth[wave][lane] = __fmul_rn(__fmul_rn(dk, dk), 1.000001f);
-    }
+    float kth;
+    if (knn_inflated_sq((unsigned)(st.keys[KMAX - 1] >> 32), kth)) s_kth[wave][lane] = kth;
     adopt(mx);
   };
-
   auto scan_group = [&](int gcc, const float4 cr) {
-    my_c[cand4_slot(lane, 0)] = cr.x;
-    my_c[cand4_slot(lane, 1)] = cr.y;
-    my_c[cand4_slot(lane, 2)] = cr.z;
-    my_id[lane] = __float_as_int(cr.w);
-    __builtin_amdgcn_wave_barrier();
-    const int clen = min(64, N - gcc * 64);
-    for (int j = 0; j < clen; j += 32) {
-      f32x2 sq[4][4];
-      float mn[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        knn_dist8(my_c + ((j >> 2) + 2 * u) * 12, qx2, qy2, qz2, sq[u]);
-        mn[u] = knn_min8(sq[u]);
-      }
-      const float m = fminf(fminf(mn[0], mn[1]), fminf(mn[2], mn[3]));
-      if (__any(valid && m <= st.bound)) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (valid && mn[u] <= st.bound) {
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-              const float sv = sq[u][t >> 1][t & 1];
-              if (sv <= st.bound && j + 8 * u + t < clen) {
-                my_q[cnt * 64 + lane] = make_uint2(__float_as_uint(sv), (unsigned)my_id[j + 8 * u + t]);
-                ++cnt;
-              }
-            }
-          }
-          if (__any(cnt > kQueue - 8)) drain();
-        }
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    knn_scan_group(my_c, my_id, my_q, lane, cr, min(64, N - gcc * 64), valid, qx2, qy2, qz2, st.bound, cnt, drain);
   };
   auto load_group = [&](int gcc) { const int ci = gcc * 64 + lane; return ci < N ? sc[ci] : pad; };
 
@@ -599,12 +575,7 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
   };
   auto test_boxes = [&]() {
     bd = INFINITY;
-    if (other) {
-      const float ex = fmaxf(fmaxf(clo.x - qhi.x, qlo.x - chi.x), 0.f);
-      const float ey = fmaxf(fmaxf(clo.y - qhi.y, qlo.y - chi.y), 0.f);
-      const float ez = fmaxf(fmaxf(clo.z - qhi.z, qlo.z - chi.z), 0.f);
-      bd = (ex * ex + ey * ey + ez * ez) * 0.99999f;
-    }
+    if (other) bd = group_box_gap2(clo, chi, qlo, qhi);
   };
   if (NCH == 1) fetch_boxes(0);
 
@@ -613,11 +584,7 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
     // the other groups with a list of its own and -- after the one barrier -- a bound all 64 candidates contributed
     // to.  (With the group scanned by its owner alone the other waves met their first group with no bound at all and
     // queued every candidate of it.)
-    my_c[cand4_slot(lane, 0)] = qr.x;
-    my_c[cand4_slot(lane, 1)] = qr.y;
-    my_c[cand4_slot(lane, 2)] = qr.z;
-    my_id[lane] = __float_as_int(qr.w);
-    __builtin_amdgcn_wave_barrier();
+    knn_stage_group(my_c, my_id, lane, qr);
     const int clen = min(64, N - g * 64);
     for (int blk = wave; blk * 8 < clen; blk += S) {
       f32x2 sq[4];
@@ -646,37 +613,10 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
       if (NCH > 1 || tier == 0) test_boxes();
       const int gl = min(max(jg - ci * 64, 0), 63);
       if (tier == 1) adopt(s_share[wave][lane]);  // the others have worked since the last look
-      unsigned long long mask =
+      const unsigned long long mask =
           tier == 0 ? __ballot(other && bd == 0.f) : __ballot(other && bd > 0.f && bd <= wave_bound);
-      if (!mask) continue;
-      int l = knn_pick_near(mask, gl);
-      mask &= ~(1ull << l);
-      float4 nxt = load_group((ci * 64 + l) * S + wave);
-      while (true) {
-        const int lcur = l;
-        const float4 cr = nxt;
-        const bool more = mask != 0;
-        if (more) {
-          l = knn_pick_near(mask, gl);
-          mask &= ~(1ull << l);
-          nxt = load_group((ci * 64 + l) * S + wave);
-        }
-        const float bdl = wave_bcast_f32(bd, lcur);
-        if (bdl <= wave_bound) {  // the bound may have tightened since the ballot
-          // box against box says "some query of the wave MIGHT reach the group" with the union of the 64 queries and
-          // the loosest of their bounds; the same test per query (point to box, own bound) is ~20 instructions
-          // against the ~450 of scanning the group, and decides most of the overlapping (tier 0) groups of a query
-          // group whose own box is large (Morton order jumps across the cloud inside it)
-          const float lx = wave_bcast_f32(clo.x, lcur), ly = wave_bcast_f32(clo.y, lcur), lz = wave_bcast_f32(clo.z, lcur);
-          const float hx = wave_bcast_f32(chi.x, lcur), hy = wave_bcast_f32(chi.y, lcur), hz = wave_bcast_f32(chi.z, lcur);
-          const float px = fmaxf(fmaxf(lx - qr.x, qr.x - hx), 0.f);
-          const float py = fmaxf(fmaxf(ly - qr.y, qr.y - hy), 0.f);
-          const float pz = fmaxf(fmaxf(lz - qr.z, qr.z - hz), 0.f);
-          const float pd = (px * px + py * py + pz * pz) * 0.99999f;
-          if (__any(valid && pd <= st.bound)) scan_group((ci * 64 + lcur) * S + wave, cr);
-        }
-        if (!more) break;
-      }
+      knn_visit_groups(mask, gl, bd, clo, chi, qr, valid, st.bound, wave_bound,
+                       [ci, wave](int l) { return (ci * 64 + l) * S + wave; }, load_group, scan_group);
     }
   }
   if (__any(cnt > 0)) drain();
@@ -711,22 +651,8 @@ __device__ __forceinline__ void knn_split_body(const float4 *__restrict__ sorted
   }
 
   if (wave == 0 && valid) {
-    const int y = __float_as_int(qr.w);  // original index of this query
-    int32_t *o_nn = nn + ((size_t)b * N + y) * K;
-    float *o_d = dist + ((size_t)b * N + y) * K;
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-      if (i < K) {
-        const unsigned tb = (unsigned)st.keys[i];
-        if (st.keys[i] == ~0ull) {
-          o_nn[i] = -1;
-          o_d[i] = FLT_MAX;
-        } else {
-          o_nn[i] = (int)(((tb % (unsigned)lad.cv) << lad.log2ct) + tb / (unsigned)lad.cv);
-          o_d[i] = __uint_as_float((unsigned)(st.keys[i] >> 32));
-        }
-      }
-    }
+    const size_t y = (size_t)b * N + __float_as_int(qr.w);  // original index of this query
+    knn_emit_list(st, K, lad, nn + y * K, dist + y * K);
   }
 }
 
@@ -755,7 +681,7 @@ __global__ __launch_bounds__(64 * S) void knn_split_kernel(const float4 *__restr
 //           groups each hold a candidate with s <= U, so at least 8 >= K candidates do and the K-th nearest has
 //           d_K <= sqrt(U) (sqrtf is correctly rounded, hence monotone).  A group without a valid candidate
 //           (N < 57 or so) makes U = +inf, which screens nothing out.
-//   keep  s <= U * 1.000001f.  The knn_insert_key margin: a relative 2^-20 in s is 2^-21 in d, more than 3 ulp, so
+//   keep  s <= U * 1.000001f.  The knn_inflated_sq margin: a relative 2^-20 in s is 2^-21 in d, more than 3 ulp, so
 //           any s above the inflated bound has sqrt(s) > sqrt(U) >= d_K strictly and loses to K candidates whatever
 //           its tb.  Two candidates with s1 < s2 but one rounded distance both stay, and tb orders them as the
 //           reference does.  U = 0 (8 copies of the query) keeps exactly the copies.
@@ -902,13 +828,7 @@ __global__ __launch_bounds__(256) void knn_small_kernel(const float *__restrict_
     }
     if (lane < K) {
       const size_t o = ((size_t)b * N + q) * K + lane;
-      if (my_hi == 0xFFFFFFFFu && my_lo == 0xFFFFFFFFu) {  // reference pads with id -1 / FLT_MAX (:110-111)
-        nn[o] = -1;
-        dist[o] = FLT_MAX;
-      } else {
-        nn[o] = (int)(((my_lo % (unsigned)lad.cv) << lad.log2ct) + my_lo / (unsigned)lad.cv);
-        dist[o] = __uint_as_float(my_hi);
-      }
+      knn_emit(((u64)my_hi << 32) | my_lo, lad, nn + o, dist + o);
     }
   }
 }
@@ -983,7 +903,7 @@ __global__ __launch_bounds__(256) void knn_anydp_kernel(const float *__restrict_
   for (int dp = 0; dp < 16; ++dp) q[dp] = (dp < Dp && y < N) ? pc[(size_t)dp * N + y] : 0.f;
   u64 keys[KMAX];
 #pragma unroll
-  for (int i = 0; i < KMAX; ++i) keys[i] = ~0ull;
+  for (int i = 0; i < KMAX; ++i) keys[i] = kKnnNoKey;
   for (int x0 = 0; x0 < N; x0 += 256) {
     __syncthreads();
     for (int dp = 0; dp < Dp; ++dp) s_c[dp][threadIdx.x] = x0 + (int)threadIdx.x < N ? pc[(size_t)dp * N + x0 + threadIdx.x] : 0.f;
@@ -1009,12 +929,7 @@ __global__ __launch_bounds__(256) void knn_anydp_kernel(const float *__restrict_
   if (y >= N) return;
   int32_t *o_nn = nn + ((size_t)b * N + y) * K;
   float *o_d = dist + ((size_t)b * N + y) * K;
-  for (int i = 0; i < K; ++i) {
-    if (keys[i] == ~0ull) { o_nn[i] = -1; o_d[i] = 3.402823466e+38f; continue; }
-    const unsigned tb = (unsigned)keys[i];
-    o_nn[i] = (int)(((tb % (unsigned)lad.cv) << lad.log2ct) + tb / (unsigned)lad.cv);
-    o_d[i] = __uint_as_float((unsigned)(keys[i] >> 32));
-  }
+  for (int i = 0; i < K; ++i) knn_emit(keys[i], lad, o_nn + i, o_d + i);
 }
 
 }  // namespace
@@ -1184,11 +1099,7 @@ __device__ __forceinline__ void knn_merge_step(KnnState<8> &st) {
   for (int i = 0; i < 8; ++i) st.keys[i] = c[i];
 }
 __device__ __forceinline__ void knn_bound_of_list(KnnState<8> &st) {
-  const unsigned hb = (unsigned)(st.keys[7] >> 32);
-  if (hb <= 0x7f800000u) {
-    const float dk = __uint_as_float(hb);
-    st.bound = __fmul_rn(__fmul_rn(dk, dk), 1.000001f);
-  }
+  knn_inflated_sq((unsigned)(st.keys[7] >> 32), st.bound);
 }
 template <int L>
 __device__ __forceinline__ void knn_merge_sublanes(KnnState<8> &st) {
@@ -1203,7 +1114,7 @@ __device__ __forceinline__ void knn_merge_sublanes(KnnState<8> &st) {
 // sends all of it through the merge.
 template <int L>
 __device__ __forceinline__ void knn_merge_after_sparse_pass(KnnState<8> &st, int sub) {
-  if (L != 4 || __any(sub != 0 && st.keys[0] != ~0ull)) {
+  if (L != 4 || __any(sub != 0 && st.keys[0] != kKnnNoKey)) {
     knn_merge_sublanes<L>(st);
     return;
   }
@@ -1284,9 +1195,8 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   cell_deposit_tables(g.sched, nc[0], nc[1], nc[2], kGridSteps - D, s_ctab);
   auto tab_code = [&](int ax, int ay, int az) { return s_ctab[0][ax & 63] | s_ctab[1][ay & 63] | s_ctab[2][az & 63]; };
   KnnState<8> st;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) st.keys[i] = ~0ull;
-  st.bound = valid ? INFINITY : -1.f;
+  knn_list_reset(st);
+  if (!valid) st.bound = -1.f;  // (takes nothing)
 
   // conservative squared distance from the query to cells cq[a] + o along one axis (0 inside the cell's own slab)
   auto axis_d2 = [&](int a, int o) {
@@ -1329,10 +1239,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   // After a merge all L lanes hold the SAME list: before they scan on, all but one empty theirs (the bound stays), or the
   // next merge would count every entry L times
   auto keep_one_copy = [&]() {
-    if (sub != 0) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) st.keys[i] = ~0ull;
-    }
+    if (sub != 0) knn_list_clear(st);
   };
   unsigned short (*s_list)[kGridRow] = reinterpret_cast<unsigned short (*)[kGridRow]>(s_raw + 3 * 64 * 4);   // [QB][kGridRow]
   int *s_cnt = reinterpret_cast<int *>(s_raw + 3 * 64 * 4 + QB * kGridRow * 2);                                // [QB]
@@ -1592,16 +1499,13 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     if (done) {
       keep_one_copy();
     } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) st.keys[i] = ~0ull;  // (the bound stays: it is the K-th distance of a superset of nothing less)
+      knn_list_clear(st);  // (the bound stays: it is the K-th distance of a superset of nothing less)
       const int NG = (N + 63) >> 6;
-      const float4 *gb = reinterpret_cast<const float4 *>(gbox) + (size_t)b * NG * 2;  // [lo.xyz,_ | hi.xyz,_]
+      const float4 *gb = reinterpret_cast<const float4 *>(gbox) + (size_t)b * NG * 2;  // (group_box.h)
 #pragma unroll 1
       for (int g = sub; g < NG; g += L) {
         const float4 lo4 = gb[2 * g], hi4 = gb[2 * g + 1];
-        const float ex = fmaxf(fmaxf(lo4.x - q[0], q[0] - hi4.x), 0.f), ey = fmaxf(fmaxf(lo4.y - q[1], q[1] - hi4.y), 0.f),
-                    ez = fmaxf(fmaxf(lo4.z - q[2], q[2] - hi4.z), 0.f);
-        if ((ex * ex + ey * ey + ez * ez) * 0.99999f > st.bound) continue;
+        if (point_box_gap2(lo4, hi4, q[0], q[1], q[2]) > st.bound) continue;
         const int j1 = min(N, g * 64 + 64);
 #pragma unroll 1
         for (int j = g * 64; j < j1; j += 8) {  // eight records in flight
@@ -1629,14 +1533,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
 #pragma unroll
       for (int i = 1; i < 8; ++i) key = slot == i ? st.keys[i] : key;
       const size_t o = ((size_t)b * N + y) * K + slot;
-      if (key == ~0ull) {  // fewer than K points: reference pads with id -1 / FLT_MAX (:110-111)
-        nn[o] = -1;
-        dist[o] = FLT_MAX;
-      } else {
-        const unsigned tb = (unsigned)key;
-        nn[o] = (int)(((tb % (unsigned)lad.cv) << lad.log2ct) + tb / (unsigned)lad.cv);
-        dist[o] = __uint_as_float((unsigned)(key >> 32));
-      }
+      knn_emit(key, lad, nn + o, dist + o);
     }
   }
 }

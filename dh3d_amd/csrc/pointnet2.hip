@@ -14,6 +14,7 @@
 
 #include "cell_grid.h"
 #include "common.h"
+#include "group_box.h"
 #include "interp_walk.h"
 #include "keys.h"
 #include "wave_ops.h"
@@ -362,8 +363,8 @@ __device__ __forceinline__ void nn3_scan(const float *s_c, const int *s_k, int k
 //   B. lane = candidate group (64 Morton-consecutive samples, box from dh3d_spatial_sort): the groups whose box lies
 //      within the loosest bound of the query group's box are dealt round-robin to the waves; before a group is scanned
 //      the same test per QUERY (point to box, own bound); steps of phase A are not scanned again.
-// Skipping is exact: the box distance carries a (1 - 1e-5) factor against roundings of a few 1e-7, and '<=' keeps a
-// candidate at exactly the third distance (a smaller index must still be seen).  Same lists, same merge as above.
+// Skipping is exact (group_box.h), and '<=' keeps a candidate at exactly the third distance (a smaller index must still
+// be seen).  Same lists, same merge as above.
 __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel(int n, int m, const float4 *__restrict__ qs,
                                                                 const float *__restrict__ qbox,
                                                                 const float4 *__restrict__ cs,
@@ -398,9 +399,7 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel(int n, int m, c
   if (lane < MG) {
     const float *cb = cbox + ((size_t)b * MG + lane) * 8;
     clx = cb[0]; cly = cb[1]; clz = cb[2]; chx = cb[4]; chy = cb[5]; chz = cb[6];
-    const float ex = fmaxf(fmaxf(clx - qhx, qlx - chx), 0.f), ey = fmaxf(fmaxf(cly - qhy, qly - chy), 0.f),
-                ez = fmaxf(fmaxf(clz - qhz, qlz - chz), 0.f);
-    bd = (ex * ex + ey * ey + ez * ez) * 0.99999f;
+    bd = group_box_gap2(clx, cly, clz, chx, chy, chz, qlx, qly, qlz, qhx, qhy, qhz);
   }
   const unsigned long long kInf = (unsigned long long)__float_as_uint(INFINITY) << 32;
   unsigned long long k1 = kInf, k2 = kInf, k3 = kInf;
@@ -446,9 +445,7 @@ __global__ __launch_bounds__(kBlock) void three_nn_pruned_kernel(int n, int m, c
                 hx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(chx), g)),
                 hy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(chy), g)),
                 hz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(chz), g));
-    const float px = fmaxf(fmaxf(lx - q.x, q.x - hx), 0.f), py = fmaxf(fmaxf(ly - q.y, q.y - hy), 0.f),
-                pz = fmaxf(fmaxf(lz - q.z, q.z - hz), 0.f);
-    if (!__any(valid && (px * px + py * py + pz * pz) * 0.99999f <= kb)) continue;
+    if (!__any(valid && point_box_gap2(lx, ly, lz, hx, hy, hz, q.x, q.y, q.z) <= kb)) continue;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int st = 2 * g + h;
