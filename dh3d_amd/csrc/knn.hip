@@ -1048,7 +1048,7 @@ DH3D_API int dh3d_knn_sorted_plan(int B, int N, int K) {
 // into their own sorted K-lists, and the lists are merged with log2(L) bitonic exchange steps.  Exact after pass 1: the K
 // nearest neighbours all lie within the K-th distance seen after pass 0, i.e. inside the box, and a skipped cell provably
 // holds nothing closer (conservative box distance, ties included).  What the box pass cannot serve (no K-th distance after
-// 27 cells, a ball wider than +-2 cells in x, more than 128 columns) restarts over the sort's 64-point group boxes; clouds
+// 27 cells nor within the +-2 block, a box of more than kGridBoxCells cells, a pass-1 pool past kGridCap) restarts over the sort's 64-point group boxes; clouds
 // whose points crowd into few cells (the sort's verdict, cells[kCellFlag]) are left to the pruned scan (dh3d_knn_grid).
 // Same distances (reference rounding order, IEEE sqrt) and the same 64-bit (distance, CUB rank) order as every other
 // kernel of this file: ids and distance bits are identical.
@@ -1062,6 +1062,59 @@ constexpr int kGridRow = kGridCap + 2;
 // 4 x 4 lanes: a padded trip stays inside the row.  (Pools of a uniform 8192-point cube: 48 on average, 77 at most.)
 constexpr int kGridScreenCap = 80;
 static_assert(kGridScreenCap % 16 == 0 && kGridScreenCap * 6 <= kGridCap * 2, "the screened drain's row");
+// Pass 1 serves a query whose box -- the cells the ball of its K-th distance meets, clipped to the grid -- has at most
+// this many cells (the 5 x 128 columns of the first versions); a wider ball goes to the group-box restart.  It also
+// bounds the operands of knn_small_div below.
+constexpr int kGridBoxCells = 640;
+
+// What a lane that looks at a cell of ANOTHER query's box needs of that query (pass 1 deals the cells of a wave's sixteen
+// queries over all its lanes): two 16-byte LDS reads.
+struct alignas(16) KnnBoxRec {
+  float4 qb;  // the query's x y z, its bound
+  int4 box;   // x: the query's cell, a byte per axis; y, z: its box as offsets from that cell, a byte per axis: -lo, hi
+              // (lo <= 0 <= hi); w: the query's first place in the wave's list of cells
+};
+__device__ __forceinline__ int knn_pack3(int x, int y, int z) { return x | (y << 8) | (z << 16); }
+__device__ __forceinline__ int knn_byte(int v, int a) { return (v >> (8 * a)) & 0xFF; }
+
+// t / d for 0 <= t < kGridBoxCells, 1 <= d <= kGridBoxCells without an integer division: m = 2^20 / d rounded up by at
+// most 2.125 (v_rcp_f32 is within one ulp: 2^20 / d is off by less than 1 / 8, the conversion truncates, + 2), so
+// d * m = 2^20 + e with 0 < e <= 2.125 d, and t * m >> 20 == t / d as long as t * e < 2^20.
+static_assert(2.125 * kGridBoxCells * kGridBoxCells < (1 << 20), "knn_small_div");
+__device__ __forceinline__ int knn_small_div(int t, int d) {
+  const unsigned m = (unsigned)(1048576.f * __builtin_amdgcn_rcpf((float)d)) + 2u;
+  return (int)(((unsigned)t * m) >> 20);
+}
+
+// The cells of the box [lo, hi] (offsets from the query's cell, lo <= 0 <= hi on every axis) that pass 0 has not served:
+// the box without its inner block [max(lo, -1), min(hi, 1)]^3, as three groups of slabs that are walked one after the other,
+//   z: the whole x y extent at the z offsets outside the inner block,   bx * by * oz cells, x fastest, then y;
+//   y: the whole x extent, the inner z, the y offsets outside,          bx * iz * oy,       x fastest, then z;
+//   x: the inner y and z, the x offsets outside,                        iy * iz * ox,       y fastest, then z.
+// An offset outside counts up from lo to the inner block and goes on behind it.  Returns the number of cells and, for
+// 0 <= t < that <= kGridBoxCells, the offsets of cell t: one definition for the count a query publishes and the place a
+// lane decodes.  (Scalars, selected by value: a select between members of a struct or an array becomes an indexed load,
+// and the aggregate goes to scratch memory.)
+__device__ __forceinline__ int knn_box_shell(int lo0, int lo1, int lo2, int hi0, int hi1, int hi2, int t, int &dx, int &dy, int &dz) {
+  const int in00 = max(lo0, -1), in01 = max(lo1, -1), in02 = max(lo2, -1);  // the inner block's first offsets
+  const int in10 = min(hi0, 1), in11 = min(hi1, 1), in12 = min(hi2, 1);     // and its last
+  const int b0 = hi0 - lo0 + 1, b1 = hi1 - lo1 + 1, b2 = hi2 - lo2 + 1;
+  const int i0 = in10 - in00 + 1, i1 = in11 - in01 + 1, i2 = in12 - in02 + 1;
+  const int nz = b0 * b1 * (b2 - i2), ny = b0 * i2 * (b1 - i1), nx = i1 * i2 * (b0 - i0);
+  const int g = t < nz ? 0 : t < nz + ny ? 1 : 2;  // the group; its slabs lie along axis 2 - g
+  t -= g == 0 ? 0 : g == 1 ? nz : nz + ny;
+  const int d1 = g == 2 ? i1 : b0, d2 = g == 0 ? b1 : i2;
+  const int u = knn_small_div(t, d1), f = t - u * d1;
+  const int k = knn_small_div(u, d2), s = u - k * d2;
+  const int slo = g == 0 ? lo2 : g == 1 ? lo1 : lo0;
+  const int sin0 = g == 0 ? in02 : g == 1 ? in01 : in00;
+  const int sin1 = g == 0 ? in12 : g == 1 ? in11 : in10;
+  const int v = k < sin0 - slo ? slo + k : sin1 + 1 + (k - (sin0 - slo));
+  dx = g == 2 ? v : lo0 + f;
+  dy = g == 2 ? in01 + f : g == 1 ? v : lo1 + s;
+  dz = g == 0 ? v : in02 + s;
+  return nz + ny + nx;
+}
 
 __device__ __forceinline__ unsigned knn_spread4(unsigned v) {  // 4 bits -> every third bit (the sort's spread6 >> 6)
   return (v & 1u) | ((v & 2u) << 2) | ((v & 4u) << 4) | ((v & 8u) << 6);
@@ -1134,7 +1187,10 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
                                                       int32_t *__restrict__ nn, float *__restrict__ dist) {
   constexpr int QB = 256 / L;  // queries per workgroup
   static_assert(SF == 0 || (L == 4 && SF <= 4), "the merged scan: 64 queries per workgroup, at most four waves");
-  constexpr int kGridLds = 3 * 64 * 4 + QB * kGridRow * 2 + QB * 4;
+  constexpr int QW = 64 / L;   // queries per wave
+  constexpr int kGridRecAt = 3 * 64 * 4 + QB * kGridRow * 2 + QB * 4;  // the deposit tables, the pool rows, their counts
+  constexpr int kGridLds = kGridRecAt + QB * (int)sizeof(KnnBoxRec);   // and pass 1's per-query records
+  static_assert(kGridRecAt % 16 == 0 && (L != 4 || kGridLds <= 40 * 1024), "16-byte records; four workgroups per CU");
   constexpr int kSplitLds = SF == 2 ? 2 * knn_split_lds_bytes<2>() : SF > 0 ? knn_split_lds_bytes<(SF > 0 ? SF : 1)>() : 0;
   __shared__ __attribute__((aligned(16))) unsigned char s_raw[kGridLds > kSplitLds ? kGridLds : kSplitLds];
   const int b = blockIdx.y, lane = threadIdx.x & 63, sub = lane & (L - 1);
@@ -1199,21 +1255,23 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   if (!valid) st.bound = -1.f;  // (takes nothing)
 
   // conservative squared distance from the query to cells cq[a] + o along one axis (0 inside the cell's own slab)
-  auto axis_d2 = [&](int a, int o) {
-    const float l = lo[a] + (float)(cq[a] + o) * w[a];
-    const float d = fmaxf(fmaxf(fmaxf(l - q[a], q[a] - (l + w[a])), 0.f) - eps[a], 0.f);
+  // (cell_d2: from coordinate qa of any query of the cloud to cell c of axis a)
+  auto cell_d2 = [&](int a, float qa, int c) __attribute__((always_inline)) {
+    const float l = lo[a] + (float)c * w[a];
+    const float d = fmaxf(fmaxf(fmaxf(l - qa, qa - (l + w[a])), 0.f) - eps[a], 0.f);
     return d * d;
   };
-  // the 5 x 5 x 5 block: everything that depends on the x offset alone is computed once (five slabs: distance, cell bits,
-  // inside the grid or not); a lane then walks (dy, dz) columns and, per column, the five x offsets with constants
-  float d2x[5];
-  unsigned bitx[5];
-  bool okx[5];
+  auto axis_d2 = [&](int a, int o) __attribute__((always_inline)) { return cell_d2(a, q[a], cq[a] + o); };
+  // the 3 x 3 x 3 block of pass 0: everything that depends on the x offset alone is computed once (three slabs: distance,
+  // cell bits, inside the grid or not); a lane then walks (dy, dz) columns and, per column, the three x offsets with constants
+  float d2x[3];
+  unsigned bitx[3];
+  bool okx[3];
 #pragma unroll
-  for (int t = 0; t < 5; ++t) {
-    const int ax = cq[0] + t - 2;
+  for (int t = 0; t < 3; ++t) {
+    const int ax = cq[0] + t - 1;
     okx[t] = (unsigned)ax <= (unsigned)gmax[0];
-    d2x[t] = okx[t] ? axis_d2(0, t - 2) : INFINITY;
+    d2x[t] = okx[t] ? axis_d2(0, t - 1) : INFINITY;
     bitx[t] = s_ctab[0][ax & 63];
   }
   // is the K-th distance strictly inside the block of radius R around the query's cell?  (faces on the grid's border
@@ -1378,52 +1436,39 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     }
     wave_lds_sync();
   };
-  // One column (dy, dz: offsets + 2) of the 5 x 5 x 5 block, the cells at the x offsets of TMASK: ranges of all of them in
-  // flight together (no load under the per-cell branches), then the box tests and the pooling.
-  auto column = [&](auto tmask, int dy, int dz) __attribute__((always_inline)) {
-    constexpr int TMASK = decltype(tmask)::value;
-    const int ay = cq[1] + dy - 2, az = cq[2] + dz - 2;
+  // One column (dy, dz in -1..1) of the inner block, its three cells: their ranges in flight together (no load under the
+  // per-cell branches), then the box tests and the pooling.
+  auto column = [&](int dy, int dz) __attribute__((always_inline)) {
+    const int ay = cq[1] + dy, az = cq[2] + dz;
     if ((unsigned)ay > (unsigned)gmax[1] || (unsigned)az > (unsigned)gmax[2]) return;
-    const float d2yz = axis_d2(1, dy - 2) + axis_d2(2, dz - 2);
+    const float d2yz = axis_d2(1, dy) + axis_d2(2, dz);
     const unsigned bityz = tab_code(0, ay, az);
-    int beg[5], end[5];
+    int beg[3], end[3];
 #pragma unroll
-    for (int t = 0; t < 5; ++t)
-      if (TMASK >> t & 1) {
-        beg[t] = ct[bityz | bitx[t]];
-        end[t] = ct[(bityz | bitx[t]) + span];
-      }
-    if constexpr (TMASK != 0b01110) {  // shell 2: most cells fail the box test -- the few that pass one by one
+    for (int t = 0; t < 3; ++t) {
+      beg[t] = ct[bityz | bitx[t]];
+      end[t] = ct[(bityz | bitx[t]) + span];
+    }
+    // (nearly) every cell is taken -- they reserve their places in the query's list together (one LDS atomic, not one per
+    // cell); cells hold 0..~8 records: the first four places are written without a loop
+    int len[3], tot = 0;
 #pragma unroll
-      for (int t = 0; t < 5; ++t)
-        if (TMASK >> t & 1) {
-          if (!okx[t] || (d2yz + d2x[t]) * 0.99999f > st.bound) continue;
-          enqueue(beg[t], end[t]);
-        }
-    } else {
-      // shells 0-1: (nearly) every cell is taken -- they reserve their places in the query's list together (one LDS atomic,
-      // not one per cell); cells hold 0..~8 records: the first four places are written without a loop
-      int len[5], tot = 0;
+    for (int t = 0; t < 3; ++t) {
+      len[t] = okx[t] && !((d2yz + d2x[t]) * 0.99999f > st.bound) ? end[t] - beg[t] : 0;
+      tot += len[t];
+    }
+    if (tot == 0) return;
+    int off = atomicAdd(&s_cnt[qs], tot);
 #pragma unroll
-      for (int t = 0; t < 5; ++t)
-        if (TMASK >> t & 1) {
-          len[t] = okx[t] && !((d2yz + d2x[t]) * 0.99999f > st.bound) ? end[t] - beg[t] : 0;
-          tot += len[t];
-        }
-      if (tot == 0) return;
-      int off = atomicAdd(&s_cnt[qs], tot);
+    for (int t = 0; t < 3; ++t) {
+      const int fit = min(len[t], kGridCap - off);  // (a full list sends the rest of the cell down the direct path)
+      unsigned short *dst = &s_list[qs][off];
 #pragma unroll
-      for (int t = 0; t < 5; ++t)
-        if (TMASK >> t & 1) {
-          const int fit = min(len[t], kGridCap - off);  // (a full list sends the rest of the cell down the direct path)
-          unsigned short *dst = &s_list[qs][off];
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (k < fit) dst[k] = (unsigned short)(beg[t] + k);
-          for (int k = 4; k < fit; ++k) dst[k] = (unsigned short)(beg[t] + k);
-          for (int k = max(fit, 0); k < len[t]; ++k) direct(beg[t] + k);
-          off += len[t];
-        }
+      for (int k = 0; k < 4; ++k)
+        if (k < fit) dst[k] = (unsigned short)(beg[t] + k);
+      for (int k = 4; k < fit; ++k) dst[k] = (unsigned short)(beg[t] + k);
+      for (int k = max(fit, 0); k < len[t]; ++k) direct(beg[t] + k);
+      off += len[t];
     }
   };
   auto begin_pass = [&]() __attribute__((always_inline)) {
@@ -1431,10 +1476,10 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
   };
-  // The columns are dealt DENSELY: walking all 25 with the other pass's columns skipped cost the wave the full body in
-  // nearly every iteration (some lane always had a live column) -- clock stamps: the first pass's 27 cells took as long
-  // as the second's 98, and the two together two thirds of the kernel.
-  // pass 0: shells 0-1 = the nine inner columns at dx in -1..1
+  // The columns are dealt DENSELY: walking all 25 of the +-2 block with the other pass's columns skipped cost the wave the
+  // full body in nearly every iteration (some lane always had a live column) -- clock stamps: the first pass's 27 cells took
+  // as long as the second's 98, and the two together two thirds of the kernel.
+  // pass 0: the nine inner columns at dx in -1..1
   begin_pass();
   if constexpr (L == 4) {
     // nine columns over four lanes are 4 + 4 + 1: a third trip through the whole column body for one lane in four.  The
@@ -1442,16 +1487,16 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
     // trips, and pooled behind them
     const int ay = cq[1] + 1, az = cq[2] + 1;
     const bool mine = sub < 3 && (unsigned)ay <= (unsigned)gmax[1] && (unsigned)az <= (unsigned)gmax[2];
-    const bool okc = sub == 0 ? okx[1] : sub == 1 ? okx[2] : okx[3];
-    const float d2c = (sub == 0 ? d2x[1] : sub == 1 ? d2x[2] : d2x[3]) + axis_d2(1, 1) + axis_d2(2, 1);
-    const unsigned code = tab_code(0, ay, az) | (sub == 0 ? bitx[1] : sub == 1 ? bitx[2] : bitx[3]);
+    const bool okc = sub == 0 ? okx[0] : sub == 1 ? okx[1] : okx[2];
+    const float d2c = (sub == 0 ? d2x[0] : sub == 1 ? d2x[1] : d2x[2]) + axis_d2(1, 1) + axis_d2(2, 1);
+    const unsigned code = tab_code(0, ay, az) | (sub == 0 ? bitx[0] : sub == 1 ? bitx[1] : bitx[2]);
     const int beg9 = ct[mine ? code : 0], end9 = ct[mine ? code + span : 0];
 #pragma unroll 1
-    for (int ci = sub; ci < 8; ci += L) column(std::integral_constant<int, 0b01110>{}, 1 + ci % 3, 1 + ci / 3);
+    for (int ci = sub; ci < 8; ci += L) column(ci % 3 - 1, ci / 3 - 1);
     if (mine && okc && !(d2c * 0.99999f > st.bound)) enqueue(beg9, end9);
   } else {
 #pragma unroll 1
-    for (int ci = sub; ci < 9; ci += L) column(std::integral_constant<int, 0b01110>{}, 1 + ci % 3, 1 + ci / 3);
+    for (int ci = sub; ci < 9; ci += L) column(ci % 3 - 1, ci / 3 - 1);
   }
   drain(std::true_type{});
   knn_merge_sublanes<L>(st);
@@ -1460,41 +1505,95 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float4 *__restrict_
   // (the 5 x 5 x 5 block of the first versions of this kernel), one cell in x / y and four thin layers in z on the ground
   // plane of a street scene whose bounding box is a tenth as high as wide.  Exact after this pass: nothing outside the box
   // is within the bound.  (The fixed block + shell-by-shell widening of the first version took 5.9 ms instead of 30 us
-  // on such a scene, tools/knn_scene_bench.py.)  Columns (dy, dz) of the box are dealt over the query's lanes, the five x
-  // offsets of a column are compile-time; a ball that is wider than that in x, or a box of more than 128 columns, or no
-  // K-th distance yet (fewer than K points in the 27 cells) goes to the restart below.
-  keep_one_copy();
-  begin_pass();
-  bool exact = false;
-  int ylo = -2, zlo = -2, ny = 5, ncol = valid ? 25 : 0;  // (no K-th distance yet, or a ball too wide for this pass: the 5 x 5 x 5 block)
+  // on such a scene, tools/knn_scene_bench.py.)
+  // The cells of the box that pass 0 has not seen (knn_box_shell) are few: on a uniform 8192-point cube 86 % of the
+  // queries have none and a wave of sixteen has ~22 together, where walking the box column by column looked ~260 ranges up
+  // in ~3 trips through a heavy body (profiles/knn_grid_box.txt).  So the wave lists them: every query publishes its count
+  // and a record of what a test of one of its cells needs, a prefix over the sixteen counts places the queries, and lane j
+  // takes cell j of the list WHOEVER'S it is -- finds the query among the prefixes, decodes the cell's offsets, tests it
+  // against that query's bound, looks its range up and reserves its places in that query's pool row.  The rows stay
+  // wave-private.  A row that is full cannot send the rest of a cell down direct() here (the lane's list is another
+  // query's): the count goes past kGridCap all the same, which marks the query for the restart below, as do a box of more
+  // than kGridBoxCells cells (nothing is enumerated for it) and, unless it ends inside the +-2 block, no K-th distance
+  // yet (fewer than K points in the 27 cells: the +-2 block is enumerated, every cell passes the test).
+  bool exact = false, wide = false;
+  int blo[3] = {0, 0, 0}, bhi[3] = {0, 0, 0};  // (an idle lane: the box of one cell, nothing outside its inner block)
   if (valid && st.bound < INFINITY) {
     const float r = sqrtf(st.bound) * 1.0001f;
-    int dlo[3], dhi[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const float inv = scl[a] / (float)(4 << drop[a]);  // cells per unit length
-      dlo[a] = min(0, max(0, (int)floorf((q[a] - r - eps[a] - lo[a]) * inv)) - cq[a]);
-      dhi[a] = max(0, min(gmax[a], (int)floorf((q[a] + r + eps[a] - lo[a]) * inv)) - cq[a]);
+      blo[a] = min(0, max(0, (int)floorf((q[a] - r - eps[a] - lo[a]) * inv)) - cq[a]);
+      bhi[a] = max(0, min(gmax[a], (int)floorf((q[a] + r + eps[a] - lo[a]) * inv)) - cq[a]);
     }
-    const int by = dhi[1] - dlo[1] + 1, bc = by * (dhi[2] - dlo[2] + 1);
-    if (dlo[0] >= -2 && dhi[0] <= 2 && bc <= 128) {
-      exact = true;
-      ylo = dlo[1]; zlo = dlo[2]; ny = by; ncol = bc;
+    wide = (bhi[0] - blo[0] + 1) * (bhi[1] - blo[1] + 1) * (bhi[2] - blo[2] + 1) > kGridBoxCells;
+    exact = !wide;
+  } else if (valid) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      blo[a] = max(-2, -cq[a]);
+      bhi[a] = min(2, gmax[a] - cq[a]);
     }
   }
+  int ncell, unused[3];
+  ncell = knn_box_shell(blo[0], blo[1], blo[2], bhi[0], bhi[1], bhi[2], 0, unused[0], unused[1], unused[2]);
+  if (wide) ncell = 0;
+  int last = ncell;  // inclusive prefix over the wave's queries (the L lanes of a query agree)
+#pragma unroll
+  for (int off = L; off < 64; off <<= 1) {
+    const int o = __shfl_up(last, off, 64);
+    if (lane >= off) last += o;
+  }
+  const int wave_cells = __builtin_amdgcn_readlane(last, 63);
+  bool full = false;
+  if (wave_cells > 0) {
+    KnnBoxRec *s_rec = reinterpret_cast<KnnBoxRec *>(s_raw + kGridRecAt);  // [QB]
+    const int q0 = qs & ~(QW - 1);  // the wave's first query
+    if (sub == 0) {
+      s_cnt[qs] = 0;
+      s_rec[qs].qb = make_float4(q[0], q[1], q[2], st.bound);
+      s_rec[qs].box = make_int4(knn_pack3(cq[0], cq[1], cq[2]), knn_pack3(-blo[0], -blo[1], -blo[2]),
+                                knn_pack3(bhi[0], bhi[1], bhi[2]), last - ncell);
+    }
+    wave_lds_sync();
+    bool pooled = false;
 #pragma unroll 1
-  for (int ci = sub; ci < ncol; ci += L) {
-    const int iz = ci / ny, dy = ylo + (ci - iz * ny), dz = zlo + iz;
-    if (abs(dy) <= 1 && abs(dz) <= 1) column(std::integral_constant<int, 0b10001>{}, dy + 2, dz + 2);  // (dx in -1..1: pass 0)
-    else column(std::integral_constant<int, 0b11111>{}, dy + 2, dz + 2);
+    for (int base = 0; base < wave_cells; base += 64) {
+      const int j = base + lane;
+      if (j >= wave_cells) continue;
+      int f = 0;  // the last query of the wave that starts at or before j: the one with a cell there
+#pragma unroll
+      for (int step = QW / 2; step > 0; step >>= 1)
+        if (s_rec[q0 + f + step].box.w <= j) f += step;
+      const float4 fq = s_rec[q0 + f].qb;
+      const int4 fb = s_rec[q0 + f].box;
+      int fd[3], fc[3];
+      knn_box_shell(-knn_byte(fb.y, 0), -knn_byte(fb.y, 1), -knn_byte(fb.y, 2), knn_byte(fb.z, 0), knn_byte(fb.z, 1),
+                    knn_byte(fb.z, 2), j - fb.w, fd[0], fd[1], fd[2]);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) fc[a] = knn_byte(fb.x, a) + fd[a];
+      const unsigned code = tab_code(fc[0], fc[1], fc[2]);
+      const int beg = ct[code], len = ct[code + span] - beg;  // (asked for ahead of the test)
+      const float d2 = (cell_d2(1, fq.y, fc[1]) + cell_d2(2, fq.z, fc[2])) + cell_d2(0, fq.x, fc[0]);
+      if (d2 * 0.99999f > fq.w || len <= 0) continue;
+      pooled = true;
+      const int off = atomicAdd(&s_cnt[q0 + f], len);
+      const int fit = min(len, kGridCap - off);
+      for (int k = 0; k < fit; ++k) s_list[q0 + f][off + k] = (unsigned short)(beg + k);
+    }
+    // (a wave that pooled nothing -- 94 % of them at 16384 points -- keeps the lists of pass 0's merge as they are)
+    if (__any(pooled)) {
+      keep_one_copy();
+      drain(std::false_type{});
+      knn_merge_after_sparse_pass<L>(st, sub);  // (0.03 insertions per query in this pass on a uniform cloud)
+      full = s_cnt[qs] > kGridCap;
+    }
   }
-  drain(std::false_type{});
-  knn_merge_after_sparse_pass<L>(st, sub);  // (0.03 insertions per query in this pass on a uniform cloud)
   // What is left -- sparse corners, outliers, clusters that put everything into a few cells -- restarts against the bound
   // it has, over the 64-point groups of the Morton order whose box the search ball meets (the sort's group boxes): exact
   // (the list is emptied first, every point within the bound is offered again, nothing twice) and bounded: N / 64 box
   // tests per query dealt over its lanes.
-  const bool done = !valid || exact || inside(2);
+  const bool done = !valid || (!full && !wide && (exact || inside(2)));
   if (__any(!done)) {
     if (done) {
       keep_one_copy();
